@@ -32,6 +32,13 @@ N = 1 adds, also never part of `value` (wall seconds of every leg: `leg_s`):
                       commitments digest, job-set memory, and at 2^22 / 2^18 a KZG identity check of one commitment by Python integers.
 `--extra-legs all` adds three legs outside SURVEY.md section 8's hot path (tools/bench_extra_legs.py).
 
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what `value` needs: it sets up, warms up, times the K steps
+and prints the line (`ms_per_step` = wall milliseconds of one timed step; `roofline` from the events inside the timed region).  Everything
+else -- the legs above, the N > 1 `msm_sharded*` legs, the per-kernel breakdown proofs (`msm_*` / `ntt_*` fields, `roofline_ntt`), the
+commitments digest of proof 0 (`commitments_sha256`; also `--check`) and `cpu_baseline` -- runs only with `--full`.
+`--dump-outputs DIR` writes the 29 commitments / opening witnesses of the last timed step (rank 0) as DIR/*.npy; the inputs are
+seeded, so the same arguments give the same arrays from run to run and build to build.
+
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (msm_accumulate) with the
 algorithmic bytes of SURVEY.md 8d (128 B per point) over its HIP-event-timed launches;
 `cpu_baseline` times the oracle's CPU restatement of the ark 0.3 algorithms at the benchmark sizes.
@@ -392,7 +399,7 @@ def parse_args():
                     help="bn254 = BASELINE.json's second-curve config (same kernels, 4-limb base field); the headline is bls12_381")
     ap.add_argument("--data", default="uniform", choices=["uniform", "benchcircuit"],
                     help="wire columns: uniform random, or BenchCircuit's periodic {6,7,-20,1} rows + 3 blinding rows (SURVEY.md 8d config 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-precompute", action="store_true", help="per-window MSM path (no window-multiples table)")
     ap.add_argument("--table-window", type=int, default=0, help="window c of the SRS table (0 = library default; 16..21), see zk_srs_precompute_ex")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for single-card rehearsals)")
@@ -424,7 +431,7 @@ def parse_args():
     ap.add_argument("--fault-rank", type=int, default=-1,
                     help="test hook: this rank dies (os._exit(41), no clean-up) in the middle of the run -- --rehearse: inside the first timed step, "
                          "between two collectives (--fault-at step) or inside the extra leg that follows the timed region (--fault-at leg); "
-                         "otherwise inside the msm_sharded leg.  The job must end non-zero within --dist-timeout, not hang; killed inside a leg, "
+                         "otherwise inside the msm_sharded leg (--full).  The job must end non-zero within --dist-timeout, not hang; killed inside a leg, "
                          "rank 0 still prints the headline line it already has, with `aborted_in_leg`")
     ap.add_argument("--fault-at", default="step", choices=["step", "leg", "hang"],
                     help="see --fault-rank; 'hang' (--rehearse): the rank stays alive inside the extra leg and never reaches its next collective")
@@ -438,16 +445,16 @@ def parse_args():
     ap.add_argument("--streams", type=int, default=1,
                     help="concurrent proof streams per GPU (threads with their own zk_ctx + HIP stream); the K steps are shared out")
     ap.add_argument("--streams-leg", type=int, default=4,
-                    help="N = 1: after the timed region, also report the throughput with this many concurrent proof streams (0/1 = skip)")
-    ap.add_argument("--no-sharded-leg", action="store_true", help="replica mode: skip the extra sharded-MSM legs")
+                    help="N = 1, --full: after the timed region, also report the throughput with this many concurrent proof streams (0/1 = skip)")
+    ap.add_argument("--no-sharded-leg", action="store_true", help="replica mode, --full: skip the extra sharded-MSM legs")
     ap.add_argument("--sharded-n22-leg", default="auto", choices=["auto", "on", "off"],
-                    help="N > 1: also time BASELINE config 3 (n = 2^22, MSMs point-sharded); auto = on for the default workload")
+                    help="N > 1, --full: also time BASELINE config 3 (n = 2^22, MSMs point-sharded); auto = on for the default workload")
     ap.add_argument("--configs", default="auto", metavar="SPEC",
-                    help="the `configs` leg (N = 1): BASELINE.json's other configurations timed by this very run, never part of `value` -- "
+                    help="the `configs` leg (N = 1, --full): BASELINE.json's other configurations timed by this very run, never part of `value` -- "
                          f"'auto' = {DEFAULT_CONFIGS} (curve:log_n:steps; config 3's size on one card, config 4, config 5's size point in the "
                          "deferred form) when the headline is the default one; 'off'; or a list of the same form")
     ap.add_argument("--extra-legs", default="auto", choices=["auto", "on", "off", "all"],
-                    help="N = 1: blocking_calls, power, drop_in, dedup and no_precompute legs; auto = on when log-n >= 16; 'all' adds the legs "
+                    help="N = 1, --full: blocking_calls, power, drop_in, dedup and no_precompute legs; auto = on when log-n >= 16; 'all' adds the legs "
                          "outside SURVEY.md section 8's hot path (data_benchcircuit, with_device_glue, full_proof)")
     ap.add_argument("--dedup", action="store_true",
                     help="NOT the headline workload: the library's commitment cache on (SURVEY.md 8f N3), 17 MSMs per proof instead of 29")
@@ -462,17 +469,37 @@ def parse_args():
                          "independent adjacent ones (4 wire iffts | h1,h2 | 4 sigma ffts | 12 coset ffts) into one launch per pass")
     ap.add_argument("--no-profile", action="store_true", help="diagnostic: no in-library HIP-event scopes in the timed region (roofline fields empty)")
     ap.add_argument("--no-check", dest="check", action="store_false",
-                    help="skip the digests: by default every leg re-proves proof 0 once OUTSIDE its timed region and the line reports "
-                         "whether the 29 commitments of each leg equal the headline's (commitments_match* fields)")
-    ap.add_argument("--check", dest="check", action="store_true", help="(default) see --no-check")
-    ap.set_defaults(check=True)
+                    help="skip the digests: by default a --full run re-proves proof 0 once OUTSIDE every leg's timed region and the line "
+                         "reports whether the 29 commitments of each leg equal the headline's (commitments_match* fields)")
+    ap.add_argument("--check", dest="check", action="store_true", help="the digests also without --full (default: on with --full), see --no-check")
+    ap.set_defaults(check=None)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the extra legs, configs, the N > 1 sharded legs, the per-kernel breakdown proofs, "
+                         "the commitments digest and the CPU baseline (off: set up, warm up, time the K steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- its 29 commitments / opening witnesses in call order -- "
+                         "as DIR/commitments.npy (float64, one row per point: the 32-bit words of the Montgomery limbs of x then y, "
+                         "least significant first; exact) and DIR/commitments_infinity.npy (float64, 1 = the point at infinity)")
     ap.add_argument("--no-hoist", action="store_true",
                     help="launch every transform where the reference calls it, instead of queueing those that do not depend on a round's "
                          "challenge behind that round's reductions (zk_kzg_round_reduce) before the host waits")
     ap.add_argument("--block-every-call", action="store_true",
                     help="the headline schedule blocks in each of its eleven PC calls (what an unchanged Prover::prove does) instead of "
                          "collecting f|h1|h2, z|z2 and the last round's four calls once per group (zk_kzg_round_begin_dev ... zk_kzg_round_end)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.check is None:
+        args.check = args.full
+    return args
+
+
+def dump_outputs(out_dir: str, points) -> None:
+    """the points one step of the schedule returns (G1Affine, Montgomery limbs), as --dump-outputs describes them"""
+    os.makedirs(out_dir, exist_ok=True)
+    xy = np.ascontiguousarray(np.stack([p.xy() for p in points]), dtype=np.uint64)
+    np.save(os.path.join(out_dir, "commitments.npy"), xy.view(np.uint32).astype(np.float64))
+    np.save(os.path.join(out_dir, "commitments_infinity.npy"), np.array([1.0 if p.infinity else 0.0 for p in points]))
 
 
 def main():
@@ -616,7 +643,7 @@ def main():
         if S == 1:
             t0 = time.perf_counter()
             for _ in range(steps):
-                lanes[0]["sched"].run_once()
+                lanes[0]["last"] = lanes[0]["sched"].run_once()
             barrier()
             dt = time.perf_counter() - t0
         else:
@@ -628,7 +655,7 @@ def main():
                     with torch.cuda.stream(ln["stream"]):
                         gate.wait()
                         for _ in range(ln["k"]):
-                            ln["sched"].run_once()
+                            ln["last"] = ln["sched"].run_once()
                 except Exception as e:  # surfaced below: a failed lane must fail the run
                     errs.append(e)
                     gate.abort()
@@ -681,7 +708,8 @@ def main():
         res = {"dt": dt, "prof": prof, "points_per_launch": hi - lo, "digest": digs[0] if digs else None,
                "exchange": getattr(lanes[0]["sched"], "exchange", None) if sharded else None, "collectives": lanes[0]["sched"].collectives,
                "ntt_bytes": lanes[0]["sched"].ntt_bytes(), "streams": S, "steps_profiled": lanes[0]["k"], "msms_run": msms_run, "kb": kb,
-               "windows": ck0.table_windows(), "window_bits": ck0.table_window_bits() if precompute else 0, "mem": ctx.round_mem_stats()}
+               "windows": ck0.table_windows(), "window_bits": ck0.table_window_bits() if precompute else 0, "mem": ctx.round_mem_stats(),
+               "last": lanes[0].get("last")}
         if dedup == "abi":
             for ln in lanes:
                 ln["ctx"].set_commit_cache(False)
@@ -699,8 +727,10 @@ def main():
     main_sharded = mode == "shard"
     log_n = args.log_n
     n = 1 << log_n
-    r = timed_region(main_sharded, args.streams)
+    r = timed_region(main_sharded, args.streams, breakdown=args.full)
     dt = r["dt"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["last"])
     proofs = steps * (1 if (main_sharded or world == 1) else world)   # replicas: every rank proves K times
     value = proofs / dt
     acc_ms, acc_n = r["prof"]["msm_accumulate"]
@@ -796,6 +826,10 @@ def main():
         "breakdown_note": f"msm_* / ntt_* are per-kernel-scope HIP-event times of {kb} extra proofs run right after the timed region with every scope on; "
                           "inside the timed region only msm_accumulate carries events (roofline)",
     }
+    if not args.full:
+        # the per-kernel breakdown takes proofs of its own after the timed region: --full only
+        for k in ("msm_g1_adds_per_s", "msm_ms_per_proof", "msm_breakdown_ms_per_proof", "ntt_GBps", "ntt_ms_per_proof", "breakdown_note"):
+            del line[k]
     # the second kernel family north_star names: the NTT passes, against the same HBM roofline (2 * 32 * N bytes per transform)
     if ntt_ms:
         ntt_ach = (r["ntt_bytes"] * kb) / (ntt_ms * 1e-3) / 1e9
@@ -821,12 +855,14 @@ def main():
     if args.grand_products:
         gp_ms, gp_n = r["prof"]["grand_product"]
         line["config"]["workload"] += " + z and z2 grand products on device"
-        line["grand_product_ms_per_proof"] = gp_ms / kb
+        if args.full:
+            line["grand_product_ms_per_proof"] = gp_ms / kb
     if args.fuse_round5:
         line["config"]["workload"] += "; round 5's four PC calls merged into one batch"
     if args.quotient:
         line["config"]["workload"] += " + pointwise quotient on device"
-        line["quotient_ms_per_proof"] = r["prof"]["quotient"][0] / kb
+        if args.full:
+            line["quotient_ms_per_proof"] = r["prof"]["quotient"][0] / kb
     if args.dedup:
         line["config"]["workload"] += f" -- WITH the commitment cache (zk_ctx_set_commit_cache): {r['msms_run']} MSMs computed per proof, the rest served from the cache"
     if S > 1:
@@ -864,9 +900,10 @@ def main():
                 res = {"error": "another rank failed this leg"}
         line[name] = res
 
-    extra = args.extra_legs in ("on", "all") or (args.extra_legs == "auto" and log_n >= 16)
-    extra_all = args.extra_legs == "all"       # legs outside SURVEY.md section 8's hot path
-    if world == 1 and S == 1 and args.streams_leg > 1:
+    # every leg below runs only with --full: a plain run is the headline alone
+    extra = args.full and (args.extra_legs in ("on", "all") or (args.extra_legs == "auto" and log_n >= 16))
+    extra_all = extra and args.extra_legs == "all"       # legs outside SURVEY.md section 8's hot path
+    if args.full and world == 1 and S == 1 and args.streams_leg > 1:
         # the GPU's throughput with several proofs in flight (a proving service): small kernels of one proof fill the
         # registers/issue slots the 2-waves/SIMD accumulate of another leaves idle
         def streams_leg():
@@ -958,7 +995,7 @@ def main():
     # ---- BASELINE.json's other configurations, timed by this very run (never part of `value`): config 3's size on one card (2^22),
     # config 4 (BN254, 2^18) and config 5's size point (2^25) -- the reference's own harness sweeps its sizes in one invocation
     # (benches/plonk.rs:95-162).  Default options throughout: the deferred form of the schedule, the library's default table window.
-    spec = args.configs
+    spec = args.configs if args.full else "off"
     if spec == "auto":
         spec = DEFAULT_CONFIGS if (world == 1 and S == 1 and log_n == 20 and cv.curve_id == 0 and args.extra_legs != "off"
                                    and not (args.no_precompute or args.dedup or args.block_every_call)) else "off"
@@ -1013,7 +1050,7 @@ def main():
                             "path with default options; per config: warm-up 1, then `steps` timed proofs; commitments digest of proof 0",
                     "rows": out, "seconds": round(time.perf_counter() - t_leg0, 2)}
         leg("configs", configs_leg)
-    if world > 1 and mode == "replica" and not args.no_sharded_leg:
+    if args.full and world > 1 and mode == "replica" and not args.no_sharded_leg:
         # the same proofs with every MSM point-sharded over the ranks (one RCCL all-gather of Jacobian partials per
         # prover round) -- single-proof latency
         def shard_leg(lg, exchange=None):
@@ -1055,7 +1092,7 @@ def main():
             leg("msm_sharded_n22", shard_leg(22))
     _LINE["leg"] = None
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             t_cb = time.perf_counter()
             try:
                 line["cpu_baseline"] = cpu_baseline(log_n, cv.curve_id, sbits)

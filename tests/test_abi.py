@@ -22,7 +22,9 @@ def header_symbols():
 
 
 def test_library_exports_every_declared_symbol():
-    L = ctypes.CDLL(_lib.LIB_PATH)
+    # loaded the way the package loads it, torch's HIP runtime first: a bare CDLL here, early in a pytest process, would leave the
+    # in-process torch of every later GPU test without a device (two HIP runtimes in one process, ark_plonk_amd/_lib.py)
+    L = _lib.lib()
     syms = header_symbols()
     assert len(syms) >= 30
     for s in syms:

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "13", "--steps", "2", "--warmup", "1", "--streams-leg", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "13", "--steps", "2", "--warmup", "1", "--full", "--streams-leg", "2",
                         "--check", "--extra-legs", "all", "--configs", "bls12_381:14:2,bn254:13:2,bls12_381:15:1"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -80,3 +80,39 @@ def test_bench_default_metric_is_baselines():
     spec.loader.exec_module(m)
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert f"proofs/sec at 2^20 constraints ({m.CURVE_TITLE['bls12_381']}, KZG10); MSM G1-adds/s" == base["metric"]
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run times exactly --steps steps and nothing besides the headline; --dump-outputs writes the 29 points of the last timed
+    step, the same arrays from run to run (seeded inputs), and they are the points of that proof: a --full run of the same size with
+    one step and no warm-up dumps proof 0, whose digest the line carries."""
+    import hashlib
+    import numpy as np
+
+    def run(out, *extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "13", *extra, "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    d = run(tmp_path / "a", "--steps", "3", "--warmup", "1")
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and abs(d["ms_per_step"] * d["value"] - 1000.0) < 1.0
+    assert d["unit"] == "proofs/s" and d["higher_is_better"] is True and isinstance(d["dtype"], str) and "roofline" in d
+    for leg in ("concurrent_streams", "blocking_calls", "power", "drop_in", "dedup", "no_precompute", "configs", "cpu_baseline",
+                "commitments_sha256", "msm_ms_per_proof", "roofline_ntt"):
+        assert leg not in d, leg
+    xy = np.load(tmp_path / "a" / "commitments.npy")
+    inf = np.load(tmp_path / "a" / "commitments_infinity.npy")
+    assert xy.dtype == np.float64 and xy.shape == (29, 2 * 6 * 2) and inf.dtype == np.float64 and inf.shape == (29,)
+    assert (xy >= 0).all() and (xy < 2.0 ** 32).all() and (xy == np.floor(xy)).all() and not inf.any()
+    assert run(tmp_path / "b", "--steps", "3", "--warmup", "1")["steps"] == 3
+    assert np.array_equal(np.load(tmp_path / "b" / "commitments.npy"), xy)
+    # proof 0 through --full: the dumped points hash to the line's commitments digest
+    d0 = run(tmp_path / "c", "--steps", "1", "--warmup", "0", "--full", "--extra-legs", "off", "--streams-leg", "0", "--no-cpu-baseline")
+    xy0 = np.load(tmp_path / "c" / "commitments.npy").astype(np.uint64).astype(np.uint32).reshape(29, -1)
+    inf0 = np.load(tmp_path / "c" / "commitments_infinity.npy")
+    digest = hashlib.sha256(b"".join(xy0[i].view(np.uint64).tobytes() + bytes([int(inf0[i])]) for i in range(29))).hexdigest()
+    assert digest == d0["commitments_sha256"]
+    assert not np.array_equal(np.load(tmp_path / "c" / "commitments.npy"), xy)     # proof 0 is not proof 3

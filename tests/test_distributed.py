@@ -187,7 +187,7 @@ def test_bench_two_ranks_matches_one_rank():
     import subprocess
     import sys
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = [os.path.join(ROOT, "bench.py"), "--log-n", "15", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--check"]
+    common = [os.path.join(ROOT, "bench.py"), "--log-n", "15", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--check"]
     one = subprocess.run([sys.executable] + common, capture_output=True, text=True, env=env, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads(one.stdout.strip().splitlines()[-1])
@@ -529,7 +529,7 @@ def test_config3_size_two_concurrent_ranks_with_a_collective():
     import sys
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    common = [os.path.join(ROOT, "bench.py"), "--log-n", "22", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--extra-legs", "off",
+    common = [os.path.join(ROOT, "bench.py"), "--log-n", "22", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--extra-legs", "off",
               "--streams-leg", "0", "--no-profile"]
     one = subprocess.run([sys.executable] + common, capture_output=True, text=True, env=env, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -732,7 +732,7 @@ def test_bench_gpus_4_one_card():
     card, inside the pool's process guard; eight ranks are rehearsed without the GPU above).  Replicas with the msm_sharded leg riding
     along, then the sharded form as the headline on both axes: the 29 commitments equal the single rank's, the line says what the
     backend saw, wall time bounded."""
-    common = ["--log-n", "13", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--check"]
+    common = ["--log-n", "13", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--check"]
     r1, l1, _ = _run_bench(common, 600)
     assert r1.returncode == 0, r1.stderr[-2000:]
     d1 = l1[-1]
@@ -763,7 +763,7 @@ def test_bench_gpus_4_one_card():
 def test_bench_killed_rank_inside_the_sharded_leg():
     """Three ranks on the card, rank 1 dies at the start of the msm_sharded leg (after the replicas' headline region): the job ends
     non-zero within a bound and rank 0's line -- the headline it had already measured -- is printed with `aborted_in_leg`."""
-    r, lines, wall = _run_bench(["--log-n", "13", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--gpus", "3", "--backend", "gloo",
+    r, lines, wall = _run_bench(["--log-n", "13", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--gpus", "3", "--backend", "gloo",
                                  "--fault-rank", "1", "--dist-timeout", "60"], 600)
     assert r.returncode != 0 and wall < 300, (r.returncode, wall)
     assert len(lines) == 1 and lines[0]["aborted_in_leg"] == "msm_sharded" and lines[0]["value"] > 0 and lines[0]["n_gpus"] == 3

@@ -3,6 +3,7 @@ plonk-gpu-sys says what include/ark_plonk_amd.h says (name, arity, pointer / int
 return value), it is the generator's current output, every library symbol is exported, and every `sys::zk_*` call of the
 hand-written crate exists with the right number of arguments.  Reference interface mirrored: plonk-core/src/commitment.rs:8-49,
 proof_system/prover.rs:32-37, circuit.rs:264-287."""
+import json
 import os
 import re
 import subprocess
@@ -132,7 +133,14 @@ def test_hand_written_crate_calls_declared_functions_with_the_right_arity():
 
 
 PATCH = os.path.join(ROOT, "rust-shim", "patches", "plonk-core-device-prover.patch")
-REF = "/root/reference"
+# what the tests need of the reference tree the patch is written against (heliaxdev/ark-plonk): the digest of every hunk's pre-image
+# there, and the transcript of its prove_with_preprocessed -- tests/golden/gen_golden_reference.py writes it from a checkout of that tree
+REF_GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_prover.json")
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+
+
+def _reference():
+    return json.load(open(REF_GOLDEN))
 
 
 def _added_lines(path_suffix):
@@ -151,14 +159,18 @@ def _added_lines(path_suffix):
 
 def test_the_prover_patch_applies_to_the_reference():
     """patches/plonk-core-device-prover.patch (commitment.rs: the DeviceBackend hook; error.rs: its error; linearisation_poly.rs:
-    compute_on_device; prover.rs: prove_on_device) applies cleanly to the reference tree this repository was built against."""
-    import shutil
-    import pytest
-    if not os.path.isdir(REF) or shutil.which("patch") is None:
-        pytest.skip("no reference tree / no patch(1) here")
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-d", REF, "-i", PATCH], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "Hunk" not in r.stdout or "FAILED" not in r.stdout
+    compute_on_device; prover.rs: prove_on_device) applies cleanly to the reference tree this repository was built against: every
+    hunk's context and removed lines are, at the hunk's own position, the lines the reference has there (their digests, taken from
+    that tree, are in tests/golden/reference_prover.json)."""
+    import hashlib
+    from gen_golden_reference import patch_hunks
+    hunks = patch_hunks(open(PATCH).read())
+    pre = _reference()["patch_preimage"]
+    assert len(hunks) == len(pre) and hunks
+    for (path, start, length, old, _), want in zip(hunks, pre):
+        assert (path, start, length) == (want["file"], want["old_start"], want["old_len"]), (path, start, length)
+        assert len(old) == length, (path, start)
+        assert hashlib.sha256("\n".join(old).encode()).hexdigest() == want["sha256"], f"{path}:{start}: the hunk does not apply to the reference"
 
 
 def _transcript_ops(src):
@@ -169,30 +181,28 @@ def _transcript_ops(src):
 
 def test_the_patched_prover_hashes_what_the_reference_hashes():
     """prove_on_device must leave the transcript byte-identical: the same appends and challenge draws, same labels, same order as
-    prove_with_preprocessed (proof_system/prover.rs:163-638).  Parsed from both sources."""
-    import pytest
-    ref_src = os.path.join(REF, "plonk-core", "src", "proof_system", "prover.rs")
-    if not os.path.exists(ref_src):
-        pytest.skip("no reference tree here")
-    text = open(ref_src).read()
-    body = text[text.index("pub fn prove_with_preprocessed"):text.index("/// Proves a circuit is satisfied, then clears the witness variables")]
-    want = _transcript_ops(body)
+    prove_with_preprocessed (proof_system/prover.rs:163-638).  The patch is parsed; the reference's sequence is known by the digests
+    tests/golden/reference_prover.json holds, taken from that source parsed the same way."""
+    from gen_golden_reference import op_digest, text_digest
+    ref = _reference()
+    want = ref["transcript_ops"]
     added = _added_lines("proof_system/prover.rs")
     got = _transcript_ops(added[added.index("fn prove_on_device"):])
-    assert len(want) == 53 and got == want
+    assert len(want) == 53 and [op_digest(op, label) for op, label in got] == want
     # values too: every appended expression names the same quantity (commitments by their role, evaluations by their field)
     def appended(src):
         src = re.sub(r"//[^\n]*", "", src)
         return [re.sub(r"\s+", "", m.group(1)) for m in re.finditer(r"append\(\s*b\"[^\"]*\",\s*([^;]*?)\)\s*;", src, flags=re.S)]
-    ref_vals, new_vals = appended(body), appended(added[added.index("fn prove_on_device"):])
-    assert len(ref_vals) == len(new_vals)
+    ref_digests, new_vals = ref["appended"], appended(added[added.index("fn prove_on_device"):])
+    assert len(ref_digests) == len(new_vals)
     role = {"w_commits[0].commitment()": "&a_comm", "w_commits[1].commitment()": "&b_comm", "w_commits[2].commitment()": "&c_comm",
             "w_commits[3].commitment()": "&d_comm", "f_poly_commit[0].commitment()": "&f_comm", "h_1_poly_commit[0].commitment()": "&h_1_comm",
             "h_2_poly_commit[0].commitment()": "&h_2_comm", "z_poly_commit[0].commitment()": "&z_comm_round3",
             "t_commits[0].commitment()": "&t_1_comm", "t_commits[1].commitment()": "&t_2_comm", "t_commits[2].commitment()": "&t_3_comm",
             "t_commits[3].commitment()": "&t_4_comm"}
-    for a, b in zip(ref_vals, new_vals):
-        assert role.get(a, a) == b, (a, b)
+    by_role = {v: k for k, v in role.items()}
+    for d, b in zip(ref_digests, new_vals):
+        assert text_digest(by_role.get(b, b)) == d, b
 
 
 def test_device_backend_trait_and_its_gpu_implementation_agree():
@@ -293,28 +303,45 @@ def _balanced(src, what):
     assert not stack, f"{what}: unclosed {stack[-1]}"
 
 
+def _residue(src, what):
+    """(closing, opening) brackets of stripped source that no pair inside it matches; two that mismatch fail the test"""
+    pairs = {")": "(", "]": "[", "}": "{"}
+    closes, opens = [], []
+    for ch in src:
+        if ch in "([{":
+            opens.append(ch)
+        elif ch in ")]}":
+            if opens:
+                assert opens[-1] == pairs[ch], f"{what}: {ch!r} closes {opens[-1]!r}"
+                opens.pop()
+            else:
+                closes.append(ch)
+    return "".join(closes), "".join(opens)
+
+
 def test_rust_sources_and_patch_have_balanced_delimiters():
     """No compiler here: at least every Rust file of the shim, and every file of plonk-core as the patch leaves it, closes what it
-    opens (a dropped brace or parenthesis in 1 000 lines of unbuildable source would otherwise go unnoticed)."""
-    import shutil
-    import tempfile
+    opens (a dropped brace or parenthesis in 1 000 lines of unbuildable source would otherwise go unnoticed).  The reference's files
+    compile, and every hunk's context and removed lines are theirs (test_the_prover_patch_applies_to_the_reference), so a patched
+    file is balanced when every hunk's new lines leave unmatched what its old lines leave unmatched -- where the new lines may close
+    some of the brackets around the hunk if they reopen the same ones at once (`} impl ... {`)."""
     for root, _, files in os.walk(os.path.join(ROOT, "rust-shim")):
         for fn in files:
             if fn.endswith(".rs"):
                 path = os.path.join(root, fn)
                 _balanced(_strip_rust(open(path).read()), os.path.relpath(path, ROOT))
-    if not os.path.isdir(REF) or shutil.which("patch") is None:
-        return
-    with tempfile.TemporaryDirectory() as tmp:
-        touched = ["plonk-core/src/commitment.rs", "plonk-core/src/error.rs", "plonk-core/src/proof_system/prover.rs",
-                   "plonk-core/src/proof_system/linearisation_poly.rs"]
-        for rel in touched:
-            os.makedirs(os.path.dirname(os.path.join(tmp, rel)), exist_ok=True)
-            shutil.copy(os.path.join(REF, rel), os.path.join(tmp, rel))
-        r = subprocess.run(["patch", "-p1", "-d", tmp, "-i", PATCH], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
-        for rel in touched:
-            _balanced(_strip_rust(open(os.path.join(tmp, rel)).read()), rel + " (patched)")
+    from gen_golden_reference import patch_hunks
+    hunks = patch_hunks(open(PATCH).read())
+    assert sorted({h[0] for h in hunks}) == sorted(["plonk-core/src/commitment.rs", "plonk-core/src/error.rs", "plonk-core/src/proof_system/prover.rs",
+                                                    "plonk-core/src/proof_system/linearisation_poly.rs"])
+    reopen = {")": "(", "]": "[", "}": "{"}
+    for path, start, _, old, new in hunks:
+        what = f"{path} (patched, hunk at line {start})"
+        c_old, o_old = _residue(_strip_rust("\n".join(old)), what)
+        c_new, o_new = _residue(_strip_rust("\n".join(new)), what)
+        assert c_new.startswith(c_old), what
+        extra = c_new[len(c_old):]
+        assert o_new == "".join(reopen[ch] for ch in reversed(extra)) + o_old, what
 
 
 def test_patched_prover_declares_what_it_uses():

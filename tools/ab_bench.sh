@@ -8,7 +8,7 @@ mkdir -p "$out"
 for rep in 1 2; do
   for lib in "$@"; do
     name=$(basename "$lib" .so)
-    ARK_PLONK_AMD_LIB="$lib" timeout -k 10 240 python bench.py --steps 8 --warmup 2 --extra-legs off --streams-leg 0 --no-cpu-baseline \
+    ARK_PLONK_AMD_LIB="$lib" timeout -k 10 240 python bench.py --steps 8 --warmup 2 --full --extra-legs off --streams-leg 0 --no-cpu-baseline \
       > "$out/${name}_$rep.json" 2> "$out/${name}_$rep.err"
     python - "$out/${name}_$rep.json" "$name" <<'PY'
 import json, sys

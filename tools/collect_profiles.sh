@@ -15,8 +15,8 @@ out=gpurun_out/prof_$tag
 dir=profiles/${tag:0:3}
 mkdir -p "$out" "$dir"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-BENCH="bench.py --steps 3 --warmup 1 --extra-legs off --streams-leg 0 --no-cpu-baseline"
-PMCB="bench.py --steps 1 --warmup 1 --extra-legs off --streams-leg 0 --no-cpu-baseline --no-check"
+BENCH="bench.py --steps 3 --warmup 1 --full --extra-legs off --streams-leg 0 --no-cpu-baseline"
+PMCB="bench.py --steps 1 --warmup 1 --full --extra-legs off --streams-leg 0 --no-cpu-baseline --no-check"
 commit=$(cat .git_head 2>/dev/null || echo unknown)
 # a discarded run first: the first minute of a session runs at other clocks than the rest (a traced run at the very start read 3.5 % above
 # the bench line that followed it)

@@ -2,7 +2,7 @@ set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/s2
 mkdir -p $out
-B="--steps 10 --warmup 3 --extra-legs off --streams-leg 0 --no-cpu-baseline"
+B="--steps 10 --warmup 3 --full --extra-legs off --streams-leg 0 --no-cpu-baseline"
 timeout -k 10 200 python3 bench.py --steps 5 --warmup 2 --extra-legs off --streams-leg 0 --no-cpu-baseline > $out/warm.log 2>&1
 for cfg in "bn254 18" "bls12_381 18" "bls12_381 16"; do
   set -- $cfg
