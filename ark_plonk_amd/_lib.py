@@ -152,6 +152,13 @@ SYMBOLS = {
     "zk_dev_download": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "zk_dev_copy": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     # N4: wire formats + transcript (host only)
+    "zk_ipa_workspace_bytes": (c_size_t, [c_int, c_size_t]),
+    "zk_ipa_powers_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "zk_ipa_round_dev": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_ipa_fold_dev": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_ipa_final_key_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "zk_ipa_fold_key_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_ipa_check_coeffs_dev": (c_int, [c_void_p, c_int, c_u32, c_void_p, c_void_p]),
     "zk_fr_serialized_size": (c_size_t, [c_int]),
     "zk_g1_compressed_size": (c_size_t, [c_int]),
     "zk_fr_serialize": (c_int, [c_int, c_void_p, ctypes.c_char_p]),

@@ -40,6 +40,8 @@ def jobs():
         ("ntt.o", "ntt.hip", [], HOST_HDRS + ["ntt_pass.cuh"]),
         ("ntt_pass_table.o", "ntt_pass_table.hip", [], []),
         ("msm_dispatch.o", "msm_dispatch.hip", [], HOST_HDRS),
+        # the inner-product-argument commitment (csrc_ipa/): a directory of its own, so that csrc/ keeps its kernel build
+        ("ipa.o", "../csrc_ipa/ipa.hip", [], HOST_HDRS),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

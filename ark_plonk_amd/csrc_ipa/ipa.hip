@@ -1,0 +1,613 @@
+// Inner-product-argument polynomial commitment (ark-poly-commit 0.3 `ipa_pc::InnerProductArgPC`, the reference's second
+// `HomomorphicCommitment`: plonk-core/src/commitment.rs:50-91): the device side of `open` and of the verifier's final-key check.
+//
+// The library keeps no IPA state: the vectors a, b and a workspace (the folded key in the MSM's internal base layout, the canonical copy
+// of a the round MSMs read, the inner-product partial sums of the next round) live in buffers the caller owns, and every challenge is
+// derived by the caller (the transcript rules are not part of the C ABI).  One opening over a key of d1 = d + 1 = 2^k points is
+//   round(first) fold(first) round fold ... round fold          k rounds, m = d1/2, d1/4, ..., 1
+// where round j computes L = MSM(key_l, a_r) + <a_r, b_l> h', R = MSM(key_r, a_l) + <a_l, b_r> h' and fold j applies the challenge:
+//   key'_i = key_l[i] + xi key_r[i]   (ipa_fold_key: one variable-base scalar multiplication per point, xi shared by every lane)
+//   a' = a_l + xi^-1 a_r, b' = b_l + xi b_r   (ipa_scalar_pass: also the canonical copy of a' and the next round's inner products)
+// Round 0 reads the registered key itself (SRS window-table path); later rounds run the per-window MSM over the folded key.
+#include "../csrc/ctx.h"
+
+#include <shared_mutex>
+
+namespace {
+
+// ---- device storage of a base-field element / affine point: the layout of the MSM's internal bases (csrc/msm_common.cuh Store,
+// ld_affine): NL signed 30-bit limbs padded to whole uint4, x then y; "no point" (infinity) is all-zero limbs
+template <class F>
+struct St {
+    static constexpr int U4 = (F::NL + 3) / 4;
+    static constexpr size_t POINT_BYTES = (size_t)2 * U4 * 16;
+};
+template <class F>
+ZK_D F ld_f(const uint4* q) {
+    F r;
+#pragma unroll
+    for (int i = 0; i < St<F>::U4; ++i) {
+        const uint4 a = q[i];
+        if (4 * i + 0 < F::NL) r.v[4 * i + 0] = a.x;
+        if (4 * i + 1 < F::NL) r.v[4 * i + 1] = a.y;
+        if (4 * i + 2 < F::NL) r.v[4 * i + 2] = a.z;
+        if (4 * i + 3 < F::NL) r.v[4 * i + 3] = a.w;
+    }
+    return r;
+}
+template <class F>
+ZK_D void st_f(uint4* q, const F& r) {
+#pragma unroll
+    for (int i = 0; i < St<F>::U4; ++i) {
+        uint4 a;
+        a.x = 4 * i + 0 < F::NL ? r.v[4 * i + 0] : 0u;
+        a.y = 4 * i + 1 < F::NL ? r.v[4 * i + 1] : 0u;
+        a.z = 4 * i + 2 < F::NL ? r.v[4 * i + 2] : 0u;
+        a.w = 4 * i + 3 < F::NL ? r.v[4 * i + 3] : 0u;
+        q[i] = a;
+    }
+}
+template <class F>
+ZK_D AffineU<F> ld_pt(const void* base, uint64_t idx) {
+    const uint4* q = reinterpret_cast<const uint4*>(base) + idx * (2 * St<F>::U4);
+    AffineU<F> p;
+    p.x = ld_f<F>(q);
+    p.y = ld_f<F>(q + St<F>::U4);
+    return p;
+}
+
+// Fr elements (32 bytes, arkworks Montgomery or canonical) as the saturated host/device type of field.cuh
+template <class Fr>
+ZK_D Fr ld_fr(const void* base, uint64_t idx) {
+    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * idx;
+    const uint4 a = q[0], b = q[1];
+    Fr r;
+    r.v[0] = a.x, r.v[1] = a.y, r.v[2] = a.z, r.v[3] = a.w;
+    r.v[4] = b.x, r.v[5] = b.y, r.v[6] = b.z, r.v[7] = b.w;
+    return r;
+}
+template <class Fr>
+ZK_D void st_fr(void* base, uint64_t idx, const Fr& x) {
+    uint4* q = reinterpret_cast<uint4*>(base) + 2 * idx;
+    q[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
+    q[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
+}
+
+// The challenge of a key fold in non-adjacent form: digit i is +1 where bit i of pos is set, -1 where bit i of neg is set; `top` is the
+// index of the highest digit (always +1), -1 for xi = 0.  A kernel argument: every lane walks the same digits.
+constexpr int NAF_WORDS = 9;     // 288 bits: a NAF has at most one digit more than the 255-bit scalar
+struct Naf {
+    uint32_t pos[NAF_WORDS];
+    uint32_t neg[NAF_WORDS];
+    int32_t top;
+};
+// word w of a kernel-argument array with a run-time (uniform) index, as a chain of selects: no copy of the array to scratch memory
+ZK_D uint32_t pick(const uint32_t (&a)[NAF_WORDS], int w) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int k = 0; k < NAF_WORDS; ++k) r = (k == w) ? a[k] : r;
+    return r;
+}
+
+constexpr uint32_t FOLD_T = 128;   // lanes per block of the key fold = points per batched inversion
+
+// dst[i] = src[i] + xi * src[i + m] for i < m, affine, internal layout.  dst may alias src (lane i alone reads src[i] and src[i + m]
+// and writes dst[i]).  Per lane: the NAF of xi as doublings and mixed additions of +-src[i + m] on the XYZZ law of ecu.cuh, one mixed
+// addition of src[i]; then the block normalises its 128 results with ONE field inversion (Montgomery's trick: product scans over the
+// ZZZ in LDS, 1/ZZZ_i = prefix_{i-1} * suffix_{i+1} / total).
+template <class Cv>
+__global__ void __launch_bounds__(FOLD_T) ipa_fold_key(const void* src, void* dst, uint64_t m, Naf nf) {
+    typedef typename Cv::FqU F;
+    typedef XYZZu<F> P;
+    __shared__ F pre[FOLD_T];
+    __shared__ F suf[FOLD_T];
+    __shared__ F inv_total;
+    const uint32_t t = threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * FOLD_T + t;
+    const bool active = i < m;
+    P acc = P::infinity();
+    if (active) {
+        const AffineU<F> q = ld_pt<F>(src, i + m);
+        if (!q.is_null() && nf.top >= 0) {
+            acc = P::from_affine(q);
+            for (int b = nf.top - 1; b >= 0; --b) {
+                acc = P::dbl(acc);
+                const uint32_t sh = (uint32_t)b & 31u;
+                const bool dp = (pick(nf.pos, b >> 5) >> sh) & 1u;
+                const bool dn = (pick(nf.neg, b >> 5) >> sh) & 1u;
+                if (dp || dn) {
+                    AffineU<F> qq;
+                    qq.x = q.x;
+                    qq.y = dn ? F::neg16(q.y) : q.y;
+                    acc = P::madd(acc, qq);
+                }
+            }
+        }
+        const AffineU<F> kl = ld_pt<F>(src, i);
+        if (!kl.is_null()) acc = P::madd(acc, kl);
+    }
+    const bool fin = active && !acc.is_inf();
+    const F z = fin ? acc.zzz : F::one();
+    // inclusive prefix and suffix products of z over the block (Hillis-Steele, log2(FOLD_T) steps each)
+    F p = z, s = z;
+    pre[t] = p;
+    suf[t] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < FOLD_T; d <<= 1) {
+        const F pl = t >= d ? pre[t - d] : F::one();
+        const F sr = t + d < FOLD_T ? suf[t + d] : F::one();
+        __syncthreads();
+        if (t >= d) p = F::mul(p, pl);
+        if (t + d < FOLD_T) s = F::mul(s, sr);
+        pre[t] = p;
+        suf[t] = s;
+        __syncthreads();
+    }
+    if (t == 0) inv_total = F::inverse(pre[FOLD_T - 1]);
+    __syncthreads();
+    if (!active) return;
+    uint4* out = reinterpret_cast<uint4*>(dst) + i * (2 * St<F>::U4);
+    if (!fin) {
+        st_f<F>(out, F::zero());
+        st_f<F>(out + St<F>::U4, F::zero());
+        return;
+    }
+    F zi3 = inv_total;                                   // 1 / ZZZ_i
+    if (t > 0) zi3 = F::mul(zi3, pre[t - 1]);
+    if (t + 1 < FOLD_T) zi3 = F::mul(zi3, suf[t + 1]);
+    const F zi = F::mul(acc.zz, zi3);                    // 1 / Z
+    const F x = F::mul(acc.x, F::sqr(zi));
+    const F y = F::mul(acc.y, zi3);
+    st_f<F>(out, F::canonical_lt2p(x));
+    st_f<F>(out + St<F>::U4, F::canonical_lt2p(y));
+}
+
+constexpr uint32_t SP_T = 256;     // lanes per block of the scalar pass
+
+// The scalar side of a round, one pass.  The vectors after the pass have length mo; lane j < mo/2 owns elements j and j + mo/2 of them
+// (the low and high halves of the NEXT round).  FOLD: a' = a_l + xi^-1 a_r, b' = b_l + xi b_r from the vectors of length 2 mo, in place;
+// otherwise a, b are read as they are (the first round).  Writes a_can = canonical a' (the round MSMs' scalars) and, per block, the
+// partial sums of <a'_r, b'_l> and <a'_l, b'_r> (Montgomery) to partials[block][2].
+template <class Cv, bool FOLD>
+__global__ void __launch_bounds__(SP_T) ipa_scalar_pass(void* a, void* b, uint64_t mo, typename Cv::Fr xi, typename Cv::Fr xi_inv, void* a_can,
+                                                        void* partials) {
+    typedef typename Cv::Fr Fr;
+    __shared__ Fr s1[SP_T];
+    __shared__ Fr s2[SP_T];
+    const uint32_t t = threadIdx.x;
+    const uint64_t j = (uint64_t)blockIdx.x * SP_T + t;
+    if (mo == 1) {                                       // the last fold: one element, no inner product follows
+        if (j == 0) {
+            Fr al = ld_fr<Fr>(a, 0);
+            if (FOLD) {
+                al = Fr::add(al, Fr::mul(xi_inv, ld_fr<Fr>(a, 1)));
+                const Fr bl = Fr::add(ld_fr<Fr>(b, 0), Fr::mul(xi, ld_fr<Fr>(b, 1)));
+                st_fr<Fr>(a, 0, al);
+                st_fr<Fr>(b, 0, bl);
+            }
+            st_fr<Fr>(a_can, 0, Fr::from_mont(al));
+        }
+        return;
+    }
+    const uint64_t h = mo >> 1;
+    Fr ip1 = Fr::zero(), ip2 = Fr::zero();
+    if (j < h) {
+        Fr al = ld_fr<Fr>(a, j), ah = ld_fr<Fr>(a, j + h), bl = ld_fr<Fr>(b, j), bh = ld_fr<Fr>(b, j + h);
+        if (FOLD) {
+            al = Fr::add(al, Fr::mul(xi_inv, ld_fr<Fr>(a, j + mo)));
+            ah = Fr::add(ah, Fr::mul(xi_inv, ld_fr<Fr>(a, j + h + mo)));
+            bl = Fr::add(bl, Fr::mul(xi, ld_fr<Fr>(b, j + mo)));
+            bh = Fr::add(bh, Fr::mul(xi, ld_fr<Fr>(b, j + h + mo)));
+            st_fr<Fr>(a, j, al);
+            st_fr<Fr>(a, j + h, ah);
+            st_fr<Fr>(b, j, bl);
+            st_fr<Fr>(b, j + h, bh);
+        }
+        st_fr<Fr>(a_can, j, Fr::from_mont(al));
+        st_fr<Fr>(a_can, j + h, Fr::from_mont(ah));
+        ip1 = Fr::mul(ah, bl);
+        ip2 = Fr::mul(al, bh);
+    }
+    s1[t] = ip1;
+    s2[t] = ip2;
+    for (uint32_t d = SP_T / 2; d >= 1; d >>= 1) {
+        __syncthreads();
+        if (t < d) {
+            ip1 = Fr::add(ip1, s1[t + d]);
+            ip2 = Fr::add(ip2, s2[t + d]);
+            s1[t] = ip1;
+            s2[t] = ip2;
+        }
+    }
+    if (t == 0) {
+        st_fr<Fr>(partials, 2 * (uint64_t)blockIdx.x, ip1);
+        st_fr<Fr>(partials, 2 * (uint64_t)blockIdx.x + 1, ip2);
+    }
+}
+
+constexpr uint32_t POW_K = 16;     // consecutive powers per lane
+
+// out[i] = z^i, i < n (Montgomery): each lane raises z to its first index, then steps by one multiplication
+template <class Cv>
+__global__ void __launch_bounds__(256) ipa_powers(typename Cv::Fr z, uint64_t n, void* out) {
+    typedef typename Cv::Fr Fr;
+    const uint64_t start = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * POW_K;
+    if (start >= n) return;
+    Fr p = Fr::pow_u64(z, start);
+    const uint64_t end = start + POW_K < n ? start + POW_K : n;
+    for (uint64_t i = start; i < end; ++i) {
+        st_fr<Fr>(out, i, p);
+        p = Fr::mul(p, z);
+    }
+}
+
+// s[k + half] = s[k] * xi for k < half (Montgomery): one bit of the check polynomial's coefficient vector
+template <class Cv>
+__global__ void __launch_bounds__(256) ipa_check_expand(void* s, uint64_t half, typename Cv::Fr xi) {
+    typedef typename Cv::Fr Fr;
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (half == 0) {
+        if (k == 0) st_fr<Fr>(s, 0, Fr::one());
+        return;
+    }
+    if (k < half) st_fr<Fr>(s, k + half, Fr::mul(ld_fr<Fr>(s, k), xi));
+}
+
+// internal layout -> ABI affine (x || y Montgomery, infinity = (0, 1) with flag 1, as GroupAffine::zero())
+template <class Cv>
+__global__ void __launch_bounds__(256) ipa_to_abi(const void* src, uint64_t n, uint32_t* out_xy, uint8_t* out_inf) {
+    typedef typename Cv::FqU F;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const AffineU<F> p = ld_pt<F>(src, i);
+    uint32_t* w = out_xy + i * 2 * F::SAT;
+    const bool inf = p.is_null();
+    if (inf) {
+        for (int k = 0; k < F::SAT; ++k) {
+            w[k] = 0;
+            w[F::SAT + k] = Cv::FqP::R(k);
+        }
+    } else {
+        p.x.to_sat(w);
+        p.y.to_sat(w + F::SAT);
+    }
+    if (out_inf) out_inf[i] = inf ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+struct Guard {
+    zk_ctx* c;
+    std::unique_lock<std::recursive_mutex> lk;
+    int prev = -1;
+    explicit Guard(zk_ctx* ctx) : c(ctx), lk(ctx->mu) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != c->device) (void)hipSetDevice(c->device);
+    }
+    ~Guard() {
+        if (prev >= 0 && prev != c->device) (void)hipSetDevice(prev);
+    }
+};
+
+inline bool curve_ok(int curve) { return curve == ZK_CURVE_BLS12_381 || curve == ZK_CURVE_BN254; }
+inline bool pow2(size_t x) { return x && !(x & (x - 1)); }
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline uint64_t blocks_of(uint64_t n, uint64_t t) { return (n + t - 1) / t; }
+
+// workspace of one opening over d1 points: [folded key: d1/2 points][a_can: d1 scalars][partials: 2 Fr per scalar-pass block]
+struct Layout {
+    size_t key = 0, a_can = 0, partials = 0, total = 0;
+};
+inline Layout layout(int curve, size_t d1) {
+    Layout l;
+    const size_t pb = msm_point_bytes(curve);
+    const size_t half = d1 / 2 ? d1 / 2 : 1;
+    const size_t n_part = blocks_of(d1 / 2 ? d1 / 2 : 1, SP_T) + 1;
+    l.key = 0;
+    l.a_can = up256(half * pb);
+    l.partials = l.a_can + up256(d1 * 32);
+    l.total = l.partials + up256(n_part * 64);
+    return l;
+}
+
+// a deferred KZG round holds the ctx's MSM buffer sets until zk_kzg_round_end
+inline bool round_open(const zk_ctx* c) { return c->pend_n != 0; }
+
+template <class Fr>
+bool fr_reduced(const uint64_t* m, Fr& out) {
+    memcpy(out.v, m, 32);
+    return Fr::reduce_once(out) == out;
+}
+
+// the NAF of a canonical scalar (8 little-endian 32-bit words)
+inline Naf make_naf(const uint32_t* k8) {
+    Naf nf;
+    memset(&nf, 0, sizeof nf);
+    nf.top = -1;
+    uint64_t k[5] = {0, 0, 0, 0, 0};
+    for (int w = 0; w < 8; ++w) k[w / 2] |= (uint64_t)k8[w] << (32 * (w & 1));
+    for (int i = 0; i < 32 * NAF_WORDS; ++i) {
+        if (!(k[0] | k[1] | k[2] | k[3] | k[4])) break;
+        if (k[0] & 1) {
+            if ((k[0] & 3) == 1) {                        // digit +1: k -= 1
+                k[0] -= 1;
+                nf.pos[i >> 5] |= 1u << (i & 31);
+            } else {                                      // digit -1: k += 1
+                for (int w = 0; w < 5; ++w)
+                    if (++k[w] != 0) break;
+                nf.neg[i >> 5] |= 1u << (i & 31);
+            }
+            nf.top = i;
+        }
+        for (int w = 0; w < 5; ++w) k[w] = (k[w] >> 1) | (w + 1 < 5 ? k[w + 1] << 63 : 0);
+    }
+    return nf;
+}
+
+template <class Cv>
+int launch_fold_key(zk_ctx* c, const void* src, void* dst, size_t m, const uint64_t* xi_mont) {
+    typedef typename Cv::Fr Fr;
+    Fr xi;
+    if (!fr_reduced<Fr>(xi_mont, xi)) return ZK_ERR_BAD_ARG;
+    const Fr k = Fr::from_mont(xi);
+    const Naf nf = make_naf(k.v);
+    ProfScope ps(c, "ipa_fold_key");
+    hipLaunchKernelGGL(ipa_fold_key<Cv>, dim3((unsigned)blocks_of(m, FOLD_T)), dim3(FOLD_T), 0, c->stream, src, dst, (uint64_t)m, nf);
+    ZK_HIP_TRY(hipGetLastError());
+    return ZK_OK;
+}
+
+template <class Cv, bool FOLD>
+int launch_scalar_pass(zk_ctx* c, void* a, void* b, size_t mo, const typename Cv::Fr& xi, const typename Cv::Fr& xi_inv, void* a_can,
+                       void* partials) {
+    const uint64_t lanes = mo > 1 ? mo / 2 : 1;
+    ProfScope ps(c, "ipa_scalar_pass");
+    hipLaunchKernelGGL((ipa_scalar_pass<Cv, FOLD>), dim3((unsigned)blocks_of(lanes, SP_T)), dim3(SP_T), 0, c->stream, a, b, (uint64_t)mo, xi,
+                       xi_inv, a_can, partials);
+    ZK_HIP_TRY(hipGetLastError());
+    return ZK_OK;
+}
+
+// host: affine out = P + k * Q (P Jacobian as the MSM returns it, Q affine Montgomery, k Montgomery Fr)
+template <class Cv>
+void add_scaled(const uint64_t* xyz, const uint64_t* q_xy, const typename Cv::Fr& k_mont, uint64_t* out_xy, uint8_t* out_inf) {
+    typedef typename Cv::Fq Fq;
+    typedef typename Cv::Fr Fr;
+    typedef XYZZ<Fq> PH;
+    constexpr int L64 = Fq::N / 2;
+    PH p;
+    Fq Z;
+    memcpy(p.x.v, xyz, 8 * L64);
+    memcpy(p.y.v, xyz + L64, 8 * L64);
+    memcpy(Z.v, xyz + 2 * L64, 8 * L64);
+    p.zz = Fq::sqr(Z);
+    p.zzz = Fq::mul(p.zz, Z);
+    Affine<Fq> q;
+    memcpy(q.x.v, q_xy, 8 * L64);
+    memcpy(q.y.v, q_xy + L64, 8 * L64);
+    const bool q_inf = q.x.is_zero() && (q.y.is_zero() || q.y == Fq::one());
+    if (!q_inf) {
+        const Fr k = Fr::from_mont(k_mont);
+        PH acc = PH::infinity();
+        for (int w = 7; w >= 0; --w)
+            for (int bit = 31; bit >= 0; --bit) {
+                acc = PH::dbl(acc);
+                if ((k.v[w] >> bit) & 1u) acc = PH::madd(acc, q);
+            }
+        p = PH::add(p, acc);
+    }
+    Affine<Fq> a;
+    if (!p.to_affine(a)) {
+        const Fq one = Fq::one();
+        memset(out_xy, 0, 8 * L64);
+        memcpy(out_xy + L64, one.v, 8 * L64);
+        if (out_inf) *out_inf = 1;
+        return;
+    }
+    memcpy(out_xy, a.x.v, 8 * L64);
+    memcpy(out_xy + L64, a.y.v, 8 * L64);
+    if (out_inf) *out_inf = 0;
+}
+
+// NULL handles, a key of another device, a key length that is not a power of two: ZK_ERR_BAD_ARG
+inline int check_key(zk_ctx* c, zk_srs* s) {
+    if (!c || !s) return ZK_ERR_BAD_ARG;
+    if (s->device != c->device || !curve_ok(s->curve) || !pow2(s->n)) return ZK_ERR_BAD_ARG;
+    return ZK_OK;
+}
+// m fits the key: round / fold j works on vectors of 2m <= d1 (first round: 2m = d1 exactly at the top, or any smaller power of two)
+inline bool m_fits(const zk_srs* s, int first_round, size_t m) {
+    if (!pow2(m)) return false;
+    return first_round ? 2 * m <= s->n : 2 * m <= s->n / 2;
+}
+
+template <class Cv>
+int round_impl(zk_ctx* c, zk_srs* s, int first_round, size_t m, void* d_a, void* d_b, void* d_work, const uint64_t* h_prime_xy,
+               uint64_t* out_lr_xy, uint8_t* out_lr_inf) {
+    typedef typename Cv::Fr Fr;
+    constexpr int L64 = Cv::Fq::N / 2;
+    const Layout ly = layout(s->curve, s->n);
+    char* w = (char*)d_work;
+    void* a_can = w + ly.a_can;
+    void* partials = w + ly.partials;
+    int rc;
+    if (first_round && (rc = launch_scalar_pass<Cv, false>(c, d_a, d_b, 2 * m, Fr::zero(), Fr::zero(), a_can, partials))) return rc;
+    // the inner products: the scalar pass's per-block partial sums (the fold before this round, or the pass above), added up here
+    const size_t nb = blocks_of(m, SP_T);
+    std::vector<uint64_t> part(nb * 8);
+    if ((rc = zk_d2h(c, part.data(), partials, nb * 64, c->stream))) return rc;
+    Fr ip1 = Fr::zero(), ip2 = Fr::zero();
+    for (size_t k = 0; k < nb; ++k) {
+        Fr x, y;
+        memcpy(x.v, &part[8 * k], 32);
+        memcpy(y.v, &part[8 * k + 4], 32);
+        ip1 = Fr::add(ip1, x);
+        ip2 = Fr::add(ip2, y);
+    }
+    uint64_t xyz_l[18], xyz_r[18];
+    const char* ac = (const char*)a_can;
+    if (first_round) {
+        if (s->pre_wstep > 1) return ZK_ERR_UNSUPPORTED;    // a window-sharded key returns partials: not an opening's MSM
+        if ((rc = zk_msm_g1_srs_partial_dev(c, s, 0, ac + 32 * m, m, xyz_l))) return rc;
+        if ((rc = zk_msm_g1_srs_partial_dev(c, s, m, ac, m, xyz_r))) return rc;
+    } else {
+        const size_t pb = msm_point_bytes(s->curve);
+        if ((rc = msm_run_dev(c, s->curve, w + ly.key, ac + 32 * m, m, xyz_l))) return rc;
+        if ((rc = msm_run_dev(c, s->curve, w + ly.key + m * pb, ac, m, xyz_r))) return rc;
+    }
+    add_scaled<Cv>(xyz_l, h_prime_xy, ip1, out_lr_xy, out_lr_inf);
+    add_scaled<Cv>(xyz_r, h_prime_xy, ip2, out_lr_xy + 2 * L64, out_lr_inf ? out_lr_inf + 1 : nullptr);
+    return ZK_OK;
+}
+
+template <class Cv>
+int fold_impl(zk_ctx* c, zk_srs* s, int first_round, size_t m, const uint64_t* xi_mont, void* d_a, void* d_b, void* d_work) {
+    typedef typename Cv::Fr Fr;
+    Fr xi;
+    if (!fr_reduced<Fr>(xi_mont, xi) || xi.is_zero()) return ZK_ERR_BAD_ARG;
+    const Fr xi_inv = Fr::inverse(xi);
+    const Layout ly = layout(s->curve, s->n);
+    char* w = (char*)d_work;
+    int rc;
+    if (first_round) {
+        std::shared_lock<std::shared_mutex> rl(s->mu);       // the registered key is read by the kernel below (queued under the lock)
+        if ((rc = launch_fold_key<Cv>(c, s->d_xy, w + ly.key, m, xi_mont))) return rc;
+    } else if ((rc = launch_fold_key<Cv>(c, w + ly.key, w + ly.key, m, xi_mont))) {
+        return rc;
+    }
+    return launch_scalar_pass<Cv, true>(c, d_a, d_b, m, xi, xi_inv, w + ly.a_can, w + ly.partials);
+}
+
+template <class Cv>
+int powers_impl(zk_ctx* c, const uint64_t* point_mont, size_t n, void* d_out) {
+    typedef typename Cv::Fr Fr;
+    Fr z;
+    if (!fr_reduced<Fr>(point_mont, z)) return ZK_ERR_BAD_ARG;
+    if (n == 0) return ZK_OK;
+    const uint64_t lanes = blocks_of(n, POW_K);
+    ProfScope ps(c, "ipa_powers");
+    hipLaunchKernelGGL(ipa_powers<Cv>, dim3((unsigned)blocks_of(lanes, 256)), dim3(256), 0, c->stream, z, (uint64_t)n, d_out);
+    ZK_HIP_TRY(hipGetLastError());
+    return ZK_OK;
+}
+
+template <class Cv>
+int check_coeffs_impl(zk_ctx* c, int curve, uint32_t log_d, const uint64_t* xis_mont, void* d_out) {
+    typedef typename Cv::Fr Fr;
+    std::vector<Fr> xi(log_d);
+    for (uint32_t j = 0; j < log_d; ++j)
+        if (!fr_reduced<Fr>(xis_mont + 4 * j, xi[j])) return ZK_ERR_BAD_ARG;
+    ProfScope ps(c, "ipa_check_coeffs");
+    hipLaunchKernelGGL(ipa_check_expand<Cv>, dim3(1), dim3(1), 0, c->stream, d_out, (uint64_t)0, Fr::one());
+    // bit (log_d - 1 - j) of k selects xi_j: xi_{log_d-1} doubles the vector first (bit 0), xi_0 last (the top bit)
+    for (uint32_t b = 0; b < log_d; ++b) {
+        const uint64_t half = (uint64_t)1 << b;
+        hipLaunchKernelGGL(ipa_check_expand<Cv>, dim3((unsigned)blocks_of(half, 256)), dim3(256), 0, c->stream, d_out, half, xi[log_d - 1 - b]);
+    }
+    ZK_HIP_TRY(hipGetLastError());
+    return fr_convert_dev(c, curve, 0, d_out, (size_t)1 << log_d, d_out);     // canonical: the MSM's scalars
+}
+
+template <class Cv>
+int to_abi(zk_ctx* c, const void* src, size_t n, void* d_out_xy, uint8_t* d_out_inf) {
+    if (n == 0) return ZK_OK;
+    hipLaunchKernelGGL(ipa_to_abi<Cv>, dim3((unsigned)blocks_of(n, 256)), dim3(256), 0, c->stream, src, (uint64_t)n, (uint32_t*)d_out_xy, d_out_inf);
+    ZK_HIP_TRY(hipGetLastError());
+    return ZK_OK;
+}
+
+template <class Cv>
+void internal_to_abi_host(const void* pt, uint64_t* out_xy, uint8_t* out_inf) {
+    typedef typename Cv::FqU F;
+    typedef typename Cv::Fq Fq;
+    constexpr int L64 = Fq::N / 2;
+    const uint32_t* w = (const uint32_t*)pt;
+    F x, y;
+    for (int k = 0; k < F::NL; ++k) {
+        x.v[k] = w[k];
+        y.v[k] = w[4 * St<F>::U4 + k];
+    }
+    const bool inf = x.limbs_zero() && y.limbs_zero();
+    if (inf) {
+        const Fq one = Fq::one();
+        memset(out_xy, 0, 8 * L64);
+        memcpy(out_xy + L64, one.v, 8 * L64);
+    } else {
+        x.to_sat((uint32_t*)out_xy);
+        y.to_sat((uint32_t*)(out_xy + L64));
+    }
+    if (out_inf) *out_inf = inf ? 1 : 0;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------------------------------ C ABI
+size_t zk_ipa_workspace_bytes(int curve_id, size_t d1) {
+    if (!curve_ok(curve_id) || !pow2(d1)) return 0;
+    return layout(curve_id, d1).total;
+}
+
+int zk_ipa_powers_dev(zk_ctx* c, int curve_id, const uint64_t* point_mont, size_t n, void* d_out) {
+    if (!c || !curve_ok(curve_id) || !point_mont || (n && !d_out)) return ZK_ERR_BAD_ARG;
+    Guard g(c);
+    return curve_id == ZK_CURVE_BLS12_381 ? powers_impl<CurveBls>(c, point_mont, n, d_out) : powers_impl<CurveBn>(c, point_mont, n, d_out);
+}
+
+int zk_ipa_round_dev(zk_ctx* c, zk_srs* key, int first_round, size_t m, const void* d_a, const void* d_b, void* d_work,
+                     const uint64_t* h_prime_xy, uint64_t* out_lr_xy, uint8_t* out_lr_inf) {
+    int rc = check_key(c, key);
+    if (rc) return rc;
+    if (!m_fits(key, first_round, m) || !d_a || !d_b || !d_work || !h_prime_xy || !out_lr_xy) return ZK_ERR_BAD_ARG;
+    Guard g(c);
+    if (round_open(c)) return ZK_ERR_PENDING;
+    void* a = const_cast<void*>(d_a);    // the first round's scalar pass reads a, b (FOLD = false writes neither)
+    void* b = const_cast<void*>(d_b);
+    return key->curve == ZK_CURVE_BLS12_381 ? round_impl<CurveBls>(c, key, first_round, m, a, b, d_work, h_prime_xy, out_lr_xy, out_lr_inf)
+                                            : round_impl<CurveBn>(c, key, first_round, m, a, b, d_work, h_prime_xy, out_lr_xy, out_lr_inf);
+}
+
+int zk_ipa_fold_dev(zk_ctx* c, zk_srs* key, int first_round, size_t m, const uint64_t* xi_mont, void* d_a, void* d_b, void* d_work) {
+    int rc = check_key(c, key);
+    if (rc) return rc;
+    if (!m_fits(key, first_round, m) || !xi_mont || !d_a || !d_b || !d_work) return ZK_ERR_BAD_ARG;
+    Guard g(c);
+    return key->curve == ZK_CURVE_BLS12_381 ? fold_impl<CurveBls>(c, key, first_round, m, xi_mont, d_a, d_b, d_work)
+                                            : fold_impl<CurveBn>(c, key, first_round, m, xi_mont, d_a, d_b, d_work);
+}
+
+int zk_ipa_final_key_dev(zk_ctx* c, int curve_id, const void* d_work, uint64_t* out_xy, uint8_t* out_inf) {
+    if (!c || !curve_ok(curve_id) || !d_work || !out_xy) return ZK_ERR_BAD_ARG;
+    Guard g(c);
+    uint64_t pt[32];
+    const size_t pb = msm_point_bytes(curve_id);
+    if (pb > sizeof pt) return ZK_ERR_UNSUPPORTED;
+    int rc = zk_d2h(c, pt, d_work, pb, c->stream);
+    if (rc) return rc;
+    if (curve_id == ZK_CURVE_BLS12_381) internal_to_abi_host<CurveBls>(pt, out_xy, out_inf);
+    else internal_to_abi_host<CurveBn>(pt, out_xy, out_inf);
+    return ZK_OK;
+}
+
+int zk_ipa_fold_key_dev(zk_ctx* c, int curve_id, size_t m, const void* d_key_xy, const uint8_t* d_key_inf, const uint64_t* xi_mont,
+                        void* d_out_xy, uint8_t* d_out_inf) {
+    if (!c || !curve_ok(curve_id) || !xi_mont || (m && (!d_key_xy || !d_out_xy))) return ZK_ERR_BAD_ARG;
+    Guard g(c);
+    if (m == 0) return ZK_OK;
+    const size_t pb = msm_point_bytes(curve_id);
+    void* tmp = nullptr;
+    if (hipMalloc(&tmp, 3 * m * pb) != hipSuccess) return ZK_ERR_OOM;
+    void* folded = (char*)tmp + 2 * m * pb;
+    int rc = msm_convert_bases_dev(c, curve_id, d_key_xy, d_key_inf, 2 * m, tmp);
+    if (!rc) rc = curve_id == ZK_CURVE_BLS12_381 ? launch_fold_key<CurveBls>(c, tmp, folded, m, xi_mont)
+                                                 : launch_fold_key<CurveBn>(c, tmp, folded, m, xi_mont);
+    if (!rc) rc = curve_id == ZK_CURVE_BLS12_381 ? to_abi<CurveBls>(c, folded, m, d_out_xy, d_out_inf) : to_abi<CurveBn>(c, folded, m, d_out_xy, d_out_inf);
+    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ZK_ERR_HIP;
+    (void)hipFree(tmp);
+    return rc;
+}
+
+int zk_ipa_check_coeffs_dev(zk_ctx* c, int curve_id, uint32_t log_d, const uint64_t* xis_mont, void* d_out) {
+    if (!c || !curve_ok(curve_id) || log_d > 32 || !d_out || (log_d && !xis_mont)) return ZK_ERR_BAD_ARG;
+    Guard g(c);
+    return curve_id == ZK_CURVE_BLS12_381 ? check_coeffs_impl<CurveBls>(c, curve_id, log_d, xis_mont, d_out)
+                                          : check_coeffs_impl<CurveBn>(c, curve_id, log_d, xis_mont, d_out);
+}

@@ -529,6 +529,40 @@ typedef struct zk_proof {
 size_t zk_proof_serialized_size(int curve_id, uint32_t n_custom_evals, const uint32_t* label_lens);
 int zk_proof_serialize(int curve_id, const zk_proof* proof, uint8_t* out, size_t cap, size_t* written);
 
+/* ---- inner-product-argument commitment (IPA) -------------------------------------------------------------------------------- */
+/* The reference's second HomomorphicCommitment (plonk-core/src/commitment.rs:50-91: ark-poly-commit 0.3 ipa_pc::InnerProductArgPC),
+ * without hiding and degree bounds, as ark-plonk uses it (prover.rs:582-618).  The committer key is a zk_srs of d1 = d + 1 = 2^k
+ * points (comm_key; zk_ipa_* refuse another length with ZK_ERR_BAD_ARG); commit and the verifier's final-key MSM are the zk_msm_g1_srs*
+ * calls over it.  An opening is driven round by round by the caller, who derives every challenge (the transcript is not part of this
+ * ABI): for m = d1/2, d1/4, ..., 1
+ *     zk_ipa_round_dev(first_round = (m == d1/2), m)  -> L, R      then    zk_ipa_fold_dev(first_round, m, xi)
+ * The state lives in the caller's device buffers: a (the combined polynomial's Montgomery coefficients, zero-padded to d1), b (the
+ * powers of the point, zk_ipa_powers_dev) and a workspace of zk_ipa_workspace_bytes (the folded key in the MSM's internal base layout,
+ * the canonical copy of a the round MSMs read, the inner-product partial sums the fold leaves for the next round): a round that is not
+ * the first reads what the fold before it left there.  Between these calls any other call on the ctx is allowed.  While a deferred KZG
+ * round is open on the ctx (zk_kzg_round_pending) zk_ipa_round_dev -- which runs MSMs -- returns ZK_ERR_PENDING. */
+/* device bytes one opening over d1 = 2^k points needs (0 for an unknown curve or a d1 that is not a power of two) */
+size_t zk_ipa_workspace_bytes(int curve_id, size_t d1);
+/* d_out[i] = point^i, i < n (Montgomery Fr, device) */
+int zk_ipa_powers_dev(zk_ctx* ctx, int curve_id, const uint64_t* point_mont, size_t n, void* d_out);
+/* One round on vectors of length 2m: L = MSM(key_l, a_r) + <a_r, b_l> h', R = MSM(key_r, a_l) + <a_l, b_r> h', affine Montgomery
+ * (out_lr_xy: L then R, 2 x 2L limbs; out_lr_inf: 2 flags, may be NULL).  The key is key[0 .. 2m) in the first round (the SRS
+ * table path) and the folded key in d_work afterwards (first_round = 0: 2m <= d1 / 2).  h_prime_xy: affine Montgomery (2L limbs). */
+int zk_ipa_round_dev(zk_ctx* ctx, zk_srs* key, int first_round, size_t m, const void* d_a, const void* d_b, void* d_work,
+                     const uint64_t* h_prime_xy, uint64_t* out_lr_xy, uint8_t* out_lr_inf);
+/* a <- a_l + xi^-1 a_r, b <- b_l + xi b_r (in place, to length m); key <- key_l + xi key_r into d_work.  xi: Montgomery, non-zero.
+ * Queued on the ctx stream. */
+int zk_ipa_fold_dev(zk_ctx* ctx, zk_srs* key, int first_round, size_t m, const uint64_t* xi_mont, void* d_a, void* d_b, void* d_work);
+/* after the last fold: final_comm_key = the one folded point in d_work (affine Montgomery); the caller reads c = a[0] itself */
+int zk_ipa_final_key_dev(zk_ctx* ctx, int curve_id, const void* d_work, uint64_t* out_xy, uint8_t* out_inf);
+/* one key fold on its own: out[i] = key[i] + xi key[i + m], i < m; ABI affine layout in and out (d_key_inf, d_out_inf: device flags,
+ * may be NULL).  Blocks until the result is written. */
+int zk_ipa_fold_key_dev(zk_ctx* ctx, int curve_id, size_t m, const void* d_key_xy, const uint8_t* d_key_inf, const uint64_t* xi_mont,
+                        void* d_out_xy, uint8_t* d_out_inf);
+/* s_k of the check polynomial s(X) = prod_j (1 + xi_j X^(2^(log_d - 1 - j))), k < 2^log_d: canonical Fr on the device, the scalars of
+ * the verifier's final-key MSM (xis_mont: log_d Montgomery challenges, xi_0 first; log_d <= 32) */
+int zk_ipa_check_coeffs_dev(zk_ctx* ctx, int curve_id, uint32_t log_d, const uint64_t* xis_mont, void* d_out);
+
 /* ---- device self-test ------------------------------------------------------------------------------ */
 /* Runs the quad-cooperative point arithmetic of the bucket-reduction kernels (csrc/ecq.cuh) against the
  * single-lane group law on n_quads point pairs incl. doubling, cancellation and infinity cases.

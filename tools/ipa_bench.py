@@ -1,0 +1,166 @@
+"""Timings of the inner-product-argument commitment (ark_plonk_amd/ipa.py) on one GPU: commit, open and check at n = 2^16, 2^18, 2^20
+(d + 1 = 2n, as ark-plonk trims the key), both curves, with a per-phase split of the open (key fold, scalar pass, round MSMs + host
+work) from the ctx's event profile, and the fold's rate in group operations per second.  With --proof-shaped, also the two openings of
+one proof (prover.rs:582-618: 11 polynomials at z, 7 at z * omega) at n = 2^18.  Prints one JSON line per configuration; --out writes
+them to a file.  Kernel times for the record come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
+
+    python tools/ipa_bench.py [--log-n 16 18 20] [--curves 0 1] [--reps 3] [--warmup 1] [--proof-shaped] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def make_key(ctx, cid, d1, seed):
+    import torch
+    import ark_plonk_amd as zk
+    from ark_plonk_amd import _lib
+    from ark_plonk_amd.ipa import IpaCommitterKey
+    cv = zk.get_curve(cid)
+    rng = np.random.default_rng(seed)
+    sc = rng.integers(0, 1 << 62, size=(d1 + 1, 4), dtype=np.uint64)
+    d_sc = torch.from_numpy(sc.view(np.int64)).cuda()
+    pts = torch.empty((d1 + 1, 2 * cv.fq_limbs), dtype=torch.int64, device="cuda")
+    ctx.use_torch_stream()
+    _lib.check(_lib.lib().zk_g1_fixed_base_batch_dev(ctx.handle, cid, d_sc.data_ptr(), d1 + 1, pts.data_ptr()))
+    host = pts.cpu().numpy().view(np.uint64)
+    h = tuple(zk.curves.fq_from_mont(cid, host[d1].reshape(2, -1)))
+    return IpaCommitterKey(host[:d1].copy(), h, cv, ctx).precompute()
+
+
+def timed(fn):
+    import torch
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t, out
+
+
+def naf_weight(x: int) -> int:
+    w = 0
+    while x:
+        if x & 1:
+            x -= 2 - (x & 3)
+            w += 1
+        x >>= 1
+    return w
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log-n", type=int, nargs="+", default=[16, 18, 20])
+    ap.add_argument("--curves", type=int, nargs="+", default=[0, 1])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--proof-shaped", action="store_true")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import torch
+    import ark_plonk_amd as zk
+    ctx = zk.Context(0)
+    lines = []
+    for cid in a.curves:
+        cv = zk.get_curve(cid)
+        for lg in a.log_n:
+            n = 1 << lg
+            d1 = 2 * n
+            ck = make_key(ctx, cid, d1, lg)
+            rng = np.random.default_rng(lg + 7)
+            polys = [zk.curves.fr_to_mont(cid, [int(x) for x in rng.integers(1, 1 << 62, size=n)]) for _ in range(2)]
+            d_polys = [torch.from_numpy(p.view(np.int64)).cuda() for p in polys]
+            z, chi = 0x1234567 + lg, 0x89ABCDE + lg
+            values = [zk.curves.fr_from_mont(cid, _eval(ctx, cid, p, z))[0] for p in d_polys]
+            for _ in range(a.warmup):
+                comms = ck.commit(d_polys)
+                proof = ck.open(d_polys, comms, z, chi)
+                assert ck.check(comms, z, values, proof, chi)
+            t_commit, t_open, t_check = [], [], []
+            prof = {"ipa_fold_key": 0.0, "ipa_scalar_pass": 0.0}
+            for _ in range(a.reps):
+                t, comms = timed(lambda: ck.commit(d_polys))
+                t_commit.append(t / len(d_polys))
+                ctx.profile(True)
+                ctx.profile_reset()
+                t, proof = timed(lambda: ck.open(d_polys, comms, z, chi))
+                for k in prof:
+                    prof[k] += ctx.profile_get(k)[0] / a.reps
+                ctx.profile(False)
+                t_open.append(t)
+                t, ok = timed(lambda: ck.check(comms, z, values, proof, chi))
+                assert ok
+                t_check.append(t)
+            # group operations of the folds of one opening: every folded point takes (NAF length - 1) doublings, (NAF weight - 1) mixed
+            # additions of +-k_r and one of k_l; the challenges are the proof's own (recomputed by the check's transcript)
+            from ark_plonk_amd.ipa import transcript_hash
+            xi = transcript_hash(cid, "blake2b", [("g1", ck._msm_host(comms, [1, chi])), ("fr", z),
+                                                  ("fr", sum(v * pow(chi, k, cv.r) for k, v in enumerate(values)) % cv.r)])
+            ops, m = 0, d1 // 2
+            for Lp, Rp in zip(proof.l_vec, proof.r_vec):
+                xi = transcript_hash(cid, "blake2b", [("fr", xi), ("g1", Lp), ("g1", Rp)])
+                ops += m * (xi.bit_length() - 1 + naf_weight(xi))
+                m //= 2
+            t_open_med = float(np.median(t_open))
+            fold_s = prof["ipa_fold_key"] / 1e3
+            line = {"curve": cv.name, "log_n": lg, "d1": d1, "commit_s": float(np.median(t_commit)), "open_s": t_open_med,
+                    "check_s": float(np.median(t_check)), "open_fold_key_s": fold_s, "open_scalar_pass_s": prof["ipa_scalar_pass"] / 1e3,
+                    "open_msm_and_host_s": t_open_med - fold_s - prof["ipa_scalar_pass"] / 1e3, "fold_group_ops": ops,
+                    "fold_gops_per_s": ops / fold_s / 1e9 if fold_s else None, "reps": a.reps}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            if a.proof_shaped and lg == 18:
+                omega = _omega(cid, lg)
+                sets = []
+                for k, (cnt, pt) in enumerate(((11, z), (7, z * omega % cv.r))):
+                    ps = [torch.from_numpy(zk.curves.fr_to_mont(cid, [int(x) for x in rng.integers(1, 1 << 62, size=n)]).view(np.int64)).cuda()
+                          for _ in range(cnt)]
+                    sets.append((ps, ck.commit(ps), pt))
+                for ps, cm, pt in sets:        # warm-up
+                    ck.open(ps, cm, pt, chi)
+                t, _ = timed(lambda: [ck.open(ps, cm, pt, chi) for ps, cm, pt in sets])
+                line = {"curve": cv.name, "log_n": lg, "proof_shaped_openings_s": t,
+                        "note": "opening-only: 11 polys at z + 7 at z*omega; the reference publishes 35.1 s per whole 2^18 IPA proof"}
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+            ck.close()
+    if a.out:
+        with open(a.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+    ctx.close()
+
+
+def _eval(ctx, cid, p, z):
+    import ctypes
+    import ark_plonk_amd as zk
+    from ark_plonk_amd import _lib
+    out = np.zeros((1, 4), dtype=np.uint64)
+    zm = zk.curves.fr_to_mont(cid, [z])
+    ptrs = (ctypes.c_void_p * 1)(p.data_ptr())
+    lens = (ctypes.c_size_t * 1)(p.shape[0])
+    ctx.use_torch_stream()
+    _lib.check(_lib.lib().zk_poly_evaluate_dev(ctx.handle, cid, 1, ptrs, lens, zm.ctypes.data, out.ctypes.data))
+    return out
+
+
+def _omega(cid, lg):
+    import ctypes
+    import ark_plonk_amd as zk
+    from ark_plonk_amd import _lib
+    info = _lib.DomainInfo()
+    _lib.check(_lib.lib().zk_domain_new(cid, 1 << lg, ctypes.byref(info)))
+    return zk.curves.fr_from_mont(cid, np.array(info.group_gen, dtype=np.uint64).reshape(1, 4))[0]
+
+
+if __name__ == "__main__":
+    main()
