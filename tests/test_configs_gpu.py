@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import ark_plonk_amd as zk
+import large_ref as lr
 from conftest import assert_is_scalar_times_g, srs_from_powers, sum_scalar_times_powers, tau_powers
 from oracle import bigint_oracle as bo
 
@@ -24,6 +25,13 @@ def _rand_scalars(n, seed, bits62=61):
     return s
 
 
+def _full_range_scalars(cid, n, seed):
+    """Scalars uniform over [0, r), the first 4096 in [r - 2^64, r): bits 253 and 254 and the top window's upper digits in use."""
+    s = lr.full_range(cid, n, seed)
+    s[:4096] = lr.near_r(cid, 4096, seed + 1)
+    return s
+
+
 def test_config3_msm_2_22_table_plain_and_8_shards(ctx, oracle_cpu):
     import torch
     cid, log_n = 0, 22
@@ -33,13 +41,20 @@ def test_config3_msm_2_22_table_plain_and_8_shards(ctx, oracle_cpu):
     scal = _rand_scalars(n, 22)
     k = sum_scalar_times_powers(oracle_cpu, cid, scal, pw_m)
     d_s = torch.from_numpy(scal.view(np.int64)).cuda()
+    full = _full_range_scalars(cid, n, 0x3F22)
+    k_full = sum_scalar_times_powers(oracle_cpu, cid, full, pw_m)
+    d_full = torch.from_numpy(full.view(np.int64)).cuda()
     ck = zk.CommitterKey(bases, cid, ctx)
     plain = ck.msm(d_s)                                   # per-window path
     assert_is_scalar_times_g(plain, k, cid)
+    plain_full = ck.msm(d_full)
+    assert_is_scalar_times_g(plain_full, k_full, cid)
     ck.precompute()
     tab = ck.msm(d_s)                                     # window-table path (8 GiB table)
     assert tab == plain
+    assert ck.msm(d_full) == plain_full
     ck.close()
+    del d_full
     # 8 point shards, as 8 ranks would hold them: every shard its own SRS slice + table, partial over its scalar slice
     G = 8
     parts = []
@@ -94,10 +109,28 @@ def test_config4_bn254_table_msm_2_18(ctx, oracle_cpu):
     bases = srs_from_powers(ctx, cid, pw_c)
     scal = _rand_scalars(n, 418, bits62=59)
     k = sum_scalar_times_powers(oracle_cpu, cid, scal, pw_m)
+    full = _full_range_scalars(cid, n, 0x3F18)
+    k_full = sum_scalar_times_powers(oracle_cpu, cid, full, pw_m)
     ck = zk.CommitterKey(bases, cid, ctx).precompute()
     got = ck.msm(torch.from_numpy(scal.view(np.int64)).cuda())
+    got_full = ck.msm(torch.from_numpy(full.view(np.int64)).cuda())
     ck.close()
     assert_is_scalar_times_g(got, k, cid)
+    assert_is_scalar_times_g(got_full, k_full, cid)
+
+
+def test_table_msm_full_range_scalars_2_20(ctx, oracle_cpu):
+    """BLS12-381, 2^20 points on the window-table path (default window), scalars over the whole of [0, r)."""
+    import torch
+    cid, n = 0, 1 << 20
+    pw_c, pw_m = tau_powers(oracle_cpu, cid, n)
+    bases = srs_from_powers(ctx, cid, pw_c)
+    full = _full_range_scalars(cid, n, 0x3F20)
+    k_full = sum_scalar_times_powers(oracle_cpu, cid, full, pw_m)
+    ck = zk.CommitterKey(bases, cid, ctx).precompute()
+    got = ck.msm(torch.from_numpy(full.view(np.int64)).cuda())
+    ck.close()
+    assert_is_scalar_times_g(got, k_full, cid)
 
 
 def test_config5_poseidon_size_point_2_25(ctx, oracle_cpu):
@@ -250,11 +283,12 @@ def test_table_window_20_identity_2_20(ctx, oracle_cpu):
 
 
 # ---- size edges: what a caller gets at the first sizes the round-3 library refused
-def test_ntt_four_passes_2_28(ctx):
+def test_ntt_four_passes_2_28(ctx, oracle_cpu):
     """log N = 28 needs a fourth pass (three passes end at 2^27).  The reference admits any domain up to the field's two-adicity
     (prover.rs:169-173, error.rs:14-21).  Checked against the three-pass transform (itself checked against the CPU restatement):
     the 2^28-point fft of 2^20 coefficients, read at every 256th point, IS their 2^20-point fft -- e[256 k] = sum_j a_j
-    w_{2^28}^(256 k j) = sum_j a_j w_{2^20}^(k j) -- and likewise on the coset; then full-length round trips of all four kinds
+    w_{2^28}^(256 k j) = sum_j a_j w_{2^20}^(k j) -- and likewise on the coset; the classes 256 k + t, t != 0, against the CPU
+    restatement through the same identity with twisted coefficients; then full-length round trips of all four kinds
     (8 GiB per vector, in place)."""
     import torch
     cid = 0
@@ -267,6 +301,16 @@ def test_ntt_four_passes_2_28(ctx):
         small = getattr(d20, name)(a)
         assert big.shape[0] == 1 << 28 and torch.equal(big[::256], small), name
         del big, small
+    # four residue classes besides t = 0: e[256 k + t] = [coset_]fft_{2^20}(f_j w_{2^28}^(t j))_k, on full-range coefficients, each
+    # class against one 2^20-point transform of the CPU restatement
+    f = lr.full_range(cid, 1 << 20, 0x2828)
+    d_f = torch.from_numpy(f.view(np.int64)).cuda()
+    for kind, name in ((0, "fft"), (2, "coset_fft")):
+        big = getattr(d28, name)(d_f)
+        for t in (1, 128, 255, int(np.random.default_rng(28 + kind).integers(2, 255))):
+            got = big[t::256].cpu().numpy().view(np.uint64)
+            assert np.array_equal(got, lr.decimated(oracle_cpu, cid, kind, 28, 20, f, t)), (name, t)
+        del big
     x = torch.randint(0, 1 << 62, (1 << 28, 4), dtype=torch.int64, device="cuda", generator=g)
     y = x.clone()
     d28.fft_in_place(y)

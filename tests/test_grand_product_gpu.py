@@ -61,7 +61,8 @@ def test_lookup_golden(cid, log_n, ctx):
 @pytest.mark.parametrize("cid", [0, 1])
 @pytest.mark.parametrize("log_n", [0, 1, 7, 11, 13])
 def test_vs_bigint_oracle(cid, log_n, ctx):
-    """Sizes below, at and above one scan chunk (64) and one term tile (2048); n = 1 and 2 included."""
+    """n = 1 and 2, less than one 256-position wavefront tile (2^7), and 8 and 32 tiles (2^11, 2^13): at most one tile per lane of the
+    1024-lane tile-total scan.  Several tiles per lane (n > 2^18) are checked row by row in test_large_grand_product_gpu.py."""
     cv = bo.CURVES[cid]
     n = 1 << log_n
     cols = [bo.seeded_scalars(cv, 0x700 + 16 * log_n + k, n) for k in range(8)]
