@@ -23,13 +23,15 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 
 FIELD_HDRS = ["field.cuh", "fieldu.cuh", "fields.cuh", "curve_params.h", "zk_common.h"]
 HOST_HDRS = FIELD_HDRS + ["ec.cuh", "ecu.cuh", "ctx.h", "../../include/ark_plonk_amd.h"]
+API_HDRS = HOST_HDRS + ["api_internal.h"]
+# the C ABI, one unit per subsystem (api_internal.h is what they share)
+API_UNITS = ("api_ctx", "residency", "srs", "commit", "round", "api_host", "api_poly")
 MSM_UNITS = ("msm_accumulate", "msm_reduce", "msm_sort", "msm_plan")      # heaviest first
 
 
 def jobs():
     """(object name, source, extra defines, header deps)"""
-    out = [
-        ("api.o", "api.hip", [], HOST_HDRS),
+    out = [(f"{u}.o", f"{u}.hip", [], API_HDRS) for u in API_UNITS] + [
         ("hostio.o", "hostio.hip", [], HOST_HDRS),
         ("wire.o", "wire.hip", [], HOST_HDRS),
         ("kzg.o", "kzg.hip", [], HOST_HDRS + ["fr_io.cuh"]),
@@ -41,7 +43,7 @@ def jobs():
         ("ntt_pass_table.o", "ntt_pass_table.hip", [], []),
         ("msm_dispatch.o", "msm_dispatch.hip", [], HOST_HDRS),
         # the inner-product-argument commitment (csrc_ipa/): a directory of its own, so that csrc/ keeps its kernel build
-        ("ipa.o", "../csrc_ipa/ipa.hip", [], HOST_HDRS),
+        ("ipa.o", "../csrc_ipa/ipa.hip", [], API_HDRS),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)
@@ -52,6 +54,32 @@ def jobs():
             out.append((f"ntt_pass_c{c}_s{s}.o", "ntt_pass_inst.hip", [f"-DZK_CURVE_SEL={c}", f"-DZK_NTT_S={s}"],
                         FIELD_HDRS + ["ntt_pass.cuh"]))
     return out
+
+
+# What a committed counter file (profiles/pmc_*.json) describes: (source, defines) of the units that hold its kernels, in hash order
+PMC_UNITS = {
+    "pmc_msm_accumulate.json": [("msm_accumulate.hip", ["-DZK_CURVE_SEL=0"])],
+    "pmc_ntt.json": [("ntt.hip", [])] + [("ntt_pass_inst.hip", ["-DZK_CURVE_SEL=0", f"-DZK_NTT_S={s}"]) for s in range(3, 10)],
+}
+
+
+def device_asm(src: str, defs=(), timeout: float = 900) -> str:
+    """gfx950 assembly of one unit's device code as the library build compiles it.  `__hip_cuid_<hex>` hashes the command line and
+    the path, so it is replaced by a fixed token; nothing else in the text depends on where or when it was compiled."""
+    import re
+    cmd = [HIPCC] + FLAGS + list(defs) + ["--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", "-"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed: " + " ".join(cmd) + "\n" + r.stderr[-4000:])
+    return re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", r.stdout)
+
+
+def device_code_sha256(units, workers: int = 8) -> str:
+    """sha256 over the device assembly of `units` ((source, defines) pairs), concatenated in the order given"""
+    import hashlib
+    with ThreadPoolExecutor(max_workers=workers) as ex:
+        texts = list(ex.map(lambda u: device_asm(*u), units))
+    return hashlib.sha256("".join(texts).encode()).hexdigest()
 
 
 def _stale(target: str, deps) -> bool:

@@ -46,6 +46,31 @@ struct CurveBn {
     static constexpr int ID = ZK_CURVE_BN254;
 };
 
+// The one place the curve id is dispatched: f(CurveBls{}) / f(CurveBn{}), or `unknown` for an id the library does not know.
+// f is a generic lambda that names the curve as decltype(cv) and calls the host function templates (ntt_run<Cv>, ...) with it:
+// the lambda's own type must never become a template argument of a kernel or a device function (that would rename the kernel).
+// The return types of the helper and of the lambdas are deduced on purpose (so `unknown` has exactly the lambda's return type): the
+// compiler then instantiates both curves' calls where the dispatch is written, Bls before Bn, and the kernels of a unit keep their
+// order in its code object.
+template <class R, class F>
+inline auto zk_on_curve(int curve, R unknown, F&& f) {
+    if (curve == ZK_CURVE_BLS12_381) return f(CurveBls{});
+    if (curve == ZK_CURVE_BN254) return f(CurveBn{});
+    return unknown;
+}
+inline bool zk_curve_ok(int curve) {
+    return zk_on_curve(curve, false, [](auto) { return true; });
+}
+// 64-bit limbs of a base-field element in the arkworks layout (0: unknown curve)
+inline int fq_limbs64(int curve) {
+    return zk_on_curve(curve, 0, [](auto cv) { return (int)decltype(cv)::Fq::N / 2; });
+}
+
+// The kernels behind a prover round take up to 16 jobs (msm_common.cuh), so a batch, a round and every per-job array hold that many
+constexpr int ZK_MAX_JOBS = 16;
+// the widest point in 64-bit limbs (BLS12-381: 6 per coordinate): sizes of host arrays that hold either curve's points
+constexpr int ZK_MAX_FQ64 = 6, ZK_MAX_AFFINE64 = 2 * ZK_MAX_FQ64, ZK_MAX_JACOBIAN64 = 3 * ZK_MAX_FQ64;
+
 #define ZK_HIP_TRY(expr)                                  \
     do {                                                  \
         hipError_t _e = (expr);                           \
@@ -274,101 +299,122 @@ struct zk_ctx {
     DevBuf coset_inv_pow[2];                     // per curve: g^-j
     size_t coset_len[2] = {0, 0};
     size_t coset_inv_len[2] = {0, 0};
-    DevBuf io_a, io_b;                           // staging for the host-buffer entry points
 
-    // MSM state: mb[0] is the working set of a single MSM; a batch (<= 16 jobs) gives every job its own
+    // MSM state: mb[0] is the working set of a single MSM; a batch (<= ZK_MAX_JOBS jobs) gives every job its own
     // set so that the jobs' bucket reductions can run as one fused launch
-    MsmBufs mb[16];
-    hipEvent_t ev_job[16] = {};
-    void* pinned = nullptr;      // virtual-window sums of up to 16 batched MSMs land here
+    MsmBufs mb[ZK_MAX_JOBS];
+    hipEvent_t ev_job[ZK_MAX_JOBS] = {};
+    void* pinned = nullptr;      // virtual-window sums of up to ZK_MAX_JOBS batched MSMs land here
     size_t pinned_cap = 0;
     void* pinned_small = nullptr;   // 4 KiB: digests of the commitment cache
     DevBuf msm_tmp;       // infinity flags staging (SRS registration)
     DevBuf stage_shared;  // the partition sort's staging area for jobs too large to own one (msm plan: shared_stage): the jobs of a round
                           // are then placed one after the other instead of by one launch per kernel
     DevBuf witness;       // the witness polynomial of zk_kzg_open*: read by the digit kernel of its MSM in stream order, so one per ctx
-    uint64_t round_flushes = 0;   // times the memory budget closed the queued jobs of a round early (zk_round_mem_stats)
 
     // host-pointer entry points (the drop-in boundary): pinned staging ring + a copy stream so that the upload of
-    // polynomial k+1 runs under the MSM of polynomial k (hostio.hip)
-    hipStream_t copy_stream = nullptr;
-    static constexpr int STAGE_SLOTS = 4;
-    static constexpr size_t STAGE_BYTES = (size_t)8 << 20;
-    void* stage_pin[STAGE_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t stage_ev[STAGE_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-    bool stage_busy[STAGE_SLOTS] = {false, false, false, false};
-    int stage_next = 0;
-    hipEvent_t ev_up[16] = {};     // "input of job k is on the device" (copy stream -> main stream)
-    uint64_t h2d_bytes = 0, d2h_bytes = 0;   // PCIe volume of the host-pointer entry points (zk_io_stats)
-    int staging_mode = 0;                     // 0 = plain hipMemcpyAsync from the caller's (pageable) buffer: measured 56 GB/s on the MI355X
-                                              // hosts, the same as pinned memory (tools/pcie_probe.py); 1 = the ctx's pinned staging ring (49 GB/s)
+    // polynomial k+1 runs under the MSM of polynomial k (hostio.hip, api_host.hip)
+    struct HostIo {
+        DevBuf a, b;                              // staging for the host-buffer entry points
+        hipStream_t copy_stream = nullptr;
+        static constexpr int STAGE_SLOTS = 4;
+        static constexpr size_t STAGE_BYTES = (size_t)8 << 20;
+        void* stage_pin[STAGE_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+        hipEvent_t stage_ev[STAGE_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+        bool stage_busy[STAGE_SLOTS] = {false, false, false, false};
+        int stage_next = 0;
+        hipEvent_t ev_up[ZK_MAX_JOBS] = {};  // "input of job k is on the device" (copy stream -> main stream)
+        uint64_t h2d_bytes = 0, d2h_bytes = 0;   // PCIe volume of the host-pointer entry points (zk_io_stats)
+        int staging_mode = 0;                     // 0 = plain hipMemcpyAsync from the caller's (pageable) buffer: measured 56 GB/s on the MI355X
+                                                  // hosts, the same as pinned memory (tools/pcie_probe.py); 1 = the ctx's pinned staging ring (49 GB/s)
+    } io;
 
     // N3: opt-in content-addressed commitment cache -- key = (srs id, input kind, length, 256-bit
-    // digest of the coefficient vector computed on the device); value = the affine commitment
-    struct CommitEntry {
-        uint64_t srs_id;
-        uint64_t n;
-        uint32_t kind;
-        uint64_t dig[4];
-        uint64_t xy[12];
-        uint8_t inf;
-    };
-    bool commit_cache_on = false;
-    size_t commit_cache_cap = 64;
-    std::list<CommitEntry> commit_cache;      // most recently used first
-    uint64_t cache_hits = 0, cache_misses = 0;
-    DevBuf digest_dev;                        // 16 jobs x 4 u64
-    uint64_t digest_key[4] = {0, 0, 0, 0};    // zk_process_key mixed with the ctx's address: keys the device digests of this cache
+    // digest of the coefficient vector computed on the device); value = the affine commitment (commit.hip)
+    struct CommitCache {
+        struct Entry {
+            uint64_t srs_id;
+            uint64_t n;
+            uint32_t kind;
+            uint64_t dig[4];
+            uint64_t xy[ZK_MAX_AFFINE64];
+            uint8_t inf;
+        };
+        bool on = false;
+        size_t cap = 64;
+        std::list<Entry> entries;                 // most recently used first
+        uint64_t hits = 0, misses = 0;
+        DevBuf digest_dev;                        // ZK_MAX_JOBS jobs x 4 u64
+        uint64_t digest_key[4] = {0, 0, 0, 0};    // zk_process_key mixed with the ctx's address: keys the device digests of this cache
+    } ccache;
 
     // Residency cache of the HOST-POINTER entry points (zk_ctx_set_residency_cache; opt-in): device copies of vectors this ctx
-    // produced (zk_ntt outputs of at most res_max_vec bytes) or uploaded, keyed by (bytes, keyed 256-bit digest of the HOST bytes).
+    // produced (zk_ntt outputs of at most max_vec bytes) or uploaded, keyed by (bytes, keyed 256-bit digest of the HOST bytes).
     // A later zk_ntt / zk_kzg_commit_batch / zk_kzg_open input with the same bytes uses the copy instead of crossing PCIe again
-    // (prover.rs:196-213: an `ifft` output goes straight back up as a `commit` input, then into `coset_fft`, `open`, ...).
-    struct ResEntry {
-        size_t bytes = 0;
-        uint64_t dig[4] = {0, 0, 0, 0};
-        bool valid = false;          // dig names the buffer's contents (false while an output is still being produced)
-        uint64_t epoch = 0;          // the call that last used it: entries of the running call are never evicted
-        uint64_t born = 0;           // the call that created it: until that call returns its bytes may still be on their way up
-        DevBuf buf;
-    };
-    bool res_on = false;
-    size_t res_cap = (size_t)2 << 30, res_max_vec = (size_t)64 << 20, res_bytes = 0;
-    std::list<ResEntry> res;         // most recently used first
-    std::vector<DevBuf> res_free;    // buffers of evicted entries, reused before anything is allocated
-    uint64_t res_epoch = 0, res_hits = 0, res_misses = 0;
-    // option "cache_verify": every hit of the commitment / residency cache is checked against the real thing (the MSM recomputed, the
-    // resident bytes compared with the caller's); a mismatch is counted and the computed / uploaded value used (zk_cache_verify_stats)
+    // (prover.rs:196-213: an `ifft` output goes straight back up as a `commit` input, then into `coset_fft`, `open`, ...).  residency.hip
+    struct Residency {
+        struct Entry {
+            size_t bytes = 0;
+            uint64_t dig[4] = {0, 0, 0, 0};
+            bool valid = false;          // dig names the buffer's contents (false while an output is still being produced)
+            uint64_t epoch = 0;          // the call that last used it: entries of the running call are never evicted
+            uint64_t born = 0;           // the call that created it: until that call returns its bytes may still be on their way up
+            DevBuf buf;
+        };
+        bool on = false;
+        size_t cap = (size_t)2 << 30, max_vec = (size_t)64 << 20, bytes = 0;
+        std::list<Entry> entries;        // most recently used first
+        std::vector<DevBuf> free_bufs;   // buffers of evicted entries, reused before anything is allocated
+        uint64_t epoch = 0, hits = 0, misses = 0;
+        std::vector<unsigned char> verify_host;
+    } res;
+    // Both caches.  Option "cache_verify": every hit of the commitment / residency cache is checked against the real thing (the MSM
+    // recomputed, the resident bytes compared with the caller's); a mismatch is counted and the computed / uploaded value used
+    // (zk_cache_verify_stats)
     bool cache_verify = false;
     bool key_from_os = false;          // zk_process_key delivered OS entropy when the ctx was created: the caches may be switched on
     uint64_t verify_checked = 0, verify_mismatch = 0;
-    std::vector<unsigned char> verify_host;
 
     // open round (zk_kzg_round_begin_dev / zk_kzg_open_begin_dev ... zk_kzg_round_end): jobs whose sort + accumulate are queued
     // on the stream and whose reduction waits for the round to close, in submission order.  Job k lives in buffer set mb[k].
-    struct PendingJob {
-        size_t n = 0;
-        bool queued = false;        // false: computed at begin (no table / short vector / commitment cache) -- result below
-        bool have_xyz = false;
-        uint64_t xyz[18] = {};
-        uint64_t xy[12] = {};
-        uint8_t inf = 0;
-    };
-    uint32_t pend_n = 0;
-    bool pend_reduced = false;      // zk_kzg_round_reduce ran: the round takes no further jobs, zk_kzg_round_end only waits
-    void* pend_partials = nullptr;  // ... as zk_kzg_round_reduce_winsums_dev: the jobs' virtual-window sums are (being) written there, on the device
-    void* pinned_jobs = nullptr;    // 16 x 512 B pinned: partials of jobs computed at submission, on their way to the device (async copies)
-    hipEvent_t round_ev = nullptr;  // recorded behind the reduction kernels of a round (msm_batch_pre_reduce)
-    uint32_t round_reduced = 0;     // jobs whose reductions are queued behind round_ev (0: none)
-    zk_srs* pend_srs = nullptr;
-    PendingJob pend[16];
+    // Written by round.hip; the MSM plan records `ev` / `n_reduced` behind a round's reduction kernels and counts `flushes`.
+    struct Round {
+        struct Job {
+            size_t n = 0;
+            bool queued = false;        // false: computed at begin (no table / short vector / commitment cache) -- result below
+            bool have_xyz = false;
+            uint64_t xyz[ZK_MAX_JACOBIAN64] = {};
+            uint64_t xy[ZK_MAX_AFFINE64] = {};
+            uint8_t inf = 0;
+        };
+        uint32_t n = 0;
+        bool reduced = false;           // zk_kzg_round_reduce ran: the round takes no further jobs, zk_kzg_round_end only waits
+        void* partials = nullptr;       // ... as zk_kzg_round_reduce_winsums_dev: the jobs' virtual-window sums are (being) written there, on the device
+        void* pinned_jobs = nullptr;    // ZK_MAX_JOBS x 512 B pinned: partials of jobs computed at submission, on their way to the device (async copies)
+        hipEvent_t ev = nullptr;        // recorded behind the reduction kernels of a round (msm_batch_pre_reduce)
+        uint32_t n_reduced = 0;         // jobs whose reductions are queued behind ev (0: none)
+        zk_srs* srs = nullptr;
+        Job jobs[ZK_MAX_JOBS];
+        uint64_t flushes = 0;           // times the memory budget closed the queued jobs of a round early (zk_round_mem_stats)
+        // the queued jobs in submission order: their slots (= buffer sets) and lengths; returns how many
+        uint32_t queued(uint32_t* slots, size_t* lens) const {
+            uint32_t nq = 0;
+            for (uint32_t k = 0; k < n; ++k)
+                if (jobs[k].queued) {
+                    slots[nq] = k;
+                    lens[nq] = jobs[k].n;
+                    ++nq;
+                }
+            return nq;
+        }
+    } round;
 };
 
 // Give back the work buffers of every buffer set no job lives in (and the shared staging area): the last resort of the memory
 // budget before a call returns ZK_ERR_OOM.  hipFree waits for the device, so kernels still reading them are safe.  ctx lock held.
 inline size_t zk_release_free_work(zk_ctx* c, int keep_slot) {
     size_t freed = 0;
-    for (int j = 0; j < 16; ++j) {
+    for (int j = 0; j < ZK_MAX_JOBS; ++j) {
         if (j == keep_slot || c->mb[j].stage_of_job != 0) continue;
         freed += c->mb[j].work_bytes();
         c->mb[j].release_work();
@@ -426,36 +472,48 @@ void ntt_ctx_free(zk_ctx* c);
 int fr_convert_dev(zk_ctx* c, int curve, int to_mont, const void* d_in, size_t n, void* d_out);
 int fr_mul_dev(zk_ctx* c, int curve, const void* a, const void* b, size_t n, void* out);
 
-// MSM over device bases/scalars; writes per-window sums back to host and combines there.
-// out_xyz: Jacobian (X,Y,Z) 3L u64 limbs on host.
-int msm_run_dev(zk_ctx* c, int curve, const void* d_bases_xy, const void* d_scalars, size_t n, uint64_t* out_xyz);
-int msm_fixed_base_dev(zk_ctx* c, int curve, const void* d_scalars, size_t n, void* d_out_xy);
-// window-multiples table of an SRS (see zk_srs::d_pre) and the MSM that uses it
-int msm_precompute_dev(zk_ctx* c, zk_srs* s, uint32_t window_bits /* 0 = default (16); 16 .. 21 */, uint32_t first_window = 0, uint32_t window_stride = 1);
-int msm_run_pre_dev(zk_ctx* c, zk_srs* s, size_t base_offset, const void* d_scalars, size_t n, uint64_t* out_xyz);
-// a batch of commitments over one SRS, queued back to back; the host blocks once per result
-// out_xy / out_inf (optional): also normalise every result to affine (n_polys x 2L limbs, n_polys flags)
-// before_job(k) (optional) is called right before job k's kernels are queued on the ctx stream
-int msm_batch_pre_dev(zk_ctx* c, zk_srs* s, uint32_t n_polys, const void* const* d_coeffs, const size_t* lens, uint64_t* out_xyz,
-                      const uint8_t* kinds = nullptr, uint64_t* out_xy = nullptr, uint8_t* out_inf = nullptr,
-                      const std::function<int(uint32_t)>* before_job = nullptr);
-// the two halves of msm_batch_pre_dev: queue sort + accumulate of n_polys jobs into the buffer sets c->mb[slot0 ..] / reduce the
-// jobs in slots[0 .. n_jobs) with one launch per reduction kernel, wait once, combine on the host
-int msm_batch_pre_begin_dev(zk_ctx* c, zk_srs* s, uint32_t slot0, uint32_t n_polys, const void* const* d_coeffs, const size_t* lens,
-                            const uint8_t* kinds = nullptr, const std::function<int(uint32_t)>* before_job = nullptr);
-// d_winsums (optional, n_jobs pointers): the job's 2 VW virtual-window sums are left there, on the device (zk_winsums_dev_bytes each)
-int msm_batch_pre_reduce_dev(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slots, const size_t* lens, void* const* d_winsums = nullptr);
-// whether (and in which geometry) the device-resident forms of the exchange exist for this SRS's table: vw = virtual windows, vb = buckets
-// of each; false for tables the reduction finishes on the host side only (window_bits >= 18) or without a table
-bool msm_partial_dev_supported(zk_ctx* c, zk_srs* s, uint32_t* vw, uint32_t* vb);
-// multi-GPU exchange on the device: bytes of one point in the internal XYZZ form; the 2 VW virtual-window sums of a job (S_v | T_v) are
-// added element-wise over the ranks and combined on the host pool as the single-GPU path combines them
-size_t msm_partial_dev_bytes(int curve);
-int g1_sum_winsums_dev(zk_ctx* c, zk_srs* s, const void* d_all, size_t ranks, uint32_t n_jobs, uint64_t* out_xy, uint8_t* out_inf);
-int g1_jacobian_to_partial_host(int curve, const uint64_t* xyz, void* out);
-int msm_batch_pre_end_dev(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slots, const size_t* lens, uint64_t* out_xyz,
-                          uint64_t* out_xy = nullptr, uint8_t* out_inf = nullptr);
 int fr_convert_stream(zk_ctx* c, int curve, const void* d_in, size_t n, void* d_out, hipStream_t st);
+
+// The MSM units are compiled once per curve (msm_common.cuh); each curve exports ONE object, its table of entry points (msm_plan.hip),
+// and callers write msm_ops(curve)->batch_pre_end(...).  An unknown curve id gets a table whose members do nothing and return
+// ZK_ERR_BAD_ARG (0 / false from the three that do not return a code): msm_dispatch.hip.  Optional pointers are passed as nullptr.
+struct MsmOps {
+    // MSM over device bases/scalars; writes per-window sums back to host and combines there.
+    // out_xyz: Jacobian (X,Y,Z) 3L u64 limbs on host.
+    int (*run)(zk_ctx* c, const void* d_bases_xy, const void* d_scalars, size_t n, uint64_t* out_xyz);
+    int (*fixed_base)(zk_ctx* c, const void* d_scalars, size_t n, void* d_out_xy);
+    // window-multiples table of an SRS (see zk_srs::d_pre) and the MSM that uses it.  window_bits: 0 = default (16); 16 .. 21
+    int (*precompute)(zk_ctx* c, zk_srs* s, uint32_t window_bits, uint32_t first_window, uint32_t window_stride);
+    int (*run_pre)(zk_ctx* c, zk_srs* s, size_t base_offset, const void* d_scalars, size_t n, uint64_t* out_xyz);
+    // a batch of commitments over one SRS, queued back to back; the host blocks once per result
+    // out_xy / out_inf (optional): also normalise every result to affine (n_polys x 2L limbs, n_polys flags)
+    // before_job(k) (optional) is called right before job k's kernels are queued on the ctx stream
+    int (*batch_pre)(zk_ctx* c, zk_srs* s, uint32_t n_polys, const void* const* d_coeffs, const size_t* lens, uint64_t* out_xyz,
+                     const uint8_t* kinds, uint64_t* out_xy, uint8_t* out_inf, const std::function<int(uint32_t)>* before_job);
+    // the two halves of batch_pre: queue sort + accumulate of n_polys jobs into the buffer sets c->mb[slot0 ..] / reduce the
+    // jobs in slots[0 .. n_jobs) with one launch per reduction kernel, wait once, combine on the host
+    int (*batch_pre_begin)(zk_ctx* c, zk_srs* s, uint32_t slot0, uint32_t n_polys, const void* const* d_coeffs, const size_t* lens,
+                           const uint8_t* kinds, const std::function<int(uint32_t)>* before_job);
+    // d_winsums (optional, n_jobs pointers): the job's 2 VW virtual-window sums are left there, on the device (zk_winsums_dev_bytes each)
+    int (*batch_pre_reduce)(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slots, const size_t* lens, void* const* d_winsums);
+    int (*batch_pre_end)(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slots, const size_t* lens, uint64_t* out_xyz, uint64_t* out_xy,
+                         uint8_t* out_inf);
+    // whether (and in which geometry) the device-resident forms of the exchange exist for this SRS's table: vw = virtual windows, vb = buckets
+    // of each; false for tables the reduction finishes on the host side only (window_bits >= 18) or without a table
+    bool (*partial_dev_supported)(zk_ctx* c, zk_srs* s, uint32_t* vw, uint32_t* vb);
+    // multi-GPU exchange on the device: bytes of one point in the internal XYZZ form; the 2 VW virtual-window sums of a job (S_v | T_v) are
+    // added element-wise over the ranks and combined on the host pool as the single-GPU path combines them
+    size_t (*partial_dev_bytes)();
+    int (*sum_winsums)(zk_ctx* c, zk_srs* s, const void* d_all, size_t ranks, uint32_t n_jobs, uint64_t* out_xy, uint8_t* out_inf);
+    int (*jacobian_to_partial_host)(const uint64_t* xyz, void* out);
+    // arkworks-layout affine bases (x||y, Montgomery R = 2^(64L)) -> device-internal points
+    int (*convert_bases)(zk_ctx* c, const void* d_xy_sat, const uint8_t* d_inf, size_t n, void* d_out_internal);
+    size_t (*point_bytes)();
+    int (*jacobian_to_affine_host)(const uint64_t* xyz, uint64_t* out_xy, uint8_t* out_inf);
+    int (*sum_partials_host)(const uint64_t* partials, size_t count, uint64_t* out_xy, uint8_t* out_inf);
+};
+const MsmOps* msm_ops(int curve);
+
 constexpr size_t ZK_PRE_MIN_N = 1u << 13;   // below this the per-window path is used
 constexpr size_t ZK_PRE_MAX_N = 1u << 26;   // ... and above this: a sorted reference of the table path is sign | 5 bits of window | 26 bits of point index
 // the limit the dispatch uses: ZK_PRE_MAX_N, or 2^pre_max_log_n of the ctx's options when that is set (test hook: the fall-back to
@@ -465,11 +523,6 @@ inline size_t zk_pre_max_n(const zk_ctx* c) {
     if (v >= 13 && v < 26) return (size_t)1 << v;
     return ZK_PRE_MAX_N;
 }
-// arkworks-layout affine bases (x||y, Montgomery R = 2^(64L)) -> device-internal points
-int msm_convert_bases_dev(zk_ctx* c, int curve, const void* d_xy_sat, const uint8_t* d_inf, size_t n, void* d_out_internal);
-size_t msm_point_bytes(int curve);
-int g1_jacobian_to_affine_host(int curve, const uint64_t* xyz, uint64_t* out_xy, uint8_t* out_inf);
-int g1_sum_partials_host(int curve, const uint64_t* partials, size_t count, uint64_t* out_xy, uint8_t* out_inf);
 int perm_product_dev(zk_ctx* c, int curve, uint32_t log_n, const void* const* d_wires, const void* const* d_sigmas,
                      const uint64_t* beta_mont, const uint64_t* gamma_mont, void* d_out, uint64_t* last_mont);
 int lookup_product_dev(zk_ctx* c, int curve, size_t n, const void* d_f, const void* d_t, const void* d_h1, const void* d_h2,

@@ -191,7 +191,7 @@ __global__ void gp_combine(GpPair g, Fr inv_t, uint64_t n, void* out) {
     st_fr<Fr>(out, i, Fr::mul(Fr::mul(pn, sd), inv_t));
 }
 
-// N (numerators) and D (denominators) are in c->io_a / c->io_b; finishes the product into d_out
+// N (numerators) and D (denominators) are in c->io.a / c->io.b; finishes the product into d_out
 template <class Fr>
 int finish_product(zk_ctx* c, uint64_t n, void* d_out, uint64_t* last_mont) {
     const uint64_t n_tiles = (n + WS_TILE - 1) / WS_TILE;
@@ -200,8 +200,8 @@ int finish_product(zk_ctx* c, uint64_t n, void* d_out, uint64_t* last_mont) {
     if ((rc = c->msm_tmp.ensure(4 * (n_tiles + 1) * 32))) return rc;
     char* t = (char*)c->msm_tmp.p;
     GpPair g;
-    g.x[0] = c->io_a.p;
-    g.x[1] = c->io_b.p;
+    g.x[0] = c->io.a.p;
+    g.x[1] = c->io.b.p;
     g.p[0] = t;
     g.a[0] = t + (n_tiles + 1) * 32;
     g.p[1] = t + 2 * (n_tiles + 1) * 32;
@@ -233,8 +233,8 @@ int perm_product(zk_ctx* c, uint32_t log_n, const void* const* d_wires, const vo
     if (log_n > (uint32_t)C::FrP::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
     const uint64_t n = 1ull << log_n;
     int rc;
-    if ((rc = c->io_a.ensure(n * 32))) return rc;
-    if ((rc = c->io_b.ensure(n * 32))) return rc;
+    if ((rc = c->io.a.ensure(n * 32))) return rc;
+    if ((rc = c->io.b.ensure(n * 32))) return rc;
     PermArgs<Fr> a;
     memcpy(a.beta.v, beta_mont, 32);
     memcpy(a.gamma.v, gamma_mont, 32);
@@ -251,7 +251,7 @@ int perm_product(zk_ctx* c, uint32_t log_n, const void* const* d_wires, const vo
     a.omega_t = Fr::pow_u64(root, TERM_T);
     ProfScope ps(c, "grand_product");
     const unsigned blocks = (unsigned)((n + (uint64_t)TERM_T * TERM_ROWS - 1) / ((uint64_t)TERM_T * TERM_ROWS));
-    hipLaunchKernelGGL(gp_perm_terms<Fr>, dim3(blocks), dim3(TERM_T), 0, c->stream, a, n, c->io_a.p, c->io_b.p);
+    hipLaunchKernelGGL(gp_perm_terms<Fr>, dim3(blocks), dim3(TERM_T), 0, c->stream, a, n, c->io.a.p, c->io.b.p);
     ZK_HIP_TRY(hipGetLastError());
     return finish_product<Fr>(c, n, d_out, last_mont);
 }
@@ -261,8 +261,8 @@ int lookup_product(zk_ctx* c, size_t n, const void* d_f, const void* d_t, const 
                    const uint64_t* eps_mont, void* d_out, uint64_t* last_mont) {
     typedef typename C::Fr Fr;
     int rc;
-    if ((rc = c->io_a.ensure(n * 32))) return rc;
-    if ((rc = c->io_b.ensure(n * 32))) return rc;
+    if ((rc = c->io.a.ensure(n * 32))) return rc;
+    if ((rc = c->io.b.ensure(n * 32))) return rc;
     LookupArgs<Fr> a;
     a.f = d_f;
     a.t = d_t;
@@ -273,8 +273,8 @@ int lookup_product(zk_ctx* c, size_t n, const void* d_f, const void* d_t, const 
     a.one_plus_delta = Fr::add(Fr::one(), a.delta);
     a.eps_opd = Fr::mul(a.eps, a.one_plus_delta);
     ProfScope ps(c, "grand_product");
-    hipLaunchKernelGGL(gp_lookup_terms<Fr>, dim3((unsigned)((n + TERM_T - 1) / TERM_T)), dim3(TERM_T), 0, c->stream, a, (uint64_t)n, c->io_a.p,
-                       c->io_b.p);
+    hipLaunchKernelGGL(gp_lookup_terms<Fr>, dim3((unsigned)((n + TERM_T - 1) / TERM_T)), dim3(TERM_T), 0, c->stream, a, (uint64_t)n, c->io.a.p,
+                       c->io.b.p);
     ZK_HIP_TRY(hipGetLastError());
     return finish_product<Fr>(c, n, d_out, last_mont);
 }
@@ -283,14 +283,10 @@ int lookup_product(zk_ctx* c, size_t n, const void* d_f, const void* d_t, const 
 
 int perm_product_dev(zk_ctx* c, int curve, uint32_t log_n, const void* const* d_wires, const void* const* d_sigmas,
                      const uint64_t* beta_mont, const uint64_t* gamma_mont, void* d_out, uint64_t* last_mont) {
-    if (curve == ZK_CURVE_BLS12_381) return perm_product<CurveBls>(c, log_n, d_wires, d_sigmas, beta_mont, gamma_mont, d_out, last_mont);
-    if (curve == ZK_CURVE_BN254) return perm_product<CurveBn>(c, log_n, d_wires, d_sigmas, beta_mont, gamma_mont, d_out, last_mont);
-    return ZK_ERR_BAD_ARG;
+    return zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) { return perm_product<decltype(cv)>(c, log_n, d_wires, d_sigmas, beta_mont, gamma_mont, d_out, last_mont); });
 }
 
 int lookup_product_dev(zk_ctx* c, int curve, size_t n, const void* d_f, const void* d_t, const void* d_h1, const void* d_h2,
                        const uint64_t* delta_mont, const uint64_t* eps_mont, void* d_out, uint64_t* last_mont) {
-    if (curve == ZK_CURVE_BLS12_381) return lookup_product<CurveBls>(c, n, d_f, d_t, d_h1, d_h2, delta_mont, eps_mont, d_out, last_mont);
-    if (curve == ZK_CURVE_BN254) return lookup_product<CurveBn>(c, n, d_f, d_t, d_h1, d_h2, delta_mont, eps_mont, d_out, last_mont);
-    return ZK_ERR_BAD_ARG;
+    return zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) { return lookup_product<decltype(cv)>(c, n, d_f, d_t, d_h1, d_h2, delta_mont, eps_mont, d_out, last_mont); });
 }

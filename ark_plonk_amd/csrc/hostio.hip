@@ -28,11 +28,11 @@ bool is_pinned(const void* p) {
 }
 
 int stage_setup(zk_ctx* c) {
-    for (int i = 0; i < zk_ctx::STAGE_SLOTS; ++i) {
-        if (!c->stage_pin[i]) {
-            if (hipHostMalloc(&c->stage_pin[i], zk_ctx::STAGE_BYTES, hipHostMallocDefault) != hipSuccess) return ZK_ERR_OOM;
-            ZK_HIP_TRY(hipEventCreateWithFlags(&c->stage_ev[i], hipEventDisableTiming));
-            c->stage_busy[i] = false;
+    for (int i = 0; i < zk_ctx::HostIo::STAGE_SLOTS; ++i) {
+        if (!c->io.stage_pin[i]) {
+            if (hipHostMalloc(&c->io.stage_pin[i], zk_ctx::HostIo::STAGE_BYTES, hipHostMallocDefault) != hipSuccess) return ZK_ERR_OOM;
+            ZK_HIP_TRY(hipEventCreateWithFlags(&c->io.stage_ev[i], hipEventDisableTiming));
+            c->io.stage_busy[i] = false;
         }
     }
     return ZK_OK;
@@ -54,11 +54,11 @@ void pooled_memcpy(zk_ctx* c, void* dst, const void* src, size_t bytes) {
 }
 
 int take_slot(zk_ctx* c, int* slot) {
-    const int s = c->stage_next;
-    c->stage_next = (s + 1) % zk_ctx::STAGE_SLOTS;
-    if (c->stage_busy[s]) {
-        ZK_HIP_TRY(hipEventSynchronize(c->stage_ev[s]));
-        c->stage_busy[s] = false;
+    const int s = c->io.stage_next;
+    c->io.stage_next = (s + 1) % zk_ctx::HostIo::STAGE_SLOTS;
+    if (c->io.stage_busy[s]) {
+        ZK_HIP_TRY(hipEventSynchronize(c->io.stage_ev[s]));
+        c->io.stage_busy[s] = false;
     }
     *slot = s;
     return ZK_OK;
@@ -255,29 +255,29 @@ int dev_digest256(const void* const* d_ptrs, const size_t* d_lens, uint32_t n_jo
 
 int zk_h2d(zk_ctx* c, void* d_dst, const void* h_src, size_t bytes, hipStream_t st) {
     if (bytes == 0) return ZK_OK;
-    c->h2d_bytes += bytes;
-    if (c->staging_mode == 0 || is_pinned(h_src)) {
+    c->io.h2d_bytes += bytes;
+    if (c->io.staging_mode == 0 || is_pinned(h_src)) {
         ZK_HIP_TRY(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, st));
         return ZK_OK;
     }
     int rc = stage_setup(c);
     if (rc) return rc;
-    for (size_t off = 0; off < bytes; off += zk_ctx::STAGE_BYTES) {
-        const size_t len = bytes - off < zk_ctx::STAGE_BYTES ? bytes - off : zk_ctx::STAGE_BYTES;
+    for (size_t off = 0; off < bytes; off += zk_ctx::HostIo::STAGE_BYTES) {
+        const size_t len = bytes - off < zk_ctx::HostIo::STAGE_BYTES ? bytes - off : zk_ctx::HostIo::STAGE_BYTES;
         int s;
         if ((rc = take_slot(c, &s))) return rc;
-        pooled_memcpy(c, c->stage_pin[s], (const char*)h_src + off, len);
-        ZK_HIP_TRY(hipMemcpyAsync((char*)d_dst + off, c->stage_pin[s], len, hipMemcpyHostToDevice, st));
-        ZK_HIP_TRY(hipEventRecord(c->stage_ev[s], st));
-        c->stage_busy[s] = true;
+        pooled_memcpy(c, c->io.stage_pin[s], (const char*)h_src + off, len);
+        ZK_HIP_TRY(hipMemcpyAsync((char*)d_dst + off, c->io.stage_pin[s], len, hipMemcpyHostToDevice, st));
+        ZK_HIP_TRY(hipEventRecord(c->io.stage_ev[s], st));
+        c->io.stage_busy[s] = true;
     }
     return ZK_OK;
 }
 
 int zk_d2h(zk_ctx* c, void* h_dst, const void* d_src, size_t bytes, hipStream_t st) {
     if (bytes == 0) return ZK_OK;
-    c->d2h_bytes += bytes;
-    if (c->staging_mode == 0 || is_pinned(h_dst)) {
+    c->io.d2h_bytes += bytes;
+    if (c->io.staging_mode == 0 || is_pinned(h_dst)) {
         ZK_HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, st));
         ZK_HIP_TRY(hipStreamSynchronize(st));
         return ZK_OK;
@@ -289,26 +289,26 @@ int zk_d2h(zk_ctx* c, void* h_dst, const void* d_src, size_t bytes, hipStream_t 
         int slot;
         size_t off, len;
     };
-    Pending ring[zk_ctx::STAGE_SLOTS];
+    Pending ring[zk_ctx::HostIo::STAGE_SLOTS];
     int head = 0, count = 0;
     auto drain_one = [&]() -> int {
         Pending& p = ring[head];
-        ZK_HIP_TRY(hipEventSynchronize(c->stage_ev[p.slot]));
-        c->stage_busy[p.slot] = false;
-        pooled_memcpy(c, (char*)h_dst + p.off, c->stage_pin[p.slot], p.len);
-        head = (head + 1) % zk_ctx::STAGE_SLOTS;
+        ZK_HIP_TRY(hipEventSynchronize(c->io.stage_ev[p.slot]));
+        c->io.stage_busy[p.slot] = false;
+        pooled_memcpy(c, (char*)h_dst + p.off, c->io.stage_pin[p.slot], p.len);
+        head = (head + 1) % zk_ctx::HostIo::STAGE_SLOTS;
         --count;
         return ZK_OK;
     };
-    for (size_t off = 0; off < bytes; off += zk_ctx::STAGE_BYTES) {
-        const size_t len = bytes - off < zk_ctx::STAGE_BYTES ? bytes - off : zk_ctx::STAGE_BYTES;
-        if (count == zk_ctx::STAGE_SLOTS && (rc = drain_one())) return rc;
+    for (size_t off = 0; off < bytes; off += zk_ctx::HostIo::STAGE_BYTES) {
+        const size_t len = bytes - off < zk_ctx::HostIo::STAGE_BYTES ? bytes - off : zk_ctx::HostIo::STAGE_BYTES;
+        if (count == zk_ctx::HostIo::STAGE_SLOTS && (rc = drain_one())) return rc;
         int s;
         if ((rc = take_slot(c, &s))) return rc;
-        ZK_HIP_TRY(hipMemcpyAsync(c->stage_pin[s], (const char*)d_src + off, len, hipMemcpyDeviceToHost, st));
-        ZK_HIP_TRY(hipEventRecord(c->stage_ev[s], st));
-        c->stage_busy[s] = true;
-        ring[(head + count) % zk_ctx::STAGE_SLOTS] = Pending{s, off, len};
+        ZK_HIP_TRY(hipMemcpyAsync(c->io.stage_pin[s], (const char*)d_src + off, len, hipMemcpyDeviceToHost, st));
+        ZK_HIP_TRY(hipEventRecord(c->io.stage_ev[s], st));
+        c->io.stage_busy[s] = true;
+        ring[(head + count) % zk_ctx::HostIo::STAGE_SLOTS] = Pending{s, off, len};
         ++count;
     }
     while (count)
@@ -317,15 +317,15 @@ int zk_d2h(zk_ctx* c, void* h_dst, const void* d_src, size_t bytes, hipStream_t 
 }
 
 void zk_io_release(zk_ctx* c) {
-    for (int i = 0; i < zk_ctx::STAGE_SLOTS; ++i) {
-        if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]);
-        if (c->stage_pin[i]) (void)hipHostFree(c->stage_pin[i]);
-        c->stage_ev[i] = nullptr;
-        c->stage_pin[i] = nullptr;
+    for (int i = 0; i < zk_ctx::HostIo::STAGE_SLOTS; ++i) {
+        if (c->io.stage_ev[i]) (void)hipEventDestroy(c->io.stage_ev[i]);
+        if (c->io.stage_pin[i]) (void)hipHostFree(c->io.stage_pin[i]);
+        c->io.stage_ev[i] = nullptr;
+        c->io.stage_pin[i] = nullptr;
     }
     for (int i = 0; i < 16; ++i)
-        if (c->ev_up[i]) (void)hipEventDestroy(c->ev_up[i]);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    c->copy_stream = nullptr;
-    c->digest_dev.release();
+        if (c->io.ev_up[i]) (void)hipEventDestroy(c->io.ev_up[i]);
+    if (c->io.copy_stream) (void)hipStreamDestroy(c->io.copy_stream);
+    c->io.copy_stream = nullptr;
+    c->ccache.digest_dev.release();
 }

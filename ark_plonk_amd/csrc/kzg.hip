@@ -230,9 +230,9 @@ int poly_evaluate(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const
     }
     a.max_chunks = (m + CHUNK - 1) / CHUNK;
     int rc;
-    if ((rc = c->io_b.ensure((size_t)n_polys * (a.max_chunks + 1) * 48 + (size_t)n_polys * 32))) return rc;
-    void* H = c->io_b.p;
-    void* d_out = (char*)c->io_b.p + (size_t)n_polys * (a.max_chunks + 1) * 48;
+    if ((rc = c->io.b.ensure((size_t)n_polys * (a.max_chunks + 1) * 48 + (size_t)n_polys * 32))) return rc;
+    void* H = c->io.b.p;
+    void* d_out = (char*)c->io.b.p + (size_t)n_polys * (a.max_chunks + 1) * 48;
     hipStream_t st = c->stream;
     {
         ProfScope ps(c, "poly_evaluate");
@@ -244,7 +244,7 @@ int poly_evaluate(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const
     }
     ZK_HIP_TRY(hipMemcpyAsync(out_mont, d_out, (size_t)n_polys * 32, hipMemcpyDeviceToHost, st));
     ZK_HIP_TRY(hipStreamSynchronize(st));
-    c->d2h_bytes += (uint64_t)n_polys * 32;
+    c->io.d2h_bytes += (uint64_t)n_polys * 32;
     return ZK_OK;
 }
 
@@ -311,19 +311,19 @@ int open_prepare(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const 
     }
     const uint64_t n_chunks = (m + CHUNK - 1) / CHUNK;
     int rc;
-    if ((rc = c->io_a.ensure(m * 32))) return rc;                       // comb
-    if ((rc = c->io_b.ensure((n_chunks * 2 + (size_t)SCAN_T * 3) * 48))) return rc;   // H | A | the scan's (h, q) pairs and carries (limb vectors)
+    if ((rc = c->io.a.ensure(m * 32))) return rc;                       // comb
+    if ((rc = c->io.b.ensure((n_chunks * 2 + (size_t)SCAN_T * 3) * 48))) return rc;   // H | A | the scan's (h, q) pairs and carries (limb vectors)
     if ((rc = c->witness.ensure(m * 32))) return rc;                      // witness, canonical
-    void* comb = c->io_a.p;
-    void* H = c->io_b.p;
-    void* A = (char*)c->io_b.p + n_chunks * 48;
+    void* comb = c->io.a.p;
+    void* H = c->io.b.p;
+    void* A = (char*)c->io.b.p + n_chunks * 48;
     const Packed zp = pack(z), zkp = pack(Fr::pow_u64(z, CHUNK));
     hipStream_t st = c->stream;
     ProfScope ps(c, "kzg_open_prep");
     const int T = 256;
     hipLaunchKernelGGL(kzg_rlc<FU>, dim3((unsigned)((m + T - 1) / T)), dim3(T), 0, st, a, m, comb);
     hipLaunchKernelGGL(kzg_chunk_horner<FU>, dim3((unsigned)((n_chunks + T - 1) / T)), dim3(T), 0, st, comb, m, zp, H, n_chunks);
-    void* HQ = (char*)c->io_b.p + n_chunks * 2 * 48;
+    void* HQ = (char*)c->io.b.p + n_chunks * 2 * 48;
     void* CR = (char*)HQ + (size_t)SCAN_T * 2 * 48;
     size_t shmem = (size_t)SCAN_T * 2 * 48;
     ZK_HIP_TRY(hipFuncSetAttribute((const void*)kzg_scan_cross<FU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
@@ -340,21 +340,15 @@ int open_prepare(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const 
 
 int poly_evaluate_dev(zk_ctx* c, int curve, uint32_t n_polys, const void* const* d_polys, const size_t* lens, const uint64_t* points_mont,
                       uint64_t* out_mont) {
-    if (curve == ZK_CURVE_BLS12_381) return poly_evaluate<CurveBls>(c, n_polys, d_polys, lens, points_mont, out_mont);
-    if (curve == ZK_CURVE_BN254) return poly_evaluate<CurveBn>(c, n_polys, d_polys, lens, points_mont, out_mont);
-    return ZK_ERR_BAD_ARG;
+    return zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) { return poly_evaluate<decltype(cv)>(c, n_polys, d_polys, lens, points_mont, out_mont); });
 }
 
 int poly_lincomb_dev(zk_ctx* c, int curve, uint32_t n_terms, const void* const* d_polys, const size_t* lens, const uint64_t* coeffs_mont,
                      void* d_out, size_t out_len) {
-    if (curve == ZK_CURVE_BLS12_381) return poly_lincomb<CurveBls>(c, n_terms, d_polys, lens, coeffs_mont, d_out, out_len);
-    if (curve == ZK_CURVE_BN254) return poly_lincomb<CurveBn>(c, n_terms, d_polys, lens, coeffs_mont, d_out, out_len);
-    return ZK_ERR_BAD_ARG;
+    return zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) { return poly_lincomb<decltype(cv)>(c, n_terms, d_polys, lens, coeffs_mont, d_out, out_len); });
 }
 
 int kzg_open_prepare_dev(zk_ctx* c, int curve, uint32_t n_polys, const void* const* d_polys, const size_t* lens,
                          const uint64_t* z_mont, const uint64_t* chal_mont, void** d_witness_canonical, size_t* wlen) {
-    if (curve == ZK_CURVE_BLS12_381) return open_prepare<CurveBls>(c, n_polys, d_polys, lens, z_mont, chal_mont, d_witness_canonical, wlen);
-    if (curve == ZK_CURVE_BN254) return open_prepare<CurveBn>(c, n_polys, d_polys, lens, z_mont, chal_mont, d_witness_canonical, wlen);
-    return ZK_ERR_BAD_ARG;
+    return zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) { return open_prepare<decltype(cv)>(c, n_polys, d_polys, lens, z_mont, chal_mont, d_witness_canonical, wlen); });
 }

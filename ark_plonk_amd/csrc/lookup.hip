@@ -341,9 +341,7 @@ int query_run(zk_ctx* c, size_t n, const void* d_q, size_t q_len, const void* co
 int lookup_query_dev(zk_ctx* c, int curve, size_t n, const void* d_q, size_t q_len, const void* const* d_w, const uint64_t* zeta_mont,
                      const void* d_table, void* d_out) {
     if (n == 0) return ZK_OK;
-    if (curve == ZK_CURVE_BLS12_381) return query_run<CurveBls>(c, n, d_q, q_len, d_w, zeta_mont, d_table, d_out);
-    if (curve == ZK_CURVE_BN254) return query_run<CurveBn>(c, n, d_q, q_len, d_w, zeta_mont, d_table, d_out);
-    return ZK_ERR_BAD_ARG;
+    return zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) { return query_run<decltype(cv)>(c, n, d_q, q_len, d_w, zeta_mont, d_table, d_out); });
 }
 
 int lookup_combine_split_dev(zk_ctx* c, const void* d_t, size_t n_t, const void* d_f, size_t n_f, void* d_h1, void* d_h2, size_t* len_h1,
@@ -358,15 +356,15 @@ int lookup_combine_split_dev(zk_ctx* c, const void* d_t, size_t n_t, const void*
     size_t w32 = (size_t)2 * M + 3 * n_t + 1 + 2;
     w32 = (w32 + 1) & ~(size_t)1;
     const size_t bytes = w32 * 4 + ((size_t)2 * n_t + 1 + nb_scan + 1) * 8;
-    int rc = c->io_b.ensure(bytes);
+    int rc = c->io.b.ensure(bytes);
     if (rc) return rc;
-    uint32_t* slots = (uint32_t*)c->io_b.p;
+    uint32_t* slots = (uint32_t*)c->io.b.p;
     uint32_t* cnt = slots + M;
     uint32_t* slot_of = cnt + M;
     uint32_t* odd = slot_of + n_t;
     uint32_t* par = odd + n_t;
     uint32_t* err = par + n_t + 1;
-    uint64_t* eo = (uint64_t*)((uint32_t*)c->io_b.p + w32);
+    uint64_t* eo = (uint64_t*)((uint32_t*)c->io.b.p + w32);
     uint64_t* off = eo + n_t;
     uint64_t* btot = off + n_t + 1;
     hipStream_t st = c->stream;
@@ -398,7 +396,7 @@ int lookup_combine_split_dev(zk_ctx* c, const void* d_t, size_t n_t, const void*
     ZK_HIP_TRY(hipMemcpyAsync(h.err, err, 8, hipMemcpyDeviceToHost, st));
     ZK_HIP_TRY(hipMemcpyAsync(&h.tot, off + n_t, 8, hipMemcpyDeviceToHost, st));
     ZK_HIP_TRY(hipStreamSynchronize(st));
-    c->d2h_bytes += 16;
+    c->io.d2h_bytes += 16;
     if (h.err[0]) return ZK_ERR_NOT_INDEXED;
     const uint32_t ne = (uint32_t)h.tot, no = (uint32_t)(h.tot >> 32);
     if ((uint64_t)ne + no != (uint64_t)n_t + n_f) return ZK_ERR_HIP;       // cannot happen: every element was counted once

@@ -1,7 +1,7 @@
 // Shared by the MSM units (msm_sort.hip, msm_accumulate.hip, msm_reduce.hip, msm_plan.hip): the device storage of field elements and
 // points, the geometry and job structs the kernels take, the plan of a window-table job, and the per-curve entry points one unit offers
 // the others.  Every unit is built once per curve (-DZK_CURVE_SEL=<0|1>, ark_plonk_amd/build.py): the names below carry the curve
-// suffix; msm_dispatch.hip dispatches the library-internal interface of ctx.h on the curve id.
+// suffix, and msm_plan.hip gathers the curve's entry points into its MsmOps table (ctx.h), which msm_ops(curve) hands to the callers.
 //
 // Pipeline (all on the ctx stream; no host round trip until the window sums are read back).  On the window-table path every step is
 // ONE launch per kernel for all the MSMs of a prover round (job = blockIdx.y, or a block range of the accumulation):
@@ -125,10 +125,10 @@ struct MsmGeom {
     }
 };
 
-// The kernels behind a prover round take up to 16 jobs (blockIdx.y, or a block-range table): the MSMs of one round are
+// The kernels behind a prover round take up to 16 jobs (ZK_MAX_JOBS of ctx.h; blockIdx.y, or a block-range table): the MSMs of one round are
 // sorted, accumulated and reduced by ONE launch of each kernel, so that launch gaps, partly filled last rounds of wavefronts and
 // the latency of the dependent-addition chains are paid once per round instead of once per MSM.
-constexpr int MAX_JOBS = 16;
+constexpr int MAX_JOBS = ZK_MAX_JOBS;
 // one job of the batched partition-sort kernels (psort_scan / psort(w)_scatter / psort(w)_final)
 struct SJob {
     const void* dig;        // digits [W][n]: int16 (c = 16) or int32 (c > 16)
@@ -323,6 +323,12 @@ int ZK_SYM(pre_queue_sort_rest)(zk_ctx* c, const PrePlan* pls, MsmBufs* const* m
 int ZK_SYM(pw_queue_accumulate)(zk_ctx* c, const MsmGeom& g, MsmBufs& mb, const void* d_bases, uint32_t n_lanes, hipStream_t st);
 int ZK_SYM(pre_queue_accumulate)(zk_ctx* c, const PrePlan* pls, MsmBufs* const* mbs, const size_t* lens, const size_t* tab_offs, uint32_t n_jobs, zk_srs* s,
                                  hipStream_t st);
+//   members of the curve's MsmOps (ctx.h describes them)
+int ZK_SYM(msm_fixed_base_dev)(zk_ctx* c, const void* d_scalars, size_t n, void* d_out_xy);
+int ZK_SYM(msm_convert_bases_dev)(zk_ctx* c, const void* d_xy_sat, const uint8_t* d_inf, size_t n, void* d_out_internal);
+int ZK_SYM(msm_precompute_dev)(zk_ctx* c, zk_srs* s, uint32_t window_bits, uint32_t w0, uint32_t wstep);
+size_t ZK_SYM(msm_point_bytes)();
+size_t ZK_SYM(msm_partial_dev_bytes)();
 // msm_reduce.hip
 int ZK_SYM(queue_reduce)(zk_ctx* c, const RJobs& jobs, uint32_t n_jobs, uint32_t nb, const MsmGeom& gr, hipStream_t st, bool queues_cleared, uint32_t raw);
 //   d_winsums (optional, n_jobs pointers): the jobs' 2 VW virtual-window sums stay on the device, internal form, instead of going to h_win

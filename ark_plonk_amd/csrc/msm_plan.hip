@@ -7,7 +7,7 @@
 // MSM unit 4 of 4 (msm_common.cuh has the pipeline): the host side -- window geometry, the plan and memory budget of a window-table job,
 // the per-window entry point (msm_run), the table entry points (msm_run_pre, the batch and the deferred rounds' begin / reduce / end),
 // the host combine of the window sums and the affine normalisation.  No kernel is defined here: the units msm_sort / msm_accumulate /
-// msm_reduce queue them (ZK_SYM entry points of msm_common.cuh).
+// msm_reduce queue them (ZK_SYM entry points of msm_common.cuh).  The unit ends with the curve's MsmOps table (ctx.h).
 #include "msm_common.cuh"
 
 #include <chrono>
@@ -558,9 +558,9 @@ int msm_batch_pre_reduce(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* 
     }
     if ((rc = ZK_SYM(pre_queue_reduce)(c, pl, mbs, n_jobs, c->pinned, st, d_winsums))) return rc;
     for (uint32_t k = 0; k < n_jobs; ++k) mbs[k]->stage_of_job = 0;
-    if (!c->round_ev) ZK_HIP_TRY(hipEventCreateWithFlags(&c->round_ev, hipEventDisableTiming));
-    ZK_HIP_TRY(hipEventRecord(c->round_ev, st));
-    c->round_reduced = n_jobs;
+    if (!c->round.ev) ZK_HIP_TRY(hipEventCreateWithFlags(&c->round.ev, hipEventDisableTiming));
+    ZK_HIP_TRY(hipEventRecord(c->round.ev, st));
+    c->round.n_reduced = n_jobs;
     return ZK_OK;
 }
 
@@ -619,15 +619,15 @@ int msm_batch_pre_end(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slo
     if (n_jobs == 0) return ZK_OK;
     if (n_jobs > (uint32_t)MAX_JOBS) return ZK_ERR_UNSUPPORTED;
     int rc;
-    if (c->round_reduced != n_jobs && (rc = msm_batch_pre_reduce<Cv>(c, s, n_jobs, slots, lens))) return rc;
-    c->round_reduced = 0;
+    if (c->round.n_reduced != n_jobs && (rc = msm_batch_pre_reduce<Cv>(c, s, n_jobs, slots, lens))) return rc;
+    c->round.n_reduced = 0;
     PrePlan pl[MAX_JOBS];
     for (uint32_t k = 0; k < n_jobs; ++k)
         if ((rc = pre_plan_geom<Cv>(c, s, lens[k], pl[k]))) return rc;
     const size_t wb = pl[0].win_bytes;
     static const bool host_timing = getenv("ZK_HOST_TIMING") != nullptr;      // diagnostic: where the host tail of a round goes
     const auto t0 = std::chrono::steady_clock::now();
-    ZK_HIP_TRY(hipEventSynchronize(c->round_ev));
+    ZK_HIP_TRY(hipEventSynchronize(c->round.ev));
     const auto t1 = std::chrono::steady_clock::now();
     struct TailTimer {
         bool on;
@@ -682,7 +682,7 @@ int msm_batch_pre(zk_ctx* c, zk_srs* s, uint32_t n_polys, const void* const* d_c
             return rc;
         }
         const uint32_t m = rc ? begun : n_polys - done;
-        if (rc) ++c->round_flushes;
+        if (rc) ++c->round.flushes;
         uint32_t slots[MAX_JOBS];
         for (uint32_t k = 0; k < m; ++k) slots[k] = k;
         rc = msm_batch_pre_end<Cv>(c, s, m, slots, lens + done, out_xyz + (size_t)done * 3 * L64, out_xy ? out_xy + (size_t)done * 2 * L64 : nullptr,
@@ -758,35 +758,29 @@ int sum_partials(const uint64_t* partials, size_t count, uint64_t* out_xy, uint8
 
 }  // namespace
 
-int ZK_SYM(msm_run_dev)(zk_ctx* c, const void* d_bases_xy, const void* d_scalars, size_t n, uint64_t* out_xyz) {
-    return msm_run<CurveSel>(c, d_bases_xy, d_scalars, n, out_xyz);
-}
-int ZK_SYM(msm_run_pre_dev)(zk_ctx* c, zk_srs* s, size_t base_offset, const void* d_scalars, size_t n, uint64_t* out_xyz) {
-    return msm_run_pre<CurveSel>(c, s, base_offset, d_scalars, n, out_xyz);
-}
-int ZK_SYM(msm_batch_pre_dev)(zk_ctx* c, zk_srs* s, uint32_t n_polys, const void* const* d_coeffs, const size_t* lens, uint64_t* out_xyz,
-                              const uint8_t* kinds, uint64_t* out_xy, uint8_t* out_inf, const std::function<int(uint32_t)>* before_job) {
-    return msm_batch_pre<CurveSel>(c, s, n_polys, d_coeffs, lens, out_xyz, kinds, out_xy, out_inf, before_job);
-}
-int ZK_SYM(msm_batch_pre_begin_dev)(zk_ctx* c, zk_srs* s, uint32_t slot0, uint32_t n_polys, const void* const* d_coeffs, const size_t* lens,
-                                    const uint8_t* kinds, const std::function<int(uint32_t)>* before_job) {
-    return msm_batch_pre_begin<CurveSel>(c, s, slot0, n_polys, d_coeffs, lens, kinds, before_job, nullptr);
-}
-int ZK_SYM(msm_batch_pre_reduce_dev)(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slots, const size_t* lens, void* const* d_winsums) {
-    return msm_batch_pre_reduce<CurveSel>(c, s, n_jobs, slots, lens, d_winsums);
-}
-bool ZK_SYM(msm_partial_dev_supported)(zk_ctx* c, zk_srs* s, uint32_t* vw, uint32_t* vb) { return partial_dev_supported<CurveSel>(c, s, vw, vb); }
-int ZK_SYM(g1_sum_winsums_dev)(zk_ctx* c, zk_srs* s, const void* d_all, size_t ranks, uint32_t n_jobs, uint64_t* out_xy, uint8_t* out_inf) {
-    return sum_winsums_dev<CurveSel>(c, s, d_all, ranks, n_jobs, out_xy, out_inf);
-}
-void ZK_SYM(g1_jacobian_to_partial_host)(const uint64_t* xyz, void* out) { jacobian_to_partial_host<CurveSel>(xyz, out); }
-int ZK_SYM(msm_batch_pre_end_dev)(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slots, const size_t* lens, uint64_t* out_xyz,
-                                  uint64_t* out_xy, uint8_t* out_inf) {
-    return msm_batch_pre_end<CurveSel>(c, s, n_jobs, slots, lens, out_xyz, out_xy, out_inf);
-}
-int ZK_SYM(g1_jacobian_to_affine_host)(const uint64_t* xyz, uint64_t* out_xy, uint8_t* out_inf) {
-    return jac_to_affine<CurveSel::Fq>(xyz, out_xy, out_inf);
-}
-int ZK_SYM(g1_sum_partials_host)(const uint64_t* partials, size_t count, uint64_t* out_xy, uint8_t* out_inf) {
-    return sum_partials<CurveSel::Fq>(partials, count, out_xy, out_inf);
-}
+// this curve's table of entry points (ctx.h: MsmOps), member by member as the struct declares them.  Host pass only: the device pass
+// would emit a constant global as a device variable, and these functions do not exist there.
+#ifndef __HIP_DEVICE_COMPILE__
+extern const MsmOps ZK_SYM(msm_ops) = {
+    msm_run<CurveSel>,
+    ZK_SYM(msm_fixed_base_dev),
+    ZK_SYM(msm_precompute_dev),
+    msm_run_pre<CurveSel>,
+    msm_batch_pre<CurveSel>,
+    [](zk_ctx* c, zk_srs* s, uint32_t slot0, uint32_t n_polys, const void* const* d_coeffs, const size_t* lens, const uint8_t* kinds,
+       const std::function<int(uint32_t)>* before_job) { return msm_batch_pre_begin<CurveSel>(c, s, slot0, n_polys, d_coeffs, lens, kinds, before_job, nullptr); },
+    msm_batch_pre_reduce<CurveSel>,
+    msm_batch_pre_end<CurveSel>,
+    partial_dev_supported<CurveSel>,
+    ZK_SYM(msm_partial_dev_bytes),
+    sum_winsums_dev<CurveSel>,
+    [](const uint64_t* xyz, void* out) {
+        jacobian_to_partial_host<CurveSel>(xyz, out);
+        return (int)ZK_OK;
+    },
+    ZK_SYM(msm_convert_bases_dev),
+    ZK_SYM(msm_point_bytes),
+    jac_to_affine<CurveSel::Fq>,
+    sum_partials<CurveSel::Fq>,
+};
+#endif

@@ -407,10 +407,9 @@ int ntt_run_batch_dev(zk_ctx* c, int curve, int kind, uint32_t log_n, uint32_t n
     if (kind < 0 || kind > 3) return ZK_ERR_BAD_ARG;
     for (uint32_t base = 0; base < n_polys; base += 16) {
         const uint32_t cnt = n_polys - base < 16 ? n_polys - base : 16;
-        int rc;
-        if (curve == ZK_CURVE_BLS12_381) rc = ntt_run<CurveBls>(c, kind, log_n, cnt, d_ins + base, in_lens + base, d_outs + base);
-        else if (curve == ZK_CURVE_BN254) rc = ntt_run<CurveBn>(c, kind, log_n, cnt, d_ins + base, in_lens + base, d_outs + base);
-        else return ZK_ERR_BAD_ARG;
+        const int rc = zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) {
+            return ntt_run<decltype(cv)>(c, kind, log_n, cnt, d_ins + base, in_lens + base, d_outs + base);
+        });
         if (rc) return rc;
     }
     return ZK_OK;
@@ -420,16 +419,11 @@ int ntt_prepare(zk_ctx* c, int curve, uint32_t log_n) {
     NttPlan* pl;
     if (log_n < 3) return ZK_OK;
     for (int inv = 0; inv < 2; ++inv) {
-        int rc;
-        if (curve == ZK_CURVE_BLS12_381) {
-            if (log_n > (uint32_t)FrBls12_381Params::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
-            rc = get_plan<CurveBls>(c, log_n, inv != 0, &pl);
-        } else if (curve == ZK_CURVE_BN254) {
-            if (log_n > (uint32_t)FrBn254Params::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
-            rc = get_plan<CurveBn>(c, log_n, inv != 0, &pl);
-        } else {
-            return ZK_ERR_BAD_ARG;
-        }
+        const int rc = zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) {
+            typedef decltype(cv) Cv;
+            if (log_n > (uint32_t)Cv::FrP::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
+            return get_plan<Cv>(c, log_n, inv != 0, &pl);
+        });
         if (rc) return rc;
     }
     return ZK_OK;
@@ -451,12 +445,11 @@ static int fr_convert_on(int curve, int to_mont, const void* d_in, size_t n, voi
     if (n == 0) return ZK_OK;
     const int T = 256;
     unsigned blocks = (unsigned)((n + T - 1) / T);
-    if (curve == ZK_CURVE_BLS12_381)
-        hipLaunchKernelGGL(fr_convert_kernel<FrBls>, dim3(blocks), dim3(T), 0, st, d_in, d_out, (uint64_t)n, to_mont);
-    else if (curve == ZK_CURVE_BN254)
-        hipLaunchKernelGGL(fr_convert_kernel<FrBn>, dim3(blocks), dim3(T), 0, st, d_in, d_out, (uint64_t)n, to_mont);
-    else
-        return ZK_ERR_BAD_ARG;
+    const int rc = zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) {
+        hipLaunchKernelGGL(fr_convert_kernel<typename decltype(cv)::Fr>, dim3(blocks), dim3(T), 0, st, d_in, d_out, (uint64_t)n, to_mont);
+        return ZK_OK;
+    });
+    if (rc) return rc;
     ZK_HIP_TRY(hipGetLastError());
     return ZK_OK;
 }
@@ -473,12 +466,11 @@ int fr_mul_dev(zk_ctx* c, int curve, const void* a, const void* b, size_t n, voi
     if (n == 0) return ZK_OK;
     const int T = 256;
     unsigned blocks = (unsigned)((n + T - 1) / T);
-    if (curve == ZK_CURVE_BLS12_381)
-        hipLaunchKernelGGL(fr_mul_kernel<FrBls>, dim3(blocks), dim3(T), 0, c->stream, a, b, out, (uint64_t)n);
-    else if (curve == ZK_CURVE_BN254)
-        hipLaunchKernelGGL(fr_mul_kernel<FrBn>, dim3(blocks), dim3(T), 0, c->stream, a, b, out, (uint64_t)n);
-    else
-        return ZK_ERR_BAD_ARG;
+    const int rc = zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) {
+        hipLaunchKernelGGL(fr_mul_kernel<typename decltype(cv)::Fr>, dim3(blocks), dim3(T), 0, c->stream, a, b, out, (uint64_t)n);
+        return ZK_OK;
+    });
+    if (rc) return rc;
     ZK_HIP_TRY(hipGetLastError());
     return ZK_OK;
 }

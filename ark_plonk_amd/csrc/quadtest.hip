@@ -85,7 +85,5 @@ int run(zk_ctx* c, uint32_t n_quads, uint32_t* h_out) {
 }  // namespace
 
 int quad_selftest_dev(zk_ctx* c, int curve, uint32_t n_quads, uint32_t* out2) {
-    if (curve == ZK_CURVE_BLS12_381) return run<CurveBls>(c, n_quads, out2);
-    if (curve == ZK_CURVE_BN254) return run<CurveBn>(c, n_quads, out2);
-    return ZK_ERR_BAD_ARG;
+    return zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) { return run<decltype(cv)>(c, n_quads, out2); });
 }

@@ -364,7 +364,5 @@ int quotient_run(zk_ctx* c, uint32_t log_n, const zk_quotient_args* q, void* d_o
 }  // namespace
 
 int quotient_evals_dev(zk_ctx* c, int curve, uint32_t log_n, const zk_quotient_args* q, void* d_out) {
-    if (curve == ZK_CURVE_BLS12_381) return quotient_run<CurveBls>(c, log_n, q, d_out);
-    if (curve == ZK_CURVE_BN254) return quotient_run<CurveBn>(c, log_n, q, d_out);
-    return ZK_ERR_BAD_ARG;
+    return zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) { return quotient_run<decltype(cv)>(c, log_n, q, d_out); });
 }

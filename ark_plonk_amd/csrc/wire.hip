@@ -306,44 +306,44 @@ struct zk_transcript {
     explicit zk_transcript(const uint8_t* l, size_t n) : st((const uint8_t*)"Merlin v1.0", 11) { transcript_append(st, (const uint8_t*)"dom-sep", 7, l, n); }
 };
 
-#define WIRE_DISPATCH(curve_id, expr_bls, expr_bn)          \
-    do {                                                    \
-        if ((curve_id) == ZK_CURVE_BLS12_381) return expr_bls; \
-        if ((curve_id) == ZK_CURVE_BN254) return expr_bn;   \
-        return ZK_ERR_BAD_ARG;                              \
-    } while (0)
+// `call` on the curve's Wire<Cv>, written with W for that type
+#define WIRE_DISPATCH(curve_id, call)                                    \
+    return zk_on_curve(curve_id, ZK_ERR_BAD_ARG, [&](auto cv) {          \
+        typedef Wire<decltype(cv)> W;                                    \
+        return call;                                                     \
+    })
 
 extern "C" {
 
 size_t zk_fr_serialized_size(int curve_id) {
-    return curve_id == ZK_CURVE_BLS12_381 ? Wire<CurveBls>::FR_BYTES : curve_id == ZK_CURVE_BN254 ? Wire<CurveBn>::FR_BYTES : 0;
+    return zk_on_curve(curve_id, (size_t)0, [](auto cv) { return (size_t)Wire<decltype(cv)>::FR_BYTES; });
 }
 size_t zk_g1_compressed_size(int curve_id) {
-    return curve_id == ZK_CURVE_BLS12_381 ? Wire<CurveBls>::FQ_BYTES : curve_id == ZK_CURVE_BN254 ? Wire<CurveBn>::FQ_BYTES : 0;
+    return zk_on_curve(curve_id, (size_t)0, [](auto cv) { return (size_t)Wire<decltype(cv)>::FQ_BYTES; });
 }
 int zk_fr_serialize(int curve_id, const uint64_t* fr_mont, uint8_t* out) {
     if (!fr_mont || !out) return ZK_ERR_BAD_ARG;
-    WIRE_DISPATCH(curve_id, Wire<CurveBls>::fr_ser(fr_mont, out), Wire<CurveBn>::fr_ser(fr_mont, out));
+    WIRE_DISPATCH(curve_id, W::fr_ser(fr_mont, out));
 }
 int zk_fr_deserialize(int curve_id, const uint8_t* in, uint64_t* fr_mont) {
     if (!fr_mont || !in) return ZK_ERR_BAD_ARG;
-    WIRE_DISPATCH(curve_id, Wire<CurveBls>::fr_de(in, fr_mont), Wire<CurveBn>::fr_de(in, fr_mont));
+    WIRE_DISPATCH(curve_id, W::fr_de(in, fr_mont));
 }
 int zk_g1_serialize_compressed(int curve_id, const uint64_t* xy_mont, uint8_t inf, uint8_t* out) {
     if (!xy_mont || !out) return ZK_ERR_BAD_ARG;
-    WIRE_DISPATCH(curve_id, Wire<CurveBls>::g1_ser_c(xy_mont, inf, out), Wire<CurveBn>::g1_ser_c(xy_mont, inf, out));
+    WIRE_DISPATCH(curve_id, W::g1_ser_c(xy_mont, inf, out));
 }
 int zk_g1_deserialize_compressed(int curve_id, const uint8_t* in, uint64_t* xy_mont, uint8_t* inf) {
     if (!xy_mont || !in) return ZK_ERR_BAD_ARG;
-    WIRE_DISPATCH(curve_id, Wire<CurveBls>::g1_de_c(in, xy_mont, inf), Wire<CurveBn>::g1_de_c(in, xy_mont, inf));
+    WIRE_DISPATCH(curve_id, W::g1_de_c(in, xy_mont, inf));
 }
 int zk_g1_serialize_uncompressed(int curve_id, const uint64_t* xy_mont, uint8_t inf, uint8_t* out) {
     if (!xy_mont || !out) return ZK_ERR_BAD_ARG;
-    WIRE_DISPATCH(curve_id, Wire<CurveBls>::g1_ser_u(xy_mont, inf, out), Wire<CurveBn>::g1_ser_u(xy_mont, inf, out));
+    WIRE_DISPATCH(curve_id, W::g1_ser_u(xy_mont, inf, out));
 }
 int zk_g1_deserialize_uncompressed(int curve_id, const uint8_t* in, uint64_t* xy_mont, uint8_t* inf) {
     if (!xy_mont || !in) return ZK_ERR_BAD_ARG;
-    WIRE_DISPATCH(curve_id, Wire<CurveBls>::g1_de_u(in, xy_mont, inf), Wire<CurveBn>::g1_de_u(in, xy_mont, inf));
+    WIRE_DISPATCH(curve_id, W::g1_de_u(in, xy_mont, inf));
 }
 
 zk_transcript* zk_transcript_new(const uint8_t* label, size_t label_len) {
@@ -381,7 +381,7 @@ int zk_transcript_append_g1(zk_transcript* t, int curve_id, const uint8_t* label
 }
 int zk_transcript_challenge_scalar(zk_transcript* t, int curve_id, const uint8_t* label, size_t label_len, uint64_t* fr_mont) {
     if (!t || !fr_mont || (!label && label_len)) return ZK_ERR_BAD_ARG;
-    WIRE_DISPATCH(curve_id, Wire<CurveBls>::challenge(t->st, label, label_len, fr_mont), Wire<CurveBn>::challenge(t->st, label, label_len, fr_mont));
+    WIRE_DISPATCH(curve_id, W::challenge(t->st, label, label_len, fr_mont));
 }
 // `PublicInputs { values: BTreeMap<usize, F> }` (pi.rs:28-36) under `label` (prover.rs:182 uses b"pi"):
 // u64 count, then (u64 position, Fr) in ascending position order.  `PublicInputs::insert` (pi.rs:56-65) drops zero values
@@ -440,7 +440,7 @@ int zk_proof_serialize(int curve_id, const zk_proof* p, uint8_t* out, size_t cap
     }
     const size_t need = zk_proof_serialized_size(curve_id, p->n_custom_evals, ll.data());
     if (cap < need) return ZK_ERR_BAD_ARG;
-    const int L = curve_id == ZK_CURVE_BLS12_381 ? 6 : 4;
+    const int L = zk_on_curve(curve_id, 4, [](auto cv) { return (int)decltype(cv)::Fq::N / 2; });   // an unknown id was refused above
     uint8_t* w = out;
     int rc;
     for (int i = 0; i < 13; ++i) {

@@ -9,7 +9,7 @@
 //   key'_i = key_l[i] + xi key_r[i]   (ipa_fold_key: one variable-base scalar multiplication per point, xi shared by every lane)
 //   a' = a_l + xi^-1 a_r, b' = b_l + xi b_r   (ipa_scalar_pass: also the canonical copy of a' and the next round's inner products)
 // Round 0 reads the registered key itself (SRS window-table path); later rounds run the per-window MSM over the folded key.
-#include "../csrc/ctx.h"
+#include "../csrc/api_internal.h"
 
 #include <shared_mutex>
 
@@ -275,20 +275,6 @@ __global__ void __launch_bounds__(256) ipa_to_abi(const void* src, uint64_t n, u
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-struct Guard {
-    zk_ctx* c;
-    std::unique_lock<std::recursive_mutex> lk;
-    int prev = -1;
-    explicit Guard(zk_ctx* ctx) : c(ctx), lk(ctx->mu) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != c->device) (void)hipSetDevice(c->device);
-    }
-    ~Guard() {
-        if (prev >= 0 && prev != c->device) (void)hipSetDevice(prev);
-    }
-};
-
-inline bool curve_ok(int curve) { return curve == ZK_CURVE_BLS12_381 || curve == ZK_CURVE_BN254; }
 inline bool pow2(size_t x) { return x && !(x & (x - 1)); }
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline uint64_t blocks_of(uint64_t n, uint64_t t) { return (n + t - 1) / t; }
@@ -299,7 +285,7 @@ struct Layout {
 };
 inline Layout layout(int curve, size_t d1) {
     Layout l;
-    const size_t pb = msm_point_bytes(curve);
+    const size_t pb = msm_ops(curve)->point_bytes();
     const size_t half = d1 / 2 ? d1 / 2 : 1;
     const size_t n_part = blocks_of(d1 / 2 ? d1 / 2 : 1, SP_T) + 1;
     l.key = 0;
@@ -308,9 +294,6 @@ inline Layout layout(int curve, size_t d1) {
     l.total = l.partials + up256(n_part * 64);
     return l;
 }
-
-// a deferred KZG round holds the ctx's MSM buffer sets until zk_kzg_round_end
-inline bool round_open(const zk_ctx* c) { return c->pend_n != 0; }
 
 template <class Fr>
 bool fr_reduced(const uint64_t* m, Fr& out) {
@@ -411,7 +394,7 @@ void add_scaled(const uint64_t* xyz, const uint64_t* q_xy, const typename Cv::Fr
 // NULL handles, a key of another device, a key length that is not a power of two: ZK_ERR_BAD_ARG
 inline int check_key(zk_ctx* c, zk_srs* s) {
     if (!c || !s) return ZK_ERR_BAD_ARG;
-    if (s->device != c->device || !curve_ok(s->curve) || !pow2(s->n)) return ZK_ERR_BAD_ARG;
+    if (s->device != c->device || !zk_curve_ok(s->curve) || !pow2(s->n)) return ZK_ERR_BAD_ARG;
     return ZK_OK;
 }
 // m fits the key: round / fold j works on vectors of 2m <= d1 (first round: 2m = d1 exactly at the top, or any smaller power of two)
@@ -443,16 +426,16 @@ int round_impl(zk_ctx* c, zk_srs* s, int first_round, size_t m, void* d_a, void*
         ip1 = Fr::add(ip1, x);
         ip2 = Fr::add(ip2, y);
     }
-    uint64_t xyz_l[18], xyz_r[18];
+    uint64_t xyz_l[ZK_MAX_JACOBIAN64], xyz_r[ZK_MAX_JACOBIAN64];
     const char* ac = (const char*)a_can;
     if (first_round) {
         if (s->pre_wstep > 1) return ZK_ERR_UNSUPPORTED;    // a window-sharded key returns partials: not an opening's MSM
         if ((rc = zk_msm_g1_srs_partial_dev(c, s, 0, ac + 32 * m, m, xyz_l))) return rc;
         if ((rc = zk_msm_g1_srs_partial_dev(c, s, m, ac, m, xyz_r))) return rc;
     } else {
-        const size_t pb = msm_point_bytes(s->curve);
-        if ((rc = msm_run_dev(c, s->curve, w + ly.key, ac + 32 * m, m, xyz_l))) return rc;
-        if ((rc = msm_run_dev(c, s->curve, w + ly.key + m * pb, ac, m, xyz_r))) return rc;
+        const size_t pb = msm_ops(s->curve)->point_bytes();
+        if ((rc = msm_ops(s->curve)->run(c, w + ly.key, ac + 32 * m, m, xyz_l))) return rc;
+        if ((rc = msm_ops(s->curve)->run(c, w + ly.key + m * pb, ac, m, xyz_r))) return rc;
     }
     add_scaled<Cv>(xyz_l, h_prime_xy, ip1, out_lr_xy, out_lr_inf);
     add_scaled<Cv>(xyz_r, h_prime_xy, ip2, out_lr_xy + 2 * L64, out_lr_inf ? out_lr_inf + 1 : nullptr);
@@ -542,14 +525,14 @@ void internal_to_abi_host(const void* pt, uint64_t* out_xy, uint8_t* out_inf) {
 
 // ------------------------------------------------------------------------------------------------------------------------ C ABI
 size_t zk_ipa_workspace_bytes(int curve_id, size_t d1) {
-    if (!curve_ok(curve_id) || !pow2(d1)) return 0;
+    if (!zk_curve_ok(curve_id) || !pow2(d1)) return 0;
     return layout(curve_id, d1).total;
 }
 
 int zk_ipa_powers_dev(zk_ctx* c, int curve_id, const uint64_t* point_mont, size_t n, void* d_out) {
-    if (!c || !curve_ok(curve_id) || !point_mont || (n && !d_out)) return ZK_ERR_BAD_ARG;
+    if (!c || !zk_curve_ok(curve_id) || !point_mont || (n && !d_out)) return ZK_ERR_BAD_ARG;
     Guard g(c);
-    return curve_id == ZK_CURVE_BLS12_381 ? powers_impl<CurveBls>(c, point_mont, n, d_out) : powers_impl<CurveBn>(c, point_mont, n, d_out);
+    return zk_on_curve(curve_id, ZK_ERR_BAD_ARG, [&](auto cv) { return powers_impl<decltype(cv)>(c, point_mont, n, d_out); });
 }
 
 int zk_ipa_round_dev(zk_ctx* c, zk_srs* key, int first_round, size_t m, const void* d_a, const void* d_b, void* d_work,
@@ -561,8 +544,8 @@ int zk_ipa_round_dev(zk_ctx* c, zk_srs* key, int first_round, size_t m, const vo
     if (round_open(c)) return ZK_ERR_PENDING;
     void* a = const_cast<void*>(d_a);    // the first round's scalar pass reads a, b (FOLD = false writes neither)
     void* b = const_cast<void*>(d_b);
-    return key->curve == ZK_CURVE_BLS12_381 ? round_impl<CurveBls>(c, key, first_round, m, a, b, d_work, h_prime_xy, out_lr_xy, out_lr_inf)
-                                            : round_impl<CurveBn>(c, key, first_round, m, a, b, d_work, h_prime_xy, out_lr_xy, out_lr_inf);
+    return zk_on_curve(key->curve, ZK_ERR_BAD_ARG,
+                       [&](auto cv) { return round_impl<decltype(cv)>(c, key, first_round, m, a, b, d_work, h_prime_xy, out_lr_xy, out_lr_inf); });
 }
 
 int zk_ipa_fold_dev(zk_ctx* c, zk_srs* key, int first_round, size_t m, const uint64_t* xi_mont, void* d_a, void* d_b, void* d_work) {
@@ -570,44 +553,42 @@ int zk_ipa_fold_dev(zk_ctx* c, zk_srs* key, int first_round, size_t m, const uin
     if (rc) return rc;
     if (!m_fits(key, first_round, m) || !xi_mont || !d_a || !d_b || !d_work) return ZK_ERR_BAD_ARG;
     Guard g(c);
-    return key->curve == ZK_CURVE_BLS12_381 ? fold_impl<CurveBls>(c, key, first_round, m, xi_mont, d_a, d_b, d_work)
-                                            : fold_impl<CurveBn>(c, key, first_round, m, xi_mont, d_a, d_b, d_work);
+    return zk_on_curve(key->curve, ZK_ERR_BAD_ARG, [&](auto cv) { return fold_impl<decltype(cv)>(c, key, first_round, m, xi_mont, d_a, d_b, d_work); });
 }
 
 int zk_ipa_final_key_dev(zk_ctx* c, int curve_id, const void* d_work, uint64_t* out_xy, uint8_t* out_inf) {
-    if (!c || !curve_ok(curve_id) || !d_work || !out_xy) return ZK_ERR_BAD_ARG;
+    if (!c || !zk_curve_ok(curve_id) || !d_work || !out_xy) return ZK_ERR_BAD_ARG;
     Guard g(c);
     uint64_t pt[32];
-    const size_t pb = msm_point_bytes(curve_id);
+    const size_t pb = msm_ops(curve_id)->point_bytes();
     if (pb > sizeof pt) return ZK_ERR_UNSUPPORTED;
     int rc = zk_d2h(c, pt, d_work, pb, c->stream);
     if (rc) return rc;
-    if (curve_id == ZK_CURVE_BLS12_381) internal_to_abi_host<CurveBls>(pt, out_xy, out_inf);
-    else internal_to_abi_host<CurveBn>(pt, out_xy, out_inf);
-    return ZK_OK;
+    return zk_on_curve(curve_id, ZK_ERR_BAD_ARG, [&](auto cv) {
+        internal_to_abi_host<decltype(cv)>(pt, out_xy, out_inf);
+        return ZK_OK;
+    });
 }
 
 int zk_ipa_fold_key_dev(zk_ctx* c, int curve_id, size_t m, const void* d_key_xy, const uint8_t* d_key_inf, const uint64_t* xi_mont,
                         void* d_out_xy, uint8_t* d_out_inf) {
-    if (!c || !curve_ok(curve_id) || !xi_mont || (m && (!d_key_xy || !d_out_xy))) return ZK_ERR_BAD_ARG;
+    if (!c || !zk_curve_ok(curve_id) || !xi_mont || (m && (!d_key_xy || !d_out_xy))) return ZK_ERR_BAD_ARG;
     Guard g(c);
     if (m == 0) return ZK_OK;
-    const size_t pb = msm_point_bytes(curve_id);
+    const size_t pb = msm_ops(curve_id)->point_bytes();
     void* tmp = nullptr;
     if (hipMalloc(&tmp, 3 * m * pb) != hipSuccess) return ZK_ERR_OOM;
     void* folded = (char*)tmp + 2 * m * pb;
-    int rc = msm_convert_bases_dev(c, curve_id, d_key_xy, d_key_inf, 2 * m, tmp);
-    if (!rc) rc = curve_id == ZK_CURVE_BLS12_381 ? launch_fold_key<CurveBls>(c, tmp, folded, m, xi_mont)
-                                                 : launch_fold_key<CurveBn>(c, tmp, folded, m, xi_mont);
-    if (!rc) rc = curve_id == ZK_CURVE_BLS12_381 ? to_abi<CurveBls>(c, folded, m, d_out_xy, d_out_inf) : to_abi<CurveBn>(c, folded, m, d_out_xy, d_out_inf);
+    int rc = msm_ops(curve_id)->convert_bases(c, d_key_xy, d_key_inf, 2 * m, tmp);
+    if (!rc) rc = zk_on_curve(curve_id, ZK_ERR_BAD_ARG, [&](auto cv) { return launch_fold_key<decltype(cv)>(c, tmp, folded, m, xi_mont); });
+    if (!rc) rc = zk_on_curve(curve_id, ZK_ERR_BAD_ARG, [&](auto cv) { return to_abi<decltype(cv)>(c, folded, m, d_out_xy, d_out_inf); });
     if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = ZK_ERR_HIP;
     (void)hipFree(tmp);
     return rc;
 }
 
 int zk_ipa_check_coeffs_dev(zk_ctx* c, int curve_id, uint32_t log_d, const uint64_t* xis_mont, void* d_out) {
-    if (!c || !curve_ok(curve_id) || log_d > 32 || !d_out || (log_d && !xis_mont)) return ZK_ERR_BAD_ARG;
+    if (!c || !zk_curve_ok(curve_id) || log_d > 32 || !d_out || (log_d && !xis_mont)) return ZK_ERR_BAD_ARG;
     Guard g(c);
-    return curve_id == ZK_CURVE_BLS12_381 ? check_coeffs_impl<CurveBls>(c, curve_id, log_d, xis_mont, d_out)
-                                          : check_coeffs_impl<CurveBn>(c, curve_id, log_d, xis_mont, d_out);
+    return zk_on_curve(curve_id, ZK_ERR_BAD_ARG, [&](auto cv) { return check_coeffs_impl<decltype(cv)>(c, curve_id, log_d, xis_mont, d_out); });
 }

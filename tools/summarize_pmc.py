@@ -44,6 +44,10 @@ def main():
         commit = open(os.path.join(here, "..", ".git_head")).read().strip() or "unknown"
     except OSError:
         pass
+    # the device code the counters describe (tests/test_abi.py recompiles it and compares)
+    sys.path.insert(0, os.path.join(here, ".."))
+    from ark_plonk_amd import build as zk_build
+    code = {name: zk_build.device_code_sha256(units) for name, units in zk_build.PMC_UNITS.items()}
     import datetime
     collected = f"{datetime.date.today().isoformat()}, 1x MI355X (gpurun box), tools/collect_profiles.sh {os.path.basename(out).split('_')[0]}: the same session as " \
                 f"{os.path.basename(out).split('_')[0]}_bench_n20.md / _pmc_sq.md / _pmc_clock.md (one discarded run first)"
@@ -55,7 +59,7 @@ def main():
                        "hbm_bytes_per_launch": (2 * f + w) * 1024,
                        "note": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes over `{cmd}`; per-launch averages; "
                                "FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies 128-B requests at 64 B), WRITE_SIZE as read.",
-                       "collected": collected, "commit": commit},
+                       "collected": collected, "commit": commit, "device_code_sha256": code["pmc_msm_accumulate.json"]},
                       open(os.path.join(top, "pmc_msm_accumulate.json"), "w"), indent=1)
             # the NTT passes of the same run, per proof: proofs = accumulate launches / launches per proof (ZK_ACC_LAUNCHES_PER_PROOF, default 5)
             per_proof = int(os.environ.get("ZK_ACC_LAUNCHES_PER_PROOF", "5"))
@@ -66,7 +70,7 @@ def main():
                        "alg_bytes_per_proof_n20": 17 * 2 * 32 * (1 << 20) + 14 * 2 * 32 * (1 << 22),
                        "note": f"sum over the NTT pass kernels of (2 x FETCH_SIZE + WRITE_SIZE) KiB x launches, divided by the {proofs} proofs of `{cmd}` "
                                "(counted from the accumulate launches); separate --pmc passes, FETCH_SIZE doubled per MI355X_MICROARCH.md",
-                       "collected": collected, "commit": commit},
+                       "collected": collected, "commit": commit, "device_code_sha256": code["pmc_ntt.json"]},
                       open(os.path.join(top, "pmc_ntt.json"), "w"), indent=1)
             break
     print(open(out + ".md").read())
