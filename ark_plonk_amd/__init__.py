@@ -13,6 +13,8 @@ from .curves import BLS12_381, BN254, get_curve  # noqa: F401
 from .domain import GeneralEvaluationDomain, Radix2EvaluationDomain  # noqa: F401
 from . import linearisation, lookup, permutation, prover, quotient, transcript  # noqa: F401
 from . import _lib, msm  # noqa: F401
+from . import compile  # noqa: F401  (circuit description -> ProverKey / VerifierKey / seeded transcript)
+from .compile import CircuitDescription, VerifierKey, assign  # noqa: F401
 from .msm import (CommitterKey, G1Affine, VariableBaseMSM, kzg_witness, srs_cache_config, srs_cache_stats, sum_partials,  # noqa: F401
                   sum_partials_batch)
 

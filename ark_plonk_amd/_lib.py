@@ -159,6 +159,9 @@ SYMBOLS = {
     "zk_ipa_final_key_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "zk_ipa_fold_key_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_ipa_check_coeffs_dev": (c_int, [c_void_p, c_int, c_u32, c_void_p, c_void_p]),
+    # circuit compilation: the wire permutation from the variable map, the witness gather
+    "zk_perm_sigma_dev": (c_int, [c_void_p, c_int, c_u32, c_void_p, c_void_p, c_size_t, c_u32, c_void_p, ctypes.POINTER(c_void_p)]),
+    "zk_fr_gather_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "zk_fr_serialized_size": (c_size_t, [c_int]),
     "zk_g1_compressed_size": (c_size_t, [c_int]),
     "zk_fr_serialize": (c_int, [c_int, c_void_p, ctypes.c_char_p]),

@@ -44,6 +44,8 @@ def jobs():
         ("msm_dispatch.o", "msm_dispatch.hip", [], HOST_HDRS),
         # the inner-product-argument commitment (csrc_ipa/): a directory of its own, so that csrc/ keeps its kernel build
         ("ipa.o", "../csrc_ipa/ipa.hip", [], API_HDRS),
+        # circuit compilation (csrc_compile/): the wire permutation from the variable map and the witness gather
+        ("compile.o", "../csrc_compile/compile.hip", [], API_HDRS),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

@@ -2,6 +2,8 @@
 one of the library's entry points, the transcript is the library's merlin, and the result is a `Proof` whose bytes are the
 reference's serialisation (proof.rs:41-103).  The circuit comes in as what the composer and `preprocess.rs` hand the prover:
 the four padded wire columns, the public inputs, and a prover key built from selector / sigma / table evaluation vectors.
+Where those come from for a circuit given by variables -- the sigma vectors from the variable map, the padded columns, the
+verifier key and the seeded transcript -- is `compile.py` (`compile`, `assign`).
 
     round 1  4 iffts, 4 commitments                                              prover.rs:188-226
     round 2  compressed table, query column, combine_split, 4 iffts, 3 commits   prover.rs:228-321   (lookup.py)

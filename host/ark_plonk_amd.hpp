@@ -370,6 +370,24 @@ inline DeviceVec permutation_evals(const Radix2EvaluationDomain& d, const Device
           "zk_perm_product_dev");
     return out;
 }
+// Permutation::compute_sigma_permutations + compute_permutation_lagrange (permutation/mod.rs:101-169): the four sigma evaluation
+// vectors from the variable map's insertion list (u32 variable / position = wire * n + row, device buffers of m entries, call order)
+inline std::vector<DeviceVec> sigma_evals(const Radix2EvaluationDomain& d, const void* d_ins_var, const void* d_ins_pos, size_t m, uint32_t num_vars) {
+    std::vector<DeviceVec> out;
+    void* p[4];
+    for (int k = 0; k < 4; ++k) {
+        out.emplace_back(d.context(), d.size());
+        p[k] = out[k].data();
+    }
+    check(zk_perm_sigma_dev(d.context().handle(), d.curve(), d.log_size_of_group(), d_ins_var, d_ins_pos, m, num_vars, nullptr, p), "zk_perm_sigma_dev");
+    return out;
+}
+// to_scalars (prover.rs:188-192): out[i] = values[index[i]]; d_index: n u32 on the device
+inline DeviceVec gather(Context& ctx, int curve, const DeviceVec& values, const void* d_index, size_t n) {
+    DeviceVec out(ctx, n);
+    check(zk_fr_gather_dev(ctx.handle(), curve, values.data(), values.size(), d_index, n, out.data()), "zk_fr_gather_dev");
+    return out;
+}
 // compute_lookup_permutation_poly up to its ifft (permutation/mod.rs:754-797)
 inline DeviceVec lookup_permutation_evals(Context& ctx, int curve, const DeviceVec& f, const DeviceVec& t, const DeviceVec& h1,
                                           const DeviceVec& h2, const uint64_t* delta_mont, const uint64_t* epsilon_mont) {

@@ -563,6 +563,27 @@ int zk_ipa_fold_key_dev(zk_ctx* ctx, int curve_id, size_t m, const void* d_key_x
  * the verifier's final-key MSM (xis_mont: log_d Montgomery challenges, xi_0 first; log_d <= 32) */
 int zk_ipa_check_coeffs_dev(zk_ctx* ctx, int curve_id, uint32_t log_d, const uint64_t* xis_mont, void* d_out);
 
+/* ---- circuit compilation (Circuit::compile, circuit.rs:226-259 -> preprocess.rs:126-423) ------------------------------------- */
+/* The wire permutation: `Permutation::compute_sigma_permutations` + `compute_permutation_lagrange` (permutation/mod.rs:101-169).
+ * n = 2^log_n.  A position is wire * n + row, wire 0..3 = Left, Right, Output, Fourth.  d_ins_var[k], d_ins_pos[k] (u32, device,
+ * k < m <= 4n) are the k-th call of `add_variable_to_map(var, wire_data)` IN CALL ORDER (which is not row order: logic.rs:212-218
+ * inserts Output(n - 1) after Left(n)); rows the composer pads and cells it never maps are not in the list.
+ * For every variable with positions p_0 .. p_{c-1} in call order: sigma(p_i) = p_{(i+1) mod c}; a position never inserted maps to
+ * itself.  d_sigma_pos (u32[4n] or NULL) receives sigma; d_sigma_evals (4 device pointers of n Montgomery Fr each, or NULL)
+ * receive d_sigma_evals[w][row] = K_w' * omega^row' for sigma(w n + row) = w' n + row', K = (1, 7, 13, 17), omega the group_gen
+ * zk_domain_new reports for n.  At least one of the two outputs is required.  The result is a pure function of the inputs.
+ * ZK_ERR_BAD_ARG: m > 4n, a position >= 4n, a variable >= num_vars, a position inserted twice (found on the device, reported by one
+ * flag word read back at the end; the outputs are then unspecified); ZK_ERR_DOMAIN_TOO_LARGE: log_n beyond the two-adicity;
+ * ZK_ERR_UNSUPPORTED: log_n > 28 (positions are 32-bit).  m = 0 gives the identity.
+ * Working memory: one device allocation per call, freed before return -- at most 16 m + m / 4 + 2 KiB bytes, + 16 n when
+ * d_sigma_pos is NULL (<= 81 n bytes).  No buffer of the ctx is used: the call runs inside an open deferred round.  Blocks once. */
+int zk_perm_sigma_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* d_ins_var, const void* d_ins_pos, size_t m, uint32_t num_vars,
+                      void* d_sigma_pos, void* const* d_sigma_evals);
+/* `to_scalars` (prover.rs:188-192): d_out[i] = d_values[d_index[i]], i < n; 32-byte elements, d_index u32 on the device.
+ * ZK_ERR_BAD_ARG when an index is >= num_values (same flag mechanism; nothing is read out of range).  Uses no buffer of the ctx
+ * (runs inside an open deferred round).  Blocks once. */
+int zk_fr_gather_dev(zk_ctx* ctx, int curve_id, const void* d_values, size_t num_values, const void* d_index, size_t n, void* d_out);
+
 /* ---- device self-test ------------------------------------------------------------------------------ */
 /* Runs the quad-cooperative point arithmetic of the bucket-reduction kernels (csrc/ecq.cuh) against the
  * single-lane group law on n_quads point pairs incl. doubling, cancellation and infinity cases.
