@@ -303,6 +303,15 @@ constexpr uint32_t PRE_BIG_ROUNDS = 8;
 
 // the table windows are 16 .. 21 bits: up to 16 bits the int16 partition sort (2^15 buckets = 256 partitions of 128)
 inline bool pre_psort16(const PrePlan& pl) { return !pl.wide && pl.g1.nb % (1u << PS_LOB) == 0 && (pl.g1.nb >> PS_LOB) <= 256; }
+// The compact form of the wide partition sort (csort_* in msm_sort.hip): a whole table of folded 17-bit windows whose job owns its
+// staging area.  The folded scalar (< 2^254, the fold's sign in bit 255) waits in the job's set instead of the int32 digits, and the
+// staged record is ONE word: sign << 31 | window << 27 | index inside the slab << 8 | low bucket bits, so at most 16 windows and
+// slabs below 2^19 scalars (nf < 2^31 keeps them below 2^18); from 8 windows on the scalars fit where the references will be.  Every other geometry keeps psortw_*.
+constexpr uint32_t CS_C = 17;
+constexpr uint32_t CS_LOB = CS_C - 9;
+inline bool pre_compact(const PrePlan& pl) {
+    return pl.wide && pl.g.c == CS_C && pl.g.neg && pl.g.W == pl.g.Wt && pl.g.w0 == 0 && pl.g.wstep == 1 && pl.g.W >= 8 && pl.g.W <= 16 && !pl.shared_stage;
+}
 // the device form of a round's result (its virtual-window sums left on the device) needs the quad-cooperative reduction of at most
 // 128 power-of-two virtual windows
 inline bool pre_partial_dev_ok(const PrePlan& p) {

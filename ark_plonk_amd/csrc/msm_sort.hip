@@ -835,6 +835,392 @@ __global__ void __launch_bounds__(PS_T) psortw_final(SJobs jobs, uint32_t P, uin
 }
 
 
+// ---- the compact form of the wide sort: whole tables of folded 17-bit windows (pre_compact, msm_common.cuh) ---------------------
+// What every MSM of a 2^19 .. 2^21 proof runs.  The int32 digit array of psortw_* is a 4 W-byte expansion of a 32-byte scalar that
+// is written once and read once, and its staged record is 6 bytes.  Here
+//   csort_fold_hist  (at submission, the only reader of the caller's vector) leaves the folded canonical scalar in the job's
+//                    `entries` buffer -- it is below 2^254, so bit 255 carries the fold's sign -- and counts the partitions;
+//   csort_scatter    cuts the W digits of its slab's scalars itself (one scalar per lane: a tile is 1024 scalars = 1024 W records,
+//                    so a (tile, partition) run is ~4 W records of 4 bytes) and stages ONE word per reference:
+//                    sign << 31 | window << 27 | index inside the slab << 8 | low 8 bucket bits;
+//   csort_final      recovers the slab of a staged record from its place in the partition (the slab cursors of psort_scan are the
+//                    starts of the slabs' runs) and writes the references in today's format; it reads a partition once.
+// 32 + 32 + 4 W (scatter) + 2 * 4 W + 4 W (final) bytes per scalar instead of 32 + 4 W + 4 W + 6 W + 2 W + 6 W + 4 W.
+
+// 17-bit field w of the scalar (w is a constant after unrolling: plain shifts)
+ZK_D uint32_t cs_bits(const uint32_t (&s)[8], uint32_t w) {
+    const uint32_t pos = w * CS_C, limb = pos >> 5, off = pos & 31;
+    uint64_t v = s[limb < 8 ? limb : 7];
+    if (limb >= 8) v = 0;
+    if (limb + 1 < 8) v |= (uint64_t)s[limb + 1] << 32;
+    return (uint32_t)(v >> off) & ((1u << CS_C) - 1u);
+}
+
+template <class Fr, bool MONT>
+__global__ void __launch_bounds__(256, 8) csort_fold_hist(const uint32_t* scalars, uint64_t n, uint32_t sp, MsmGeom g, uint4* folded,
+                                                       uint32_t* hist /* [256][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
+    __shared__ uint32_t lc[256];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        scan_counter[0] = 0;
+        combine_q[0] = 0;
+        combine_q[1] = 0;
+    }
+    lc[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t lo = (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n;
+    const uint64_t hi = lo + sp < n ? lo + sp : n;
+    constexpr uint32_t half = 1u << (CS_C - 1);
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * i;
+        uint4 a = q[0], b = q[1];
+        Fr x;
+        x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
+        x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
+        if (MONT) x = Fr::from_mont(x);
+        const bool flip = scalar_fold(x.v, g);        // now x <= (r - 1) / 2 < 2^254
+        uint32_t carry = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 16; ++w) {
+            if (w < g.W) {
+                const uint32_t raw = cs_bits(x.v, w) + carry;
+                carry = raw >= half ? 1u : 0u;
+                const uint32_t mag = carry ? (1u << CS_C) - raw : raw;      // |digit|: the sign does not move the bucket
+                if (mag != 0) atomicAdd(&lc[(mag - 1) >> CS_LOB], 1u);
+            }
+        }
+        folded[2 * i] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
+        folded[2 * i + 1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7] | (flip ? 0x80000000u : 0u));
+    }
+    __syncthreads();
+    hist[(uint64_t)threadIdx.x * PS_SLABS + blockIdx.x] = lc[threadIdx.x];
+}
+
+// dynamic LDS: rec[W * PS_T].  Record in LDS: partition << 23 | sign << 22 | window << 18 | lane << 8 | low bucket bits.
+// Two workgroups per CU, as psortw_scatter has (8 waves per SIMD = 64 registers, under 80 KiB of LDS): one places its tile while the
+// other loads.
+__global__ void __launch_bounds__(PS_T, 8) csort_scatter(SJobs jobs, uint32_t W) {
+    extern __shared__ uint32_t rec[];
+    const SJob& J = jobs.j[blockIdx.y];
+    const uint4* folded = (const uint4*)J.dig;
+    const uint64_t n = J.n;
+    const uint32_t sp = J.sp;
+    const uint32_t* cursors = J.hist;
+    const uint32_t* part_start = J.part_start;
+    uint32_t* stage = J.stage_ref;
+    constexpr uint32_t LOM = (1u << CS_LOB) - 1u, half = 1u << (CS_C - 1);
+    __shared__ uint32_t cnt[256], toff[257], gcur[256], stmp[4];
+    const uint32_t t = threadIdx.x;
+    if (t < 256) gcur[t] = part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x];
+    const uint64_t lo = (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n;
+    const uint64_t hi = lo + sp < n ? lo + sp : n;
+    const uint32_t len = (uint32_t)(hi - lo);
+    // the scalars of the tile after the current one are requested while the current one is cut, counted and placed
+    uint4 na = make_uint4(0, 0, 0, 0), nb = na;
+    auto fetch = [&](uint32_t tb) {
+        if (tb + t < len) {
+            na = folded[2 * (lo + tb + t)];
+            nb = folded[2 * (lo + tb + t) + 1];
+        }
+    };
+    if (len) fetch(0);
+    for (uint32_t tb = 0; tb < len; tb += PS_T) {
+        __syncthreads();
+        if (t < 256) cnt[t] = 0;
+        __syncthreads();
+        const bool have = tb + t < len;
+        uint32_t s[8] = {na.x, na.y, na.z, na.w, nb.x, nb.y, nb.z, nb.w & 0x7fffffffu};
+        const uint32_t flip = nb.w >> 31;
+        if (tb + PS_T < len) fetch(tb + PS_T);
+        uint32_t pk[16];
+        uint32_t carry = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 16; ++w) {
+            pk[w] = 0xffffffffu;
+            if (have && w < W) {
+                const uint32_t raw = cs_bits(s, w) + carry;
+                carry = raw >= half ? 1u : 0u;
+                const uint32_t mag = carry ? (1u << CS_C) - raw : raw;
+                if (mag != 0) {
+                    const uint32_t b = mag - 1;
+                    pk[w] = ((b >> CS_LOB) << 23) | ((carry ^ flip) << 22) | (w << 18) | (t << 8) | (b & LOM);
+                    atomicAdd(&cnt[b >> CS_LOB], 1u);
+                }
+            }
+        }
+        __syncthreads();
+        {
+            const uint32_t c = t < 256 ? cnt[t] : 0u;
+            const uint32_t ex = scan256_excl(c, t, stmp);
+            if (t < 256) toff[t] = ex;
+            if (t == 255) toff[256] = ex + c;
+        }
+        __syncthreads();
+        if (t < 256) cnt[t] = toff[t];
+        __syncthreads();
+#pragma unroll
+        for (uint32_t w = 0; w < 16; ++w)
+            if (pk[w] != 0xffffffffu) rec[atomicAdd(&cnt[pk[w] >> 23], 1u)] = pk[w];
+        __syncthreads();
+        const uint32_t total = toff[256];       // <= W * PS_T
+#pragma unroll
+        for (uint32_t k = 0; k < 16; ++k) {
+            const uint32_t qq = k * PS_T + t;   // consecutive lanes -> consecutive records of a partition's run
+            if (qq < total) {
+                const uint32_t r = rec[qq];
+                const uint32_t pp = r >> 23;
+                const uint32_t rel = tb + ((r >> 8) & (PS_T - 1u));        // index inside the slab
+                stage[gcur[pp] + (qq - toff[pp])] = (((r >> 22) & 1u) << 31) | (((r >> 18) & 15u) << 27) | (rel << 8) | (r & LOM);
+            }
+        }
+        __syncthreads();
+        if (t < 256) gcur[t] += toff[t + 1] - toff[t];
+    }
+}
+
+// one workgroup per partition, 256 buckets; dynamic LDS: curs[PS_SLABS + 1] | sorted[PS_TILE] | skey[PS_TILE] (u8) | slab_of[PS_TILE] (u16).
+// A partition of up to CS_RT tiles (65536 references; a uniform 2^20-point job has 61440) is read from memory ONCE, into registers,
+// and its low bits are counted ONCE, per tile: the bucket starts are the sums over the tiles, and every (tile, bucket) run's place in
+// the sorted tile and in `entries` comes from the same counts (lane = (tile, bucket)).  The kernel is bound by its LDS atomics and
+// barriers, not by memory (one workgroup per CU): two atomics per reference and two barriers per tile instead of psortw_final's
+// three and eight.  Longer partitions are left to csort_final_long (two kernels: in one, the two paths' registers do not overlay).
+constexpr uint32_t CS_RT = 4;
+__global__ void __launch_bounds__(PS_T) csort_final(SJobs jobs, uint32_t P) {
+    extern __shared__ uint32_t lds[];
+    const SJob& J = jobs.j[blockIdx.y];
+    const uint32_t* stage = J.stage_ref;
+    const uint32_t* part_start = J.part_start;
+    uint32_t* entries = J.entries;
+    uint32_t* offsets = J.offsets;
+    const uint32_t n = (uint32_t)J.n, sp = J.sp;         // table path: n <= 2^26
+    constexpr uint32_t PER = PS_TILE / PS_T, NB = 1u << CS_LOB, LOM = NB - 1u;
+    static_assert(NB == 256 && PS_SLABS == 1024 && PS_T == PS_SLABS && CS_RT * NB == PS_T, "one slab cursor and one (tile, bucket) per lane");
+    __shared__ uint32_t pos[CS_RT * NB];     // (tile, bucket): references counted, then the running place inside the sorted tile
+    __shared__ uint32_t dst[CS_RT * NB];     // (tile, bucket): entries[dst + i] takes place i of the sorted tile
+    __shared__ uint32_t tmp_a[16], tmp_b[16];
+    uint32_t* curs = lds;                    // start of every slab's run, relative to the partition's; curs[PS_SLABS] = its length
+    uint32_t* sorted = curs + PS_SLABS + 1;
+    uint8_t* skey = reinterpret_cast<uint8_t*>(sorted + PS_TILE);
+    uint16_t* slab_of = reinterpret_cast<uint16_t*>(skey + PS_TILE);
+    const uint32_t p = blockIdx.x, t = threadIdx.x;
+    const uint32_t s = part_start[p], e = part_start[p + 1];
+    const uint32_t len = e - s;
+    if (len > CS_RT * PS_TILE) return;
+    uint32_t all[CS_RT][PER];
+    {
+        const uint32_t* mine = stage + s + t;
+#pragma unroll
+        for (uint32_t r = 0; r < CS_RT; ++r)
+#pragma unroll
+            for (uint32_t k = 0; k < PER; ++k) {
+                const uint32_t i = (r * PER + k) * PS_T;
+                if (i + t < len) all[r][k] = mine[i];
+            }
+    }
+    curs[t] = J.hist[(uint64_t)p * PS_SLABS + t];
+    if (t == 0) curs[PS_SLABS] = len;
+    pos[t] = 0;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < CS_RT; ++r)
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k)
+            if ((r * PER + k) * PS_T + t < len) atomicAdd(&pos[r * NB + (all[r][k] & LOM)], 1u);
+    __syncthreads();
+    {
+        // lane = (tile r, bucket j).  Two exclusive scans over the buckets, inside every group of four wavefronts: of the tile's own
+        // counts (the runs of the sorted tile) and of the buckets' totals over the tiles (the bucket starts; every group computes them)
+        const uint32_t r = t >> 8, j = t & (NB - 1u), wv = t >> 6;
+        const uint32_t c = pos[t];
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < CS_RT; ++q) {
+            const uint32_t v = pos[q * NB + j];
+            if (q < r) before += v;
+            total += v;
+        }
+        uint32_t inc_a = c, inc_b = total;
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t oa = __shfl_up(inc_a, d, 64), ob = __shfl_up(inc_b, d, 64);
+            if ((t & 63) >= d) {
+                inc_a += oa;
+                inc_b += ob;
+            }
+        }
+        if ((t & 63) == 63) {
+            tmp_a[wv] = inc_a;
+            tmp_b[wv] = inc_b;
+        }
+        __syncthreads();          // (every lane has read the counts by now)
+        uint32_t add_a = 0, add_b = 0;
+        for (uint32_t w = wv & ~3u; w < wv; ++w) {
+            add_a += tmp_a[w];
+            add_b += tmp_b[w];
+        }
+        const uint32_t in_tile = inc_a + add_a - c;               // where the tile's run of bucket j starts in the sorted tile
+        const uint32_t start = s + inc_b + add_b - total;         // where bucket j starts in the list
+        pos[t] = in_tile;
+        dst[t] = start + before - in_tile;
+        if (r == 0) offsets[p * NB + j] = start;
+        if (p == P - 1 && t == 0) offsets[P * NB] = e;
+    }
+    // The slab that staged a record is the one whose run holds the record's place in the partition.  Lane t writes slab t's number
+    // over the part of its run inside the tile (~60 places for ~270 of the lanes); a run longer than a wavefront (a slab of equal
+    // scalars) is written by the lane's whole wavefront instead.
+    const uint32_t run0 = curs[t], run1 = curs[t + 1];
+    auto mark_slabs = [&](uint32_t a0) {
+        const uint32_t a1 = a0 + PS_TILE < len ? a0 + PS_TILE : len, l = t & 63;
+        const uint32_t r0 = run0 > a0 ? run0 : a0, r1 = run1 < a1 ? run1 : a1;
+        const bool wide = r1 > r0 && r1 - r0 > 64;
+        if (!wide)
+            for (uint32_t q = r0; q < r1; ++q) slab_of[q - a0] = (uint16_t)t;
+        unsigned long long todo = __ballot(wide);
+        while (todo) {
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const uint32_t b0 = __shfl(r0, src, 64), b1 = __shfl(r1, src, 64);
+            for (uint32_t q = b0 + l; q < b1; q += 64) slab_of[q - a0] = (uint16_t)((t & ~63u) + (uint32_t)src);
+        }
+    };
+    mark_slabs(0);
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < CS_RT; ++r) {
+        if (r * PS_TILE >= len) break;       // (the same for every lane)
+        const uint32_t m = len - r * PS_TILE < PS_TILE ? len - r * PS_TILE : PS_TILE;
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;
+            if (i < m) {
+                const uint32_t v = all[r][k];
+                const uint32_t slab = slab_of[i];
+                const uint32_t first = slab * sp < n ? slab * sp : n;
+                const uint32_t q = atomicAdd(&pos[r * NB + (v & LOM)], 1u);
+                sorted[q] = (v & 0x80000000u) | (((v >> 27) & 15u) << 26) | (first + ((v >> 8) & 0x7ffffu));
+                skey[q] = (uint8_t)(v & LOM);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;   // consecutive lanes -> consecutive positions of a bucket's run
+            if (i < m) entries[dst[r * NB + skey[i]] + i] = sorted[i];
+        }
+        if ((r + 1) * PS_TILE < len) mark_slabs((r + 1) * PS_TILE);
+        __syncthreads();
+    }
+}
+
+// The partitions csort_final leaves: longer than CS_RT tiles (skewed scalars: a handful of values repeated; jobs beyond 2^20 points).
+// Read twice, as psortw_final reads them -- a counting pass, then tile by tile with the next tile requested ahead -- and the slab of
+// a record found by a 10-step search over the cursors.  dynamic LDS: curs[PS_SLABS] | sorted[PS_TILE] | skey[PS_TILE] (u8)
+__global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P) {
+    extern __shared__ uint32_t lds[];
+    const SJob& J = jobs.j[blockIdx.y];
+    const uint32_t* stage = J.stage_ref;
+    const uint32_t* part_start = J.part_start;
+    uint32_t* entries = J.entries;
+    uint32_t* offsets = J.offsets;
+    const uint32_t n = (uint32_t)J.n, sp = J.sp;         // table path: n <= 2^26
+    constexpr uint32_t PER = PS_TILE / PS_T, NB = 1u << CS_LOB, LOM = NB - 1u;
+    static_assert(NB == 256 && PS_SLABS == 1024 && PS_T == PS_SLABS, "scan256_excl; one slab cursor per lane; 10-step search");
+    __shared__ uint32_t cnt[NB], cur[NB], toff[NB + 1], stmp[4];
+    uint32_t* curs = lds;                    // start of every slab's run, relative to the partition's
+    uint32_t* sorted = curs + PS_SLABS;
+    uint8_t* skey = reinterpret_cast<uint8_t*>(sorted + PS_TILE);
+    const uint32_t p = blockIdx.x, t = threadIdx.x;
+    const uint32_t s = part_start[p], e = part_start[p + 1];
+    if (e - s <= CS_RT * PS_TILE) return;
+    curs[t] = J.hist[(uint64_t)p * PS_SLABS + t];
+    if (t < NB) cnt[t] = 0;
+    __syncthreads();
+    {   // count the low bits: eight loads in flight per lane (count_keys)
+        uint32_t i = s + t;
+        for (; i + 7 * PS_T < e; i += 8 * PS_T) {
+            uint32_t v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = stage[i + k * PS_T];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) atomicAdd(&cnt[v[k] & LOM], 1u);
+        }
+        for (; i < e; i += PS_T) atomicAdd(&cnt[stage[i] & LOM], 1u);
+    }
+    __syncthreads();
+    {
+        const uint32_t ex = scan256_excl(t < NB ? cnt[t] : 0u, t, stmp);
+        if (t < NB) cur[t] = s + ex;
+    }
+    __syncthreads();
+    if (t < NB) offsets[p * NB + t] = cur[t];
+    if (p == P - 1 && t == 0) offsets[P * NB] = e;
+    // the tile after the current one is requested while the current one is counted, scanned and placed
+    uint32_t nr[PER];
+    auto fetch = [&](uint32_t base) {
+        const uint32_t m = e - base < PS_TILE ? e - base : PS_TILE;
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;
+            if (i < m) nr[k] = stage[base + i];
+        }
+    };
+    if (s < e) fetch(s);
+    for (uint32_t base = s; base < e; base += PS_TILE) {
+        const uint32_t m = e - base < PS_TILE ? e - base : PS_TILE;
+        __syncthreads();
+        if (t < NB) cnt[t] = 0;
+        __syncthreads();
+        uint32_t vr[PER];
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) vr[k] = nr[k];
+        if (base + PS_TILE < e) fetch(base + PS_TILE);
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;
+            if (i < m) atomicAdd(&cnt[vr[k] & LOM], 1u);
+        }
+        __syncthreads();
+        {
+            const uint32_t c = t < NB ? cnt[t] : 0u;
+            const uint32_t ex = scan256_excl(c, t, stmp);
+            if (t < NB) toff[t] = ex;
+            if (t == NB - 1) toff[NB] = ex + c;
+        }
+        __syncthreads();
+        if (t < NB) cnt[t] = toff[t];      // running position inside the tile
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;
+            if (i < m) {
+                // the slab that staged this record: the last one whose run starts at or before the record's place in the partition
+                const uint32_t at = base - s + i;
+                uint32_t slab = 0;
+#pragma unroll
+                for (uint32_t step = PS_SLABS / 2; step >= 1; step >>= 1)
+                    if (curs[slab + step] <= at) slab += step;
+                const uint32_t r = vr[k];
+                const uint32_t first = slab * sp < n ? slab * sp : n;
+                const uint32_t ref = (r & 0x80000000u) | (((r >> 27) & 15u) << 26) | (first + ((r >> 8) & 0x7ffffu));
+                const uint32_t q = atomicAdd(&cnt[r & LOM], 1u);
+                sorted[q] = ref;
+                skey[q] = (uint8_t)(r & LOM);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;   // consecutive lanes -> consecutive positions of a bucket's run
+            if (i < m) {
+                const uint32_t j = skey[i];
+                entries[cur[j] + (i - toff[j])] = sorted[i];
+            }
+        }
+        __syncthreads();
+        if (t < NB) cur[t] += toff[t + 1] - toff[t];
+    }
+}
+
+
 // ---------------------------------------------------------------------------------------- host side
 // per-window path: S slabs of scalars per window
 template <class Cv>
@@ -881,6 +1267,15 @@ int pre_queue_digits(zk_ctx* c, const PrePlan& pl, MsmBufs& mb, const void* d_sc
         uint32_t* scan_counter = part_total + P;
         uint32_t* combine_q = (uint32_t*)mb.part_key.p + PRE_Q_OFF;
         uint32_t* hist = (uint32_t*)mb.counts.p;
+        if (pre_compact(pl)) {                            // the folded scalars wait where the digits would (32 <= 4 W bytes per scalar)
+            uint4* folded = (uint4*)mb.entries.p;
+            if (mont) hipLaunchKernelGGL((csort_fold_hist<FrS, true>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp, pl.g,
+                                         folded, hist, scan_counter, combine_q);
+            else hipLaunchKernelGGL((csort_fold_hist<FrS, false>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp, pl.g,
+                                    folded, hist, scan_counter, combine_q);
+            ZK_HIP_TRY(hipGetLastError());
+            return ZK_OK;
+        }
         int32_t* dig32 = (int32_t*)mb.entries.p;          // the digits wait in the buffer of the sorted references (pre_sizes)
         if (mont) hipLaunchKernelGGL((psortw_digits_hist<FrS, true>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp, pl.g,
                                      lob, dig32, hist, scan_counter, combine_q);
@@ -949,7 +1344,7 @@ int pre_queue_sort_rest(zk_ctx* c, const PrePlan* pls, MsmBufs* const* mbs, cons
         MsmBufs& mb = *mbs[k];
         SJob& J = sj.j[k];
         void* stage = pls[k].shared_stage ? c->stage_shared.p : mb.stage.p;
-        J.dig = mb.entries.p;           // overwritten by the placement kernel once the scatter has read them
+        J.dig = mb.entries.p;           // (compact form: the folded scalars) overwritten by the placement kernel once the scatter has read them
         J.n = lens[k];
         J.sp = psort_slab_len(lens[k]);
         J.hist = (uint32_t*)mb.counts.p;
@@ -962,7 +1357,16 @@ int pre_queue_sort_rest(zk_ctx* c, const PrePlan* pls, MsmBufs* const* mbs, cons
         J.offsets = (uint32_t*)mb.offsets.p;
     }
     hipLaunchKernelGGL(psort_scan, dim3(P, n_jobs), dim3(PS_SLABS), 0, st, sj, P);
-    if (p0.wide) {
+    if (pre_compact(p0)) {                                // (all jobs of a launch share the table's geometry and own their staging)
+        const size_t lds_s = (size_t)p0.g.W * PS_T * 4, lds_f = ((size_t)PS_SLABS + 1 + PS_TILE) * 4 + (size_t)PS_TILE * 3,
+                     lds_l = ((size_t)PS_SLABS + PS_TILE) * 4 + PS_TILE;
+        ZK_HIP_TRY(hipFuncSetAttribute((const void*)csort_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+        hipLaunchKernelGGL(csort_scatter, dim3(PS_SLABS, n_jobs), dim3(PS_T), lds_s, st, sj, p0.g.W);
+        ZK_HIP_TRY(hipFuncSetAttribute((const void*)csort_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
+        hipLaunchKernelGGL(csort_final, dim3(P, n_jobs), dim3(PS_T), lds_f, st, sj, P);
+        ZK_HIP_TRY(hipFuncSetAttribute((const void*)csort_final_long, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l));
+        hipLaunchKernelGGL(csort_final_long, dim3(P, n_jobs), dim3(PS_T), lds_l, st, sj, P);
+    } else if (p0.wide) {
         const uint32_t lob = p0.g.c - 9;
         hipLaunchKernelGGL(psortw_scatter, dim3(PS_SLABS, n_jobs), dim3(PS_T), 0, st, sj, p0.g.W, lob);
         const uint32_t NB = 1u << lob;

@@ -1,0 +1,62 @@
+"""Compile-time guard on the kernels of the compact sort form (csort_* in csrc/msm_sort.hip; gfx950 device code, hipcc's own
+`-Rpass-analysis=kernel-resource-usage` remarks; no GPU needed): no register spill, no scratch, and at least as many workgroups of
+the launch shape resident per CU as the psortw_* kernel each replaces."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+LDS_PER_CU = 160 * 1024          # gfx950
+WAVES_PER_SIMD, SIMDS = 8, 4
+PS_T, PS_SLABS, PS_STILE, PS_TILE = 1024, 1024, 8192, 16384        # csrc/msm_common.cuh
+W, NB17 = 15, 256                                                   # the flagship geometry: 15 windows of 17 bits, 2^8 buckets per partition
+
+
+def workgroups_per_cu(k, threads, dynamic_lds):
+    """resident workgroups of `threads` lanes: by wavefront slots at the kernel's occupancy, and by LDS (static + dynamic)"""
+    waves = threads // 64
+    by_waves = (min(k["Occupancy"], WAVES_PER_SIMD) * SIMDS) // waves
+    lds = k["LDS Size"] + dynamic_lds
+    return min(by_waves, LDS_PER_CU // lds if lds else by_waves)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
+def test_compact_sort_kernels_registers_spills_and_residency():
+    src = os.path.join(ROOT, "ark_plonk_amd", "csrc", "msm_sort.hip")
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-pragma-unroll-threshold=1000000", "--cuda-device-only",
+           "-DZK_CURVE_SEL=0", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
+    err = subprocess.run(cmd, capture_output=True, text=True, timeout=1500).stderr
+    kernels, cur = {}, None
+    for line in err.splitlines():
+        m = re.search(r"remark: .*?Function Name: (\S+)", line)
+        if m:
+            cur = kernels.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark: .*?\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = int(m.group(2))
+
+    def find(name, *more):
+        # Itanium mangling inside the anonymous namespace: <length><name>E for a plain function, <length><name>I... for a template
+        tag = f"{len(name)}{name}" + ("I" if more else "E")
+        hits = [v for k, v in kernels.items() if tag in k and all(p in k for p in more)]
+        assert len(hits) == 1, (name, more, [k for k in kernels if name in k])
+        return hits[0]
+
+    new = {"fold_t": find("csort_fold_hist", "Lb1E"), "fold_f": find("csort_fold_hist", "Lb0E"), "scatter": find("csort_scatter"),
+           "final": find("csort_final"), "long": find("csort_final_long")}
+    for name, k in new.items():
+        assert k["VGPRs Spill"] == 0 and k["ScratchSize"] == 0, (name, k)
+    # launch shapes and dynamic LDS as pre_queue_digits / pre_queue_sort_rest set them
+    old_digits = workgroups_per_cu(find("psortw_digits_hist", "Lb1E"), 256, 0)
+    assert workgroups_per_cu(new["fold_t"], 256, 0) >= old_digits, (new["fold_t"], old_digits)
+    assert workgroups_per_cu(new["fold_f"], 256, 0) >= workgroups_per_cu(find("psortw_digits_hist", "Lb0E"), 256, 0)
+    old_scatter = workgroups_per_cu(find("psortw_scatter"), PS_T, 0)
+    assert workgroups_per_cu(new["scatter"], PS_T, W * PS_T * 4) >= old_scatter, (new["scatter"], old_scatter)
+    old_final = workgroups_per_cu(find("psortw_final"), PS_T, (3 * NB17 + 1 + 16 + PS_TILE) * 4 + PS_TILE * 2)
+    assert workgroups_per_cu(new["final"], PS_T, (PS_SLABS + 1 + PS_TILE) * 4 + PS_TILE * 3) >= old_final, (new["final"], old_final)
+    assert workgroups_per_cu(new["long"], PS_T, (PS_SLABS + PS_TILE) * 4 + PS_TILE) >= old_final, (new["long"], old_final)
