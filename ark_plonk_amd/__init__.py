@@ -15,10 +15,13 @@ from . import linearisation, lookup, permutation, prover, quotient, transcript  
 from . import _lib, msm  # noqa: F401
 from . import compile  # noqa: F401  (circuit description -> ProverKey / VerifierKey / seeded transcript)
 from .compile import CircuitDescription, VerifierKey, assign  # noqa: F401
+from . import circuit_check  # noqa: F401  (which rows of a circuit a witness violates, before the proof)
+from .circuit_check import BIT_NAMES, CheckReport, CircuitNotSatisfied, check_circuit  # noqa: F401
 from .msm import (CommitterKey, G1Affine, VariableBaseMSM, kzg_witness, srs_cache_config, srs_cache_stats, sum_partials,  # noqa: F401
                   sum_partials_batch)
 
 __all__ = [
     "Context", "default_context", "BLS12_381", "BN254", "get_curve", "GeneralEvaluationDomain",
     "Radix2EvaluationDomain", "CommitterKey", "G1Affine", "VariableBaseMSM", "kzg_witness", "sum_partials", "sum_partials_batch", "srs_cache_stats", "srs_cache_config", "permutation", "quotient", "lookup", "linearisation", "prover", "transcript",
+    "circuit_check", "check_circuit", "CheckReport", "CircuitNotSatisfied", "BIT_NAMES",
 ]

@@ -56,6 +56,18 @@ class ZkProof(ctypes.Structure):
     ]
 
 
+class CircuitCheckArgs(ctypes.Structure):
+    """zk_circuit_check_args"""
+    _fields_ = ([(k, c_void_p) for k in ("w_l", "w_r", "w_o", "w_4", "pi", "q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_arith", "q_range", "q_logic",
+                                         "q_fixed_group_add", "q_variable_group_add", "q_lookup")]
+                + [("sigma", c_void_p * 4), ("table", c_void_p * 4), ("table_rows", c_size_t), ("coeff_a", c_u64 * 4), ("coeff_d", c_u64 * 4)])
+
+
+class CircuitCheckSummary(ctypes.Structure):
+    """zk_circuit_check_summary"""
+    _fields_ = [("failing_rows", c_u64), ("first_row", c_u64), ("first_mask", c_u32), ("reserved", c_u32), ("bit_count", c_u64 * 32)]
+
+
 # every symbol include/ark_plonk_amd.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "zk_strerror": (ctypes.c_char_p, [c_int]),
@@ -162,6 +174,8 @@ SYMBOLS = {
     # circuit compilation: the wire permutation from the variable map, the witness gather
     "zk_perm_sigma_dev": (c_int, [c_void_p, c_int, c_u32, c_void_p, c_void_p, c_size_t, c_u32, c_void_p, ctypes.POINTER(c_void_p)]),
     "zk_fr_gather_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    # circuit check: per-row masks of violated constraints (CircuitCheckArgs, CircuitCheckSummary)
+    "zk_circuit_check_dev": (c_int, [c_void_p, c_int, c_u32, c_void_p, c_void_p, c_void_p]),
     "zk_fr_serialized_size": (c_size_t, [c_int]),
     "zk_g1_compressed_size": (c_size_t, [c_int]),
     "zk_fr_serialize": (c_int, [c_int, c_void_p, ctypes.c_char_p]),

@@ -46,6 +46,8 @@ def jobs():
         ("ipa.o", "../csrc_ipa/ipa.hip", [], API_HDRS),
         # circuit compilation (csrc_compile/): the wire permutation from the variable map and the witness gather
         ("compile.o", "../csrc_compile/compile.hip", [], API_HDRS),
+        # the circuit check (csrc_check/): per-row masks of violated gate, copy and lookup constraints
+        ("check.o", "../csrc_check/check.hip", [], API_HDRS),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

@@ -93,11 +93,20 @@ class Proof:
                                [self.evaluations[k] for k in PROOF_EVAL_FIELDS], [(k, self.evaluations[k]) for k in CUSTOM_EVAL_LABELS], self.curve)
 
 
-def prove(pk: ProverKey, ck, wires, public_inputs: dict, preprocessed: Transcript, coeff_a_mont, coeff_d_mont, lean: bool = False) -> Proof:
-    """`Prover::prove_with_preprocessed` (prover.rs:163-638) on the device: see `_prove`.  A failure between a round's first
+def prove(pk: ProverKey, ck, wires, public_inputs: dict, preprocessed: Transcript, coeff_a_mont, coeff_d_mont, lean: bool = False,
+          check: bool = False) -> Proof:
+    """`Prover::prove_with_preprocessed` (prover.rs:163-638) on the device: see `_prove`.  check=True first asks the device which rows
+    the witness violates (`circuit_check.check_circuit`: before the transcript is touched, before any transform or commitment) and
+    raises `CircuitNotSatisfied` with the report instead of computing a proof no verifier accepts; the proof of a satisfied circuit is
+    the same bytes either way.  A failure between a round's first
     `commit_begin` and its `round_end` (the "challenges must be different" assertion, an out-of-memory inside a transform) would leave
     the round open on the ctx -- every later blocking commit / open / MSM would return ZK_ERR_PENDING -- so the round is dropped
     (`zk_kzg_round_abort`) before the exception travels on."""
+    if check:
+        from .circuit_check import CircuitNotSatisfied, check_circuit
+        report = check_circuit(pk, wires, public_inputs, coeff_a_mont, coeff_d_mont, ctx=pk.domain._ctx_for(wires[0]))
+        if not report.ok:
+            raise CircuitNotSatisfied(report)
     try:
         return _prove(pk, ck, wires, public_inputs, preprocessed, coeff_a_mont, coeff_d_mont, lean)
     except BaseException:

@@ -388,6 +388,13 @@ inline DeviceVec gather(Context& ctx, int curve, const DeviceVec& values, const 
     check(zk_fr_gather_dev(ctx.handle(), curve, values.data(), values.size(), d_index, n, out.data()), "zk_fr_gather_dev");
     return out;
 }
+// Which rows does a witness violate (check_circuit_satisfied, composer.rs:661-814, on the device and for every constraint)?  The summary;
+// `mask` (optional, u32[n] on the device) receives one word per row, bits as the header tabulates them.  `d` = the size-n domain.
+inline zk_circuit_check_summary circuit_check(const Radix2EvaluationDomain& d, const zk_circuit_check_args& args, void* d_mask = nullptr) {
+    zk_circuit_check_summary out;
+    check(zk_circuit_check_dev(d.context().handle(), d.curve(), d.log_size_of_group(), &args, d_mask, &out), "zk_circuit_check_dev");
+    return out;
+}
 // compute_lookup_permutation_poly up to its ifft (permutation/mod.rs:754-797)
 inline DeviceVec lookup_permutation_evals(Context& ctx, int curve, const DeviceVec& f, const DeviceVec& t, const DeviceVec& h1,
                                           const DeviceVec& h2, const uint64_t* delta_mont, const uint64_t* epsilon_mont) {

@@ -584,6 +584,50 @@ int zk_perm_sigma_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* d_i
  * (runs inside an open deferred round).  Blocks once. */
 int zk_fr_gather_dev(zk_ctx* ctx, int curve_id, const void* d_values, size_t num_values, const void* d_index, size_t n, void* d_out);
 
+/* ---- circuit check: which rows does a witness violate? ------------------------------------------------------------------------- */
+/* The reference's `StandardComposer::check_circuit_satisfied` (constraint_system/composer.rs:661-814, feature `trace`) walks the gates
+ * on the host and stops at the first failing one; it covers arithmetic, logic and range.  Here every row of the padded circuit is
+ * tested on the device, BEFORE a proof is computed, against the summands of the identities the quotient enforces, one by one and with
+ * no random challenge.  d_mask[i] (u32, n = 2^log_n rows) gets one bit per violated constraint of row i:
+ *   bit 0       arith      q_arith (q_m ab + q_l a + q_r b + q_o c + q_4 d + q_c) + pi[i] != 0          (arithmetic.rs:51-63)
+ *   bits 1-4    range0-3   q_range != 0 and delta(c-4d), delta(b-4c), delta(a-4b), delta(d_n-4a) != 0  (range.rs:47-63)
+ *   bits 5-9    logic0-4   q_logic != 0 and delta(la), delta(lb), delta(ld), c - la lb,
+ *                          q_c (9 ld - 3 (la+lb)) + 3 (la+lb+ld) - 2 F != 0                            (logic.rs:65-133)
+ *   bits 10-13  fixed0-3   q_fixed_group_add != 0 and bit (bit-1) (bit+1), bit q_c - c, the x and the y equation of the step
+ *                                                                                     (ecc/fixed_base_scalar_mul.rs:88-156)
+ *   bits 14-16  curve0-2   q_variable_group_add != 0 and a d - d_n, the x and the y equation of the sum (ecc/curve_addition.rs:62-97)
+ *   bit 17      lookup     q_lookup != 0 and (a, b, c, d) equals no row of the table (all four columns compared in full; a table of
+ *                          0 rows fails every such row)
+ *   bits 18-21  copy_l/r/o/4   the cell (wire k, row i) and the cell sigma[k][i] points to hold different values
+ * a b c d: the wires at row i; a_n b_n d_n: w_l w_r w_4 at row (i + 1) mod n; delta(f) = f (f-1) (f-2) (f-3); la = a_n - 4a,
+ * lb = b_n - 4b, ld = d_n - 4d, F as in logic.rs:104-133.  sigma[k][i] = K_w' * omega^row' (K = 1, 7, 13, 17) is decoded through a device
+ * map of the 4n identity encodings, so any key works, compiled or written by hand; an entry that is no such encoding is
+ * ZK_ERR_BAD_ARG (one flag word, read back with the summary), not a mask bit.
+ * All columns: device vectors of n Montgomery Fr in canonical form (evaluations over the domain, not coefficients). */
+typedef struct zk_circuit_check_args {
+    const void *w_l, *w_r, *w_o, *w_4, *pi;          /* pi may be NULL (= zeros) */
+    const void *q_m, *q_l, *q_r, *q_o, *q_4, *q_c, *q_arith, *q_range, *q_logic, *q_fixed_group_add, *q_variable_group_add, *q_lookup;
+    const void* sigma[4];                            /* left, right, out, fourth: evaluations over the domain */
+    const void* table[4];                            /* four columns of table_rows rows (may be NULL when table_rows = 0) */
+    size_t table_rows;                               /* <= n; duplicates allowed (the padding repeats row 0) */
+    uint64_t coeff_a[4], coeff_d[4];                 /* P::COEFF_A, P::COEFF_D of the embedded twisted Edwards curve */
+} zk_circuit_check_args;
+typedef struct zk_circuit_check_summary {
+    uint64_t failing_rows;                           /* rows with a non-zero mask */
+    uint64_t first_row;                              /* the smallest of them; n when there is none */
+    uint32_t first_mask, reserved;                   /* its mask */
+    uint64_t bit_count[32];                          /* rows that have bit b set */
+} zk_circuit_check_summary;
+/* args: a zk_circuit_check_args; out: a zk_circuit_check_summary (host); d_mask: u32[n] on the device, or NULL when the summary is
+ * enough.  (Both structs cross as untyped pointers, like the column buffers: the bindings are generated and checked against a fixed
+ * set of struct parameter types.)  Returns ZK_OK whether or not the circuit is satisfied -- the summary says which.
+ * ZK_ERR_BAD_ARG: a null ctx / args / out (before anything else), a null column, table_rows > n, a sigma entry that is no identity
+ * encoding; ZK_ERR_DOMAIN_TOO_LARGE: log_n beyond the two-adicity; ZK_ERR_UNSUPPORTED: log_n > 28 (positions are 32-bit).
+ * Working memory: one device allocation per call, freed before return -- 160 n + 4 * (the power of two >= 2 table_rows) + 8 KiB bytes,
+ * + 4 n when d_mask is NULL (<= 172 n + 8 KiB).  No buffer of the ctx is used: the call runs inside an open deferred round.
+ * Blocks once. */
+int zk_circuit_check_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* args, void* d_mask, void* out);
+
 /* ---- device self-test ------------------------------------------------------------------------------ */
 /* Runs the quad-cooperative point arithmetic of the bucket-reduction kernels (csrc/ecq.cuh) against the
  * single-lane group law on n_quads point pairs incl. doubling, cancellation and infinity cases.

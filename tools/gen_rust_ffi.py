@@ -24,7 +24,8 @@ SCALAR = {
     "char": "c_char", "void": "c_void",
 }
 OPAQUE = {"zk_ctx": "ZkCtx", "zk_srs": "ZkSrs", "zk_transcript": "ZkTranscript"}
-STRUCTS = {"zk_domain_info": "ZkDomainInfo", "zk_quotient_args": "ZkQuotientArgs", "zk_proof": "ZkProof"}
+STRUCTS = {"zk_domain_info": "ZkDomainInfo", "zk_quotient_args": "ZkQuotientArgs", "zk_proof": "ZkProof",
+           "zk_circuit_check_args": "ZkCircuitCheckArgs", "zk_circuit_check_summary": "ZkCircuitCheckSummary"}
 
 
 def strip_comments(text: str) -> str:
