@@ -24,6 +24,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 FIELD_HDRS = ["field.cuh", "fieldu.cuh", "fields.cuh", "curve_params.h", "zk_common.h"]
 HOST_HDRS = FIELD_HDRS + ["ec.cuh", "ecu.cuh", "ctx.h", "../../include/ark_plonk_amd.h"]
 API_HDRS = HOST_HDRS + ["api_internal.h"]
+# helpers with one definition each: Fr / 32-byte element access; the quotient's bounded lazy arithmetic; the MSM's point storage
+FR_IO, ZBOUND, POINT_IO = ["fr_io.cuh"], ["fr_io.cuh", "zbound.cuh"], ["point_io.cuh"]
 # the C ABI, one unit per subsystem (api_internal.h is what they share)
 API_UNITS = ("api_ctx", "residency", "srs", "commit", "round", "api_host", "api_poly")
 MSM_UNITS = ("msm_accumulate", "msm_reduce", "msm_sort", "msm_plan")      # heaviest first
@@ -34,26 +36,25 @@ def jobs():
     out = [(f"{u}.o", f"{u}.hip", [], API_HDRS) for u in API_UNITS] + [
         ("hostio.o", "hostio.hip", [], HOST_HDRS),
         ("wire.o", "wire.hip", [], HOST_HDRS),
-        ("kzg.o", "kzg.hip", [], HOST_HDRS + ["fr_io.cuh"]),
-        ("lookup.o", "lookup.hip", [], HOST_HDRS + ["fr_io.cuh"]),
-        ("grand_product.o", "grand_product.hip", [], HOST_HDRS),
-        ("quotient.o", "quotient.hip", [], HOST_HDRS),
+        ("kzg.o", "kzg.hip", [], HOST_HDRS + FR_IO),
+        ("lookup.o", "lookup.hip", [], HOST_HDRS + FR_IO),
+        ("grand_product.o", "grand_product.hip", [], HOST_HDRS + FR_IO),
+        ("quotient.o", "quotient.hip", [], HOST_HDRS + ZBOUND),
         ("quadtest.o", "quadtest.hip", [], HOST_HDRS + ["ecq.cuh"]),
-        ("ntt.o", "ntt.hip", [], HOST_HDRS + ["ntt_pass.cuh"]),
+        ("ntt.o", "ntt.hip", [], HOST_HDRS + FR_IO + ["ntt_pass.cuh"]),
         ("ntt_pass_table.o", "ntt_pass_table.hip", [], []),
         ("msm_dispatch.o", "msm_dispatch.hip", [], HOST_HDRS),
-        # the inner-product-argument commitment (csrc_ipa/): a directory of its own, so that csrc/ keeps its kernel build
-        ("ipa.o", "../csrc_ipa/ipa.hip", [], API_HDRS),
-        # circuit compilation (csrc_compile/): the wire permutation from the variable map and the witness gather
-        ("compile.o", "../csrc_compile/compile.hip", [], API_HDRS),
-        # the circuit check (csrc_check/): per-row masks of violated gate, copy and lookup constraints
-        ("check.o", "../csrc_check/check.hip", [], API_HDRS),
+        # the inner-product-argument commitment; circuit compilation (the wire permutation from the variable map, the witness gather);
+        # the circuit check (per-row masks of violated gate, copy and lookup constraints)
+        ("ipa.o", "ipa.hip", [], API_HDRS + FR_IO + POINT_IO),
+        ("compile.o", "compile.hip", [], API_HDRS + FR_IO),
+        ("check.o", "check.hip", [], API_HDRS + ZBOUND),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)
         for unit in MSM_UNITS:
             out.append((f"{unit}_c{c}.o", f"{unit}.hip", [f"-DZK_CURVE_SEL={c}"] + os.environ.get("ARK_PLONK_AMD_MSM_FLAGS", "").split(),
-                        HOST_HDRS + ["msm_common.cuh"] + (["ecq.cuh"] if unit == "msm_reduce" else [])))
+                        HOST_HDRS + POINT_IO + ["msm_common.cuh"] + (["ecq.cuh"] if unit == "msm_reduce" else [])))
         for s in range(3, 10):
             out.append((f"ntt_pass_c{c}_s{s}.o", "ntt_pass_inst.hip", [f"-DZK_CURVE_SEL={c}", f"-DZK_NTT_S={s}"],
                         FIELD_HDRS + ["ntt_pass.cuh"]))

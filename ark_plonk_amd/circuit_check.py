@@ -1,4 +1,4 @@
-"""Which rows of a circuit does a witness violate?  `check_circuit` runs zk_circuit_check_dev (csrc_check/check.hip) over a `ProverKey`
+"""Which rows of a circuit does a witness violate?  `check_circuit` runs zk_circuit_check_dev (csrc/check.hip) over a `ProverKey`
 and the four wire columns BEFORE a proof is computed: every row gets a 32-bit mask of the constraints it breaks -- the summands of the
 gate identities the quotient enforces, one by one, the copy constraints behind sigma, membership of the lookup rows in the table --
 and the report names the rows.  The reference's counterpart, `StandardComposer::check_circuit_satisfied` (composer.rs:661-814, feature

@@ -4,7 +4,7 @@ table, the public-input rows -- to the `ProverKey` `prover.prove` takes, the `Ve
 step `to_scalars` (prover.rs:188-192) as `assign`.
 
     padding (preprocess.rs:61-88, lookup/multiset.rs:70-79)        torch copies
-    sigma evaluations (permutation/mod.rs:101-169)                 zk_perm_sigma_dev   (csrc_compile/compile.hip)
+    sigma evaluations (permutation/mod.rs:101-169)                 zk_perm_sigma_dev   (csrc/compile.hip)
     16 + 4 iffts, 16 coset ffts over 4n (preprocess.rs:138-349)    ProverKey (zk_ntt_dev)
     16 + 4 commitments (preprocess.rs:351-374, lookup :63-64)      two deferred rounds on the ctx (a round holds at most 16 jobs)
     VerifierKey::seed_transcript (widget/mod.rs:252-278)           transcript.seed_transcript

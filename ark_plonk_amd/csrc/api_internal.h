@@ -1,4 +1,4 @@
-// What the units of the C ABI (api_ctx / residency / srs / commit / round / api_host / api_poly .hip, csrc_ipa/ipa.hip) share.
+// What the units of the C ABI (api_ctx / residency / srs / commit / round / api_host / api_poly .hip, ipa.hip, compile.hip, check.hip) share.
 // Every function is listed once, with the locks its caller holds.  Not part of the C ABI.
 #pragma once
 #include "ctx.h"
@@ -13,6 +13,10 @@ inline void fq_one_sat(int curve, uint64_t* out) {
         return 0;
     });
 }
+
+// offsets inside one working-memory allocation, and the grid of a one-lane-per-item launch
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline unsigned blocks_of(uint64_t n, uint64_t t) { return (unsigned)((n + t - 1) / t); }
 
 // the ctx lock, and the ctx's device made current for the calling thread
 struct Guard {

@@ -3,7 +3,7 @@
 //
 // The reference's counterpart is `StandardComposer::check_circuit_satisfied` (plonk-core/src/constraint_system/composer.rs:661-814,
 // feature `trace`): serial, stops at the first failing gate, arithmetic / logic / range only, no copy constraints, no lookups.  Here
-// every row is tested at once against the summands of the identities the quotient enforces (csrc/quotient.hip; widget/arithmetic.rs:
+// every row is tested at once against the summands of the identities the quotient enforces (quotient.hip; widget/arithmetic.rs:
 // 51-63, range.rs:47-63, logic.rs:65-133, ecc/fixed_base_scalar_mul.rs:88-156, ecc/curve_addition.rs:62-97), taken one by one, with no
 // random challenge: a bit is set iff the selector of its widget and its term are both non-zero (DESIGN.md section 6d has the table).
 //   check_gates     bits 0-16: one lane per row, "next row" = (i + 1) mod n; plain store of the row's word
@@ -18,12 +18,13 @@
 // encodings are pairwise distinct), masks are OR-ed, the summary is sums and a minimum of integers.
 //
 // Field arithmetic of check_gates: the 29-bit-limb type of the quotient kernel (fieldu.cuh), lazily reduced, with the bound carried in
-// the type (Z<F, B>, ld_rp: restated from csrc/quotient.hip, whose device code must not move).  Zero has several encodings there
+// the type (Z<F, B>, to_rp: zbound.cuh, the one definition this unit and quotient.hip include).  Zero has several encodings there
 // (0, r, 2r, ...): every zero test is made on a value below 2r (a Montgomery product), which is 0 or r exactly.
 //
 // Working memory: one allocation per call, freed before return, no buffer of the ctx (the call runs inside an open deferred round):
 // 128 n (identity keys) + 32 n (their map) + 4 * capacity(table_rows) (<= 8 n) + 4 n when the caller takes no mask + 8 KiB.
-#include "../csrc/api_internal.h"
+#include "api_internal.h"
+#include "zbound.cuh"
 
 namespace {
 
@@ -35,37 +36,6 @@ constexpr size_t HEAD = 1024;                      // flag word at 0, summary at
 constexpr uint32_t CTAB = 48;                     // multiples of r held for the load conversion
 
 constexpr uint32_t BIT_ARITH = 0, BIT_RANGE = 1, BIT_LOGIC = 5, BIT_FIXED = 10, BIT_CURVE = 14, BIT_LOOKUP = 17, BIT_COPY = 18;
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline unsigned blocks_of(uint64_t n, uint64_t t) { return (unsigned)((n + t - 1) / t); }
-
-// ---------------------------------------------------------------------------------------------------------------- 32-byte values
-struct El {
-    uint4 a, b;
-};
-ZK_D El ld_el(const void* base, uint64_t i) {
-    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * i;
-    El e;
-    e.a = q[0];
-    e.b = q[1];
-    return e;
-}
-ZK_D bool el_eq(const El& x, const El& y) {
-    return x.a.x == y.a.x && x.a.y == y.a.y && x.a.z == y.a.z && x.a.w == y.a.w && x.b.x == y.b.x && x.b.y == y.b.y && x.b.z == y.b.z &&
-           x.b.w == y.b.w;
-}
-ZK_D bool el_zero(const El& x) { return (x.a.x | x.a.y | x.a.z | x.a.w | x.b.x | x.b.y | x.b.z | x.b.w) == 0; }
-// the mix of csrc/lookup.hip's el_hash, chained over the elements of a key
-ZK_D uint64_t el_mix(uint64_t h, const El& e) {
-    h ^= ((uint64_t)e.a.y << 32 | e.a.x) * 0x9E3779B97F4A7C15ull;
-    h ^= ((uint64_t)e.a.w << 32 | e.a.z) * 0xC2B2AE3D27D4EB4Full;
-    h ^= ((uint64_t)e.b.y << 32 | e.b.x) * 0x165667B19E3779F9ull;
-    h ^= ((uint64_t)e.b.w << 32 | e.b.z) * 0xD6E8FEB86659FD93ull;
-    h ^= h >> 33;
-    h *= 0xFF51AFD7ED558CCDull;
-    h ^= h >> 29;
-    return h;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- key map
 // A key is W field elements: element k of key i is col[k][i] (W = 4: a table row; W = 1: an identity encoding).
@@ -127,20 +97,6 @@ __global__ void __launch_bounds__(CT) map_build(uint32_t* slots, uint32_t cap_ma
 // ---------------------------------------------------------------------------------------------------------------- identity keys
 // consts: K_0..K_3 (Montgomery), then omega^(2^j), j < MAX_LOG_N.  keys[w * n + row] = K_w * omega^row, canonical like every sigma entry.
 constexpr uint32_t N_CONSTS = 4 + MAX_LOG_N;
-template <class Fr>
-ZK_D Fr ld_fr(const void* base, uint64_t idx) {
-    const El e = ld_el(base, idx);
-    Fr r;
-    r.v[0] = e.a.x, r.v[1] = e.a.y, r.v[2] = e.a.z, r.v[3] = e.a.w;
-    r.v[4] = e.b.x, r.v[5] = e.b.y, r.v[6] = e.b.z, r.v[7] = e.b.w;
-    return r;
-}
-template <class Fr>
-ZK_D void st_fr(void* base, uint64_t idx, const Fr& x) {
-    uint4* q = reinterpret_cast<uint4*>(base) + 2 * idx;
-    q[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-    q[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-}
 template <class Cv>
 __global__ void __launch_bounds__(CT) check_id_keys(uint32_t log_n, const void* consts, void* keys) {
     typedef typename Cv::Fr Fr;
@@ -231,52 +187,7 @@ __global__ void check_finish(const uint32_t* mask, uint64_t n, zk_circuit_check_
 }
 
 // ---------------------------------------------------------------------------------------------------------------- gate terms
-// Z<F, B> holds a value < (B / 10) * r.  A Montgomery product needs a * b < 2^261 * r / r^2 ~ 70 r^2 (169 r^2 on BN254) and returns
-// < 2r; sums add their bounds; a difference a - b adds the smallest of 2r / 8r / 16r that covers b.  Every rule is a static_assert.
-template <class F, int B>
-struct Z {
-    F v;
-    ZK_D Z() {}
-    ZK_D Z(const F& f) : v(f) {}
-    template <int B2>
-    ZK_D Z(const Z<F, B2>& o) : v(o.v) {      // widening only
-        static_assert(B2 <= B, "bound would shrink");
-    }
-};
-template <class F, int A, int B>
-ZK_D Z<F, 20> operator*(const Z<F, A>& a, const Z<F, B>& b) {
-    static_assert(A * B <= 6400, "Montgomery product operands too large");
-    return {F::mul(a.v, b.v)};
-}
-template <class F, int A>
-ZK_D Z<F, 20> zsqr(const Z<F, A>& a) {
-    static_assert(A * A <= 6400, "square operand too large");
-    return {F::sqr(a.v)};
-}
-template <class F, int A, int B>
-ZK_D Z<F, A + B> operator+(const Z<F, A>& a, const Z<F, B>& b) {
-    static_assert(A + B <= 600, "sum too large for the 261-bit container");
-    return {F::add(a.v, b.v)};
-}
-template <int B>
-struct SubK {
-    static_assert(B <= 160, "subtrahend above 16r");
-    static constexpr int K = B <= 20 ? 20 : B <= 80 ? 80 : 160;
-};
-template <class F, int A, int B>
-ZK_D Z<F, A + SubK<B>::K> operator-(const Z<F, A>& a, const Z<F, B>& b) {
-    static_assert(A + SubK<B>::K <= 600, "difference too large for the 261-bit container");
-    if constexpr (SubK<B>::K == 20) return {F::sub2(a.v, b.v)};
-    else if constexpr (SubK<B>::K == 80) return {F::sub8(a.v, b.v)};
-    else return {F::sub16(a.v, b.v)};
-}
-// value != 0 mod r, exactly: a value below 2r is 0 or r when it is a multiple of r; anything larger goes through a product with one
-template <class F, int B>
-ZK_D bool nonzero(const Z<F, B>& t, const Z<F, 10>& one) {
-    if constexpr (B <= 20) return !t.v.is_zero_mod_reduced();
-    else return !(t * one).v.is_zero_mod_reduced();
-}
-
+// the quotient kernel's bounded lazy arithmetic and load conversion (zbound.cuh): Z<F, B>, nonzero, to_rp, delta4
 template <class F>
 struct CArgsU {
     const void *w_l, *w_r, *w_o, *w_4, *pi;
@@ -287,37 +198,6 @@ struct CArgsU {
     uint32_t ratio_fx;                          // floor(2^BITS / r * 2^10) - 1
     uint32_t top_shift;                         // BITS - 29 * (NL - 1)
 };
-
-// arkworks Montgomery value x * 2^256 (canonical, 8 words) -> x * 2^261 mod r, < 1.2 r (csrc/quotient.hip ld_rp): shift left by 5 bits,
-// subtract q2 * r with q2 = floor(floor(32 v / 2^BITS) * (2^BITS / r)) <= 32 v / r (leaves < 2.15 r), then r once more if still >= r.
-template <class F>
-ZK_D Z<F, 12> to_rp(const El& e, const uint32_t (*rtab)[F::NL], uint32_t ratio_fx, uint32_t top_shift) {
-    uint32_t w[8] = {e.a.x, e.a.y, e.a.z, e.a.w, e.b.x, e.b.y, e.b.z, e.b.w};
-    F l = F::split_words(w);
-    F s;
-#pragma unroll
-    for (int i = F::NL - 1; i >= 1; --i) s.v[i] = ((l.v[i] << 5) | (l.v[i - 1] >> 24)) & (i == F::NL - 1 ? 0xffffffffu : F::M);
-    s.v[0] = (l.v[0] << 5) & F::M;
-    const uint32_t q2 = ((s.v[F::NL - 1] >> top_shift) * ratio_fx) >> 10;
-    F t;
-#pragma unroll
-    for (int i = 0; i < F::NL; ++i) t.v[i] = s.v[i] - rtab[q2][i];
-    F::normalize(t);
-    F d;
-#pragma unroll
-    for (int i = 0; i < F::NL; ++i) d.v[i] = t.v[i] - rtab[1][i];
-    F::normalize(d);
-    const bool neg = ((int32_t)d.v[F::NL - 1]) < 0;
-    F r;
-#pragma unroll
-    for (int i = 0; i < F::NL; ++i) r.v[i] = neg ? t.v[i] : d.v[i];
-    return Z<F, 12>(r);
-}
-
-template <class F, int B>
-ZK_D Z<F, 20> delta4(const Z<F, B>& f, const Z<F, 10>& one, const Z<F, 10>& c2, const Z<F, 10>& c3) {   // f(f-1)(f-2)(f-3)
-    return (f * (f - one)) * ((f - c2) * (f - c3));
-}
 
 // One lane per row; every column is read as two 16-byte words per lane, consecutive lanes consecutive rows.  A selector is tested on the
 // words it was loaded as (canonical input: zero is all-zero words), and a widget whose selector is zero is skipped by the lane -- its
@@ -414,18 +294,9 @@ struct Work {
     }
 };
 
-// arkworks-form Fr (R = 2^256) -> the canonical R' = 2^261 residue as 29-bit limbs
-template <class Cv>
-typename Cv::FrU to_rp_host(const typename Cv::Fr& v) {
-    typename Cv::Fr t = v;
-    for (int k = 0; k < 5; ++k) t = Cv::Fr::add(t, t);
-    return Cv::FrU::split_words(t.v);
-}
-
 template <class Cv>
 void fill_args(CArgsU<typename Cv::FrU>& A, const zk_circuit_check_args* q) {
     typedef typename Cv::Fr Fr;
-    typedef typename Cv::FrU FU;
     A.w_l = q->w_l; A.w_r = q->w_r; A.w_o = q->w_o; A.w_4 = q->w_4; A.pi = q->pi;
     A.q_m = q->q_m; A.q_l = q->q_l; A.q_r = q->q_r; A.q_o = q->q_o; A.q_4 = q->q_4; A.q_c = q->q_c; A.q_arith = q->q_arith;
     A.q_range = q->q_range; A.q_logic = q->q_logic; A.q_fixed = q->q_fixed_group_add; A.q_var = q->q_variable_group_add;
@@ -434,19 +305,7 @@ void fill_args(CArgsU<typename Cv::FrU>& A, const zk_circuit_check_args* q) {
     A.coeff_a = U(ldc(q->coeff_a)); A.coeff_d = U(ldc(q->coeff_d)); A.one = U(Fr::one());
     A.c2 = U(Fr::from_u32(2)); A.c3 = U(Fr::from_u32(3)); A.c4 = U(Fr::from_u32(4)); A.c9 = U(Fr::from_u32(9));
     A.c18 = U(Fr::from_u32(18)); A.c81 = U(Fr::from_u32(81)); A.c83 = U(Fr::from_u32(83));
-    // q * r as 29-bit limbs, and floor(2^BITS / r * 2^10) - 1
-    uint32_t rw[8];
-    for (int i = 0; i < 8; ++i) rw[i] = Cv::FrP::MOD(i);
-    FU acc = FU::zero();
-    const FU rl = FU::split_words(rw);
-    for (uint32_t k = 0; k < CTAB; ++k) {
-        for (int i = 0; i < FU::NL; ++i) A.rtab[k][i] = acc.v[i];
-        acc = FU::add(acc, rl);
-    }
-    long double rv = 0;
-    for (int i = Fr::N - 1; i >= 0; --i) rv = rv * 4294967296.0L + (long double)Cv::FrP::MOD(i);
-    A.ratio_fx = (uint32_t)floorl(ldexpl(1.0L, Cv::FrP::BITS + 10) / rv) - 1;
-    A.top_shift = (uint32_t)(Cv::FrP::BITS - 29 * (FU::NL - 1));
+    rp_table<Cv>(A.rtab, CTAB, A.ratio_fx, A.top_shift);
 }
 
 inline uint64_t capacity_for(uint64_t keys) {

@@ -21,7 +21,8 @@
 // Working memory: one allocation per call, freed before return (so the calls use no buffer of the ctx and run inside an open deferred
 // round).  With m <= 4n insertions: 16 m bytes (two key/value buffer pairs; 8 m when one pass is enough, none when num_vars = 1)
 // + m / 4 (digit counts) + 16 n when the caller takes no positions + 2 KiB.  At most 81 n bytes: 340 MB at n = 2^22.
-#include "../csrc/api_internal.h"
+#include "api_internal.h"
+#include "fr_io.cuh"
 
 namespace {
 
@@ -37,26 +38,6 @@ constexpr uint32_t SORT_TILE = SORT_T * SORT_ITEMS;
 constexpr uint32_t RADIX = 256;
 
 constexpr uint32_t SCAN_T = 256, SCAN_ITEMS = 4, SCAN_CHUNK = SCAN_T * SCAN_ITEMS;
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline uint64_t blocks_of(uint64_t n, uint64_t t) { return (n + t - 1) / t; }
-
-// Fr elements (32 bytes) as two 16-byte accesses
-template <class Fr>
-ZK_D Fr ld_fr(const void* base, uint64_t idx) {
-    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * idx;
-    const uint4 a = q[0], b = q[1];
-    Fr r;
-    r.v[0] = a.x, r.v[1] = a.y, r.v[2] = a.z, r.v[3] = a.w;
-    r.v[4] = b.x, r.v[5] = b.y, r.v[6] = b.z, r.v[7] = b.w;
-    return r;
-}
-template <class Fr>
-ZK_D void st_fr(void* base, uint64_t idx, const Fr& x) {
-    uint4* q = reinterpret_cast<uint4*>(base) + 2 * idx;
-    q[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-    q[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-}
 
 // ---------------------------------------------------------------------------------------------------------------- range check
 // Every entry is looked at before any kernel uses one as an address; the kernels below guard their own writes as well, so a bad
@@ -326,7 +307,7 @@ int sigma_impl(zk_ctx* c, uint32_t log_n, const uint32_t* ins_var, const uint32_
             const uint32_t* pos_s = ins_pos;
             {
                 ProfScope ps(c, "perm_sigma_sort");
-                hipLaunchKernelGGL(sigma_check, dim3((unsigned)blocks_of(m, 256)), dim3(256), 0, st, ins_var, ins_pos, (uint64_t)m, num_vars,
+                hipLaunchKernelGGL(sigma_check, dim3(blocks_of(m, 256)), dim3(256), 0, st, ins_var, ins_pos, (uint64_t)m, num_vars,
                                    (uint32_t)n_pos, d_flag);
                 for (uint32_t i = 0; i < passes; ++i) {
                     uint32_t* key_out = (uint32_t*)(w + o_sort + (size_t)(2 * (i & 1u)) * sort_one);
@@ -343,7 +324,7 @@ int sigma_impl(zk_ctx* c, uint32_t log_n, const uint32_t* ins_var, const uint32_
                 ZK_HIP_TRY(hipGetLastError());
             }
             ProfScope ps(c, "perm_sigma_rotate");
-            hipLaunchKernelGGL(sigma_rotate, dim3((unsigned)blocks_of(m, 256)), dim3(256), 0, st, var_s, pos_s, (uint64_t)m, (uint32_t)n_pos,
+            hipLaunchKernelGGL(sigma_rotate, dim3(blocks_of(m, 256)), dim3(256), 0, st, var_s, pos_s, (uint64_t)m, (uint32_t)n_pos,
                                sigma_pos, d_flag);
             ZK_HIP_TRY(hipGetLastError());
         }
@@ -364,7 +345,7 @@ int sigma_impl(zk_ctx* c, uint32_t log_n, const uint32_t* ins_var, const uint32_
             if (r2) return r2;
         }
         ProfScope ps(c, "perm_sigma_encode");
-        hipLaunchKernelGGL(sigma_encode<Cv>, dim3((unsigned)blocks_of(n_pos, 256)), dim3(256), 0, st, sigma_pos, log_n,
+        hipLaunchKernelGGL(sigma_encode<Cv>, dim3(blocks_of(n_pos, 256)), dim3(256), 0, st, sigma_pos, log_n,
                            (const void*)(w + o_consts), out);
         ZK_HIP_TRY(hipGetLastError());
         return ZK_OK;
@@ -391,7 +372,7 @@ int gather_impl(zk_ctx* c, const void* d_values, size_t num_values, const uint32
     auto body = [&]() -> int {
         ZK_HIP_TRY(hipMemsetAsync(d_flag, 0, 256, st));
         ProfScope ps(c, "fr_gather");
-        hipLaunchKernelGGL(fr_gather<Cv>, dim3((unsigned)blocks_of(n, 256)), dim3(256), 0, st, d_values, (uint64_t)num_values, d_index, (uint64_t)n,
+        hipLaunchKernelGGL(fr_gather<Cv>, dim3(blocks_of(n, 256)), dim3(256), 0, st, d_values, (uint64_t)num_values, d_index, (uint64_t)n,
                            d_out, d_flag);
         ZK_HIP_TRY(hipGetLastError());
         return ZK_OK;

@@ -1,10 +1,59 @@
-// Loads / stores of scalar-field elements for the kernels that work on the 29-bit-limb Fr type (kzg.hip, lookup.hip):
-// 32-byte arkworks elements <-> limbs with no domain change, lazily reduced limb vectors (48 bytes), and the kernel-argument
-// form of a constant multiplier.
+// Loads / stores of scalar-field elements, defined once for every unit that is free to include it:
+// the 32-byte element as the 8 x 32-bit-word type of field.cuh (ld_fr / st_fr) and as an opaque value (El: equality, zero test,
+// hash mix), and for the kernels that work on the 29-bit-limb Fr type (kzg.hip, lookup.hip): 32-byte arkworks elements <-> limbs
+// with no domain change, lazily reduced limb vectors (48 bytes), and the kernel-argument form of a constant multiplier.
 #pragma once
 #include "zk_common.h"
 
 namespace {
+
+// ---- the 32-byte element as two 16-byte accesses: the saturated type of field.cuh (arkworks Montgomery or canonical, as stored)
+template <class Fr>
+ZK_D Fr ld_fr(const void* base, uint64_t idx) {
+    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * idx;
+    uint4 a = q[0], b = q[1];
+    Fr r;
+    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
+    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
+    return r;
+}
+template <class Fr>
+ZK_D void st_fr(void* base, uint64_t idx, const Fr& r) {
+    uint4* q = reinterpret_cast<uint4*>(base) + 2 * idx;
+    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
+}
+
+// ---- the same 32 bytes as a value that is only compared and hashed (lookup.hip's multiset table, check.hip's key maps)
+struct El {
+    uint4 a, b;
+};
+ZK_D El ld_el(const void* base, uint64_t i) {
+    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * i;
+    El e;
+    e.a = q[0];
+    e.b = q[1];
+    return e;
+}
+ZK_D bool el_eq(const El& x, const El& y) {
+    return x.a.x == y.a.x && x.a.y == y.a.y && x.a.z == y.a.z && x.a.w == y.a.w && x.b.x == y.b.x && x.b.y == y.b.y && x.b.z == y.b.z &&
+           x.b.w == y.b.w;
+}
+ZK_D bool el_zero(const El& x) { return (x.a.x | x.a.y | x.a.z | x.a.w | x.b.x | x.b.y | x.b.z | x.b.w) == 0; }
+// 64-bit mix, chained over the elements of a key: h = 0 for the first (or only) element
+ZK_D uint64_t el_mix(uint64_t h, const El& e) {
+    h ^= ((uint64_t)e.a.y << 32 | e.a.x) * 0x9E3779B97F4A7C15ull;
+    h ^= ((uint64_t)e.a.w << 32 | e.a.z) * 0xC2B2AE3D27D4EB4Full;
+    h ^= ((uint64_t)e.b.y << 32 | e.b.x) * 0x165667B19E3779F9ull;
+    h ^= ((uint64_t)e.b.w << 32 | e.b.z) * 0xD6E8FEB86659FD93ull;
+    h ^= h >> 33;
+    h *= 0xFF51AFD7ED558CCDull;
+    h ^= h >> 29;
+    return h;
+}
+ZK_D uint32_t el_hash(const El& e) { return (uint32_t)el_mix(0, e); }
+
+// ---- the 29-bit-limb type
 
 struct Packed {            // a field element as 8 little-endian words (kernel argument form)
     uint32_t w[8];

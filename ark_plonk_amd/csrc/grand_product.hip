@@ -12,24 +12,9 @@
 // Field elements are canonical Montgomery residues, so the result is bit-identical with the serial loop.
 // A zero denominator makes the reference panic (`inverse().unwrap()`); here it is ZK_ERR_NOT_INVERTIBLE.
 #include "ctx.h"
+#include "fr_io.cuh"
 
 namespace {
-
-template <class Fr>
-ZK_D Fr ld_fr(const void* base, uint64_t idx) {
-    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * idx;
-    uint4 a = q[0], b = q[1];
-    Fr r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-template <class Fr>
-ZK_D void st_fr(void* base, uint64_t idx, const Fr& r) {
-    uint4* q = reinterpret_cast<uint4*>(base) + 2 * idx;
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
 
 constexpr uint32_t TERM_T = 256;     // lanes per workgroup of the term kernels
 constexpr uint32_t TERM_ROWS = 8;    // rows per lane (row = blk*T*ROWS + j*T + lane: coalesced)

@@ -9,69 +9,17 @@
 //   key'_i = key_l[i] + xi key_r[i]   (ipa_fold_key: one variable-base scalar multiplication per point, xi shared by every lane)
 //   a' = a_l + xi^-1 a_r, b' = b_l + xi b_r   (ipa_scalar_pass: also the canonical copy of a' and the next round's inner products)
 // Round 0 reads the registered key itself (SRS window-table path); later rounds run the per-window MSM over the folded key.
-#include "../csrc/api_internal.h"
+#include "api_internal.h"
+#include "fr_io.cuh"
+#include "point_io.cuh"
 
 #include <shared_mutex>
 
 namespace {
 
-// ---- device storage of a base-field element / affine point: the layout of the MSM's internal bases (csrc/msm_common.cuh Store,
-// ld_affine): NL signed 30-bit limbs padded to whole uint4, x then y; "no point" (infinity) is all-zero limbs
-template <class F>
-struct St {
-    static constexpr int U4 = (F::NL + 3) / 4;
-    static constexpr size_t POINT_BYTES = (size_t)2 * U4 * 16;
-};
-template <class F>
-ZK_D F ld_f(const uint4* q) {
-    F r;
-#pragma unroll
-    for (int i = 0; i < St<F>::U4; ++i) {
-        const uint4 a = q[i];
-        if (4 * i + 0 < F::NL) r.v[4 * i + 0] = a.x;
-        if (4 * i + 1 < F::NL) r.v[4 * i + 1] = a.y;
-        if (4 * i + 2 < F::NL) r.v[4 * i + 2] = a.z;
-        if (4 * i + 3 < F::NL) r.v[4 * i + 3] = a.w;
-    }
-    return r;
-}
-template <class F>
-ZK_D void st_f(uint4* q, const F& r) {
-#pragma unroll
-    for (int i = 0; i < St<F>::U4; ++i) {
-        uint4 a;
-        a.x = 4 * i + 0 < F::NL ? r.v[4 * i + 0] : 0u;
-        a.y = 4 * i + 1 < F::NL ? r.v[4 * i + 1] : 0u;
-        a.z = 4 * i + 2 < F::NL ? r.v[4 * i + 2] : 0u;
-        a.w = 4 * i + 3 < F::NL ? r.v[4 * i + 3] : 0u;
-        q[i] = a;
-    }
-}
-template <class F>
-ZK_D AffineU<F> ld_pt(const void* base, uint64_t idx) {
-    const uint4* q = reinterpret_cast<const uint4*>(base) + idx * (2 * St<F>::U4);
-    AffineU<F> p;
-    p.x = ld_f<F>(q);
-    p.y = ld_f<F>(q + St<F>::U4);
-    return p;
-}
-
-// Fr elements (32 bytes, arkworks Montgomery or canonical) as the saturated host/device type of field.cuh
-template <class Fr>
-ZK_D Fr ld_fr(const void* base, uint64_t idx) {
-    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * idx;
-    const uint4 a = q[0], b = q[1];
-    Fr r;
-    r.v[0] = a.x, r.v[1] = a.y, r.v[2] = a.z, r.v[3] = a.w;
-    r.v[4] = b.x, r.v[5] = b.y, r.v[6] = b.z, r.v[7] = b.w;
-    return r;
-}
-template <class Fr>
-ZK_D void st_fr(void* base, uint64_t idx, const Fr& x) {
-    uint4* q = reinterpret_cast<uint4*>(base) + 2 * idx;
-    q[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-    q[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-}
+// The folded key keeps the layout of the MSM's internal bases (point_io.cuh: NL limbs padded to whole uint4, x then y; "no point"
+// -- infinity -- is all-zero limbs); a and b are Fr elements as the saturated type of field.cuh (fr_io.cuh).
+using namespace zkmsm;
 
 // The challenge of a key fold in non-adjacent form: digit i is +1 where bit i of pos is set, -1 where bit i of neg is set; `top` is the
 // index of the highest digit (always +1), -1 for xi = 0.  A kernel argument: every lane walks the same digits.
@@ -107,7 +55,7 @@ __global__ void __launch_bounds__(FOLD_T) ipa_fold_key(const void* src, void* ds
     const bool active = i < m;
     P acc = P::infinity();
     if (active) {
-        const AffineU<F> q = ld_pt<F>(src, i + m);
+        const AffineU<F> q = ld_affine<F>(src, i + m);
         if (!q.is_null() && nf.top >= 0) {
             acc = P::from_affine(q);
             for (int b = nf.top - 1; b >= 0; --b) {
@@ -123,7 +71,7 @@ __global__ void __launch_bounds__(FOLD_T) ipa_fold_key(const void* src, void* ds
                 }
             }
         }
-        const AffineU<F> kl = ld_pt<F>(src, i);
+        const AffineU<F> kl = ld_affine<F>(src, i);
         if (!kl.is_null()) acc = P::madd(acc, kl);
     }
     const bool fin = active && !acc.is_inf();
@@ -146,10 +94,10 @@ __global__ void __launch_bounds__(FOLD_T) ipa_fold_key(const void* src, void* ds
     if (t == 0) inv_total = F::inverse(pre[FOLD_T - 1]);
     __syncthreads();
     if (!active) return;
-    uint4* out = reinterpret_cast<uint4*>(dst) + i * (2 * St<F>::U4);
+    uint4* out = reinterpret_cast<uint4*>(dst) + i * (2 * Store<F>::U4);
     if (!fin) {
-        st_f<F>(out, F::zero());
-        st_f<F>(out + St<F>::U4, F::zero());
+        st_fu<F>(out, F::zero());
+        st_fu<F>(out + Store<F>::U4, F::zero());
         return;
     }
     F zi3 = inv_total;                                   // 1 / ZZZ_i
@@ -158,8 +106,8 @@ __global__ void __launch_bounds__(FOLD_T) ipa_fold_key(const void* src, void* ds
     const F zi = F::mul(acc.zz, zi3);                    // 1 / Z
     const F x = F::mul(acc.x, F::sqr(zi));
     const F y = F::mul(acc.y, zi3);
-    st_f<F>(out, F::canonical_lt2p(x));
-    st_f<F>(out + St<F>::U4, F::canonical_lt2p(y));
+    st_fu<F>(out, F::canonical_lt2p(x));
+    st_fu<F>(out + Store<F>::U4, F::canonical_lt2p(y));
 }
 
 constexpr uint32_t SP_T = 256;     // lanes per block of the scalar pass
@@ -259,7 +207,7 @@ __global__ void __launch_bounds__(256) ipa_to_abi(const void* src, uint64_t n, u
     typedef typename Cv::FqU F;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const AffineU<F> p = ld_pt<F>(src, i);
+    const AffineU<F> p = ld_affine<F>(src, i);
     uint32_t* w = out_xy + i * 2 * F::SAT;
     const bool inf = p.is_null();
     if (inf) {
@@ -276,8 +224,6 @@ __global__ void __launch_bounds__(256) ipa_to_abi(const void* src, uint64_t n, u
 
 // ---------------------------------------------------------------------------------------------------------------- host side
 inline bool pow2(size_t x) { return x && !(x & (x - 1)); }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline uint64_t blocks_of(uint64_t n, uint64_t t) { return (n + t - 1) / t; }
 
 // workspace of one opening over d1 points: [folded key: d1/2 points][a_can: d1 scalars][partials: 2 Fr per scalar-pass block]
 struct Layout {
@@ -334,7 +280,7 @@ int launch_fold_key(zk_ctx* c, const void* src, void* dst, size_t m, const uint6
     const Fr k = Fr::from_mont(xi);
     const Naf nf = make_naf(k.v);
     ProfScope ps(c, "ipa_fold_key");
-    hipLaunchKernelGGL(ipa_fold_key<Cv>, dim3((unsigned)blocks_of(m, FOLD_T)), dim3(FOLD_T), 0, c->stream, src, dst, (uint64_t)m, nf);
+    hipLaunchKernelGGL(ipa_fold_key<Cv>, dim3(blocks_of(m, FOLD_T)), dim3(FOLD_T), 0, c->stream, src, dst, (uint64_t)m, nf);
     ZK_HIP_TRY(hipGetLastError());
     return ZK_OK;
 }
@@ -344,7 +290,7 @@ int launch_scalar_pass(zk_ctx* c, void* a, void* b, size_t mo, const typename Cv
                        void* partials) {
     const uint64_t lanes = mo > 1 ? mo / 2 : 1;
     ProfScope ps(c, "ipa_scalar_pass");
-    hipLaunchKernelGGL((ipa_scalar_pass<Cv, FOLD>), dim3((unsigned)blocks_of(lanes, SP_T)), dim3(SP_T), 0, c->stream, a, b, (uint64_t)mo, xi,
+    hipLaunchKernelGGL((ipa_scalar_pass<Cv, FOLD>), dim3(blocks_of(lanes, SP_T)), dim3(SP_T), 0, c->stream, a, b, (uint64_t)mo, xi,
                        xi_inv, a_can, partials);
     ZK_HIP_TRY(hipGetLastError());
     return ZK_OK;
@@ -468,7 +414,7 @@ int powers_impl(zk_ctx* c, const uint64_t* point_mont, size_t n, void* d_out) {
     if (n == 0) return ZK_OK;
     const uint64_t lanes = blocks_of(n, POW_K);
     ProfScope ps(c, "ipa_powers");
-    hipLaunchKernelGGL(ipa_powers<Cv>, dim3((unsigned)blocks_of(lanes, 256)), dim3(256), 0, c->stream, z, (uint64_t)n, d_out);
+    hipLaunchKernelGGL(ipa_powers<Cv>, dim3(blocks_of(lanes, 256)), dim3(256), 0, c->stream, z, (uint64_t)n, d_out);
     ZK_HIP_TRY(hipGetLastError());
     return ZK_OK;
 }
@@ -484,7 +430,7 @@ int check_coeffs_impl(zk_ctx* c, int curve, uint32_t log_d, const uint64_t* xis_
     // bit (log_d - 1 - j) of k selects xi_j: xi_{log_d-1} doubles the vector first (bit 0), xi_0 last (the top bit)
     for (uint32_t b = 0; b < log_d; ++b) {
         const uint64_t half = (uint64_t)1 << b;
-        hipLaunchKernelGGL(ipa_check_expand<Cv>, dim3((unsigned)blocks_of(half, 256)), dim3(256), 0, c->stream, d_out, half, xi[log_d - 1 - b]);
+        hipLaunchKernelGGL(ipa_check_expand<Cv>, dim3(blocks_of(half, 256)), dim3(256), 0, c->stream, d_out, half, xi[log_d - 1 - b]);
     }
     ZK_HIP_TRY(hipGetLastError());
     return fr_convert_dev(c, curve, 0, d_out, (size_t)1 << log_d, d_out);     // canonical: the MSM's scalars
@@ -493,7 +439,7 @@ int check_coeffs_impl(zk_ctx* c, int curve, uint32_t log_d, const uint64_t* xis_
 template <class Cv>
 int to_abi(zk_ctx* c, const void* src, size_t n, void* d_out_xy, uint8_t* d_out_inf) {
     if (n == 0) return ZK_OK;
-    hipLaunchKernelGGL(ipa_to_abi<Cv>, dim3((unsigned)blocks_of(n, 256)), dim3(256), 0, c->stream, src, (uint64_t)n, (uint32_t*)d_out_xy, d_out_inf);
+    hipLaunchKernelGGL(ipa_to_abi<Cv>, dim3(blocks_of(n, 256)), dim3(256), 0, c->stream, src, (uint64_t)n, (uint32_t*)d_out_xy, d_out_inf);
     ZK_HIP_TRY(hipGetLastError());
     return ZK_OK;
 }
@@ -507,7 +453,7 @@ void internal_to_abi_host(const void* pt, uint64_t* out_xy, uint8_t* out_inf) {
     F x, y;
     for (int k = 0; k < F::NL; ++k) {
         x.v[k] = w[k];
-        y.v[k] = w[4 * St<F>::U4 + k];
+        y.v[k] = w[4 * Store<F>::U4 + k];
     }
     const bool inf = x.limbs_zero() && y.limbs_zero();
     if (inf) {

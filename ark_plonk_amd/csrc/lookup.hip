@@ -21,31 +21,6 @@ namespace {
 
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 
-struct El {
-    uint4 a, b;
-};
-ZK_D El ld_el(const void* base, uint64_t i) {
-    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * i;
-    El e;
-    e.a = q[0];
-    e.b = q[1];
-    return e;
-}
-ZK_D bool el_eq(const El& x, const El& y) {
-    return x.a.x == y.a.x && x.a.y == y.a.y && x.a.z == y.a.z && x.a.w == y.a.w && x.b.x == y.b.x && x.b.y == y.b.y && x.b.z == y.b.z &&
-           x.b.w == y.b.w;
-}
-ZK_D uint32_t el_hash(const El& e) {
-    uint64_t h = ((uint64_t)e.a.y << 32 | e.a.x) * 0x9E3779B97F4A7C15ull;
-    h ^= ((uint64_t)e.a.w << 32 | e.a.z) * 0xC2B2AE3D27D4EB4Full;
-    h ^= ((uint64_t)e.b.y << 32 | e.b.x) * 0x165667B19E3779F9ull;
-    h ^= ((uint64_t)e.b.w << 32 | e.b.z) * 0xD6E8FEB86659FD93ull;
-    h ^= h >> 33;
-    h *= 0xFF51AFD7ED558CCDull;
-    h ^= h >> 29;
-    return (uint32_t)h;
-}
-
 // One atomic per DISTINCT slot among the live lanes of a wavefront (the reference pads every non-lookup row of the query and
 // every padding row of the table with one value, so one slot can take most of the traffic: ~9 ns per atomic on one address,
 // 12 ms per proof before this).  add != 0: cnt[slot] += lanes in the group; add == 0: slots[slot] = min(slots[slot], the group's

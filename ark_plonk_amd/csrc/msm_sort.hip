@@ -1,7 +1,12 @@
 // MSM unit 1 of 4 (msm_common.cuh): digits and the sort of the (point, sign) references by bucket.
 //
-// Two sorts live here.  The window-table path (every commitment of a proof) uses the two-pass PARTITION sort (psort_* for 16-bit
-// windows, psortw_* for 17 .. 21 bits) over its one shared bucket set, the jobs of a prover round batched in one launch per kernel.
+// The window-table path (every commitment of a proof) uses a two-pass PARTITION sort over its one shared bucket set, the jobs of a
+// prover round batched in one launch per kernel.  It comes in three forms, chosen by the table's geometry (msm_common.cuh):
+//   pre_psort16   psort_*   windows up to 16 bits: int16 digits, 2^15 buckets = 256 partitions of 128
+//   pre_compact   csort_*   a whole table of folded 17-bit windows whose job owns its staging area (every MSM of a 2^19 .. 2^21
+//                           proof): the folded scalar waits instead of the digits, one staged word per reference
+//   else          psortw_*  every other wide geometry (17 .. 21 bits, window-sharded or shared-stage tables): int32 digits, 2^(c-9)
+//                           buckets per partition
 // The per-window path (zk_msm_g1 over caller bases, vectors below 2^13 or beyond 2^26 points, SRS without a table) keeps round 1's
 // LDS COUNTING sort (msm_hist / msm_scan1-3 / msm_scatter): its windows are 3 .. 16 bits -- the window is a measured step function
 // of the length (make_geom) -- and a partition needs at least 2^7 buckets, and its references carry 31 bits of point index where the
@@ -251,21 +256,28 @@ ZK_HD uint32_t psort_slab_len(uint64_t n) {
     sp = (sp + 1) & ~1ull;
     return (uint32_t)(sp < 2 ? 2 : sp);
 }
+// slab blockIdx.x of a job's n scalars: [lo, hi), empty past the end
+ZK_D uint64_t slab_lo(uint64_t n, uint32_t sp) { return (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n; }
+ZK_D uint64_t slab_hi(uint64_t lo, uint64_t n, uint32_t sp) { return lo + sp < n ? lo + sp : n; }
+// What the first kernel of a job's sort clears for the kernels behind it: the counter psort_scan's last workgroup is found by, and
+// the counters of the job's two combine queues (msm_combine*)
+ZK_D void reset_job_counters(uint32_t* scan_counter, uint32_t* combine_q) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        scan_counter[0] = 0;
+        combine_q[0] = 0;
+        combine_q[1] = 0;
+    }
+}
 
 // digits of the slab's scalars (as msm_digits2: two scalars per lane, 16-bit windows) + the slab's partition counts
 template <class Fr, bool MONT>
 __global__ void __launch_bounds__(256) psort_digits_hist(const uint32_t* scalars, uint64_t n, uint32_t sp, int16_t* dig,
                                                          uint32_t* hist /* [256][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
     __shared__ uint32_t lc[256];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        scan_counter[0] = 0;
-        combine_q[0] = 0;      // counters of the combine queues of this job (msm_combine*)
-        combine_q[1] = 0;
-    }
+    reset_job_counters(scan_counter, combine_q);
     lc[threadIdx.x] = 0;
     __syncthreads();
-    const uint64_t lo = (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n;
-    const uint64_t hi = lo + sp < n ? lo + sp : n;      // n even, sp even: the range holds whole pairs
+    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);      // n even, sp even: the range holds whole pairs
     for (uint64_t i0 = lo + 2 * threadIdx.x; i0 < hi; i0 += 512) {
         uint32_t sc[2][8];
 #pragma unroll
@@ -301,15 +313,10 @@ __global__ void __launch_bounds__(256) psort_digits_hist(const uint32_t* scalars
 __global__ void __launch_bounds__(PS_T) psort_hist(const int16_t* dig, uint64_t n, uint32_t W, uint32_t sp, uint32_t P,
                                                    uint32_t* hist /* [P][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
     extern __shared__ uint32_t lc[];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        scan_counter[0] = 0;
-        combine_q[0] = 0;
-        combine_q[1] = 0;
-    }
+    reset_job_counters(scan_counter, combine_q);
     for (uint32_t j = threadIdx.x; j < P; j += PS_T) lc[j] = 0;
     __syncthreads();
-    const uint64_t lo = (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n;
-    const uint64_t hi = lo + sp < n ? lo + sp : n;
+    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
     const uint32_t len = (uint32_t)(hi - lo);
     for (uint32_t q = threadIdx.x; q < W * len; q += PS_T) {
         const uint32_t w = q / len, ii = q - w * len;
@@ -320,6 +327,18 @@ __global__ void __launch_bounds__(PS_T) psort_hist(const int16_t* dig, uint64_t 
     for (uint32_t j = threadIdx.x; j < P; j += PS_T) hist[(uint64_t)j * PS_SLABS + blockIdx.x] = lc[j];
 }
 
+// inclusive scan of one value per lane inside every wavefront: the first step of the workgroup scans below
+ZK_D uint32_t wave_scan_incl(uint32_t v, uint32_t t) {
+    uint32_t inc = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d, 64);
+        if ((t & 63) >= d) inc += o;
+    }
+    return inc;
+}
+// The workgroup scans (scan128_excl, scan256_excl, scan1024_excl) stay three functions: their barriers differ (128: none behind its LDS
+// read; 256: one behind it; 1024: one in front of its LDS write, as it is called twice in a row on one tmp).
 ZK_D uint32_t scan1024_excl(uint32_t v, uint32_t t, uint32_t* tmp);
 
 // per partition: exclusive scan of its PS_SLABS slab counts in place (coalesced); the workgroup that finishes
@@ -357,12 +376,7 @@ __global__ void __launch_bounds__(PS_SLABS) psort_scan(SJobs jobs, uint32_t P) {
 
 // exclusive scan of 256 values held by lanes 0..255 of a workgroup (every lane calls it); tmp: 4 LDS words
 ZK_D uint32_t scan256_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
-    uint32_t inc = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if ((t & 63) >= d) inc += o;
-    }
+    uint32_t inc = wave_scan_incl(v, t);
     if (t < 256 && (t & 63) == 63) tmp[t >> 6] = inc;
     __syncthreads();
     uint32_t add = 0;
@@ -388,8 +402,7 @@ __global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, ui
     __shared__ uint32_t rec[PS_STILE];       // k (14 bits) | neg << 14 | low bits << 15 | partition << 22
     const uint32_t t = threadIdx.x;
     if (t < 256) gcur[t] = t < P ? part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x] : 0u;
-    const uint64_t lo = (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n;
-    const uint64_t hi = lo + sp < n ? lo + sp : n;
+    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
     const uint32_t len = (uint32_t)(hi - lo);
     const uint32_t total_digits = W * len;           // the slab: W windows x len scalars, visited window-major
     // the digits of the tile after the current one are requested while the current one is counted and placed
@@ -467,12 +480,7 @@ __global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, ui
 
 // exclusive scan of 128 values held by lanes 0..127 of a workgroup (every lane calls it); tmp: one LDS word
 ZK_D uint32_t scan128_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
-    uint32_t inc = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if ((t & 63) >= d) inc += o;
-    }
+    uint32_t inc = wave_scan_incl(v, t);
     if (t == 63) *tmp = inc;
     __syncthreads();
     if (t >= 64 && t < 128) inc += *tmp;
@@ -584,15 +592,10 @@ template <class Fr, bool MONT>
 __global__ void __launch_bounds__(256) psortw_digits_hist(const uint32_t* scalars, uint64_t n, uint32_t sp, MsmGeom g, uint32_t lob, int32_t* dig,
                                                           uint32_t* hist /* [256][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
     __shared__ uint32_t lc[256];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        scan_counter[0] = 0;
-        combine_q[0] = 0;
-        combine_q[1] = 0;
-    }
+    reset_job_counters(scan_counter, combine_q);
     lc[threadIdx.x] = 0;
     __syncthreads();
-    const uint64_t lo = (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n;
-    const uint64_t hi = lo + sp < n ? lo + sp : n;
+    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
     const uint32_t half = 1u << (g.c - 1), cmask = (1u << g.c) - 1u;
     for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) {
         const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * i;
@@ -635,8 +638,7 @@ __global__ void __launch_bounds__(PS_T) psortw_scatter(SJobs jobs, uint32_t W, u
     __shared__ uint16_t rlo[PS_STILE];       // low bucket bits of the record at the same position
     const uint32_t t = threadIdx.x;
     if (t < 256) gcur[t] = part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x];
-    const uint64_t lo = (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n;
-    const uint64_t hi = lo + sp < n ? lo + sp : n;
+    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
     const uint32_t len = (uint32_t)(hi - lo);
     const uint32_t total_digits = W * len;
     // the digits of the tile after the current one are requested while the current one is counted and placed
@@ -716,12 +718,7 @@ __global__ void __launch_bounds__(PS_T) psortw_scatter(SJobs jobs, uint32_t W, u
 
 // exclusive scan of one value per lane over a 1024-lane workgroup; tmp: 16 LDS words
 ZK_D uint32_t scan1024_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
-    uint32_t inc = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if ((t & 63) >= d) inc += o;
-    }
+    uint32_t inc = wave_scan_incl(v, t);
     __syncthreads();
     if ((t & 63) == 63) tmp[t >> 6] = inc;
     __syncthreads();
@@ -860,15 +857,10 @@ template <class Fr, bool MONT>
 __global__ void __launch_bounds__(256, 8) csort_fold_hist(const uint32_t* scalars, uint64_t n, uint32_t sp, MsmGeom g, uint4* folded,
                                                        uint32_t* hist /* [256][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
     __shared__ uint32_t lc[256];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        scan_counter[0] = 0;
-        combine_q[0] = 0;
-        combine_q[1] = 0;
-    }
+    reset_job_counters(scan_counter, combine_q);
     lc[threadIdx.x] = 0;
     __syncthreads();
-    const uint64_t lo = (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n;
-    const uint64_t hi = lo + sp < n ? lo + sp : n;
+    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
     constexpr uint32_t half = 1u << (CS_C - 1);
     for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) {
         const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * i;
@@ -911,8 +903,7 @@ __global__ void __launch_bounds__(PS_T, 8) csort_scatter(SJobs jobs, uint32_t W)
     __shared__ uint32_t cnt[256], toff[257], gcur[256], stmp[4];
     const uint32_t t = threadIdx.x;
     if (t < 256) gcur[t] = part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x];
-    const uint64_t lo = (uint64_t)blockIdx.x * sp < n ? (uint64_t)blockIdx.x * sp : n;
-    const uint64_t hi = lo + sp < n ? lo + sp : n;
+    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
     const uint32_t len = (uint32_t)(hi - lo);
     // the scalars of the tile after the current one are requested while the current one is cut, counted and placed
     uint4 na = make_uint4(0, 0, 0, 0), nb = na;
@@ -1222,6 +1213,13 @@ __global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P)
 
 
 // ---------------------------------------------------------------------------------------- host side
+// f(std::true_type) for Montgomery input (a commit: into_repr is fused into the digit kernel), f(std::false_type) for canonical
+template <class F>
+void on_mont(bool mont, F&& f) {
+    if (mont) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // per-window path: S slabs of scalars per window
 template <class Cv>
 int pw_queue_sort(zk_ctx* c, const MsmGeom& g, uint32_t S, MsmBufs& mb, const void* d_scalars, size_t n, hipStream_t st) {
@@ -1269,18 +1267,18 @@ int pre_queue_digits(zk_ctx* c, const PrePlan& pl, MsmBufs& mb, const void* d_sc
         uint32_t* hist = (uint32_t*)mb.counts.p;
         if (pre_compact(pl)) {                            // the folded scalars wait where the digits would (32 <= 4 W bytes per scalar)
             uint4* folded = (uint4*)mb.entries.p;
-            if (mont) hipLaunchKernelGGL((csort_fold_hist<FrS, true>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp, pl.g,
-                                         folded, hist, scan_counter, combine_q);
-            else hipLaunchKernelGGL((csort_fold_hist<FrS, false>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp, pl.g,
-                                    folded, hist, scan_counter, combine_q);
+            on_mont(mont, [&](auto M) {
+                hipLaunchKernelGGL((csort_fold_hist<FrS, decltype(M)::value>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp,
+                                   pl.g, folded, hist, scan_counter, combine_q);
+            });
             ZK_HIP_TRY(hipGetLastError());
             return ZK_OK;
         }
         int32_t* dig32 = (int32_t*)mb.entries.p;          // the digits wait in the buffer of the sorted references (pre_sizes)
-        if (mont) hipLaunchKernelGGL((psortw_digits_hist<FrS, true>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp, pl.g,
-                                     lob, dig32, hist, scan_counter, combine_q);
-        else hipLaunchKernelGGL((psortw_digits_hist<FrS, false>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp, pl.g,
-                                lob, dig32, hist, scan_counter, combine_q);
+        on_mont(mont, [&](auto M) {
+            hipLaunchKernelGGL((psortw_digits_hist<FrS, decltype(M)::value>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp,
+                               pl.g, lob, dig32, hist, scan_counter, combine_q);
+        });
         ZK_HIP_TRY(hipGetLastError());
         return ZK_OK;
     }
@@ -1295,15 +1293,16 @@ int pre_queue_digits(zk_ctx* c, const PrePlan& pl, MsmBufs& mb, const void* d_sc
     uint32_t* hist = (uint32_t*)mb.counts.p;
     if (pairs && P == 256) {
         // digits and the per-slab partition counts in one kernel
-        if (mont) hipLaunchKernelGGL((psort_digits_hist<FrS, true>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp,
-                                     dig, hist, scan_counter, combine_q);
-        else hipLaunchKernelGGL((psort_digits_hist<FrS, false>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp,
-                                dig, hist, scan_counter, combine_q);
+        on_mont(mont, [&](auto M) {
+            hipLaunchKernelGGL((psort_digits_hist<FrS, decltype(M)::value>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp,
+                               dig, hist, scan_counter, combine_q);
+        });
     } else {
         if (pairs) {
             unsigned b2 = (unsigned)((n / 2 + T - 1) / T);
-            if (mont) hipLaunchKernelGGL((msm_digits2<FrS, true>), dim3(b2), dim3(T), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, pl.g, dig);
-            else hipLaunchKernelGGL((msm_digits2<FrS, false>), dim3(b2), dim3(T), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, pl.g, dig);
+            on_mont(mont, [&](auto M) {
+                hipLaunchKernelGGL((msm_digits2<FrS, decltype(M)::value>), dim3(b2), dim3(T), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, pl.g, dig);
+            });
         } else {
             const void* canon = d_scalars;
             if (mont) {   // odd length: separate into_repr pass, then the one-scalar-per-lane kernel

@@ -17,26 +17,11 @@
 // twiddles stored as w * 2^261 mod r so the data never leave the arkworks (R = 2^256) domain.
 // HBM-side the transform is 2 * N * 32 B algorithmic bytes; the kernel is integer-VALU bound.
 #include "ctx.h"
+#include "fr_io.cuh"
 
 #include "ntt_pass.cuh"
 
 namespace {
-
-template <class Fr>
-ZK_D Fr ld_fr(const void* base, uint64_t idx) {
-    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * idx;
-    uint4 a = q[0], b = q[1];
-    Fr r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-template <class Fr>
-ZK_D void st_fr(void* base, uint64_t idx, const Fr& r) {
-    uint4* q = reinterpret_cast<uint4*>(base) + 2 * idx;
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
 
 // ------------------------------------------------------------------------------------ table builders
 template <class Fr>

@@ -15,71 +15,15 @@
 //     unity: 4 inversions on the host instead of 4n;
 //   * l1_alpha_sq = coset_fft(alpha^2 L1) (quotient_poly.rs:292-294) is alpha^2 * l1 by linearity.
 #include "ctx.h"
+#include "zbound.cuh"
 
 namespace {
-
-template <class Fr>
-ZK_D Fr ld_fr(const void* base, uint64_t idx) {
-    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * idx;
-    uint4 a = q[0], b = q[1];
-    Fr r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-template <class Fr>
-ZK_D void st_fr(void* base, uint64_t idx, const Fr& r) {
-    uint4* q = reinterpret_cast<uint4*>(base) + 2 * idx;
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
 
 constexpr uint32_t QT = 256;     // lanes per workgroup
 constexpr uint32_t QROWS = 4;    // points per lane: i = blk*QT*QROWS + j*QT + lane (coalesced; X steps by w^QT)
 constexpr uint32_t QTAB = 48;    // multiples of r held for the load conversion
 
-// ---- arithmetic: the 29-bit-limb Fr type of the NTT (fieldu.cuh), lazily reduced, with the bound carried in the TYPE.
-// Z<F, B> holds a value < (B / 10) * r.  A Montgomery product needs a * b < 2^261 * r / r^2 ~ 70 r^2 (169 r^2 on BN254) and
-// returns < 2r; sums add their bounds; a difference a - b adds the smallest of 2r / 8r / 16r that covers b.  Every rule is a
-// static_assert, so a formula that could overflow does not compile.
-template <class F, int B>
-struct Z {
-    F v;
-    ZK_D Z() {}
-    ZK_D Z(const F& f) : v(f) {}
-    template <int B2>
-    ZK_D Z(const Z<F, B2>& o) : v(o.v) {      // widening only
-        static_assert(B2 <= B, "bound would shrink");
-    }
-};
-template <class F, int A, int B>
-ZK_D Z<F, 20> operator*(const Z<F, A>& a, const Z<F, B>& b) {
-    static_assert(A * B <= 6400, "Montgomery product operands too large");
-    return {F::mul(a.v, b.v)};
-}
-template <class F, int A>
-ZK_D Z<F, 20> zsqr(const Z<F, A>& a) {
-    static_assert(A * A <= 6400, "square operand too large");
-    return {F::sqr(a.v)};
-}
-template <class F, int A, int B>
-ZK_D Z<F, A + B> operator+(const Z<F, A>& a, const Z<F, B>& b) {
-    static_assert(A + B <= 600, "sum too large for the 261-bit container");
-    return {F::add(a.v, b.v)};
-}
-template <int B>
-struct SubK {
-    static_assert(B <= 160, "subtrahend above 16r");
-    static constexpr int K = B <= 20 ? 20 : B <= 80 ? 80 : 160;
-};
-template <class F, int A, int B>
-ZK_D Z<F, A + SubK<B>::K> operator-(const Z<F, A>& a, const Z<F, B>& b) {
-    static_assert(A + SubK<B>::K <= 600, "difference too large for the 261-bit container");
-    if constexpr (SubK<B>::K == 20) return {F::sub2(a.v, b.v)};
-    else if constexpr (SubK<B>::K == 80) return {F::sub8(a.v, b.v)};
-    else return {F::sub16(a.v, b.v)};
-}
-
+// arithmetic: the 29-bit-limb Fr type of the NTT (fieldu.cuh), lazily reduced, with the bound carried in the type (zbound.cuh)
 template <class F>
 struct QArgsU {
     const void *w_l, *w_r, *w_o, *w_4, *z, *z2, *f, *table, *h1, *h2, *pi, *l1;
@@ -97,40 +41,6 @@ struct QArgsU {
     uint32_t ratio_fx;                          // floor(2^BITS / r * 2^10) - 1
     uint32_t top_shift;                         // BITS - 29 * (NL - 1)
 };
-
-// arkworks Montgomery value x * 2^256 (canonical, 8 words) -> x * 2^261 mod r, < 1.2 r:
-// shift left by 5 bits (32 v < 32 r < 2^260), subtract q2 * r with q2 = floor(floor(32 v / 2^BITS) * (2^BITS / r)) <= 32 v / r
-// (leaves < 2.15 r), then r once more if the rest is still >= r.
-template <class F>
-ZK_D Z<F, 12> ld_rp(const void* base, uint64_t idx, const uint32_t (*rtab)[F::NL], uint32_t ratio_fx, uint32_t top_shift) {
-    const uint4* q = reinterpret_cast<const uint4*>(base) + 2 * idx;
-    uint4 a = q[0], b = q[1];
-    uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    F l = F::split_words(w);
-    F s;
-#pragma unroll
-    for (int i = F::NL - 1; i >= 1; --i) s.v[i] = ((l.v[i] << 5) | (l.v[i - 1] >> 24)) & (i == F::NL - 1 ? 0xffffffffu : F::M);
-    s.v[0] = (l.v[0] << 5) & F::M;
-    const uint32_t q2 = ((s.v[F::NL - 1] >> top_shift) * ratio_fx) >> 10;
-    F t;
-#pragma unroll
-    for (int i = 0; i < F::NL; ++i) t.v[i] = s.v[i] - rtab[q2][i];
-    F::normalize(t);
-    F d;
-#pragma unroll
-    for (int i = 0; i < F::NL; ++i) d.v[i] = t.v[i] - rtab[1][i];
-    F::normalize(d);
-    const bool neg = ((int32_t)d.v[F::NL - 1]) < 0;
-    F r;
-#pragma unroll
-    for (int i = 0; i < F::NL; ++i) r.v[i] = neg ? t.v[i] : d.v[i];
-    return Z<F, 12>(r);
-}
-
-template <class F, int B>
-ZK_D Z<F, 20> delta4(const Z<F, B>& f, const Z<F, 10>& one, const Z<F, 10>& c2, const Z<F, 10>& c3) {   // f(f-1)(f-2)(f-3)
-    return (f * (f - one)) * ((f - c2) * (f - c3));
-}
 
 // The argument block (28 pointers + the field constants + the table of multiples of r) is read through a pointer.
 // 256 VGPRs (25 spilled on BLS12-381): 2 waves per SIMD; 8.7 -> 5.0 ms for the 2^22 points of an n = 2^20 proof against the saturated
@@ -249,15 +159,6 @@ __global__ void __launch_bounds__(QT, 2) quotient_points(const QArgsU<F>* __rest
     }
 }
 
-// host: arkworks-form Fr (R = 2^256) -> the canonical R' = 2^261 residue as 29-bit limbs
-template <class C>
-typename C::FrU to_rp_host(const typename C::Fr& v) {
-    typedef typename C::Fr Fr;
-    Fr t = v;
-    for (int k = 0; k < 5; ++k) t = Fr::add(t, t);
-    return C::FrU::split_words(t.v);
-}
-
 template <class C>
 int quotient_run(zk_ctx* c, uint32_t log_n, const zk_quotient_args* q, void* d_out) {
     typedef typename C::Fr Fr;
@@ -335,21 +236,7 @@ int quotient_run(zk_ctx* c, uint32_t log_n, const zk_quotient_args* q, void* d_o
         A.inv_vh[k] = U(Fr::mul(Fr::inverse(vh), inv32));
         cur = Fr::mul(cur, wn);
     }
-    {   // q * r as 29-bit limbs, and floor(2^BITS / r * 2^10) - 1
-        uint32_t rw[8];
-        for (int i = 0; i < 8; ++i) rw[i] = C::FrP::MOD(i);
-        FU acc = FU::zero();
-        const FU rl = FU::split_words(rw);
-        for (uint32_t k = 0; k < QTAB; ++k) {
-            for (int i = 0; i < FU::NL; ++i) A.rtab[k][i] = acc.v[i];
-            acc = FU::add(acc, rl);
-        }
-        long double rv = 0;
-        for (int i = Fr::N - 1; i >= 0; --i) rv = rv * 4294967296.0L + (long double)C::FrP::MOD(i);
-        const long double ratio = ldexpl(1.0L, C::FrP::BITS + 10) / rv;
-        A.ratio_fx = (uint32_t)floorl(ratio) - 1;
-        A.top_shift = (uint32_t)(C::FrP::BITS - 29 * (FU::NL - 1));
-    }
+    rp_table<C>(A.rtab, QTAB, A.ratio_fx, A.top_shift);
     ProfScope ps(c, "quotient");
     int rc = c->msm_tmp.ensure(sizeof A);
     if (rc) return rc;

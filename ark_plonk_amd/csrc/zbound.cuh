@@ -1,0 +1,122 @@
+// Bounded lazy arithmetic over the 29-bit-limb Fr type of the NTT (fieldu.cuh), with the bound carried in the TYPE, and the load
+// conversion into its R' = 2^261 Montgomery form.  Shared by the quotient kernel (quotient.hip) and the gate terms of the circuit
+// check (check.hip), which tests the very summands the quotient enforces: a bound rule is corrected here, once, for both.
+#pragma once
+#include "fr_io.cuh"
+
+#include <cmath>
+
+namespace {
+
+// Z<F, B> holds a value < (B / 10) * r.  A Montgomery product needs a * b < 2^261 * r / r^2 ~ 70 r^2 (169 r^2 on BN254) and
+// returns < 2r; sums add their bounds; a difference a - b adds the smallest of 2r / 8r / 16r that covers b.  Every rule is a
+// static_assert, so a formula that could overflow does not compile.
+template <class F, int B>
+struct Z {
+    F v;
+    ZK_D Z() {}
+    ZK_D Z(const F& f) : v(f) {}
+    template <int B2>
+    ZK_D Z(const Z<F, B2>& o) : v(o.v) {      // widening only
+        static_assert(B2 <= B, "bound would shrink");
+    }
+};
+template <class F, int A, int B>
+ZK_D Z<F, 20> operator*(const Z<F, A>& a, const Z<F, B>& b) {
+    static_assert(A * B <= 6400, "Montgomery product operands too large");
+    return {F::mul(a.v, b.v)};
+}
+template <class F, int A>
+ZK_D Z<F, 20> zsqr(const Z<F, A>& a) {
+    static_assert(A * A <= 6400, "square operand too large");
+    return {F::sqr(a.v)};
+}
+template <class F, int A, int B>
+ZK_D Z<F, A + B> operator+(const Z<F, A>& a, const Z<F, B>& b) {
+    static_assert(A + B <= 600, "sum too large for the 261-bit container");
+    return {F::add(a.v, b.v)};
+}
+template <int B>
+struct SubK {
+    static_assert(B <= 160, "subtrahend above 16r");
+    static constexpr int K = B <= 20 ? 20 : B <= 80 ? 80 : 160;
+};
+template <class F, int A, int B>
+ZK_D Z<F, A + SubK<B>::K> operator-(const Z<F, A>& a, const Z<F, B>& b) {
+    static_assert(A + SubK<B>::K <= 600, "difference too large for the 261-bit container");
+    if constexpr (SubK<B>::K == 20) return {F::sub2(a.v, b.v)};
+    else if constexpr (SubK<B>::K == 80) return {F::sub8(a.v, b.v)};
+    else return {F::sub16(a.v, b.v)};
+}
+// value != 0 mod r, exactly.  Zero has several encodings (0, r, 2r, ...): a value below 2r is 0 or r when it is a multiple of r;
+// anything larger goes through a product with one
+template <class F, int B>
+ZK_D bool nonzero(const Z<F, B>& t, const Z<F, 10>& one) {
+    if constexpr (B <= 20) return !t.v.is_zero_mod_reduced();
+    else return !(t * one).v.is_zero_mod_reduced();
+}
+
+template <class F, int B>
+ZK_D Z<F, 20> delta4(const Z<F, B>& f, const Z<F, 10>& one, const Z<F, 10>& c2, const Z<F, 10>& c3) {   // f(f-1)(f-2)(f-3)
+    return (f * (f - one)) * ((f - c2) * (f - c3));
+}
+
+// arkworks Montgomery value x * 2^256 (canonical, 8 words) -> x * 2^261 mod r, < 1.2 r:
+// shift left by 5 bits (32 v < 32 r < 2^260), subtract q2 * r with q2 = floor(floor(32 v / 2^BITS) * (2^BITS / r)) <= 32 v / r
+// (leaves < 2.15 r), then r once more if the rest is still >= r.  rtab[q] = q * r, ratio_fx and top_shift: rp_table below.
+template <class F>
+ZK_D Z<F, 12> to_rp(const El& e, const uint32_t (*rtab)[F::NL], uint32_t ratio_fx, uint32_t top_shift) {
+    uint32_t w[8] = {e.a.x, e.a.y, e.a.z, e.a.w, e.b.x, e.b.y, e.b.z, e.b.w};
+    F l = F::split_words(w);
+    F s;
+#pragma unroll
+    for (int i = F::NL - 1; i >= 1; --i) s.v[i] = ((l.v[i] << 5) | (l.v[i - 1] >> 24)) & (i == F::NL - 1 ? 0xffffffffu : F::M);
+    s.v[0] = (l.v[0] << 5) & F::M;
+    const uint32_t q2 = ((s.v[F::NL - 1] >> top_shift) * ratio_fx) >> 10;
+    F t;
+#pragma unroll
+    for (int i = 0; i < F::NL; ++i) t.v[i] = s.v[i] - rtab[q2][i];
+    F::normalize(t);
+    F d;
+#pragma unroll
+    for (int i = 0; i < F::NL; ++i) d.v[i] = t.v[i] - rtab[1][i];
+    F::normalize(d);
+    const bool neg = ((int32_t)d.v[F::NL - 1]) < 0;
+    F r;
+#pragma unroll
+    for (int i = 0; i < F::NL; ++i) r.v[i] = neg ? t.v[i] : d.v[i];
+    return Z<F, 12>(r);
+}
+template <class F>
+ZK_D Z<F, 12> ld_rp(const void* base, uint64_t idx, const uint32_t (*rtab)[F::NL], uint32_t ratio_fx, uint32_t top_shift) {
+    return to_rp<F>(ld_el(base, idx), rtab, ratio_fx, top_shift);
+}
+
+// ---- host side
+// arkworks-form Fr (R = 2^256) -> the canonical R' = 2^261 residue as 29-bit limbs
+template <class Cv>
+typename Cv::FrU to_rp_host(const typename Cv::Fr& v) {
+    typename Cv::Fr t = v;
+    for (int k = 0; k < 5; ++k) t = Cv::Fr::add(t, t);
+    return Cv::FrU::split_words(t.v);
+}
+// what to_rp reads: rtab[q] = q * r as 29-bit limbs for q < len, ratio_fx = floor(2^BITS / r * 2^10) - 1 and
+// top_shift = BITS - 29 * (NL - 1).  len must cover the largest q2 (32 v / r < 32, and the estimate never exceeds it).
+template <class Cv>
+void rp_table(uint32_t (*rtab)[Cv::FrU::NL], uint32_t len, uint32_t& ratio_fx, uint32_t& top_shift) {
+    typedef typename Cv::FrU FU;
+    uint32_t rw[8];
+    for (int i = 0; i < 8; ++i) rw[i] = Cv::FrP::MOD(i);
+    FU acc = FU::zero();
+    const FU rl = FU::split_words(rw);
+    for (uint32_t k = 0; k < len; ++k) {
+        for (int i = 0; i < FU::NL; ++i) rtab[k][i] = acc.v[i];
+        acc = FU::add(acc, rl);
+    }
+    long double rv = 0;
+    for (int i = Cv::Fr::N - 1; i >= 0; --i) rv = rv * 4294967296.0L + (long double)Cv::FrP::MOD(i);
+    ratio_fx = (uint32_t)floorl(ldexpl(1.0L, Cv::FrP::BITS + 10) / rv) - 1;
+    top_shift = (uint32_t)(Cv::FrP::BITS - 29 * (FU::NL - 1));
+}
+
+}  // namespace

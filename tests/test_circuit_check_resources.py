@@ -1,4 +1,4 @@
-"""Compile-time guard on the kernels of the circuit check (csrc_check/check.hip; hipcc's `-Rpass-analysis=kernel-resource-usage`
+"""Compile-time guard on the kernels of the circuit check (csrc/check.hip; hipcc's `-Rpass-analysis=kernel-resource-usage`
 remarks, no GPU needed): no kernel of the unit, for either curve, uses scratch memory or spills a register.  The gate kernel holds the
 terms of five widgets; a spill there would put it behind the quotient kernel it is a subset of."""
 import os
@@ -15,7 +15,7 @@ KERNELS = ("check_gates", "check_id_keys", "map_build", "check_copy", "check_loo
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
 def test_check_kernels_use_no_scratch():
     from ark_plonk_amd import build
-    src = os.path.join(ROOT, "ark_plonk_amd", "csrc_check", "check.hip")
+    src = os.path.join(ROOT, "ark_plonk_amd", "csrc", "check.hip")
     cmd = [HIPCC] + build.FLAGS + ["--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
     err = subprocess.run(cmd, capture_output=True, text=True, timeout=1500).stderr
     kernels, cur = {}, None

@@ -1,4 +1,4 @@
-"""CPU side of the inner-product-argument commitment (ark_plonk_amd/ipa.py, ark_plonk_amd/csrc_ipa/): the test oracle's two groups
+"""CPU side of the inner-product-argument commitment (ark_plonk_amd/ipa.py, ark_plonk_amd/csrc/ipa.hip): the test oracle's two groups
 agree byte for byte, its check accepts honest proofs and rejects every single tamper, the transcript's encoding of the point at
 infinity, and the key-fold kernel's register budget (gfx950 device code compiled here, no GPU)."""
 import hashlib
@@ -119,7 +119,7 @@ def test_transcript_hash_maps_into_the_field_by_rejection():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
 def test_fold_kernel_has_no_spills_and_no_scratch():
-    src = os.path.join(ROOT, "ark_plonk_amd", "csrc_ipa", "ipa.hip")
+    src = os.path.join(ROOT, "ark_plonk_amd", "csrc", "ipa.hip")
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-pragma-unroll-threshold=1000000", "--cuda-device-only",
            "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
     err = subprocess.run(cmd, capture_output=True, text=True, timeout=1500).stderr

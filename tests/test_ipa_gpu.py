@@ -1,4 +1,4 @@
-"""The inner-product-argument commitment on the MI355X (ark_plonk_amd/ipa.py over ark_plonk_amd/csrc_ipa/ipa.hip) against the
+"""The inner-product-argument commitment on the MI355X (ark_plonk_amd/ipa.py over ark_plonk_amd/csrc/ipa.hip) against the
 pure-Python oracle of tests/ipa_oracle.py: the key-fold kernel with its edge cases, whole openings byte for byte, the device check,
 the final key through the SRS table path, and the ABI's behaviour next to KZG work on the same ctx.  Keys are known-logarithm test
 keys G_i = k_i G (generated on the device by the fixed-base utility), so the oracle does Fr arithmetic only."""
