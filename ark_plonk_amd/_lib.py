@@ -68,6 +68,16 @@ class CircuitCheckSummary(ctypes.Structure):
     _fields_ = [("failing_rows", c_u64), ("first_row", c_u64), ("first_mask", c_u32), ("reserved", c_u32), ("bit_count", c_u64 * 32)]
 
 
+class GadgetArgs(ctypes.Structure):
+    """zk_gadget_args"""
+    _fields_ = [("kind", c_u32), ("num_bits", c_u32), ("flags", c_u32), ("reserved", c_u32), ("calls", c_u64), ("row0", c_u64), ("var0", c_u64),
+                ("inputs", c_void_p * 4), ("coeff", c_void_p * 6), ("coeff_const", c_u64 * 24), ("pi", c_void_p), ("coeff_a", c_u64 * 4),
+                ("coeff_d", c_u64 * 4), ("table", c_void_p)]
+
+
+ZK_GADGET_POLY, ZK_GADGET_RANGE, ZK_GADGET_LOGIC, ZK_GADGET_CURVE_ADD, ZK_GADGET_FIXED_BASE = range(5)
+ZK_GADGET_COMPUTE_OUT, ZK_GADGET_XOR = 1, 2
+
 # every symbol include/ark_plonk_amd.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "zk_strerror": (ctypes.c_char_p, [c_int]),
@@ -176,6 +186,11 @@ SYMBOLS = {
     "zk_fr_gather_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     # circuit check: per-row masks of violated constraints (CircuitCheckArgs, CircuitCheckSummary)
     "zk_circuit_check_dev": (c_int, [c_void_p, c_int, c_u32, c_void_p, c_void_p, c_void_p]),
+    # gadget circuits and their witnesses (GadgetArgs)
+    "zk_gadget_shape": (c_int, [c_int, c_int, c_u32, c_u32, c_size_t, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32),
+                                ctypes.POINTER(c_size_t)]),
+    "zk_gadget_layout_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
+    "zk_gadget_witness_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
     "zk_fr_serialized_size": (c_size_t, [c_int]),
     "zk_g1_compressed_size": (c_size_t, [c_int]),
     "zk_fr_serialize": (c_int, [c_int, c_void_p, ctypes.c_char_p]),

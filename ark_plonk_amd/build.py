@@ -49,6 +49,8 @@ def jobs():
         ("ipa.o", "ipa.hip", [], API_HDRS + FR_IO + POINT_IO),
         ("compile.o", "compile.hip", [], API_HDRS + FR_IO),
         ("check.o", "check.hip", [], API_HDRS + ZBOUND),
+        # the device composer: gadget segments (rows, ids, selectors, insertions) and the values of the variables they create
+        ("gadgets.o", "gadgets.hip", [], API_HDRS + FR_IO),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

@@ -1,0 +1,347 @@
+"""`StandardComposer` (plonk-core/src/constraint_system/) for batched gadget calls, on the device: `Composer` produces what
+`compile.compile` consumes -- the `CircuitDescription`, built once per circuit -- and what `compile.assign` consumes -- the
+(num_vars, 4) value vector, replayed per proof (csrc/gadgets.hip: zk_gadget_layout_dev, zk_gadget_witness_dev).
+
+A SEGMENT is B calls of one gadget with the same parameters; by definition it is what the reference's composer holds after that gadget
+is called B times in a row, call k with the k-th input variables: rows, new variables in `add_input` order and `add_variable_to_map`
+calls in call order, the cells the reference pushes without mapping (range.rs:185-187) and the logic gate's Output(n - 1) after Left(n)
+included.  Variable handles are int32 device tensors of shape (B,) (a single id broadcasts), gadgets return the handles the reference
+returns, so segments chain without a host copy:
+
+    c = Composer("bls12_381", ctx, coeffs=(a, d))
+    x = c.inputs(1024)                          # values arrive at assign time
+    c.range_gate(x, 64)
+    px, py = c.fixed_base_scalar_mul(x, G)
+    desc = c.description()                      # -> compile.compile(desc, ck)
+    values = c.assign([x_values])               # -> compile.assign(desc, values)
+
+A new composer starts as `StandardComposer::new()` does (composer.rs:231-235, 580-648): variable 0 constrained to zero on row 0, three
+blinding rows over variables 1 .. 8, whose values `assign` takes or draws.
+
+gadget                  rows per call        new variables     insertions
+arithmetic family       1                    0 or 1            4
+range_gate(bits)        ceil(bits/8) + 2     bits / 2          4 ceil(bits/8) + 5
+xor_gate / and_gate     bits / 2 + 1         2 bits            2 bits + 4
+point_addition_gate     2                    3                 8
+fixed_base_scalar_mul   M + 5                4 M + 3           4 (M + 5)         M = bits of the scalar field (255 / 254)"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, lib
+from .compile import CircuitDescription, padded_size
+from .context import check_dev_tensor, default_context
+from .curves import fr_to_mont, get_curve
+from .prover import SELECTORS
+
+_REC_SHIFT = 30
+_PRELUDE_ROWS, _PRELUDE_VARS = 4, 9
+
+
+def edwards_add(p: int, ca: int, cd: int, p1, p2):
+    """the affine twisted Edwards law a x^2 + y^2 = 1 + d x^2 y^2 on Python integers (ark-ec GroupAffine::add)"""
+    (x1, y1), (x2, y2) = p1, p2
+    t = cd * x1 * x2 * y1 * y2 % p
+    return (x1 * y2 + y1 * x2) * pow(1 + t, -1, p) % p, (y1 * y2 - ca * x1 * x2) * pow(1 - t, -1, p) % p
+
+
+class Composer:
+    def __init__(self, curve="bls12_381", ctx=None, coeffs=(0, 0), device=None):
+        import torch
+        self.curve = get_curve(curve)
+        self.ctx = ctx or default_context(0 if device is None else device)
+        self.device = torch.device("cuda", self.ctx.device)
+        self.coeffs = (int(coeffs[0]) % self.curve.r, int(coeffs[1]) % self.curve.r)
+        self._coeff_mont = [fr_to_mont(self.curve, [v])[0] for v in self.coeffs]
+        self.m_bits = self.curve.r.bit_length()
+        self.n_gates, self.num_vars = _PRELUDE_ROWS, _PRELUDE_VARS
+        self.public_inputs = {}                         # row -> integer, as given at build time
+        self._program = []                              # ("inputs", var0, B) / ("segment", record) in build order
+        self._n_inputs = 0
+        # StandardComposer::new(): constrain_to_constant(zero_var, 0) and add_blinding_factors
+        one = fr_to_mont(self.curve, [1])[0].view(np.int64)
+        sel = {name: torch.zeros((_PRELUDE_ROWS, 4), dtype=torch.int64) for name in SELECTORS}
+        sel["q_l"][0] = torch.from_numpy(one)
+        sel["q_arith"][0] = torch.from_numpy(one)
+        wires = [[0, 1, 5, 5], [0, 2, 6, 6], [0, 3, 7, 0], [0, 4, 8, 0]]
+        self._ids = [[torch.tensor(w, dtype=torch.int32, device=self.device)] for w in wires]
+        self._sel = {name: [sel[name].to(self.device)] for name in SELECTORS}
+        self._ins_var = [torch.tensor([wires[w][r] for r in range(_PRELUDE_ROWS) for w in range(4)], dtype=torch.int32, device=self.device)]
+        self._ins_rec = [torch.tensor([(w << _REC_SHIFT) | r for r in range(_PRELUDE_ROWS) for w in range(4)], dtype=torch.int64)
+                         .to(torch.int32).to(self.device)]
+
+    # ------------------------------------------------------------------------------------------------------------ handles
+    def zero_var(self) -> int:
+        return 0
+
+    def _own(self, t):
+        t._composer = self
+        return t
+
+    def inputs(self, B: int):
+        """B fresh variables whose values arrive at assign time (`add_input`), as a handle"""
+        import torch
+        B = int(B)
+        if B < 1:
+            raise ValueError("at least one variable expected")
+        v0 = self.num_vars
+        self.num_vars += B
+        self._program.append(("inputs", v0, B))
+        self._n_inputs += 1
+        return self._own(torch.arange(v0, v0 + B, dtype=torch.int32, device=self.device))
+
+    def _batch(self, handles, B=None) -> int:
+        sizes = {int(h.numel()) for h in handles if hasattr(h, "numel") and int(h.numel()) != 1}
+        if B is not None:
+            sizes.add(int(B))
+        if len(sizes) > 1:
+            raise ValueError(f"handles of different batch sizes: {sorted(sizes)}")
+        B = sizes.pop() if sizes else 1
+        if B < 1:
+            raise ValueError("a segment holds at least one call")
+        return B
+
+    def _handle(self, h, B: int):
+        import torch
+        if hasattr(h, "numel"):
+            if getattr(h, "_composer", self) is not self:
+                raise ValueError("a variable handle of another composer")
+            if h.dtype != torch.int32 or h.device != self.device or h.dim() > 1:
+                raise ValueError("a variable handle is an int32 device tensor of shape (B,)")
+            h = h.reshape(-1)
+            return h.contiguous() if h.numel() == B else h.expand(B).contiguous()
+        h = int(h)
+        if not 0 <= h < self.num_vars:
+            raise ValueError(f"variable {h} is not defined")
+        return torch.full((B,), h, dtype=torch.int32, device=self.device)
+
+    def _column(self, vals):
+        import torch
+        return torch.from_numpy(fr_to_mont(self.curve, vals).view(np.int64)).to(self.device)
+
+    # ------------------------------------------------------------------------------------------------------------ segments
+    def _shape(self, kind, num_bits=0, flags=0, B=1):
+        r, v, i, w = _lib.c_u32(), _lib.c_u32(), _lib.c_u32(), _lib.c_size_t()
+        check(lib().zk_gadget_shape(kind, self.curve.curve_id, num_bits, flags, B, ctypes.byref(r), ctypes.byref(v), ctypes.byref(i),
+                                    ctypes.byref(w)), "zk_gadget_shape")
+        return r.value, v.value, i.value, w.value
+
+    def _args(self, seg) -> _lib.GadgetArgs:
+        a = _lib.GadgetArgs()
+        a.kind, a.num_bits, a.flags, a.calls, a.row0, a.var0 = seg["kind"], seg["num_bits"], seg["flags"], seg["B"], seg["row0"], seg["var0"]
+        for w, h in enumerate(seg["inputs"]):
+            a.inputs[w] = None if h is None else h.data_ptr()
+        for j, cf in enumerate(seg["coeff"]):
+            if hasattr(cf, "data_ptr"):
+                a.coeff[j] = cf.data_ptr()
+            else:
+                for t, limb in enumerate(fr_to_mont(self.curve, [cf])[0]):
+                    a.coeff_const[4 * j + t] = int(limb)
+        for t in range(4):
+            a.coeff_a[t], a.coeff_d[t] = int(self._coeff_mont[0][t]), int(self._coeff_mont[1][t])
+        if seg["table"] is not None:
+            a.table = seg["table"].data_ptr()
+        return a
+
+    def _segment(self, kind, B, inputs, num_bits=0, flags=0, coeff=(0,) * 6, pi=None, table=None) -> dict:
+        import torch
+        R, V, I, _ = self._shape(kind, num_bits, flags, B)
+        cf = []
+        for c_ in coeff:
+            if hasattr(c_, "data_ptr"):
+                if check_dev_tensor(c_, 4, self.ctx.device) != B:
+                    raise ValueError(f"a coefficient column holds one Montgomery row per call ({B})")
+            elif not isinstance(c_, (int, np.integer)):
+                c_ = self._column(list(c_))
+                if int(c_.shape[0]) != B:
+                    raise ValueError(f"a coefficient column holds one value per call ({B})")
+            cf.append(c_)
+        if pi is not None:
+            pi = [int(v) % self.curve.r for v in (pi if hasattr(pi, "__len__") else [pi] * B)]
+            if len(pi) != B:
+                raise ValueError(f"one public input per call ({B}) expected")
+        seg = {"kind": kind, "num_bits": num_bits, "flags": flags, "B": B, "row0": self.n_gates, "var0": self.num_vars, "R": R, "V": V,
+               "inputs": list(inputs) + [None] * (4 - len(inputs)), "coeff": cf, "pi": pi, "table": table}
+        N = B * R
+        ids = torch.empty((4, N), dtype=torch.int32, device=self.device)
+        sel = [torch.empty((N, 4), dtype=torch.int64, device=self.device) for _ in SELECTORS]
+        ins_var = torch.empty(B * I, dtype=torch.int32, device=self.device)
+        ins_rec = torch.empty(B * I, dtype=torch.int32, device=self.device)
+        a = self._args(seg)
+        self.ctx.use_torch_stream()
+        check(lib().zk_gadget_layout_dev(self.ctx.handle, self.curve.curve_id, ctypes.addressof(a), ids.data_ptr(),
+                                         (ctypes.c_void_p * 12)(*[t.data_ptr() for t in sel]), ins_var.data_ptr(), ins_rec.data_ptr()),
+              "zk_gadget_layout_dev")
+        for w in range(4):
+            self._ids[w].append(ids[w])
+        for name, t in zip(SELECTORS, sel):
+            self._sel[name].append(t)
+        self._ins_var.append(ins_var)
+        self._ins_rec.append(ins_rec)
+        if pi is not None:
+            self.public_inputs.update({seg["row0"] + k: v for k, v in enumerate(pi)})
+        self.n_gates += N
+        self.num_vars += B * V
+        self._program.append(("segment", seg))
+        return seg
+
+    def _new_vars(self, seg, offset: int):
+        """the handle of new variable `offset` of every call of the segment"""
+        import torch
+        return self._own(seg["var0"] + offset + seg["V"] * torch.arange(seg["B"], dtype=torch.int32, device=self.device))
+
+    # ------------------------------------------------------------------------------------------------------------ gadgets
+    def arithmetic_gate(self, a, b, c=None, d=None, q_m=0, q_l=0, q_r=0, q_o=-1, q_c=0, q_4=0, pi=None, B=None):
+        """`arithmetic_gate` (arithmetic.rs:103-168): one row q_m a b + q_l a + q_r b + q_o c + q_4 d + q_c + pi = 0 per call.  A
+        coefficient is an integer (constant for the segment), a sequence of B integers or a (B, 4) Montgomery device column; pi an
+        integer or B integers (host values given at build time, replaceable per row at assign time).  With c=None the output is a new
+        variable whose value is (q_m a b + q_l a + q_r b + q_c + q_4 d + pi) (-q_o), exactly as arithmetic.rs:144-155 writes it: it
+        MULTIPLIES by -q_o, it does not divide -- the row is satisfied for q_o = -1 (the default) and q_o = 1 only.  Returns c."""
+        B = self._batch([h for h in (a, b, c, d) if h is not None], B)
+        hs = [self._handle(a, B), self._handle(b, B), None if c is None else self._handle(c, B), self._handle(0 if d is None else d, B)]
+        seg = self._segment(_lib.ZK_GADGET_POLY, B, hs, flags=_lib.ZK_GADGET_COMPUTE_OUT if c is None else 0,
+                            coeff=(q_m, q_l, q_r, q_o, q_4, q_c), pi=pi)
+        return self._new_vars(seg, 0) if c is None else self._own(hs[2])
+
+    def poly_gate(self, a, b, c, q_m=0, q_l=0, q_r=0, q_o=0, q_c=0, pi=None, B=None):
+        """`poly_gate` (composer.rs:269-312)"""
+        self.arithmetic_gate(a, b, c, None, q_m, q_l, q_r, q_o, q_c, 0, pi, B)
+        return a, b, c
+
+    def constrain_to_constant(self, a, constant, pi=None):
+        """`constrain_to_constant` (composer.rs:318-335): a - constant + pi = 0; constant: an integer or one per call"""
+        r = self.curve.r
+        neg = (-int(constant)) % r if isinstance(constant, (int, np.integer)) else [(-int(v)) % r for v in constant]
+        B = None if isinstance(neg, int) else len(neg)
+        self.arithmetic_gate(a, a, a, None, 0, 1, 0, 0, neg, 0, pi, B)
+
+    def assert_equal(self, a, b):
+        """`assert_equal` (composer.rs:339-350)"""
+        self.arithmetic_gate(a, b, 0, None, 0, 1, -1, 0, 0, 0)
+
+    def boolean_gate(self, a):
+        """`boolean_gate` (boolean.rs:25-51): a a - a = 0"""
+        return self.arithmetic_gate(a, a, a, None, 1, 0, 0, -1, 0, 0)
+
+    @staticmethod
+    def _check_bits(num_bits) -> int:
+        num_bits = int(num_bits)
+        if num_bits % 2 or not 2 <= num_bits <= 256:
+            raise ValueError("num_bits must be even and in 2 .. 256")
+        return num_bits
+
+    def range_gate(self, x, num_bits: int):
+        """`range_gate` (range.rs:27-195); the closing assert_equal row is satisfied iff the value is below 2^num_bits"""
+        num_bits = self._check_bits(num_bits)
+        B = self._batch([x])
+        self._segment(_lib.ZK_GADGET_RANGE, B, [self._handle(x, B)], num_bits=num_bits)
+
+    def _logic(self, a, b, num_bits, flags):
+        num_bits = self._check_bits(num_bits)
+        B = self._batch([a, b])
+        seg = self._segment(_lib.ZK_GADGET_LOGIC, B, [self._handle(a, B), self._handle(b, B)], num_bits=num_bits, flags=flags)
+        return self._new_vars(seg, 4 * (num_bits // 2 - 1) + 3)
+
+    def xor_gate(self, a, b, num_bits: int):
+        """`xor_gate` (logic.rs:322-329): the variable of the last fourth wire.  As in the reference nothing ties the last input
+        prefixes back to a and b."""
+        return self._logic(a, b, num_bits, _lib.ZK_GADGET_XOR)
+
+    def and_gate(self, a, b, num_bits: int):
+        """`and_gate` (logic.rs:338-345)"""
+        return self._logic(a, b, num_bits, 0)
+
+    def point_addition_gate(self, p1, p2):
+        """`point_addition_gate` (variable_base_gate.rs:24-93): points are (x, y) pairs of handles; returns (x3, y3)"""
+        hs = [p1[0], p1[1], p2[0], p2[1]]
+        B = self._batch(hs)
+        seg = self._segment(_lib.ZK_GADGET_CURVE_ADD, B, [self._handle(h, B) for h in hs])
+        return self._new_vars(seg, 1), self._new_vars(seg, 2)
+
+    def fixed_base_table(self, base):
+        """(3 M, 4) Montgomery rows: x, y, x y of 2^(M-1-i) G for row i (fixed_base.rs:19-36, 58-60), on Python integers"""
+        p, (ca, cd), M = self.curve.r, self.coeffs, self.m_bits
+        pts = [(int(base[0]) % p, int(base[1]) % p)]
+        for _ in range(M - 1):
+            pts.append(edwards_add(p, ca, cd, pts[-1], pts[-1]))
+        flat = []
+        for x, y in reversed(pts):
+            flat += [x, y, x * y % p]
+        return self._column(flat)
+
+    def fixed_base_scalar_mul(self, scalar, base):
+        """`fixed_base_scalar_mul` (fixed_base.rs:51-160): base an affine point (x, y) of the embedded curve as integers; returns the
+        handles (acc_x, acc_y) of the product.  A scalar whose width-2 NAF has more than M digits is refused at assign time."""
+        B = self._batch([scalar])
+        seg = self._segment(_lib.ZK_GADGET_FIXED_BASE, B, [self._handle(scalar, B)], table=self.fixed_base_table(base))
+        return self._new_vars(seg, 4 * self.m_bits), self._new_vars(seg, 4 * self.m_bits + 1)
+
+    # ------------------------------------------------------------------------------------------------------------ results
+    def _pi_limbs(self, overrides=None) -> dict:
+        pi = dict(self.public_inputs)
+        for row, v in (overrides or {}).items():
+            if row not in pi:
+                raise ValueError(f"row {row} holds no public input")
+            pi[row] = int(v) % self.curve.r
+        return pi
+
+    def description(self) -> CircuitDescription:
+        import torch
+        n = padded_size(self.n_gates)
+        rec = torch.cat(self._ins_rec).to(torch.int64) & 0xFFFFFFFF     # the kernels write the records as unsigned words
+        ins_pos = ((rec >> _REC_SHIFT) * n + (rec & ((1 << _REC_SHIFT) - 1))).to(torch.int32).contiguous()
+        rows = sorted(self.public_inputs)
+        limbs = fr_to_mont(self.curve, [self.public_inputs[r_] for r_ in rows])
+        return CircuitDescription(self.n_gates, {name: torch.cat(self._sel[name]).contiguous() for name in SELECTORS},
+                                  [torch.cat(w).contiguous() for w in self._ids], self.num_vars, torch.cat(self._ins_var).contiguous(), ins_pos,
+                                  [], {r_: limbs[i] for i, r_ in enumerate(rows)}, self.curve.name)
+
+    def assign(self, inputs, blinding=None, public_inputs=None):
+        """The (num_vars, 4) values `compile.assign` takes: the witness kernels replayed segment by segment in build order.
+        inputs: one (B, 4) Montgomery device tensor per `inputs()` call, in call order; blinding: the (8, 4) values of variables 1 .. 8,
+        a `torch.Generator` that draws them, or None (a fresh generator); public_inputs: {row: integer} replacing build-time values.
+        With public inputs in the circuit returns (values, {row: 4 Montgomery limbs}) -- the dict `prove` takes."""
+        import torch
+        if hasattr(inputs, "data_ptr"):
+            inputs = [inputs]
+        if len(inputs) != self._n_inputs:
+            raise ValueError(f"{self._n_inputs} input tensors expected")
+        pi = self._pi_limbs(public_inputs)
+        values = torch.zeros((self.num_vars, 4), dtype=torch.int64, device=self.device)
+        if blinding is None or isinstance(blinding, torch.Generator):
+            gen = blinding if blinding is not None else torch.Generator(device=self.device)
+            if blinding is None:
+                gen.seed()
+            blinding = torch.randint(0, 1 << 62, (8, 4), dtype=torch.int64, device=gen.device, generator=gen).to(self.device)
+            blinding[:, 3] &= (1 << 60) - 1             # below 2^252: a reduced element of either scalar field
+        if check_dev_tensor(blinding, 4, self.ctx.device) != 8:
+            raise ValueError("8 blinding values expected")
+        values[1:_PRELUDE_VARS] = blinding
+        it = iter(inputs)
+        self.ctx.use_torch_stream()
+        for what, *rest in self._program:
+            if what == "inputs":
+                v0, B = rest
+                t = next(it)
+                if check_dev_tensor(t, 4, self.ctx.device) != B:
+                    raise ValueError(f"{B} input values expected")
+                values[v0:v0 + B] = t
+                continue
+            seg = rest[0]
+            if seg["V"] == 0:
+                continue
+            a = self._args(seg)
+            keep = None
+            if seg["pi"] is not None:
+                keep = self._column([pi[seg["row0"] + k] for k in range(seg["B"])])
+                a.pi = keep.data_ptr()
+            check(lib().zk_gadget_witness_dev(self.ctx.handle, self.curve.curve_id, ctypes.addressof(a), values.data_ptr(), self.num_vars),
+                  "zk_gadget_witness_dev")
+        if not pi:
+            return values
+        rows = sorted(pi)
+        limbs = fr_to_mont(self.curve, [pi[r_] for r_ in rows])
+        return values, {r_: limbs[i] for i, r_ in enumerate(rows)}

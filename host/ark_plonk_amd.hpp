@@ -395,6 +395,27 @@ inline zk_circuit_check_summary circuit_check(const Radix2EvaluationDomain& d, c
     check(zk_circuit_check_dev(d.context().handle(), d.curve(), d.log_size_of_group(), &args, d_mask, &out), "zk_circuit_check_dev");
     return out;
 }
+// The device composer (constraint_system/{arithmetic,boolean,range,logic}.rs, ecc/): one SEGMENT = args.calls calls of one gadget.
+// gadget_shape: rows, new variables and insertions of ONE call, and the device bytes a witness of `calls` calls allocates.
+struct GadgetShape {
+    uint32_t rows = 0, vars = 0, insertions = 0;
+    size_t work_bytes = 0;
+};
+inline GadgetShape gadget_shape(int kind, int curve, uint32_t num_bits = 0, uint32_t flags = 0, size_t calls = 1) {
+    GadgetShape s;
+    check(zk_gadget_shape(kind, curve, num_bits, flags, calls, &s.rows, &s.vars, &s.insertions, &s.work_bytes), "zk_gadget_shape");
+    return s;
+}
+// the rows of the segment: d_wire_ids u32[4][calls * rows], twelve selector columns of calls * rows elements (the order of the header),
+// the insertions (variable, wire << 30 | absolute row) in call order
+inline void gadget_layout(Context& ctx, int curve, const zk_gadget_args& args, void* d_wire_ids, void* const* d_selectors, void* d_ins_var,
+                          void* d_ins_rec) {
+    check(zk_gadget_layout_dev(ctx.handle(), curve, &args, d_wire_ids, d_selectors, d_ins_var, d_ins_rec), "zk_gadget_layout_dev");
+}
+// the values of the segment's new variables into `values` (one element per variable of the circuit); segments are replayed in build order
+inline void gadget_witness(Context& ctx, int curve, const zk_gadget_args& args, DeviceVec& values) {
+    check(zk_gadget_witness_dev(ctx.handle(), curve, &args, values.data(), values.size()), "zk_gadget_witness_dev");
+}
 // compute_lookup_permutation_poly up to its ifft (permutation/mod.rs:754-797)
 inline DeviceVec lookup_permutation_evals(Context& ctx, int curve, const DeviceVec& f, const DeviceVec& t, const DeviceVec& h1,
                                           const DeviceVec& h2, const uint64_t* delta_mont, const uint64_t* epsilon_mont) {

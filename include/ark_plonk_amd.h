@@ -628,6 +628,71 @@ typedef struct zk_circuit_check_summary {
  * Blocks once. */
 int zk_circuit_check_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* args, void* d_mask, void* out);
 
+/* ---- gadget circuits and their witnesses (constraint_system/{arithmetic,boolean,range,logic}.rs, ecc/) -------------------------- */
+/* A SEGMENT is `calls` calls of one gadget with the same parameters: by definition what `StandardComposer` holds after the gadget is
+ * called that many times in a row, call k with the k-th input variables -- rows, new variables in `add_input` order and
+ * `add_variable_to_map` calls in call order, the cells the reference pushes without mapping (range.rs:185-187) and the logic gate's
+ * Output(n - 1) after Left(n) included.  Every gadget has a fixed shape per call (R rows, V new variables, I insertions), so call k
+ * owns rows row0 + k R .., variables var0 + k V .. and insertions k I ..; M = MODULUS_BITS of Fr (255 / 254):
+ *   kind                  reference                                         R                  V            I
+ *   ZK_GADGET_POLY        arithmetic_gate, poly_gate, constrain_to_constant,
+ *                         assert_equal, boolean_gate                        1                  0 or 1       4
+ *   ZK_GADGET_RANGE       range_gate(num_bits)                              ceil(bits/8) + 2   bits / 2     4 ceil(bits/8) + 5
+ *   ZK_GADGET_LOGIC       xor_gate / and_gate(num_bits)                     bits / 2 + 1       2 bits       2 bits + 4
+ *   ZK_GADGET_CURVE_ADD   point_addition_gate                               2                  3            8
+ *   ZK_GADGET_FIXED_BASE  fixed_base_scalar_mul                             M + 5              4 M + 3      4 (M + 5)
+ * Values (zk_gadget_witness_dev; canonical Montgomery Fr, what zk_fr_gather_dev and the circuit check take):
+ *   POLY with ZK_GADGET_COMPUTE_OUT: (q_m a b + q_l a + q_r b + q_c + q_4 d + pi) (-q_o), as arithmetic.rs:144-155 writes it -- a
+ *       product with -q_o, NOT a division by it;
+ *   RANGE: accumulator j = (v mod 2^bits) >> (bits - 2 (j + 1)), v the canonical integer of the input -- the closing assert_equal row is
+ *       satisfied iff v < 2^bits, as in the reference;
+ *   LOGIC: per quad the two input prefixes (the same formula), the product of the two quads, the prefix of a ^ b or a & b;
+ *   CURVE_ADD: x1 y2, then x3 = (x1 y2 + y1 x2) / (1 + d x1 x2 y1 y2), y3 = (y1 y2 - a x1 x2) / (1 - d x1 x2 y1 y2);
+ *   FIXED_BASE: the digit of weight 2^j of the width-2 NAF of the scalar e is bit j+1 of 3e minus bit j+1 of e (find_wnaf(2)); row i
+ *       uses the digit of weight 2^(M-1-i) and holds the point and scalar accumulators before it and xy_alpha = x y of the addend
+ *       +-2^(M-1-i) G, or 0.
+ * ZK_ERR_BAD_ARG, by one flag word read back once per call: an input id that is not smaller than var0 (an undefined variable); a
+ * scalar whose NAF has more than M digits (3e >= 2^(M+1); the reference asserts); a zero denominator of the group law.  The outputs
+ * of a refused call are unspecified; nothing is read or written outside the buffers. */
+#define ZK_GADGET_POLY 0
+#define ZK_GADGET_RANGE 1
+#define ZK_GADGET_LOGIC 2
+#define ZK_GADGET_CURVE_ADD 3
+#define ZK_GADGET_FIXED_BASE 4
+#define ZK_GADGET_COMPUTE_OUT 1                      /* flags, POLY: the output wire is a new variable whose value is computed */
+#define ZK_GADGET_XOR 2                              /* flags, LOGIC: q_c = q_logic = -1 (XOR); without it +1 (AND) */
+typedef struct zk_gadget_args {
+    uint32_t kind, num_bits, flags, reserved;
+    uint64_t calls;                                  /* B >= 1 */
+    uint64_t row0, var0;                             /* first row and first new variable of the segment (var0 >= 1) */
+    const void* inputs[4];                           /* u32[calls] variable ids on the device -- POLY: a, b, c (unless computed), d (NULL:
+                                                      * the zero variable); RANGE: the witness; LOGIC: a, b; CURVE_ADD: x1, y1, x2, y2;
+                                                      * FIXED_BASE: the scalar */
+    const void* coeff[6];                            /* POLY: q_m q_l q_r q_o q_4 q_c as columns of `calls` Montgomery Fr, or NULL ... */
+    uint64_t coeff_const[24];                        /* ... for the constant coeff_const[4 j .. 4 j + 4) */
+    const void* pi;                                  /* POLY: the public input of every call (Montgomery Fr, device), or NULL; read by
+                                                      * the witness of a computed output only */
+    uint64_t coeff_a[4], coeff_d[4];                 /* P::COEFF_A, P::COEFF_D of the embedded twisted Edwards curve (Montgomery) */
+    const void* table;                               /* FIXED_BASE: 3 M Montgomery Fr on the device, row i: x, y, x y of 2^(M-1-i) G */
+} zk_gadget_args;
+/* Host only: the shape of one call and the device bytes a witness of `calls` calls allocates (layout: 256). */
+int zk_gadget_shape(int kind, int curve_id, uint32_t num_bits, uint32_t flags, size_t calls, uint32_t* rows, uint32_t* vars, uint32_t* insertions,
+                    size_t* work_bytes);
+/* args: a zk_gadget_args (crosses as an untyped pointer, like zk_circuit_check_args).  With N = calls * R and m = calls * I:
+ * d_wire_ids u32[4][N] (Left, Right, Output, Fourth of every row of the segment); d_selectors: 12 device pointers of N Montgomery Fr
+ * in the order q_m q_l q_r q_o q_4 q_c q_arith q_range q_logic q_fixed_group_add q_variable_group_add q_lookup; d_ins_var, d_ins_rec
+ * u32[m]: the insertions in call order, a record being wire << 30 | row with the ABSOLUTE row (row0 included) -- independent of the
+ * padded size; position = wire * n + row once n is known.  ZK_ERR_BAD_ARG: a null ctx / args (before anything else), a null buffer,
+ * num_bits odd or outside 2 .. 256, an input id >= var0; ZK_ERR_UNSUPPORTED: rows beyond 2^28 or variables beyond 2^31.
+ * Working memory: one device allocation of 256 bytes, freed before return.  Runs inside an open deferred round.  Blocks once. */
+int zk_gadget_layout_dev(zk_ctx* ctx, int curve_id, const void* args, void* d_wire_ids, void* const* d_selectors, void* d_ins_var,
+                         void* d_ins_rec);
+/* The values of the segment's new variables into d_values[var0 .. var0 + calls * V) (num_vars rows of Montgomery Fr); the inputs'
+ * values are read from the same vector, so segments are replayed in build order.  Working memory: one device allocation, freed on
+ * every path -- 256 bytes, + 96 (M + 1) calls for FIXED_BASE (the projective accumulators between its two phases).  No buffer of
+ * the ctx is used: the call runs inside an open deferred round.  Blocks once. */
+int zk_gadget_witness_dev(zk_ctx* ctx, int curve_id, const void* args, void* d_values, size_t num_vars);
+
 /* ---- device self-test ------------------------------------------------------------------------------ */
 /* Runs the quad-cooperative point arithmetic of the bucket-reduction kernels (csrc/ecq.cuh) against the
  * single-lane group law on n_quads point pairs incl. doubling, cancellation and infinity cases.

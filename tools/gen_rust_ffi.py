@@ -25,7 +25,8 @@ SCALAR = {
 }
 OPAQUE = {"zk_ctx": "ZkCtx", "zk_srs": "ZkSrs", "zk_transcript": "ZkTranscript"}
 STRUCTS = {"zk_domain_info": "ZkDomainInfo", "zk_quotient_args": "ZkQuotientArgs", "zk_proof": "ZkProof",
-           "zk_circuit_check_args": "ZkCircuitCheckArgs", "zk_circuit_check_summary": "ZkCircuitCheckSummary"}
+           "zk_circuit_check_args": "ZkCircuitCheckArgs", "zk_circuit_check_summary": "ZkCircuitCheckSummary",
+           "zk_gadget_args": "ZkGadgetArgs"}
 
 
 def strip_comments(text: str) -> str:
