@@ -63,17 +63,17 @@ struct MsmGeom {
 // sorted, accumulated and reduced by ONE launch of each kernel, so that launch gaps, partly filled last rounds of wavefronts and
 // the latency of the dependent-addition chains are paid once per round instead of once per MSM.
 constexpr int MAX_JOBS = ZK_MAX_JOBS;
-// one job of the batched partition-sort kernels (psort_scan / psort(w)_scatter / psort(w)_final)
+// one job of the batched partition-sort kernels (psort_scan, then psort_scatter / psort_final or their csort_* forms)
 struct SJob {
-    const void* dig;        // digits [W][n]: int16 (c = 16) or int32 (c > 16)
+    const void* dig;        // digits [W][n]: int16 (c = 16) or int32 (c > 16); compact form: the folded scalars
     uint64_t n;             // scalars
     uint32_t sp, pad;       // scalars per slab
-    uint32_t* hist;         // [P][PS_SLABS] slab counts -> cursors
-    uint32_t* part_start;   // P + 1 partition starts
-    uint32_t* part_total;   // P
-    uint32_t* counter;
+    uint32_t* hist;         // [PS_PARTS][PS_SLABS] slab counts -> cursors
+    uint32_t* part_start;   // PS_PARTS + 1 partition starts
+    uint32_t* part_total;   // PS_PARTS
+    uint32_t* counter;      // psort_scan's; 0 between the kernels
     uint32_t* stage_ref;    // references in partition order ...
-    void* stage_lo;         // ... and their low bucket bits (uint8 / uint16)
+    void* stage_lo;         // ... and their low bucket bits (uint8 at c = 16, uint16 above; compact form: none)
     uint32_t* entries;      // references in bucket order
     uint32_t* offsets;      // bucket starts, offsets[nb] = references in the list
 };
@@ -111,7 +111,8 @@ struct RJobs {
 };
 
 
-constexpr uint32_t PS_LOB = 7;        // low bucket bits ordered inside a partition of the two-pass sort (msm_sort.hip)
+constexpr uint32_t PS_PARTS = 256;    // partitions of the two-pass sort (msm_sort.hip): the high 8 of a table window's c - 1 bucket bits;
+                                      // the low lob = c - 9 bits are ordered inside a partition
 constexpr uint32_t PS_T = 1024;
 constexpr uint32_t PS_SLABS = 1024;   // workgroups of the partition passes
 constexpr uint32_t PS_STILE = 8192;   // digits ordered in LDS at a time by the partition scatter: 8 per lane
@@ -222,7 +223,7 @@ struct PrePlan {
     uint64_t nf;
     uint32_t chunk_l, n_lanes, max_lanes;
     size_t win_bytes;
-    bool wide;          // c > 16: int32 digits, 2^(c-9) buckets per sort partition
+    bool wide;          // c > 16: int32 digits and uint16 low bucket bits in the sort (int16 and uint8 at c = 16)
     bool wide_red;      // more than 2^16 shared buckets: three-level device reduction (up to 2^16 the virtual-window reduction of the
                         // c = 16 table serves, with virtual windows of 1024 buckets)
     bool shared_stage;  // the sort's staging area (5-6 B per reference) is the ctx's, not the job's: the jobs of a round are placed one
@@ -235,12 +236,10 @@ struct PrePlan {
 constexpr uint64_t PRE_BIG_NF = 1ull << 27;
 constexpr uint32_t PRE_BIG_ROUNDS = 8;
 
-// the table windows are 16 .. 21 bits: up to 16 bits the int16 partition sort (2^15 buckets = 256 partitions of 128)
-inline bool pre_psort16(const PrePlan& pl) { return !pl.wide && pl.g1.nb % (1u << PS_LOB) == 0 && (pl.g1.nb >> PS_LOB) <= 256; }
 // The compact form of the wide partition sort (csort_* in msm_sort.hip): a whole table of folded 17-bit windows whose job owns its
 // staging area.  The folded scalar (< 2^254, the fold's sign in bit 255) waits in the job's set instead of the int32 digits, and the
 // staged record is ONE word: sign << 31 | window << 27 | index inside the slab << 8 | low bucket bits, so at most 16 windows and
-// slabs below 2^19 scalars (nf < 2^31 keeps them below 2^18); from 8 windows on the scalars fit where the references will be.  Every other geometry keeps psortw_*.
+// slabs below 2^19 scalars (nf < 2^31 keeps them below 2^18); from 8 windows on the scalars fit where the references will be.  Every other geometry keeps psort_*.
 constexpr uint32_t CS_C = 17;
 constexpr uint32_t CS_LOB = CS_C - 9;
 inline bool pre_compact(const PrePlan& pl) {

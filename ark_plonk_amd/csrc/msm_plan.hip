@@ -211,7 +211,7 @@ void pre_sizes(const PrePlan& pl, PreSizes& z) {
     typedef typename Cv::FqU F;
     constexpr size_t PT = (size_t)4 * Store<F>::WORDS * 4;
     memset(&z, 0, sizeof z);
-    z.counts = (size_t)256 * PS_SLABS * 4;                       // slab counts of the 256 sort partitions -> cursors
+    z.counts = (size_t)PS_PARTS * PS_SLABS * 4;                  // slab counts of the sort partitions -> cursors
     z.offsets = (size_t)(pl.g.B + 1) * 4;
     // the sorted references.  The job's digits (int16 / int32 per reference) live here first: the digit kernel writes them, the
     // partition scatter reads them into the staging area, and only then the placement kernel overwrites them with the references

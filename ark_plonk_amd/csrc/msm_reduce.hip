@@ -670,7 +670,7 @@ int pre_queue_reduce(zk_ctx* c, const PrePlan* pls, MsmBufs* const* mbs, uint32_
         jobs.lanes[k] = mb.acc_n_lanes;
         jobs.nbk[k] = p0.g1.nb;
     }
-    // the queue counters were cleared by the job's sort (psort_hist / the memset of the fallback sort)
+    // the queue counters were cleared by the job's sort (its digit kernel: reset_job_counters / the memset of the fallback sort)
     if (p0.wide_red) {
         void* d_vw[MAX_JOBS];
         void* d_seg3[MAX_JOBS];

@@ -1,12 +1,15 @@
 // MSM unit 1 of 4 (msm_common.cuh): digits and the sort of the (point, sign) references by bucket.
 //
 // The window-table path (every commitment of a proof) uses a two-pass PARTITION sort over its one shared bucket set, the jobs of a
-// prover round batched in one launch per kernel.  It comes in three forms, chosen by the table's geometry (msm_common.cuh):
-//   pre_psort16   psort_*   windows up to 16 bits: int16 digits, 2^15 buckets = 256 partitions of 128
+// prover round batched in one launch per kernel.  A table window is c = 16 .. 21 bits, so the 2^(c-1) shared buckets are always
+// PS_PARTS = 256 partitions (the high 8 bucket bits) of 2^lob buckets, lob = c - 9.  The sort comes in two forms, chosen by the
+// table's geometry (msm_common.cuh):
 //   pre_compact   csort_*   a whole table of folded 17-bit windows whose job owns its staging area (every MSM of a 2^19 .. 2^21
 //                           proof): the folded scalar waits instead of the digits, one staged word per reference
-//   else          psortw_*  every other wide geometry (17 .. 21 bits, window-sharded or shared-stage tables): int32 digits, 2^(c-9)
-//                           buckets per partition
+//   else          psort_*   every other geometry (16 .. 21 bits; window-sharded or shared-stage tables): a digit array, and a staged
+//                           reference with its low bucket bits beside it.  One digit kernel for all of them (int16 digits at
+//                           c = 16, int32 above: PrePlan::wide) and one scan; the scatter and the placement kernel take lob as an
+//                           argument above 16 bits, and the 16-bit table keeps bodies with lob = 7 built in (psort_*16)
 // The per-window path (zk_msm_g1 over caller bases, vectors below 2^13 or beyond 2^26 points, SRS without a table) keeps round 1's
 // LDS COUNTING sort (msm_hist / msm_scan1-3 / msm_scatter): its windows are 3 .. 16 bits -- the window is a measured step function
 // of the length (make_geom) -- and a partition needs at least 2^7 buckets, and its references carry 31 bits of point index where the
@@ -94,37 +97,6 @@ __global__ void msm_digits(const uint32_t* scalars, uint64_t n, MsmGeom g, int16
         uint32_t row;
         // (the int16 store cannot hold -(-32768): make_geom never folds scalars at c = 16, see the assert there)
         if (g.owns(w, row)) dig[(uint64_t)row * n + i] = (int16_t)(flip ? -d : d);
-    }
-}
-
-// Two scalars per lane (n even; c = 16, W = 16): 32-byte vector loads, one 4-byte store per window instead of two 2-byte
-// ones.  MONT: the input is a Montgomery coefficient (a commit): into_repr is fused here instead of a
-// separate conversion pass over the vector.
-template <class Fr, bool MONT>
-__global__ void msm_digits2(const uint32_t* scalars, uint64_t n, MsmGeom g, int16_t* dig) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (2 * t >= n) return;
-    uint32_t s[2][8];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * (2 * t + h);
-        uint4 a = q[0], b = q[1];
-        Fr x;
-        x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
-        x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
-        if (MONT) x = Fr::from_mont(x);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s[h][i] = x.v[i];
-    }
-    // 16-bit windows, 16 of them (the window-table geometry): digit w is half-word w of the scalar
-    uint32_t c0 = 0, c1 = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        uint32_t r0 = ((s[0][w >> 1] >> (16 * (w & 1))) & 0xffffu) + c0;
-        uint32_t r1 = ((s[1][w >> 1] >> (16 * (w & 1))) & 0xffffu) + c1;
-        c0 = r0 >= 0x8000u ? 1u : 0u;     // raw >= 2^15 -> digit raw - 2^16 (its low 16 bits are unchanged), carry 1
-        c1 = r1 >= 0x8000u ? 1u : 0u;
-        *reinterpret_cast<uint32_t*>(dig + (uint64_t)w * n + 2 * t) = (r0 & 0xffffu) | (r1 << 16);
     }
 }
 
@@ -242,12 +214,12 @@ __global__ void msm_scatter(const int16_t* dig, uint64_t n, MsmGeom g, uint32_t 
 // ---- two-pass partition sort for the shared-bucket path (one "window" of nf digits, nb buckets) ----
 // The single-pass counting sort above leaves every slab only ~4 references per bucket, so its scatter
 // writes 16-byte runs at random places (measured: 513 MB leaving L2 per launch for 67 MB of output).
-// Here the references first go to P = nb/128 partitions by the high bucket bits -- every (slab, partition)
-// run is ~1 KiB contiguous -- and one workgroup per partition then orders its ~nf/P references by the low
-// 7 bits out of L2.  psort_digits_hist (or psort_hist) / psort_scan / psort_scatter / psort_final; order
-// inside a bucket is arbitrary (the sums are commutative).  Measured at 2^20: 0.23 ms against 0.33 ms for
-// msm_hist + msm_scan1/2/3 + msm_scatter; what is left is the ~64 distinct cache lines every wave-store of
-// the two placement kernels touches.
+// Here the references first go to PS_PARTS = 256 partitions by the high 8 bucket bits -- every (slab, partition)
+// run is ~1 KiB contiguous -- and one workgroup per partition then orders its ~nf/256 references by the low
+// lob = c - 9 bits (128 ... 4096 buckets per partition) out of L2.  psort_digits_hist (or its 16-bit pairs form) /
+// psort_scan / psort_scatter / psort_final; order inside a bucket is arbitrary (the sums are commutative).
+// Measured at 2^20, c = 16: 0.23 ms against 0.33 ms for msm_hist + msm_scan1/2/3 + msm_scatter; what is left is
+// the ~64 distinct cache lines every wave-store of the two placement kernels touches.
 
 // A slab of the partition sort = a range of SCALARS with all their W digits (dig[w*n + i], i in the range), so
 // that the kernel that produces the digits can count them too.  sp = scalars per slab (even).
@@ -269,11 +241,50 @@ ZK_D void reset_job_counters(uint32_t* scan_counter, uint32_t* combine_q) {
     }
 }
 
-// digits of the slab's scalars (as msm_digits2: two scalars per lane, 16-bit windows) + the slab's partition counts
+// Digits of the slab's scalars + the slab's partition counts: the kernel every geometry can take.  One scalar per lane; it walks
+// all Wt windows (the carries run through every one) and keeps the rows the table owns.  Dig = int16_t serves c = 16, int32_t the
+// wider windows.  into_repr of a commit's Montgomery coefficients is fused in (MONT).
+template <class Fr, bool MONT, class Dig>
+__global__ void __launch_bounds__(256) psort_digits_hist(const uint32_t* scalars, uint64_t n, uint32_t sp, MsmGeom g, uint32_t lob, Dig* dig,
+                                                         uint32_t* hist /* [PS_PARTS][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
+    __shared__ uint32_t lc[PS_PARTS];
+    reset_job_counters(scan_counter, combine_q);
+    lc[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
+    const uint32_t half = 1u << (g.c - 1), cmask = (1u << g.c) - 1u;
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * i;
+        uint4 a = q[0], b = q[1];
+        Fr x;
+        x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
+        x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
+        if (MONT) x = Fr::from_mont(x);
+        const bool flip = scalar_fold(x.v, g);
+        uint32_t carry = 0;
+        for (uint32_t w = 0; w < g.Wt; ++w) {
+            const uint32_t raw = (scalar_bits(x.v, w * g.c, g.c) & cmask) + carry;
+            carry = raw >= half ? 1u : 0u;
+            int32_t d = carry ? (int32_t)raw - (int32_t)(1u << g.c) : (int32_t)raw;
+            if (flip) d = -d;
+            uint32_t row;
+            if (!g.owns(w, row)) continue;
+            dig[(uint64_t)row * n + i] = (Dig)d;
+            if (d != 0) atomicAdd(&lc[(uint32_t)((d < 0 ? -d : d) - 1) >> lob], 1u);
+        }
+    }
+    __syncthreads();
+    hist[(uint64_t)threadIdx.x * PS_SLABS + blockIdx.x] = lc[threadIdx.x];
+}
+
+// The fast path of a whole 16-bit table (c = 16, W = Wt = 16, no fold) over an even number of scalars: two scalars per lane, digit w
+// is half-word w of the scalar, 32-byte vector loads and one 4-byte store per window instead of two 2-byte ones.
 template <class Fr, bool MONT>
-__global__ void __launch_bounds__(256) psort_digits_hist(const uint32_t* scalars, uint64_t n, uint32_t sp, int16_t* dig,
-                                                         uint32_t* hist /* [256][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
-    __shared__ uint32_t lc[256];
+__global__ void __launch_bounds__(256) psort_digits_hist_pairs16(const uint32_t* scalars, uint64_t n, uint32_t sp, int16_t* dig,
+                                                                 uint32_t* hist /* [PS_PARTS][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
+    static_assert(PRE_C == 16, "half-word digits");
+    constexpr uint32_t LOB = PRE_C - 9;      // lob = c - 9, as for every table window
+    __shared__ uint32_t lc[PS_PARTS];
     reset_job_counters(scan_counter, combine_q);
     lc[threadIdx.x] = 0;
     __syncthreads();
@@ -301,30 +312,12 @@ __global__ void __launch_bounds__(256) psort_digits_hist(const uint32_t* scalars
             r0 &= 0xffffu;
             r1 &= 0xffffu;
             *reinterpret_cast<uint32_t*>(dig + (uint64_t)w * n + i0) = r0 | (r1 << 16);
-            if (r0) atomicAdd(&lc[((c0 ? 0x10000u - r0 : r0) - 1u) >> PS_LOB], 1u);
-            if (r1) atomicAdd(&lc[((c1 ? 0x10000u - r1 : r1) - 1u) >> PS_LOB], 1u);
+            if (r0) atomicAdd(&lc[((c0 ? 0x10000u - r0 : r0) - 1u) >> LOB], 1u);
+            if (r1) atomicAdd(&lc[((c1 ? 0x10000u - r1 : r1) - 1u) >> LOB], 1u);
         }
     }
     __syncthreads();
     hist[(uint64_t)threadIdx.x * PS_SLABS + blockIdx.x] = lc[threadIdx.x];
-}
-
-// the same counts from an existing digit array (lengths the fused kernel does not take)
-__global__ void __launch_bounds__(PS_T) psort_hist(const int16_t* dig, uint64_t n, uint32_t W, uint32_t sp, uint32_t P,
-                                                   uint32_t* hist /* [P][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
-    extern __shared__ uint32_t lc[];
-    reset_job_counters(scan_counter, combine_q);
-    for (uint32_t j = threadIdx.x; j < P; j += PS_T) lc[j] = 0;
-    __syncthreads();
-    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
-    const uint32_t len = (uint32_t)(hi - lo);
-    for (uint32_t q = threadIdx.x; q < W * len; q += PS_T) {
-        const uint32_t w = q / len, ii = q - w * len;
-        const int32_t d = dig[(uint64_t)w * n + lo + ii];
-        if (d != 0) atomicAdd(&lc[(uint32_t)((d < 0 ? -d : d) - 1) >> PS_LOB], 1u);
-    }
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < P; j += PS_T) hist[(uint64_t)j * PS_SLABS + blockIdx.x] = lc[j];
 }
 
 // inclusive scan of one value per lane inside every wavefront: the first step of the workgroup scans below
@@ -337,13 +330,14 @@ ZK_D uint32_t wave_scan_incl(uint32_t v, uint32_t t) {
     }
     return inc;
 }
-// The workgroup scans (scan128_excl, scan256_excl, scan1024_excl) stay three functions: their barriers differ (128: none behind its LDS
-// read; 256: one behind it; 1024: one in front of its LDS write, as it is called twice in a row on one tmp).
+// The workgroup scans (scan128_excl, scan256_excl, scan1024_excl) stay three functions: their barriers differ (128: none behind its
+// LDS read; 256: one behind its LDS read; 1024: one in front of its LDS write, as it is called twice in a row on one tmp).
 ZK_D uint32_t scan1024_excl(uint32_t v, uint32_t t, uint32_t* tmp);
 
 // per partition: exclusive scan of its PS_SLABS slab counts in place (coalesced); the workgroup that finishes
-// last (a counter, no waiting) then scans the P (<= 256) partition totals into part_start[0..P].
-// `counter` must be 0 on entry (psort_hist clears it) and is left 0.  Both scans are wave shuffles plus one LDS step
+// last (a counter, no waiting) then scans the P partition totals into part_start[0..P].  P is always PS_PARTS: it stays an argument
+// here, and in csort_final / csort_final_long, only so that the code these kernels compile to does not move.
+// `counter` must be 0 on entry (the job's digit kernel clears it: reset_job_counters) and is left 0.  Both scans are wave shuffles plus one LDS step
 // (scan1024_excl): as twenty-barrier Hillis-Steele loops over LDS this kernel was 13 us of every MSM's sort.
 __global__ void __launch_bounds__(PS_SLABS) psort_scan(SJobs jobs, uint32_t P) {
     static_assert(PS_SLABS == 1024, "scan1024_excl");
@@ -386,9 +380,253 @@ ZK_D uint32_t scan256_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
 }
 
 // references (sign<<31 | window<<26 | index, as msm_scatter writes them) + their low bucket bits -> partition order.
+// A tile of PS_STILE digits is ordered by partition in LDS first, so the records (4 bytes + a Lo) leave as runs of consecutive
+// addresses, one run per partition and tile.
+template <class Dig, class Lo>
+__global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, uint32_t lob) {
+    static_assert(PS_PARTS == 256, "scan256_excl");
+    constexpr uint32_t PER = PS_STILE / PS_T;
+    const SJob& J = jobs.j[blockIdx.y];
+    const Dig* dig = (const Dig*)J.dig;
+    const uint64_t n = J.n;
+    const uint32_t sp = J.sp;
+    const uint32_t* cursors = J.hist;
+    const uint32_t* part_start = J.part_start;
+    uint32_t* stage_ref = J.stage_ref;
+    Lo* stage_lo = (Lo*)J.stage_lo;
+    const uint32_t LOM = (1u << lob) - 1u;
+    __shared__ uint32_t cnt[PS_PARTS], toff[PS_PARTS + 1], gcur[PS_PARTS], stmp[4];
+    __shared__ uint32_t rec[PS_STILE];       // k (14 bits) | neg << 14 | partition << 15
+    __shared__ Lo rlo[PS_STILE];             // low bucket bits of the record at the same position
+    const uint32_t t = threadIdx.x;
+    if (t < PS_PARTS) gcur[t] = part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x];
+    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
+    const uint32_t len = (uint32_t)(hi - lo);
+    const uint32_t total_digits = W * len;
+    // the digits of the tile after the current one are requested while the current one is counted and placed
+    int32_t nd[PER];
+    auto fetch = [&](uint32_t base) {
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t q = base + k * PS_T + t;
+            nd[k] = 0;
+            if (q < total_digits) {
+                const uint32_t w = q / len, ii = q - w * len;
+                nd[k] = dig[(uint64_t)w * n + lo + ii];
+            }
+        }
+    };
+    if (total_digits) fetch(0);
+    for (uint32_t base = 0; base < total_digits; base += PS_STILE) {
+        __syncthreads();
+        if (t < PS_PARTS) cnt[t] = 0;
+        __syncthreads();
+        int32_t vd[PER];
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) vd[k] = nd[k];
+        if (base + PS_STILE < total_digits) fetch(base + PS_STILE);
+        uint32_t pk[PER];
+        Lo pl[PER];
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;
+            pk[k] = 0xffffffffu;
+            pl[k] = 0;
+            const int32_t d = vd[k];      // 0 past the end of the slab
+            if (d != 0) {
+                const uint32_t neg = d < 0 ? 1u : 0u;
+                const uint32_t b = (uint32_t)((neg ? -d : d) - 1);
+                pk[k] = i | (neg << 14) | ((b >> lob) << 15);
+                pl[k] = (Lo)(b & LOM);
+                atomicAdd(&cnt[b >> lob], 1u);
+            }
+        }
+        __syncthreads();
+        {
+            const uint32_t c = t < PS_PARTS ? cnt[t] : 0u;
+            const uint32_t ex = scan256_excl(c, t, stmp);
+            if (t < PS_PARTS) toff[t] = ex;
+            if (t == PS_PARTS - 1) toff[PS_PARTS] = ex + c;
+        }
+        __syncthreads();
+        if (t < PS_PARTS) cnt[t] = toff[t];
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k)
+            if (pk[k] != 0xffffffffu) {
+                const uint32_t at = atomicAdd(&cnt[pk[k] >> 15], 1u);
+                rec[at] = pk[k];
+                rlo[at] = pl[k];
+            }
+        __syncthreads();
+        const uint32_t total = toff[PS_PARTS];
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t qq = k * PS_T + t;
+            if (qq < total) {
+                const uint32_t r = rec[qq];
+                const uint32_t pp = r >> 15;
+                const uint32_t q = base + (r & 0x3fffu), w = q / len, ii = q - w * len;
+                const uint32_t ref = (w << 26) | (uint32_t)(lo + ii) | (((r >> 14) & 1u) << 31);
+                const uint32_t dst = gcur[pp] + (qq - toff[pp]);
+                stage_ref[dst] = ref;
+                stage_lo[dst] = rlo[qq];
+            }
+        }
+        __syncthreads();
+        if (t < PS_PARTS) gcur[t] += toff[t + 1] - toff[t];
+    }
+}
+
+// one workgroup per partition: count the low bits, publish the bucket offsets, then place the references
+// tile by tile: a tile of PS_TILE references is ordered in LDS first, so that the global stores are runs
+// of consecutive addresses (one run per bucket and tile) instead of 64 different cache lines per wave-store.
+// (Wave-private counters were tried for the counting: 16 x 128 write streams per workgroup made it slower.)
+
+// counts of the keys key[i], i = first, first + PS_T, ... < end, into the LDS table cnt.  Eight loads in flight per lane: written
+// as a plain loop the compiler keeps ONE (load, wait, LDS atomic) per iteration, and the pass over a partition's ~60 keys per
+// lane was sixty memory round trips in a row -- most of the kernel's time.
+template <class K>
+ZK_D void count_keys(const K* key, uint32_t first, uint32_t end, uint32_t* cnt) {
+    uint32_t i = first;
+    for (; i + 7 * PS_T < end; i += 8 * PS_T) {
+        uint32_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = key[i + k * PS_T];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) atomicAdd(&cnt[v[k]], 1u);
+    }
+    for (; i < end; i += PS_T) atomicAdd(&cnt[key[i]], 1u);
+}
+
+// exclusive scan of one value per lane over a 1024-lane workgroup; tmp: 16 LDS words
+ZK_D uint32_t scan1024_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
+    uint32_t inc = wave_scan_incl(v, t);
+    __syncthreads();
+    if ((t & 63) == 63) tmp[t >> 6] = inc;
+    __syncthreads();
+    uint32_t add = 0;
+    for (uint32_t w = 0; w < (t >> 6); ++w) add += tmp[w];
+    return inc + add - v;
+}
+
+// dynamic LDS: cnt[NB] | cur[NB] | toff[NB + 1] | tmp[16] | sorted[PS_TILE] | skey[PS_TILE] (Lo), NB = 2^lob buckets
+constexpr size_t psort_final_lds(uint32_t lob, size_t lo_bytes) { return ((size_t)3 * (1u << lob) + 1 + 16 + PS_TILE) * 4 + PS_TILE * lo_bytes; }
+template <class Lo>
+__global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t lob) {
+    extern __shared__ uint32_t lds[];
+    const SJob& J = jobs.j[blockIdx.y];
+    const uint32_t* stage_ref = J.stage_ref;
+    const Lo* stage_lo = (const Lo*)J.stage_lo;
+    const uint32_t* part_start = J.part_start;
+    uint32_t* entries = J.entries;
+    uint32_t* offsets = J.offsets;
+    constexpr uint32_t PER = PS_TILE / PS_T;
+    const uint32_t NB = 1u << lob;
+    const uint32_t K = NB > PS_T ? NB / PS_T : 1u;       // counters per lane in the scans
+    uint32_t* cnt = lds;
+    uint32_t* cur = cnt + NB;
+    uint32_t* toff = cur + NB;
+    uint32_t* tmp = toff + NB + 1;
+    uint32_t* sorted = tmp + 16;
+    Lo* skey = reinterpret_cast<Lo*>(sorted + PS_TILE);
+    const uint32_t p = blockIdx.x, t = threadIdx.x;
+    const uint32_t s = part_start[p], e = part_start[p + 1];
+    for (uint32_t j = t; j < NB; j += PS_T) cnt[j] = 0;
+    __syncthreads();
+    count_keys(stage_lo, s + t, e, cnt);
+    __syncthreads();
+    // exclusive scan of cnt[0 .. NB): lane t owns counters [t*K, (t+1)*K)
+    auto scan_counts = [&](uint32_t* dst, uint32_t add, bool with_total) {
+        uint32_t mine = 0;
+        if (t * K < NB)
+            for (uint32_t k = 0; k < K; ++k) mine += cnt[t * K + k];
+        uint32_t ex = scan1024_excl(mine, t, tmp);
+        if (t * K < NB) {
+            for (uint32_t k = 0; k < K; ++k) {
+                const uint32_t c = cnt[t * K + k];
+                dst[t * K + k] = add + ex;
+                ex += c;
+            }
+            if (with_total && (t + 1) * K == NB) dst[NB] = add + ex;
+        }
+        __syncthreads();
+    };
+    scan_counts(cur, s, false);
+    for (uint32_t j = t; j < NB; j += PS_T) offsets[p * NB + j] = cur[j];
+    if (p == PS_PARTS - 1 && t == 0) offsets[PS_PARTS * NB] = e;
+    // the tile after the current one is requested while the current one is counted, scanned and placed: its 16 references and
+    // keys per lane sit in registers across the barriers instead of costing a memory round trip at the top of every tile
+    uint32_t nr[PER];
+    Lo nk[PER];
+    auto fetch = [&](uint32_t base) {
+        const uint32_t m = e - base < PS_TILE ? e - base : PS_TILE;
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;
+            if (i < m) {
+                nr[k] = stage_ref[base + i];
+                nk[k] = stage_lo[base + i];
+            }
+        }
+    };
+    if (s < e) fetch(s);
+    for (uint32_t base = s; base < e; base += PS_TILE) {
+        const uint32_t m = e - base < PS_TILE ? e - base : PS_TILE;
+        __syncthreads();
+        for (uint32_t j = t; j < NB; j += PS_T) cnt[j] = 0;
+        __syncthreads();
+        uint32_t vr[PER];
+        Lo vk[PER];
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            vr[k] = nr[k];
+            vk[k] = nk[k];
+        }
+        if (base + PS_TILE < e) fetch(base + PS_TILE);
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;
+            if (i < m) atomicAdd(&cnt[vk[k]], 1u);
+        }
+        __syncthreads();
+        scan_counts(toff, 0u, true);
+        for (uint32_t j = t; j < NB; j += PS_T) cnt[j] = toff[j];      // running position inside the tile
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;
+            if (i < m) {
+                const uint32_t q = atomicAdd(&cnt[vk[k]], 1u);
+                sorted[q] = vr[k];
+                skey[q] = vk[k];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            const uint32_t i = k * PS_T + t;
+            if (i < m) {
+                const uint32_t j = skey[i];
+                entries[cur[j] + (i - toff[j])] = sorted[i];
+            }
+        }
+        __syncthreads();
+        for (uint32_t j = t; j < NB; j += PS_T) cur[j] += toff[j + 1] - toff[j];
+    }
+}
+
+
+// ---- the 16-bit table's own scatter and placement kernels -----------------------------------------------------------------------
+// The same two passes as psort_scatter<Dig, Lo> / psort_final<Lo> with lob a constant: the 7 low bits ride in the record word of the
+// scatter's tile, the 128 counters of a partition are scanned by one wavefront pair (scan128_excl) and the LDS is static.  Every
+// table below 2^19 points runs them; P is always PS_PARTS and stays an argument for the reason psort_scan gives.
+constexpr uint32_t PS_LOB = PRE_C - 9;      // lob = c - 9, as for every table window
+
+// references (sign<<31 | window<<26 | index, as msm_scatter writes them) + their low bucket bits -> partition order.
 // A tile of PS_STILE digits is ordered by partition in LDS first (packed: position in the tile, sign, low bits,
 // partition), so the 8-byte records leave as runs of consecutive addresses, one run per partition and tile.
-__global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, uint32_t P) {
+__global__ void __launch_bounds__(PS_T) psort_scatter16(SJobs jobs, uint32_t W, uint32_t P) {
     constexpr uint32_t PER = PS_STILE / PS_T, LOM = (1u << PS_LOB) - 1u;
     const SJob& J = jobs.j[blockIdx.y];
     const int16_t* dig = (const int16_t*)J.dig;
@@ -398,10 +636,10 @@ __global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, ui
     const uint32_t* part_start = J.part_start;
     uint32_t* stage_ref = J.stage_ref;
     uint8_t* stage_lo = (uint8_t*)J.stage_lo;
-    __shared__ uint32_t cnt[256], toff[257], gcur[256], stmp[4];
+    __shared__ uint32_t cnt[PS_PARTS], toff[PS_PARTS + 1], gcur[PS_PARTS], stmp[4];
     __shared__ uint32_t rec[PS_STILE];       // k (14 bits) | neg << 14 | low bits << 15 | partition << 22
     const uint32_t t = threadIdx.x;
-    if (t < 256) gcur[t] = t < P ? part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x] : 0u;
+    if (t < PS_PARTS) gcur[t] = t < P ? part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x] : 0u;
     const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
     const uint32_t len = (uint32_t)(hi - lo);
     const uint32_t total_digits = W * len;           // the slab: W windows x len scalars, visited window-major
@@ -421,7 +659,7 @@ __global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, ui
     if (total_digits) fetch(0);
     for (uint32_t base = 0; base < total_digits; base += PS_STILE) {
         __syncthreads();
-        if (t < 256) cnt[t] = 0;
+        if (t < PS_PARTS) cnt[t] = 0;
         __syncthreads();
         int32_t vd[PER];
 #pragma unroll
@@ -442,19 +680,19 @@ __global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, ui
         }
         __syncthreads();
         {
-            const uint32_t c = t < 256 ? cnt[t] : 0u;
+            const uint32_t c = t < PS_PARTS ? cnt[t] : 0u;
             const uint32_t ex = scan256_excl(c, t, stmp);
-            if (t < 256) toff[t] = ex;
-            if (t == 255) toff[256] = ex + c;
+            if (t < PS_PARTS) toff[t] = ex;
+            if (t == PS_PARTS - 1) toff[PS_PARTS] = ex + c;
         }
         __syncthreads();
-        if (t < 256) cnt[t] = toff[t];
+        if (t < PS_PARTS) cnt[t] = toff[t];
         __syncthreads();
 #pragma unroll
         for (uint32_t k = 0; k < PER; ++k)
             if (pk[k] != 0xffffffffu) rec[atomicAdd(&cnt[pk[k] >> 22], 1u)] = pk[k];
         __syncthreads();
-        const uint32_t total = toff[256];
+        const uint32_t total = toff[PS_PARTS];
 #pragma unroll
         for (uint32_t k = 0; k < PER; ++k) {
             const uint32_t qq = k * PS_T + t;   // consecutive lanes -> consecutive records of a partition's run
@@ -469,14 +707,9 @@ __global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, ui
             }
         }
         __syncthreads();
-        if (t < 256) gcur[t] += toff[t + 1] - toff[t];
+        if (t < PS_PARTS) gcur[t] += toff[t + 1] - toff[t];
     }
 }
-
-// one workgroup per partition: count the low bits, publish the bucket offsets, then place the references
-// tile by tile: a tile of PS_TILE references is ordered in LDS first, so that the global stores are runs
-// of consecutive addresses (one run per bucket and tile) instead of 64 different cache lines per wave-store.
-// (Wave-private counters were tried for the counting: 16 x 128 write streams per workgroup made it slower.)
 
 // exclusive scan of 128 values held by lanes 0..127 of a workgroup (every lane calls it); tmp: one LDS word
 ZK_D uint32_t scan128_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
@@ -486,22 +719,7 @@ ZK_D uint32_t scan128_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
     if (t >= 64 && t < 128) inc += *tmp;
     return inc - v;
 }
-// counts of the keys key[i], i = first, first + PS_T, ... < end, into the LDS table cnt.  Eight loads in flight per lane: written
-// as a plain loop the compiler keeps ONE (load, wait, LDS atomic) per iteration, and the pass over a partition's ~60 keys per
-// lane was sixty memory round trips in a row -- most of the kernel's time.
-template <class K>
-ZK_D void count_keys(const K* key, uint32_t first, uint32_t end, uint32_t* cnt) {
-    uint32_t i = first;
-    for (; i + 7 * PS_T < end; i += 8 * PS_T) {
-        uint32_t v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = key[i + k * PS_T];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) atomicAdd(&cnt[v[k]], 1u);
-    }
-    for (; i < end; i += PS_T) atomicAdd(&cnt[key[i]], 1u);
-}
-__global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t P) {
+__global__ void __launch_bounds__(PS_T) psort_final16(SJobs jobs, uint32_t P) {
     constexpr uint32_t NB = 1u << PS_LOB, PER = PS_TILE / PS_T;
     const SJob& J = jobs.j[blockIdx.y];
     const uint32_t* stage_ref = J.stage_ref;
@@ -583,257 +801,8 @@ __global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t P) {
     }
 }
 
-
-// ---- the same partition sort for window tables with c > 16 (2^(c-1) shared buckets, c <= 21) ---------------------------
-// Still P = 256 partitions by the high 8 bucket bits; the low part grows to lob = c - 9 bits (128 ... 4096 buckets per
-// partition), so the digits are int32, the staged low bits uint16 and the LDS tables of the second pass are sized at
-// launch.  One scalar per lane in the digit kernel (a 4-byte store per window either way).
-template <class Fr, bool MONT>
-__global__ void __launch_bounds__(256) psortw_digits_hist(const uint32_t* scalars, uint64_t n, uint32_t sp, MsmGeom g, uint32_t lob, int32_t* dig,
-                                                          uint32_t* hist /* [256][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
-    __shared__ uint32_t lc[256];
-    reset_job_counters(scan_counter, combine_q);
-    lc[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
-    const uint32_t half = 1u << (g.c - 1), cmask = (1u << g.c) - 1u;
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) {
-        const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * i;
-        uint4 a = q[0], b = q[1];
-        Fr x;
-        x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
-        x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
-        if (MONT) x = Fr::from_mont(x);
-        const bool flip = scalar_fold(x.v, g);
-        uint32_t carry = 0;
-        for (uint32_t w = 0; w < g.Wt; ++w) {
-            const uint32_t raw = (scalar_bits(x.v, w * g.c, g.c) & cmask) + carry;
-            carry = raw >= half ? 1u : 0u;
-            int32_t d = carry ? (int32_t)raw - (int32_t)(1u << g.c) : (int32_t)raw;
-            if (flip) d = -d;
-            uint32_t row;
-            if (!g.owns(w, row)) continue;
-            dig[(uint64_t)row * n + i] = d;
-            if (d != 0) atomicAdd(&lc[(uint32_t)((d < 0 ? -d : d) - 1) >> lob], 1u);
-        }
-    }
-    __syncthreads();
-    hist[(uint64_t)threadIdx.x * PS_SLABS + blockIdx.x] = lc[threadIdx.x];
-}
-
-
-__global__ void __launch_bounds__(PS_T) psortw_scatter(SJobs jobs, uint32_t W, uint32_t lob) {
-    constexpr uint32_t PER = PS_STILE / PS_T;
-    const SJob& J = jobs.j[blockIdx.y];
-    const int32_t* dig = (const int32_t*)J.dig;
-    const uint64_t n = J.n;
-    const uint32_t sp = J.sp;
-    const uint32_t* cursors = J.hist;
-    const uint32_t* part_start = J.part_start;
-    uint32_t* stage_ref = J.stage_ref;
-    uint16_t* stage_lo = (uint16_t*)J.stage_lo;
-    const uint32_t LOM = (1u << lob) - 1u;
-    __shared__ uint32_t cnt[256], toff[257], gcur[256], stmp[4];
-    __shared__ uint32_t rec[PS_STILE];       // k (14 bits) | neg << 14 | partition << 15
-    __shared__ uint16_t rlo[PS_STILE];       // low bucket bits of the record at the same position
-    const uint32_t t = threadIdx.x;
-    if (t < 256) gcur[t] = part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x];
-    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
-    const uint32_t len = (uint32_t)(hi - lo);
-    const uint32_t total_digits = W * len;
-    // the digits of the tile after the current one are requested while the current one is counted and placed
-    int32_t nd[PER];
-    auto fetch = [&](uint32_t base) {
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t q = base + k * PS_T + t;
-            nd[k] = 0;
-            if (q < total_digits) {
-                const uint32_t w = q / len, ii = q - w * len;
-                nd[k] = dig[(uint64_t)w * n + lo + ii];
-            }
-        }
-    };
-    if (total_digits) fetch(0);
-    for (uint32_t base = 0; base < total_digits; base += PS_STILE) {
-        __syncthreads();
-        if (t < 256) cnt[t] = 0;
-        __syncthreads();
-        int32_t vd[PER];
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) vd[k] = nd[k];
-        if (base + PS_STILE < total_digits) fetch(base + PS_STILE);
-        uint32_t pk[PER];
-        uint16_t pl[PER];
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;
-            pk[k] = 0xffffffffu;
-            pl[k] = 0;
-            const int32_t d = vd[k];      // 0 past the end of the slab
-            if (d != 0) {
-                const uint32_t neg = d < 0 ? 1u : 0u;
-                const uint32_t b = (uint32_t)((neg ? -d : d) - 1);
-                pk[k] = i | (neg << 14) | ((b >> lob) << 15);
-                pl[k] = (uint16_t)(b & LOM);
-                atomicAdd(&cnt[b >> lob], 1u);
-            }
-        }
-        __syncthreads();
-        {
-            const uint32_t c = t < 256 ? cnt[t] : 0u;
-            const uint32_t ex = scan256_excl(c, t, stmp);
-            if (t < 256) toff[t] = ex;
-            if (t == 255) toff[256] = ex + c;
-        }
-        __syncthreads();
-        if (t < 256) cnt[t] = toff[t];
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k)
-            if (pk[k] != 0xffffffffu) {
-                const uint32_t at = atomicAdd(&cnt[pk[k] >> 15], 1u);
-                rec[at] = pk[k];
-                rlo[at] = pl[k];
-            }
-        __syncthreads();
-        const uint32_t total = toff[256];
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t qq = k * PS_T + t;
-            if (qq < total) {
-                const uint32_t r = rec[qq];
-                const uint32_t pp = r >> 15;
-                const uint32_t q = base + (r & 0x3fffu), w = q / len, ii = q - w * len;
-                const uint32_t ref = (w << 26) | (uint32_t)(lo + ii) | (((r >> 14) & 1u) << 31);
-                const uint32_t dst = gcur[pp] + (qq - toff[pp]);
-                stage_ref[dst] = ref;
-                stage_lo[dst] = rlo[qq];
-            }
-        }
-        __syncthreads();
-        if (t < 256) gcur[t] += toff[t + 1] - toff[t];
-    }
-}
-
-// exclusive scan of one value per lane over a 1024-lane workgroup; tmp: 16 LDS words
-ZK_D uint32_t scan1024_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
-    uint32_t inc = wave_scan_incl(v, t);
-    __syncthreads();
-    if ((t & 63) == 63) tmp[t >> 6] = inc;
-    __syncthreads();
-    uint32_t add = 0;
-    for (uint32_t w = 0; w < (t >> 6); ++w) add += tmp[w];
-    return inc + add - v;
-}
-
-// one workgroup per partition, NB = 2^lob buckets; dynamic LDS: cnt[NB] | cur[NB] | toff[NB + 1] | tmp[16] | sorted[PS_TILE] | skey[PS_TILE] (u16)
-__global__ void __launch_bounds__(PS_T) psortw_final(SJobs jobs, uint32_t P, uint32_t lob) {
-    extern __shared__ uint32_t lds[];
-    const SJob& J = jobs.j[blockIdx.y];
-    const uint32_t* stage_ref = J.stage_ref;
-    const uint16_t* stage_lo = (const uint16_t*)J.stage_lo;
-    const uint32_t* part_start = J.part_start;
-    uint32_t* entries = J.entries;
-    uint32_t* offsets = J.offsets;
-    constexpr uint32_t PER = PS_TILE / PS_T;
-    const uint32_t NB = 1u << lob;
-    const uint32_t K = NB > PS_T ? NB / PS_T : 1u;       // counters per lane in the scans
-    uint32_t* cnt = lds;
-    uint32_t* cur = cnt + NB;
-    uint32_t* toff = cur + NB;
-    uint32_t* tmp = toff + NB + 1;
-    uint32_t* sorted = tmp + 16;
-    uint16_t* skey = reinterpret_cast<uint16_t*>(sorted + PS_TILE);
-    const uint32_t p = blockIdx.x, t = threadIdx.x;
-    const uint32_t s = part_start[p], e = part_start[p + 1];
-    for (uint32_t j = t; j < NB; j += PS_T) cnt[j] = 0;
-    __syncthreads();
-    count_keys(stage_lo, s + t, e, cnt);
-    __syncthreads();
-    // exclusive scan of cnt[0 .. NB): lane t owns counters [t*K, (t+1)*K)
-    auto scan_counts = [&](uint32_t* dst, uint32_t add, bool with_total) {
-        uint32_t mine = 0;
-        if (t * K < NB)
-            for (uint32_t k = 0; k < K; ++k) mine += cnt[t * K + k];
-        uint32_t ex = scan1024_excl(mine, t, tmp);
-        if (t * K < NB) {
-            for (uint32_t k = 0; k < K; ++k) {
-                const uint32_t c = cnt[t * K + k];
-                dst[t * K + k] = add + ex;
-                ex += c;
-            }
-            if (with_total && (t + 1) * K == NB) dst[NB] = add + ex;
-        }
-        __syncthreads();
-    };
-    scan_counts(cur, s, false);
-    for (uint32_t j = t; j < NB; j += PS_T) offsets[p * NB + j] = cur[j];
-    if (p == P - 1 && t == 0) offsets[P * NB] = e;
-    // the tile after the current one is requested while the current one is counted, scanned and placed: its 16 references and
-    // keys per lane sit in registers across the barriers instead of costing a memory round trip at the top of every tile
-    uint32_t nr[PER];
-    uint16_t nk[PER];
-    auto fetch = [&](uint32_t base) {
-        const uint32_t m = e - base < PS_TILE ? e - base : PS_TILE;
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;
-            if (i < m) {
-                nr[k] = stage_ref[base + i];
-                nk[k] = stage_lo[base + i];
-            }
-        }
-    };
-    if (s < e) fetch(s);
-    for (uint32_t base = s; base < e; base += PS_TILE) {
-        const uint32_t m = e - base < PS_TILE ? e - base : PS_TILE;
-        __syncthreads();
-        for (uint32_t j = t; j < NB; j += PS_T) cnt[j] = 0;
-        __syncthreads();
-        uint32_t vr[PER];
-        uint16_t vk[PER];
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            vr[k] = nr[k];
-            vk[k] = nk[k];
-        }
-        if (base + PS_TILE < e) fetch(base + PS_TILE);
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;
-            if (i < m) atomicAdd(&cnt[vk[k]], 1u);
-        }
-        __syncthreads();
-        scan_counts(toff, 0u, true);
-        for (uint32_t j = t; j < NB; j += PS_T) cnt[j] = toff[j];      // running position inside the tile
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;
-            if (i < m) {
-                const uint32_t q = atomicAdd(&cnt[vk[k]], 1u);
-                sorted[q] = vr[k];
-                skey[q] = vk[k];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;
-            if (i < m) {
-                const uint32_t j = skey[i];
-                entries[cur[j] + (i - toff[j])] = sorted[i];
-            }
-        }
-        __syncthreads();
-        for (uint32_t j = t; j < NB; j += PS_T) cur[j] += toff[j + 1] - toff[j];
-    }
-}
-
-
 // ---- the compact form of the wide sort: whole tables of folded 17-bit windows (pre_compact, msm_common.cuh) ---------------------
-// What every MSM of a 2^19 .. 2^21 proof runs.  The int32 digit array of psortw_* is a 4 W-byte expansion of a 32-byte scalar that
+// What every MSM of a 2^19 .. 2^21 proof runs.  The int32 digit array of psort_* is a 4 W-byte expansion of a 32-byte scalar that
 // is written once and read once, and its staged record is 6 bytes.  Here
 //   csort_fold_hist  (at submission, the only reader of the caller's vector) leaves the folded canonical scalar in the job's
 //                    `entries` buffer -- it is below 2^254, so bit 255 carries the fold's sign -- and counts the partitions;
@@ -855,8 +824,8 @@ ZK_D uint32_t cs_bits(const uint32_t (&s)[8], uint32_t w) {
 
 template <class Fr, bool MONT>
 __global__ void __launch_bounds__(256, 8) csort_fold_hist(const uint32_t* scalars, uint64_t n, uint32_t sp, MsmGeom g, uint4* folded,
-                                                       uint32_t* hist /* [256][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
-    __shared__ uint32_t lc[256];
+                                                       uint32_t* hist /* [PS_PARTS][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
+    __shared__ uint32_t lc[PS_PARTS];
     reset_job_counters(scan_counter, combine_q);
     lc[threadIdx.x] = 0;
     __syncthreads();
@@ -888,7 +857,7 @@ __global__ void __launch_bounds__(256, 8) csort_fold_hist(const uint32_t* scalar
 }
 
 // dynamic LDS: rec[W * PS_T].  Record in LDS: partition << 23 | sign << 22 | window << 18 | lane << 8 | low bucket bits.
-// Two workgroups per CU, as psortw_scatter has (8 waves per SIMD = 64 registers, under 80 KiB of LDS): one places its tile while the
+// Two workgroups per CU, as psort_scatter has (8 waves per SIMD = 64 registers, under 80 KiB of LDS): one places its tile while the
 // other loads.
 __global__ void __launch_bounds__(PS_T, 8) csort_scatter(SJobs jobs, uint32_t W) {
     extern __shared__ uint32_t rec[];
@@ -900,7 +869,7 @@ __global__ void __launch_bounds__(PS_T, 8) csort_scatter(SJobs jobs, uint32_t W)
     const uint32_t* part_start = J.part_start;
     uint32_t* stage = J.stage_ref;
     constexpr uint32_t LOM = (1u << CS_LOB) - 1u, half = 1u << (CS_C - 1);
-    __shared__ uint32_t cnt[256], toff[257], gcur[256], stmp[4];
+    __shared__ uint32_t cnt[PS_PARTS], toff[PS_PARTS + 1], gcur[PS_PARTS], stmp[4];
     const uint32_t t = threadIdx.x;
     if (t < 256) gcur[t] = part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x];
     const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
@@ -972,7 +941,7 @@ __global__ void __launch_bounds__(PS_T, 8) csort_scatter(SJobs jobs, uint32_t W)
 // A partition of up to CS_RT tiles (65536 references; a uniform 2^20-point job has 61440) is read from memory ONCE, into registers,
 // and its low bits are counted ONCE, per tile: the bucket starts are the sums over the tiles, and every (tile, bucket) run's place in
 // the sorted tile and in `entries` comes from the same counts (lane = (tile, bucket)).  The kernel is bound by its LDS atomics and
-// barriers, not by memory (one workgroup per CU): two atomics per reference and two barriers per tile instead of psortw_final's
+// barriers, not by memory (one workgroup per CU): two atomics per reference and two barriers per tile instead of psort_final's
 // three and eight.  Longer partitions are left to csort_final_long (two kernels: in one, the two paths' registers do not overlay).
 constexpr uint32_t CS_RT = 4;
 __global__ void __launch_bounds__(PS_T) csort_final(SJobs jobs, uint32_t P) {
@@ -1103,7 +1072,7 @@ __global__ void __launch_bounds__(PS_T) csort_final(SJobs jobs, uint32_t P) {
 }
 
 // The partitions csort_final leaves: longer than CS_RT tiles (skewed scalars: a handful of values repeated; jobs beyond 2^20 points).
-// Read twice, as psortw_final reads them -- a counting pass, then tile by tile with the next tile requested ahead -- and the slab of
+// Read twice, as psort_final reads them -- a counting pass, then tile by tile with the next tile requested ahead -- and the slab of
 // a record found by a 10-step search over the cursors.  dynamic LDS: curs[PS_SLABS] | sorted[PS_TILE] | skey[PS_TILE] (u8)
 __global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P) {
     extern __shared__ uint32_t lds[];
@@ -1247,75 +1216,58 @@ int pw_queue_sort(zk_ctx* c, const MsmGeom& g, uint32_t S, MsmBufs& mb, const vo
     return ZK_OK;
 }
 
+// The words of a job's part_key in front of its combine queues (PRE_Q_OFF): PS_PARTS + 1 partition starts | PS_PARTS totals | the
+// counter psort_scan finds its last workgroup by
+struct PartKey {
+    uint32_t *part_start, *part_total, *scan_counter, *combine_q;
+    explicit PartKey(MsmBufs& mb)
+        : part_start((uint32_t*)mb.part_key.p), part_total(part_start + PS_PARTS + 1), scan_counter(part_total + PS_PARTS), combine_q(part_start + PRE_Q_OFF) {}
+};
+static_assert(2 * PS_PARTS + 2 <= PRE_Q_OFF, "the partition-sort words end in front of the combine queues");
+
 // The sort of a table-path job comes in two pieces.  `pre_queue_digits` is the only kernel that reads the caller's scalars
-// (digits + the slab counts of the 256 partitions; into_repr of a commit's Montgomery coefficients fused in): it is queued when
+// (digits + the slab counts of the PS_PARTS partitions; into_repr of a commit's Montgomery coefficients fused in): it is queued when
 // the job is submitted, so the input vector is consumed in stream order at the call, as before.  `pre_queue_sort_rest` -- scan,
 // partition scatter, final placement -- takes the jobs of a round as ONE launch per kernel (blockIdx.y = job).
 template <class Cv>
 int pre_queue_digits(zk_ctx* c, const PrePlan& pl, MsmBufs& mb, const void* d_scalars, size_t n, hipStream_t st, bool mont) {
     ProfScope ps(c, "msm_sort", st);
     typedef typename Cv::Fr FrS;
-    const int T = 256;
-    const uint32_t sp = psort_slab_len(n);
-    int rc;
-    if (pl.wide) {
-        const uint32_t lob = pl.g.c - 9, P = 256;
-        uint32_t* part_start = (uint32_t*)mb.part_key.p;
-        uint32_t* part_total = part_start + P + 1;
-        uint32_t* scan_counter = part_total + P;
-        uint32_t* combine_q = (uint32_t*)mb.part_key.p + PRE_Q_OFF;
-        uint32_t* hist = (uint32_t*)mb.counts.p;
-        if (pre_compact(pl)) {                            // the folded scalars wait where the digits would (32 <= 4 W bytes per scalar)
-            uint4* folded = (uint4*)mb.entries.p;
-            on_mont(mont, [&](auto M) {
-                hipLaunchKernelGGL((csort_fold_hist<FrS, decltype(M)::value>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp,
-                                   pl.g, folded, hist, scan_counter, combine_q);
-            });
-            ZK_HIP_TRY(hipGetLastError());
-            return ZK_OK;
-        }
-        int32_t* dig32 = (int32_t*)mb.entries.p;          // the digits wait in the buffer of the sorted references (pre_sizes)
-        on_mont(mont, [&](auto M) {
-            hipLaunchKernelGGL((psortw_digits_hist<FrS, decltype(M)::value>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp,
-                               pl.g, lob, dig32, hist, scan_counter, combine_q);
-        });
-        ZK_HIP_TRY(hipGetLastError());
-        return ZK_OK;
-    }
-    if (!pre_psort16(pl)) return ZK_ERR_UNSUPPORTED;     // the table windows are 16 .. 21 bits: 2^15 buckets = 256 partitions of 128
-    int16_t* dig = (int16_t*)mb.entries.p;
-    const bool pairs = (n & 1) == 0 && pl.g.c == 16 && pl.g.W == 16 && pl.g.Wt == 16 && !pl.g.neg;        // two scalars per lane
-    const uint32_t P = pl.g1.nb >> PS_LOB;
-    uint32_t* part_start = (uint32_t*)mb.part_key.p;    // P + 1 partition starts | P totals | scan counter
-    uint32_t* part_total = part_start + P + 1;
-    uint32_t* scan_counter = part_total + P;
-    uint32_t* combine_q = (uint32_t*)mb.part_key.p + PRE_Q_OFF;
+    const uint32_t sp = psort_slab_len(n), lob = pl.g.c - 9;
+    const PartKey pk(mb);
+    const uint32_t* scalars = (const uint32_t*)d_scalars;
     uint32_t* hist = (uint32_t*)mb.counts.p;
-    if (pairs && P == 256) {
-        // digits and the per-slab partition counts in one kernel
-        on_mont(mont, [&](auto M) {
-            hipLaunchKernelGGL((psort_digits_hist<FrS, decltype(M)::value>), dim3(PS_SLABS), dim3(256), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, sp,
-                               dig, hist, scan_counter, combine_q);
-        });
-    } else {
-        if (pairs) {
-            unsigned b2 = (unsigned)((n / 2 + T - 1) / T);
-            on_mont(mont, [&](auto M) {
-                hipLaunchKernelGGL((msm_digits2<FrS, decltype(M)::value>), dim3(b2), dim3(T), 0, st, (const uint32_t*)d_scalars, (uint64_t)n, pl.g, dig);
-            });
-        } else {
-            const void* canon = d_scalars;
-            if (mont) {   // odd length: separate into_repr pass, then the one-scalar-per-lane kernel
-                if ((rc = mb.scalars.ensure(n * 32))) return rc;
-                if ((rc = fr_convert_stream(c, Cv::ID, d_scalars, n, mb.scalars.p, st))) return rc;
-                canon = mb.scalars.p;
-            }
-            unsigned blocks = (unsigned)((n + T - 1) / T);
-            hipLaunchKernelGGL(msm_digits, dim3(blocks), dim3(T), 0, st, (const uint32_t*)canon, (uint64_t)n, pl.g, dig);
-        }
-        hipLaunchKernelGGL(psort_hist, dim3(PS_SLABS), dim3(PS_T), P * 4, st, dig, (uint64_t)n, pl.g.W, sp, P, hist, scan_counter, combine_q);
-    }
+    // the digits (compact form: the folded scalars, 32 <= 4 W bytes each) wait in the buffer of the sorted references (pre_sizes)
+    void* dig = mb.entries.p;
+    on_mont(mont, [&](auto M) {
+        constexpr bool MONT = decltype(M)::value;
+        const dim3 grid(PS_SLABS), block(PS_PARTS);      // a lane per partition count
+        if (pre_compact(pl))
+            hipLaunchKernelGGL((csort_fold_hist<FrS, MONT>), grid, block, 0, st, scalars, (uint64_t)n, sp, pl.g, (uint4*)dig, hist, pk.scan_counter, pk.combine_q);
+        else if (pl.wide)
+            hipLaunchKernelGGL((psort_digits_hist<FrS, MONT, int32_t>), grid, block, 0, st, scalars, (uint64_t)n, sp, pl.g, lob, (int32_t*)dig, hist,
+                               pk.scan_counter, pk.combine_q);
+        else if ((n & 1) == 0 && pl.g.c == PRE_C && pl.g.W == 16 && pl.g.Wt == 16 && !pl.g.neg)      // a whole 16-bit table, whole pairs
+            hipLaunchKernelGGL((psort_digits_hist_pairs16<FrS, MONT>), grid, block, 0, st, scalars, (uint64_t)n, sp, (int16_t*)dig, hist, pk.scan_counter,
+                               pk.combine_q);
+        else
+            // odd lengths and window-sharded 16-bit tables.  int16 holds every digit of a 16-bit window except +32768, which only a
+            // negated -32768 could be: make_geom never folds scalars at c = 16 (see there), so no digit is negated
+            hipLaunchKernelGGL((psort_digits_hist<FrS, MONT, int16_t>), grid, block, 0, st, scalars, (uint64_t)n, sp, pl.g, lob, (int16_t*)dig, hist,
+                               pk.scan_counter, pk.combine_q);
+    });
     ZK_HIP_TRY(hipGetLastError());
+    return ZK_OK;
+}
+
+// partition scatter and final placement of a round's jobs with lob = c - 9 as an argument: the windows above 16 bits
+template <class Dig, class Lo>
+int queue_psort_passes(const SJobs& sj, uint32_t n_jobs, const MsmGeom& g, hipStream_t st) {
+    const uint32_t lob = g.c - 9;
+    const size_t lds = psort_final_lds(lob, sizeof(Lo));
+    hipLaunchKernelGGL((psort_scatter<Dig, Lo>), dim3(PS_SLABS, n_jobs), dim3(PS_T), 0, st, sj, g.W, lob);
+    ZK_HIP_TRY(hipFuncSetAttribute((const void*)psort_final<Lo>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((psort_final<Lo>), dim3(PS_PARTS, n_jobs), dim3(PS_T), lds, st, sj, lob);
     return ZK_OK;
 }
 
@@ -1336,45 +1288,41 @@ int pre_queue_sort_rest(zk_ctx* c, const PrePlan* pls, MsmBufs* const* mbs, cons
     }
     ProfScope ps(c, "msm_sort", st);
     const PrePlan& p0 = pls[0];
-    const uint32_t P = p0.wide ? 256u : p0.g1.nb >> PS_LOB;
     SJobs sj;
     memset(&sj, 0, sizeof sj);
     for (uint32_t k = 0; k < n_jobs; ++k) {
         MsmBufs& mb = *mbs[k];
         SJob& J = sj.j[k];
+        const PartKey pk(mb);
         void* stage = pls[k].shared_stage ? c->stage_shared.p : mb.stage.p;
         J.dig = mb.entries.p;           // (compact form: the folded scalars) overwritten by the placement kernel once the scatter has read them
         J.n = lens[k];
         J.sp = psort_slab_len(lens[k]);
         J.hist = (uint32_t*)mb.counts.p;
-        J.part_start = (uint32_t*)mb.part_key.p;
-        J.part_total = J.part_start + P + 1;
-        J.counter = J.part_total + P;
+        J.part_start = pk.part_start;
+        J.part_total = pk.part_total;
+        J.counter = pk.scan_counter;
         J.stage_ref = (uint32_t*)stage;
         J.stage_lo = (char*)stage + (size_t)pls[k].nf * 4;
         J.entries = (uint32_t*)mb.entries.p;
         J.offsets = (uint32_t*)mb.offsets.p;
     }
-    hipLaunchKernelGGL(psort_scan, dim3(P, n_jobs), dim3(PS_SLABS), 0, st, sj, P);
+    hipLaunchKernelGGL(psort_scan, dim3(PS_PARTS, n_jobs), dim3(PS_SLABS), 0, st, sj, PS_PARTS);
     if (pre_compact(p0)) {                                // (all jobs of a launch share the table's geometry and own their staging)
         const size_t lds_s = (size_t)p0.g.W * PS_T * 4, lds_f = ((size_t)PS_SLABS + 1 + PS_TILE) * 4 + (size_t)PS_TILE * 3,
                      lds_l = ((size_t)PS_SLABS + PS_TILE) * 4 + PS_TILE;
         ZK_HIP_TRY(hipFuncSetAttribute((const void*)csort_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
         hipLaunchKernelGGL(csort_scatter, dim3(PS_SLABS, n_jobs), dim3(PS_T), lds_s, st, sj, p0.g.W);
         ZK_HIP_TRY(hipFuncSetAttribute((const void*)csort_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-        hipLaunchKernelGGL(csort_final, dim3(P, n_jobs), dim3(PS_T), lds_f, st, sj, P);
+        hipLaunchKernelGGL(csort_final, dim3(PS_PARTS, n_jobs), dim3(PS_T), lds_f, st, sj, PS_PARTS);
         ZK_HIP_TRY(hipFuncSetAttribute((const void*)csort_final_long, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l));
-        hipLaunchKernelGGL(csort_final_long, dim3(P, n_jobs), dim3(PS_T), lds_l, st, sj, P);
-    } else if (p0.wide) {
-        const uint32_t lob = p0.g.c - 9;
-        hipLaunchKernelGGL(psortw_scatter, dim3(PS_SLABS, n_jobs), dim3(PS_T), 0, st, sj, p0.g.W, lob);
-        const uint32_t NB = 1u << lob;
-        const size_t lds = ((size_t)3 * NB + 1 + 16 + PS_TILE) * 4 + (size_t)PS_TILE * 2;
-        ZK_HIP_TRY(hipFuncSetAttribute((const void*)psortw_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(psortw_final, dim3(P, n_jobs), dim3(PS_T), lds, st, sj, P, lob);
+        hipLaunchKernelGGL(csort_final_long, dim3(PS_PARTS, n_jobs), dim3(PS_T), lds_l, st, sj, PS_PARTS);
+    } else if (!p0.wide) {
+        hipLaunchKernelGGL(psort_scatter16, dim3(PS_SLABS, n_jobs), dim3(PS_T), 0, st, sj, p0.g.W, PS_PARTS);
+        hipLaunchKernelGGL(psort_final16, dim3(PS_PARTS, n_jobs), dim3(PS_T), 0, st, sj, PS_PARTS);
     } else {
-        hipLaunchKernelGGL(psort_scatter, dim3(PS_SLABS, n_jobs), dim3(PS_T), 0, st, sj, p0.g.W, P);
-        hipLaunchKernelGGL(psort_final, dim3(P, n_jobs), dim3(PS_T), 0, st, sj, P);
+        const int rc = queue_psort_passes<int32_t, uint16_t>(sj, n_jobs, p0.g, st);
+        if (rc) return rc;
     }
     ZK_HIP_TRY(hipGetLastError());
     return ZK_OK;

@@ -8,7 +8,10 @@
  *
  * Data formats (identical bytes to arkworks 0.3 in-memory values):
  *   Fr element  : 4 x uint64 little-endian limbs, Montgomery form (value * 2^256 mod r), < r.
- *   Fr scalar   : 4 x uint64 little-endian limbs, canonical integer (PrimeField::into_repr), < r.
+ *   Fr scalar   : 4 x uint64 little-endian limbs, canonical integer (PrimeField::into_repr), < r.  No entry point checks
+ *                 that: window tables whose scalars are folded (17 bits and wider) bring an integer in [r, 2^256) below r on the
+ *                 way, a 16-bit table does not -- there such an integer with bits 240 .. 254 all set loses the carry out of its
+ *                 top window and the sum is wrong, without an error.
  *   Fq element  : L x uint64 limbs (L = 6 BLS12-381, 4 BN254), Montgomery form (R = 2^(64L)).
  *   G1 affine   : x || y (2L limbs, packed) (arkworks' GroupAffine is not repr(C): the shim copies x, y, infinity).
  *                 The point at infinity is accepted in three encodings: inf_flags[i] != 0 (x, y ignored),

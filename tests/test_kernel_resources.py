@@ -42,8 +42,10 @@ def test_msm_kernels_registers_and_spills():
     assert acc["VGPRs Spill"] == 0 and acc["ScratchSize"] == 0 and 168 < acc["VGPRs"] <= 256 and acc["Occupancy"] == 2, acc
     fin = find("msm_win_finish_q", "Li512E")
     assert fin["VGPRs Spill"] == 0 and fin["VGPRs"] <= 256, fin
-    for name in ("psort_scan", "psortw_scatter", "psortw_final", "psort_scatter", "psort_final"):
-        k = find(f"{len(name)}{name}E")                     # Itanium mangling: <length><name>E inside the anonymous namespace
+    # Itanium mangling inside the anonymous namespace: <length><name>E for a plain function, <length><name>I<args>E for a template
+    # (s = int16, i = int32 digits; h = uint8, t = uint16 low bucket bits)
+    for name in ("10psort_scanE", "15psort_scatter16E", "13psort_scatterIitE", "13psort_final16E", "11psort_finalItE"):
+        k = find(name)
         assert k["VGPRs Spill"] == 0 and k["ScratchSize"] == 0, (name, k)
 
 

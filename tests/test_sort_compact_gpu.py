@@ -1,8 +1,10 @@
 """The compact form of the wide partition sort (csort_* in csrc/msm_sort.hip: whole tables of folded 17-bit windows) against the CPU
 oracle's Pippenger, limb for limb, through the public calls -- with inputs chosen to break a packed staging record, the slab
-recovery of the placement kernel or a run boundary.  Geometries the form does not take (16-bit BN254 table, a 20-bit table, a
-window-sharded table: `pre_compact` in csrc/msm_common.cuh refuses them, so they run psort_* / psortw_*) agree with the same oracle.
-Several expected points are the point at infinity or a single multiple of one base: that is intended."""
+recovery of the placement kernel or a run boundary.  Geometries the form does not take (16-bit tables, a 20-bit table, a
+window-sharded table: `pre_compact` in csrc/msm_common.cuh refuses them, so they run the psort_* family -- int16 digits and uint8
+low bucket bits at 16 bits, int32 and uint16 above) agree with the same oracle.  The 16-bit cases reach every digit kernel of that
+window: the two-scalars-per-lane kernel of even lengths over a whole table, and the generic kernel with int16 digits for odd
+lengths and window-sharded tables.  Several expected points are the point at infinity or a single multiple of one base: that is intended."""
 import numpy as np
 import pytest
 
@@ -26,24 +28,28 @@ def _rand_canonical(rng, n, top_bits=62):
     return s
 
 
-def scalar_cases(cv, n, seed=1):
-    """name -> (n, 4) canonical scalars.  No GPU needed: the oracle can be run on these anywhere."""
+def scalar_cases(cv, n, seed=1, c=17):
+    """name -> (n, 4) canonical scalars.  No GPU needed: the oracle can be run on these anywhere.  c: the window bits of the table the
+    skewed cases are cut for (all_equal, one_partition, last_partition are built digit by digit: 2^(c-1) buckets per window, 256
+    sort partitions of 2^(c-9))."""
     r = cv.r
     rng = np.random.default_rng(seed)
+    nw, half, per_part = 256 // c, 1 << (c - 1), 1 << (c - 9)       # whole windows in 256 bits: 15 of 17 bits, 16 of 16
     out = {}
     out["random"] = _rand_canonical(rng, n)
     # one bucket of every window holds all n references (the workgroup-per-bucket class of the combine)
     k = 0
-    for w in range(15):
-        k |= (0x1234 + 77 * w) << (17 * w)
+    for w in range(nw):
+        k |= (0x1234 + 77 * w) << (c * w)
     out["all_equal"] = np.tile(_limbs([k]), (n, 1))
-    # every digit of every scalar in sort partition 0: |digit| in 1 .. 256
-    d = rng.integers(1, 257, size=(n, 15))
+    # every digit of every scalar in sort partition 0: |digit| in 1 .. 2^(c-9) (256 at c = 17)
+    d = rng.integers(1, per_part + 1, size=(n, nw))
     m = min(n, 4096)
     reps = (n + m - 1) // m
-    out["one_partition"] = np.tile(_limbs([sum(int(d[i, w]) << (17 * w) for w in range(15)) for i in range(m)]), (reps, 1))[:n]
-    # ... and in the last one (|digit| = 2^16 - 255 .. 2^16: the carry runs through every window)
-    top = [sum((65536 - int(d[i, w]) + 1) << (17 * w) for w in range(14)) for i in range(m)]
+    out["one_partition"] = np.tile(_limbs([sum(int(d[i, w]) << (c * w) for w in range(nw)) for i in range(m)]), (reps, 1))[:n]
+    # ... and in the last one (|digit| = 2^(c-1) - 2^(c-9) + 1 .. 2^(c-1): the carry runs through every window; at c = 16 the
+    # digit -32768 is the lowest an int16 holds)
+    top = [sum((half - int(d[i, w]) + 1) << (c * w) for w in range(nw - 1)) for i in range(m)]
     out["last_partition"] = np.tile(_limbs(top), (reps, 1))[:n]
     # blocks of 128 equal scalars, 16 values: a slab's run inside a partition is longer than a wavefront, the partition itself short
     vals = _limbs([int.from_bytes(rng.bytes(31), "little") for _ in range(16)])
@@ -61,6 +67,12 @@ def scalar_cases(cv, n, seed=1):
     mixed = _rand_canonical(rng, n, 63)        # up to 2^255 > r: a few per cent are reduced below r first, half are folded
     mixed[:: 7] = _limbs([r - 1])[0]
     mixed[3:: 11] = _limbs([(r + 1) // 2])[0]
+    if c == 16:
+        # No fold at 16 bits, so nothing brings an unreduced scalar below r there, and the ABI asks for canonical scalars: above r the
+        # top window can carry out of the 256 bits (bits 240 .. 254 all set, plus a carry).  Same values mod r.
+        big = [i for i in range(n) if int(mixed[i, 3]) >= (r >> 192)]
+        if big:
+            mixed[big] = _limbs([sum(int(mixed[i, j]) << (64 * j) for j in range(4)) % r for i in big])
     out["random_with_edges"] = mixed
     return out
 
@@ -231,7 +243,7 @@ def test_bn254_sixteen_bit_table_keeps_its_kernels_and_agrees(ctx, oracle_cpu):
 
 
 def test_twenty_bit_table_and_window_sharded_rows_keep_their_kernels_and_agree(ctx, oracle_cpu):
-    """c = 20 (psortw_* with 2048 buckets per partition) and a 17-bit table of which a rank owns every other row (the digit kernel
+    """c = 20 (psort_* with int32 digits and 2048 buckets per partition) and a 17-bit table of which a rank owns every other row (the digit kernel
     walks all windows and keeps the owned ones): neither is the compact form's geometry."""
     n = 1 << 14
     bases, bases_h = _small_key(ctx, 0, n, 2017)
@@ -253,3 +265,71 @@ def test_twenty_bit_table_and_window_sharded_rows_keep_their_kernels_and_agree(c
     ck = zk.CommitterKey(bases, 0, ctx).precompute(17)
     _assert_point(ck.msm(_dev(scal)), exp_xy, exp_inf, "c=17 whole")
     ck.close()
+
+
+@pytest.fixture(scope="module", params=[0, 1], ids=["bls12_381", "bn254"])
+def key16(request, ctx):
+    """2^14 points k_i G with a whole table of 16-bit windows (16 rows): what every table below 2^19 points is"""
+    cid = request.param
+    bases, bases_h = _small_key(ctx, cid, 1 << 14, 1600 + cid)
+    ck = zk.CommitterKey(bases, cid, ctx).precompute(16)
+    assert ck.table_windows() == 16 and ck.table_rows() == (0, 1, 16)
+    yield cid, ck, bases, bases_h
+    ck.close()
+
+
+def _mont(oracle_cpu, cid, scal):
+    return oracle_cpu.convert(cid, "fr", True, np.ascontiguousarray(scal))
+
+
+# 2^13: the smallest length of the table path, even (two scalars per lane in the digit kernel); + 1: odd (the generic digit kernel)
+@pytest.mark.parametrize("form", ["canonical", "montgomery"])
+@pytest.mark.parametrize("n", [1 << 13, (1 << 13) + 1])
+def test_sixteen_bit_table_even_and_odd_lengths_against_the_oracle(n, form, key16, oracle_cpu):
+    cid, ck, _, bases_h = key16
+    cases = scalar_cases(zk.get_curve(cid), n, seed=16 * n + cid, c=16)
+    for name in ("random_with_edges", "all_equal", "one_partition", "last_partition", "zeros"):
+        scal = cases[name]
+        if form == "canonical":
+            exp_xy, exp_inf = oracle_cpu.msm_g1(cid, bases_h[:n], scal)
+            got = ck.msm(_dev(scal))
+        else:
+            if name == "random_with_edges":
+                scal = scal >> np.uint64(2)         # (every limb: below r of either curve, as into_mont asks)
+            mont = _mont(oracle_cpu, cid, scal)
+            exp_xy, exp_inf = oracle_cpu.kzg_commit(cid, bases_h, mont)
+            got = ck.commit(_dev(mont))
+        if name == "zeros":
+            assert exp_inf
+        _assert_point(got, exp_xy, exp_inf, f"{name} n={n} {form} curve {cid}")
+
+
+def test_sixteen_bit_window_sharded_rows_agree(ctx, key16, oracle_cpu):
+    """A 16-bit table of which a rank owns every other row: the generic digit kernel walks all 16 windows and keeps the owned rows as
+    int16 digits (an odd length, so that nothing but that kernel could take it either way)."""
+    cid, _, bases, bases_h = key16
+    n = (1 << 13) + 1
+    scal = scalar_cases(zk.get_curve(cid), n, seed=2016 + cid, c=16)["random_with_edges"]
+    exp_xy, exp_inf = oracle_cpu.msm_g1(cid, bases_h[:n], scal)
+    parts = []
+    for g in range(2):
+        ckw = zk.CommitterKey(bases[:n], cid, ctx).precompute(16, rows=(g, 2))
+        assert ckw.table_rows() == (g, 2, 8) and ckw.table_windows() == 16
+        parts.append(ckw.commit_batch_partial([_dev(scal)], canonical=[True]))
+        ckw.close()
+    _assert_point(zk.sum_partials_batch(np.stack(parts), cid)[0], exp_xy, exp_inf, f"c=16, rows (g, 2), curve {cid}")
+
+
+def test_sixteen_bit_deferred_round_of_mixed_lengths(key16, oracle_cpu):
+    """Four jobs of one deferred round over the whole 16-bit table, even and odd lengths, Montgomery and canonical: one launch of the
+    scatter and of the placement kernel (job = blockIdx.y) over jobs whose slabs differ in length."""
+    cid, ck, _, bases_h = key16
+    cv = zk.get_curve(cid)
+    lens = [8192, 8193, 12001, 1 << 14]
+    scal = [scalar_cases(cv, ln, seed=ln + cid, c=16)[nm] for ln, nm in zip(lens, ["random", "last_partition", "random_with_edges", "one_partition"])]
+    mont = [_mont(oracle_cpu, cid, scal[0] >> np.uint64(2)), _mont(oracle_cpu, cid, scal[1])]           # (below r of either curve)
+    want = [oracle_cpu.kzg_commit(cid, bases_h, m) for m in mont] + [oracle_cpu.msm_g1(cid, bases_h[: s.shape[0]], s) for s in scal[2:]]
+    ck.commit_begin([_dev(m) for m in mont])
+    assert ck.commit_begin([_dev(s) for s in scal[2:]], canonical=[True, True]) == 4
+    for k, (pt, (exp_xy, exp_inf)) in enumerate(zip(ck.round_end(), want)):
+        _assert_point(pt, exp_xy, exp_inf, f"job {k} of {lens[k]} curve {cid}")

@@ -1,6 +1,10 @@
-"""Compile-time guard on the kernels of the compact sort form (csort_* in csrc/msm_sort.hip; gfx950 device code, hipcc's own
-`-Rpass-analysis=kernel-resource-usage` remarks; no GPU needed): no register spill, no scratch, and at least as many workgroups of
-the launch shape resident per CU as the psortw_* kernel each replaces."""
+"""Compile-time guard on the kernels of the table sort (csrc/msm_sort.hip; gfx950 device code, hipcc's own
+`-Rpass-analysis=kernel-resource-usage` remarks; no GPU needed).  The compact form (csort_*): no register spill, no scratch, and at
+least as many workgroups of the launch shape resident per CU as the psort_* kernel (int32 digits, uint16 low bits) each replaces.
+The 16-bit table: the generic digit kernel on int16 digits neither spills nor uses scratch, nor do psort_scatter16 / psort_final16;
+the scatter keeps two workgroups of 1024 lanes per CU.  The placement kernel holds ONE (115 registers = 4 wavefronts per SIMD, and
+83472 bytes of LDS): its sorted tile and keys alone are 80 KiB, half a CU's LDS, so a second one cannot fit at PS_TILE = 16384
+whatever the counters beside them take.  The test pins that one."""
 import os
 import re
 import subprocess
@@ -14,6 +18,11 @@ LDS_PER_CU = 160 * 1024          # gfx950
 WAVES_PER_SIMD, SIMDS = 8, 4
 PS_T, PS_SLABS, PS_STILE, PS_TILE = 1024, 1024, 8192, 16384        # csrc/msm_common.cuh
 W, NB17 = 15, 256                                                   # the flagship geometry: 15 windows of 17 bits, 2^8 buckets per partition
+
+
+def psort_final_lds(lob, lo_bytes):
+    """dynamic LDS of psort_final<Lo>: psort_final_lds in csrc/msm_sort.hip, which its launch uses"""
+    return (3 * (1 << lob) + 1 + 16 + PS_TILE) * 4 + PS_TILE * lo_bytes
 
 
 def workgroups_per_cu(k, threads, dynamic_lds):
@@ -52,11 +61,24 @@ def test_compact_sort_kernels_registers_spills_and_residency():
     for name, k in new.items():
         assert k["VGPRs Spill"] == 0 and k["ScratchSize"] == 0, (name, k)
     # launch shapes and dynamic LDS as pre_queue_digits / pre_queue_sort_rest set them
-    old_digits = workgroups_per_cu(find("psortw_digits_hist", "Lb1E"), 256, 0)
+    old_digits = workgroups_per_cu(find("psort_digits_hist", "Lb1EiE"), 256, 0)
     assert workgroups_per_cu(new["fold_t"], 256, 0) >= old_digits, (new["fold_t"], old_digits)
-    assert workgroups_per_cu(new["fold_f"], 256, 0) >= workgroups_per_cu(find("psortw_digits_hist", "Lb0E"), 256, 0)
-    old_scatter = workgroups_per_cu(find("psortw_scatter"), PS_T, 0)
+    assert workgroups_per_cu(new["fold_f"], 256, 0) >= workgroups_per_cu(find("psort_digits_hist", "Lb0EiE"), 256, 0)
+    old_scatter = workgroups_per_cu(find("psort_scatter", "IitE"), PS_T, 0)
     assert workgroups_per_cu(new["scatter"], PS_T, W * PS_T * 4) >= old_scatter, (new["scatter"], old_scatter)
-    old_final = workgroups_per_cu(find("psortw_final"), PS_T, (3 * NB17 + 1 + 16 + PS_TILE) * 4 + PS_TILE * 2)
+    assert psort_final_lds(8, 2) == (3 * NB17 + 1 + 16 + PS_TILE) * 4 + PS_TILE * 2
+    old_final = workgroups_per_cu(find("psort_final", "ItE"), PS_T, psort_final_lds(8, 2))
     assert workgroups_per_cu(new["final"], PS_T, (PS_SLABS + 1 + PS_TILE) * 4 + PS_TILE * 3) >= old_final, (new["final"], old_final)
     assert workgroups_per_cu(new["long"], PS_T, (PS_SLABS + PS_TILE) * 4 + PS_TILE) >= old_final, (new["long"], old_final)
+    # the 16-bit instantiations: lob = 16 - 9
+    for mont in ("Lb1EsE", "Lb0EsE"):
+        k = find("psort_digits_hist", mont)
+        assert k["VGPRs Spill"] == 0 and k["ScratchSize"] == 0, (mont, k)
+    narrow_scatter = find("psort_scatter16")
+    narrow_final = find("psort_final16")
+    for k in (narrow_scatter, narrow_final):
+        assert k["VGPRs Spill"] == 0 and k["ScratchSize"] == 0, k
+    assert workgroups_per_cu(narrow_scatter, PS_T, 0) >= 2, narrow_scatter
+    # one workgroup by LDS whatever the registers; 128 registers is what a 1024-lane workgroup can have at all without spilling
+    assert narrow_final["VGPRs"] <= 128, narrow_final
+    assert workgroups_per_cu(narrow_final, PS_T, 0) == 1, narrow_final
