@@ -23,7 +23,18 @@ arithmetic family       1                    0 or 1            4
 range_gate(bits)        ceil(bits/8) + 2     bits / 2          4 ceil(bits/8) + 5
 xor_gate / and_gate     bits / 2 + 1         2 bits            2 bits + 4
 point_addition_gate     2                    3                 8
-fixed_base_scalar_mul   M + 5                4 M + 3           4 (M + 5)         M = bits of the scalar field (255 / 254)"""
+fixed_base_scalar_mul   M + 5                4 M + 3           4 (M + 5)         M = bits of the scalar field (255 / 254)
+add_witness_to_circuit_description  1        1                 4                 (csrc/gadgets_ext.hip from here on)
+is_zero_with_output     2                    2                 8
+is_eq_with_output       3                    3                 12
+conditional_select      4                    4                 16
+conditional_point_select  8                  8                 32
+conditional_point_neg   5                    5                 20
+variable_base_scalar_mul  8 M + 2            9 M + 257         32 M + 8
+lookup_gate             1                    0                 4                 against `Composer.lookup_table` (a `LookupTable`)
+
+conditional_select_zero / _one, add_affine, add_public_affine, add_affine_to_circuit_description, assert_equal_point,
+assert_equal_public_point and identity are compositions of the rows above with the reference's names."""
 from __future__ import annotations
 
 import ctypes
@@ -38,6 +49,8 @@ from .curves import fr_to_mont, get_curve
 from .prover import SELECTORS
 
 _REC_SHIFT = 30
+_TABLE_MAX_BITS = 12                                    # per operand: a block holds at most 2^24 rows
+_TABLE_OPS = {"add": 0, "mul": 1, "xor": 2, "and": 3}
 _PRELUDE_ROWS, _PRELUDE_VARS = 4, 9
 
 
@@ -46,6 +59,84 @@ def edwards_add(p: int, ca: int, cd: int, p1, p2):
     (x1, y1), (x2, y2) = p1, p2
     t = cd * x1 * x2 * y1 * y2 % p
     return (x1 * y2 + y1 * x2) * pow(1 + t, -1, p) % p, (y1 * y2 - ca * x1 * x2) * pow(1 - t, -1, p) % p
+
+
+class LookupTable:
+    """`LookupTable` (lookup/lookup_table.rs): rows of four field elements in insertion order.  `insert_row` takes integers;
+    the `insert_multi_*(lower_bound, n)` blocks -- every (a, b) with lower_bound <= a, b < 2^n, c = op(a, b) mod 2^n and the tag of the
+    operation (add 0, mul 1, xor -1, and 2) -- are recorded and filled on the device when the columns are asked for
+    (zk_lookup_table_dev: one lane per row)."""
+
+    def __init__(self):
+        self._blocks = []                               # ("rows", [[a, b, c, d], ...]) / ("multi", op, lower_bound, n)
+
+    def insert_row(self, a, b, c, d):
+        if not self._blocks or self._blocks[-1][0] != "rows":
+            self._blocks.append(("rows", []))
+        self._blocks[-1][1].append([int(a), int(b), int(c), int(d)])
+
+    def _multi(self, op, lower_bound, n):
+        lower_bound, n = int(lower_bound), int(n)
+        if not 0 <= n <= _TABLE_MAX_BITS:
+            raise ValueError(f"a table block holds operands of at most {_TABLE_MAX_BITS} bits")
+        if not 0 <= lower_bound <= 1 << n:
+            raise ValueError("lower_bound must lie in 0 .. 2^n")
+        if lower_bound < 1 << n:                        # an empty range inserts nothing, as the reference's loops
+            self._blocks.append(("multi", op, lower_bound, n))
+
+    def insert_multi_add(self, lower_bound, n):
+        self._multi("add", lower_bound, n)
+
+    def insert_multi_mul(self, lower_bound, n):
+        self._multi("mul", lower_bound, n)
+
+    def insert_multi_xor(self, lower_bound, n):
+        self._multi("xor", lower_bound, n)
+
+    def insert_multi_and(self, lower_bound, n):
+        self._multi("and", lower_bound, n)
+
+    @classmethod
+    def _of(cls, op, lower_bound, n):
+        t = cls()
+        t._multi(op, lower_bound, n)
+        return t
+
+    @classmethod
+    def add_table(cls, lower_bound, n):
+        return cls._of("add", lower_bound, n)
+
+    @classmethod
+    def mul_table(cls, lower_bound, n):
+        return cls._of("mul", lower_bound, n)
+
+    @classmethod
+    def xor_table(cls, lower_bound, n):
+        return cls._of("xor", lower_bound, n)
+
+    def size(self) -> int:
+        return sum(len(b[1]) if b[0] == "rows" else ((1 << b[3]) - b[2]) ** 2 for b in self._blocks)
+
+    def columns(self, curve, ctx, device):
+        """the four (size, 4) Montgomery columns on the device, blocks concatenated in insertion order"""
+        import torch
+        curve = get_curve(curve)
+        rows = self.size()
+        cols = [torch.empty((rows, 4), dtype=torch.int64, device=device) for _ in range(4)]
+        at = 0
+        ctx.use_torch_stream()
+        for b in self._blocks:
+            if b[0] == "rows":
+                m = len(b[1])
+                for w in range(4):
+                    cols[w][at:at + m] = torch.from_numpy(fr_to_mont(curve, [r_[w] % curve.r for r_ in b[1]]).view(np.int64)).to(device)
+            else:
+                _, op, lower, n = b
+                m = ((1 << n) - lower) ** 2
+                check(lib().zk_lookup_table_dev(ctx.handle, curve.curve_id, _TABLE_OPS[op], lower, n, *[c[at:].data_ptr() for c in cols]),
+                      "zk_lookup_table_dev")
+            at += m
+        return cols
 
 
 class Composer:
@@ -61,6 +152,7 @@ class Composer:
         self.public_inputs = {}                         # row -> integer, as given at build time
         self._program = []                              # ("inputs", var0, B) / ("segment", record) in build order
         self._n_inputs = 0
+        self.lookup_table = LookupTable()               # `StandardComposer::lookup_table`: assigned by the circuit
         # StandardComposer::new(): constrain_to_constant(zero_var, 0) and add_blinding_factors
         one = fr_to_mont(self.curve, [1])[0].view(np.int64)
         sel = {name: torch.zeros((_PRELUDE_ROWS, 4), dtype=torch.int64) for name in SELECTORS}
@@ -133,7 +225,10 @@ class Composer:
         a = _lib.GadgetArgs()
         a.kind, a.num_bits, a.flags, a.calls, a.row0, a.var0 = seg["kind"], seg["num_bits"], seg["flags"], seg["B"], seg["row0"], seg["var0"]
         for w, h in enumerate(seg["inputs"]):
-            a.inputs[w] = None if h is None else h.data_ptr()
+            if w < 4:
+                a.inputs[w] = None if h is None else h.data_ptr()
+            else:
+                a.inputs_ext[w - 4] = None if h is None else h.data_ptr()
         for j, cf in enumerate(seg["coeff"]):
             if hasattr(cf, "data_ptr"):
                 a.coeff[j] = cf.data_ptr()
@@ -164,7 +259,7 @@ class Composer:
             if len(pi) != B:
                 raise ValueError(f"one public input per call ({B}) expected")
         seg = {"kind": kind, "num_bits": num_bits, "flags": flags, "B": B, "row0": self.n_gates, "var0": self.num_vars, "R": R, "V": V,
-               "inputs": list(inputs) + [None] * (4 - len(inputs)), "coeff": cf, "pi": pi, "table": table}
+               "inputs": list(inputs) + [None] * max(0, 4 - len(inputs)), "coeff": cf, "pi": pi, "table": table}
         N = B * R
         ids = torch.empty((4, N), dtype=torch.int32, device=self.device)
         sel = [torch.empty((N, 4), dtype=torch.int64, device=self.device) for _ in SELECTORS]
@@ -279,6 +374,109 @@ class Composer:
         seg = self._segment(_lib.ZK_GADGET_FIXED_BASE, B, [self._handle(scalar, B)], table=self.fixed_base_table(base))
         return self._new_vars(seg, 4 * self.m_bits), self._new_vars(seg, 4 * self.m_bits + 1)
 
+    # ------------------------------------------------------------------------------------------------------------ csrc/gadgets_ext.hip
+    def _ext(self, kind, handles, B=None, **kw):
+        B = self._batch([h for h in handles if h is not None], B)
+        return self._segment(kind, B, [None if h is None else self._handle(h, B) for h in handles], **kw)
+
+    def add_witness_to_circuit_description(self, value, B=None):
+        """`add_witness_to_circuit_description` (composer.rs:192-196): a new variable fixed to `value` -- an integer (B calls of it) or
+        one integer per call -- by a row of the circuit description.  Returns the variable."""
+        r = self.curve.r
+        neg = (-int(value)) % r if isinstance(value, (int, np.integer)) else [(-int(v)) % r for v in value]
+        B = (1 if B is None else int(B)) if isinstance(neg, int) else len(neg)
+        seg = self._segment(_lib.ZK_GADGET_CONST_WITNESS, B, [], coeff=(0, 0, 0, 0, 0, neg))
+        return self._new_vars(seg, 0)
+
+    def is_zero_with_output(self, a):
+        """`is_zero_with_output` (composer.rs:355-383): the variable b = (a == 0), with y = 1 / a (1 when a = 0) beside it"""
+        return self._new_vars(self._ext(_lib.ZK_GADGET_IS_ZERO, [a]), 1)
+
+    def is_eq_with_output(self, a, b):
+        """`is_eq_with_output` (composer.rs:387-392): is_zero of the difference a - b"""
+        return self._new_vars(self._ext(_lib.ZK_GADGET_IS_EQ, [a, b]), 2)
+
+    def conditional_select(self, bit, choice_a, choice_b):
+        """`conditional_select` (composer.rs:404-433): bit == 1 => choice_a, bit == 0 => choice_b; four rows"""
+        return self._new_vars(self._ext(_lib.ZK_GADGET_SELECT, [bit, choice_a, choice_b]), 3)
+
+    def conditional_point_select(self, point_1, point_0, bit):
+        """`conditional_point_select` (ecc/mod.rs:145-155): bit == 1 => point_1, bit == 0 => point_0"""
+        seg = self._ext(_lib.ZK_GADGET_POINT_SELECT, [bit, point_1[0], point_0[0], point_1[1], point_0[1]])
+        return self._new_vars(seg, 3), self._new_vars(seg, 7)
+
+    def conditional_point_neg(self, bit, point):
+        """`conditional_point_neg` (ecc/mod.rs:165-182): bit == 1 => (-x, y), bit == 0 => (x, y)"""
+        seg = self._ext(_lib.ZK_GADGET_POINT_NEG, [bit, point[0]])
+        return self._new_vars(seg, 4), point[1]
+
+    def variable_base_scalar_mul(self, scalar, point):
+        """`variable_base_scalar_mul` (ecc/scalar_mul/variable_base.rs:27-95): scalar a variable, point a pair of variables; returns
+        the handles of the product.  8 M + 2 rows per call; a zero denominator of the group law on the way is refused at assign time."""
+        seg = self._ext(_lib.ZK_GADGET_VAR_BASE, [scalar, point[0], point[1]])
+        return self._new_vars(seg, seg["V"] - 2), self._new_vars(seg, seg["V"] - 1)
+
+    def lookup_gate(self, a, b, c, d=None, pi=None, B=None):
+        """`lookup_gate` (lookup.rs:18-65): the row (a, b, c, d) must be a row of `self.lookup_table`; d=None is the zero variable"""
+        seg = self._ext(_lib.ZK_GADGET_LOOKUP, [a, b, c, d], B, pi=pi)
+        return self._own(seg["inputs"][2])
+
+    # ---- compositions of the rows above, with the reference's names
+    def conditional_select_zero(self, bit, value):
+        """`conditional_select_zero` (composer.rs:444-453): bit * value"""
+        return self.arithmetic_gate(bit, value, q_m=1)
+
+    def conditional_select_one(self, bit, value):
+        """`conditional_select_one` (composer.rs:464-488): 1 - bit + bit * value"""
+        return self.arithmetic_gate(bit, value, q_m=1, q_l=-1, q_c=1)
+
+    def identity(self, B=1):
+        """`Point::identity` (ecc/mod.rs:58-62): (zero_var, a new variable fixed to one)"""
+        return 0, self.add_witness_to_circuit_description(1, B)
+
+    # A call of the point helpers below handles x, then y; B calls in a row therefore interleave the coordinates -- variables
+    # x_0 y_0 x_1 y_1 ... and rows likewise -- which is one segment of 2 B calls over interleaved handles.
+    def _pair(self, hx, hy, B=None):
+        import torch
+        B = self._batch([hx, hy], B)
+        return self._own(torch.stack([self._handle(hx, B), self._handle(hy, B)], dim=1).reshape(-1)), B
+
+    @staticmethod
+    def _pair_ints(vx, vy, B, sign=1):
+        one = lambda v: [sign * int(v)] * B if isinstance(v, (int, np.integer)) else [sign * int(t) for t in v]  # noqa: E731
+        xs, ys = one(vx), one(vy)
+        if len(xs) != B or len(ys) != B:
+            raise ValueError(f"one point per call ({B}) expected")
+        return [c_ for q in zip(xs, ys) for c_ in q]
+
+    def add_affine(self, B=1):
+        """`add_affine` (ecc/mod.rs:82-84): ONE `inputs(2 B)` whose (2 B, 4) values arrive at assign time interleaved, x_0 y_0 x_1 y_1
+        ...; returns the handles (x, y)"""
+        h = self.inputs(2 * int(B))
+        return self._own(h[0::2].contiguous()), self._own(h[1::2].contiguous())
+
+    def add_public_affine(self, point, B=1):
+        """`add_public_affine` (ecc/mod.rs:88-93): `add_affine`, both coordinates bound to the public point (integers, or B each)"""
+        pt = self.add_affine(B)
+        self.assert_equal_public_point(pt, point)
+        return pt
+
+    def add_affine_to_circuit_description(self, point, B=1):
+        """`add_affine_to_circuit_description` (ecc/mod.rs:97-106): coordinates are integers (B calls of them) or B each"""
+        B = B if isinstance(point[0], (int, np.integer)) else len(point[0])
+        h = self.add_witness_to_circuit_description(self._pair_ints(point[0], point[1], B))
+        return self._own(h[0::2].contiguous()), self._own(h[1::2].contiguous())
+
+    def assert_equal_point(self, lhs, rhs):
+        """`assert_equal_point` (ecc/mod.rs:127-130)"""
+        B = self._batch([lhs[0], lhs[1], rhs[0], rhs[1]])
+        self.assert_equal(self._pair(lhs[0], lhs[1], B)[0], self._pair(rhs[0], rhs[1], B)[0])
+
+    def assert_equal_public_point(self, point, public_point):
+        """`assert_equal_public_point` (ecc/mod.rs:110-117): coordinates are integers or one per call"""
+        h, B = self._pair(point[0], point[1])
+        self.constrain_to_constant(h, 0, pi=self._pair_ints(public_point[0], public_point[1], B, -1))
+
     # ------------------------------------------------------------------------------------------------------------ results
     def _pi_limbs(self, overrides=None) -> dict:
         pi = dict(self.public_inputs)
@@ -290,14 +488,18 @@ class Composer:
 
     def description(self) -> CircuitDescription:
         import torch
-        n = padded_size(self.n_gates)
+        has_lookup = any(what == "segment" and rest[0]["kind"] == _lib.ZK_GADGET_LOOKUP for what, *rest in self._program)
+        if has_lookup and self.lookup_table.size() == 0:
+            raise ValueError("the circuit has lookup gates but `lookup_table` is empty")
+        table_cols = self.lookup_table.columns(self.curve, self.ctx, self.device) if self.lookup_table.size() else []
+        n = padded_size(self.n_gates, self.lookup_table.size())
         rec = torch.cat(self._ins_rec).to(torch.int64) & 0xFFFFFFFF     # the kernels write the records as unsigned words
         ins_pos = ((rec >> _REC_SHIFT) * n + (rec & ((1 << _REC_SHIFT) - 1))).to(torch.int32).contiguous()
         rows = sorted(self.public_inputs)
         limbs = fr_to_mont(self.curve, [self.public_inputs[r_] for r_ in rows])
         return CircuitDescription(self.n_gates, {name: torch.cat(self._sel[name]).contiguous() for name in SELECTORS},
                                   [torch.cat(w).contiguous() for w in self._ids], self.num_vars, torch.cat(self._ins_var).contiguous(), ins_pos,
-                                  [], {r_: limbs[i] for i, r_ in enumerate(rows)}, self.curve.name)
+                                  table_cols, {r_: limbs[i] for i, r_ in enumerate(rows)}, self.curve.name)
 
     def assign(self, inputs, blinding=None, public_inputs=None):
         """The (num_vars, 4) values `compile.assign` takes: the witness kernels replayed segment by segment in build order.

@@ -1,0 +1,161 @@
+// What the two units of the device composer (gadgets.hip, gadgets_ext.hip) share, each helper defined once: the shape table of every
+// gadget kind, the access to a segment's inputs and coefficients, the guarded value store, the shared block inversion and the flagged
+// launch (one working-memory allocation per call, one flag word read back once).  Not part of the C ABI.
+#pragma once
+#include "api_internal.h"
+#include "fr_io.cuh"
+
+namespace {
+
+constexpr uint32_t GT = 256;                       // lanes per workgroup, every kernel
+constexpr uint32_t FLAG_INPUT = 1, FLAG_SCALAR = 2, FLAG_DENOM = 4;
+constexpr uint32_t REC_SHIFT = 30;                 // insertion record: wire << 30 | row (rows are below 2^28)
+constexpr uint64_t MAX_ROWS = (uint64_t)1 << 28, MAX_VARS = (uint64_t)1 << 31;
+// selector columns in the order of prover.SELECTORS
+constexpr int Q_M = 0, Q_L = 1, Q_R = 2, Q_O = 3, Q_4 = 4, Q_C = 5, Q_ARITH = 6, Q_RANGE = 7, Q_LOGIC = 8, Q_FIXED = 9, Q_VAR = 10, Q_LOOKUP = 11;
+constexpr int N_SEL = 12;
+constexpr uint32_t LAST_KIND = ZK_GADGET_LOOKUP;
+
+struct Shape {
+    uint32_t rows, vars, ins;
+};
+ZK_HD Shape gadget_shape(uint32_t kind, uint32_t num_bits, uint32_t flags, uint32_t m_bits) {
+    Shape s = {0, 0, 0};
+    const uint32_t g = (num_bits + 7) / 8;
+    switch (kind) {
+    case ZK_GADGET_POLY: s = {1, (flags & ZK_GADGET_COMPUTE_OUT) ? 1u : 0u, 4}; break;
+    case ZK_GADGET_RANGE: s = {g + 2, num_bits / 2, 4 * g + 5}; break;
+    case ZK_GADGET_LOGIC: s = {num_bits / 2 + 1, 2 * num_bits, 2 * num_bits + 4}; break;
+    case ZK_GADGET_CURVE_ADD: s = {2, 3, 8}; break;
+    case ZK_GADGET_FIXED_BASE: s = {m_bits + 5, 4 * m_bits + 3, 4 * (m_bits + 5)}; break;
+    case ZK_GADGET_CONST_WITNESS: s = {1, 1, 4}; break;
+    case ZK_GADGET_IS_ZERO: s = {2, 2, 8}; break;
+    case ZK_GADGET_IS_EQ: s = {3, 3, 12}; break;
+    case ZK_GADGET_SELECT: s = {4, 4, 16}; break;
+    case ZK_GADGET_POINT_SELECT: s = {8, 8, 32}; break;
+    case ZK_GADGET_POINT_NEG: s = {5, 5, 20}; break;
+    case ZK_GADGET_VAR_BASE: s = {8 * m_bits + 2, 9 * m_bits + 257, 32 * m_bits + 8}; break;
+    case ZK_GADGET_LOOKUP: s = {1, 0, 4}; break;
+    default: break;
+    }
+    return s;
+}
+// the device bytes a witness of `calls` calls allocates beyond the 256 of the flag word: the projective accumulators between the two
+// phases of a scalar multiplication, (X, Y, Z) of 32 bytes each
+inline size_t gadget_work_bytes(uint32_t kind, uint32_t m_bits, uint64_t calls) {
+    if (kind == ZK_GADGET_FIXED_BASE) return (size_t)96 * (m_bits + 1) * calls;
+    if (kind == ZK_GADGET_VAR_BASE) return (size_t)96 * (2 * m_bits + 1) * calls;
+    return 0;
+}
+
+struct SelPtrs {
+    void* p[N_SEL];
+};
+
+// input w of call k: inputs[0 .. 4), then inputs_ext
+ZK_D uint32_t input_id(const zk_gadget_args& a, int w, uint64_t k) {
+    const uint32_t* p = (const uint32_t*)(w < 4 ? a.inputs[w] : a.inputs_ext[w - 4]);
+    return p ? p[k] : 0u;
+}
+template <class Fr>
+ZK_D Fr fr_words(const uint64_t* w) {
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        r.v[2 * i] = (uint32_t)w[i];
+        r.v[2 * i + 1] = (uint32_t)(w[i] >> 32);
+    }
+    return r;
+}
+template <class Fr>
+ZK_D Fr coeff_of(const zk_gadget_args& a, int j, uint64_t k) {
+    return a.coeff[j] ? ld_fr<Fr>(a.coeff[j], k) : fr_words<Fr>(a.coeff_const + 4 * j);
+}
+ZK_D uint32_t pick4(const uint32_t (&id)[4], uint32_t w) { return w == 0 ? id[0] : w == 1 ? id[1] : w == 2 ? id[2] : id[3]; }
+
+// ---------------------------------------------------------------------------------------------------------------- witness helpers
+template <class Fr>
+ZK_D Fr ld_input(const void* values, const zk_gadget_args& a, int w, uint64_t k, uint32_t* flag) {
+    const uint32_t* p = (const uint32_t*)(w < 4 ? a.inputs[w] : a.inputs_ext[w - 4]);
+    if (!p) return Fr::zero();
+    const uint32_t id = p[k];
+    if (id >= a.var0) {
+        atomicOr(flag, FLAG_INPUT);
+        return Fr::zero();
+    }
+    return ld_fr<Fr>(values, id);
+}
+template <class Fr>
+ZK_D void st_value(void* values, uint64_t num_vars, uint64_t id, const Fr& v) {
+    if (id < num_vars) st_fr<Fr>(values, id, v);
+}
+// 1 / z for every lane of the block with ONE field inversion: inclusive prefix and suffix products of z over the block in LDS
+// (Hillis-Steele), 1 / z_t = prefix_{t-1} * suffix_{t+1} / total -- the scan of ipa_fold_key.  z must be non-zero in every lane.
+template <class Fr>
+ZK_D Fr block_inverse(const Fr& z, Fr* pre, Fr* suf, Fr* inv_total) {
+    const uint32_t t = threadIdx.x;
+    Fr p = z, s = z;
+    pre[t] = p;
+    suf[t] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < GT; d <<= 1) {
+        const Fr pl = t >= d ? pre[t - d] : Fr::one();
+        const Fr sr = t + d < GT ? suf[t + d] : Fr::one();
+        __syncthreads();
+        if (t >= d) p = Fr::mul(p, pl);
+        if (t + d < GT) s = Fr::mul(s, sr);
+        pre[t] = p;
+        suf[t] = s;
+        __syncthreads();
+    }
+    if (t == 0) *inv_total = Fr::inverse(pre[GT - 1]);
+    __syncthreads();
+    Fr zi = *inv_total;
+    if (t > 0) zi = Fr::mul(zi, pre[t - 1]);
+    if (t + 1 < GT) zi = Fr::mul(zi, suf[t + 1]);
+    return zi;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+struct Work {
+    void* base = nullptr;
+    ~Work() {
+        if (base) (void)hipFree(base);                     // waits for the device: nothing queued still reads it
+    }
+};
+
+// the limits on rows and variables every kind shares
+inline int check_extent(const zk_gadget_args& a, const Shape& s) {
+    if (a.calls == 0 || s.rows == 0) return ZK_ERR_BAD_ARG;
+    if (a.calls > MAX_ROWS || a.row0 > MAX_ROWS || a.row0 + a.calls * s.rows > MAX_ROWS) return ZK_ERR_UNSUPPORTED;
+    if (a.var0 == 0 || a.var0 > MAX_VARS || a.var0 + a.calls * s.vars > MAX_VARS) return ZK_ERR_UNSUPPORTED;
+    return ZK_OK;
+}
+
+template <class Cv, class Body>
+int run_flagged(zk_ctx* c, size_t work_bytes, Body&& body) {
+    Work wk;
+    if (hipMalloc(&wk.base, 256 + work_bytes) != hipSuccess) {
+        wk.base = nullptr;
+        return ZK_ERR_OOM;
+    }
+    uint32_t* d_flag = (uint32_t*)wk.base;
+    hipStream_t st = c->stream;
+    int rc = [&]() -> int {
+        ZK_HIP_TRY(hipMemsetAsync(d_flag, 0, 256, st));
+        return body(d_flag, (void*)((char*)wk.base + 256));
+    }();
+    uint32_t flag = 0;
+    if (!rc) rc = zk_d2h(c, &flag, d_flag, 4, st);                // the one read-back; also the wait before the buffer is freed
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    return flag ? ZK_ERR_BAD_ARG : ZK_OK;
+}
+
+}  // namespace
+
+// ---- gadgets_ext.hip: the kinds after ZK_GADGET_FIXED_BASE; ctx lock held, args already copied, buffers checked for null
+int gadget_ext_layout(zk_ctx* c, int curve_id, const zk_gadget_args& a, uint32_t* d_ids, void* const* d_sel, uint32_t* d_ins_var, uint32_t* d_ins_rec);
+int gadget_ext_witness(zk_ctx* c, int curve_id, const zk_gadget_args& a, void* d_values, uint64_t num_vars);

@@ -24,60 +24,11 @@
 // its own addresses: a refused call leaves unspecified values, never an access outside the buffers.
 //
 // Working memory: one allocation per call, freed on every path; 256 bytes, + 96 (M + 1) B for a fixed-base witness.  No buffer of the
-// ctx is used, so both calls run inside an open deferred round.
-#include "api_internal.h"
-#include "fr_io.cuh"
+// ctx is used, so both calls run inside an open deferred round.  The kinds after ZK_GADGET_FIXED_BASE are dispatched to gadgets_ext.hip;
+// what the two units share is defined once in gadget_common.cuh.
+#include "gadget_common.cuh"
 
 namespace {
-
-constexpr uint32_t GT = 256;                       // lanes per workgroup, every kernel
-constexpr uint32_t FLAG_INPUT = 1, FLAG_SCALAR = 2, FLAG_DENOM = 4;
-constexpr uint32_t REC_SHIFT = 30;                 // insertion record: wire << 30 | row (rows are below 2^28)
-constexpr uint64_t MAX_ROWS = (uint64_t)1 << 28, MAX_VARS = (uint64_t)1 << 31;
-// selector columns in the order of prover.SELECTORS
-constexpr int Q_M = 0, Q_L = 1, Q_R = 2, Q_O = 3, Q_4 = 4, Q_C = 5, Q_ARITH = 6, Q_RANGE = 7, Q_LOGIC = 8, Q_FIXED = 9, Q_VAR = 10;
-constexpr int N_SEL = 12;
-
-struct Shape {
-    uint32_t rows, vars, ins;
-};
-ZK_HD Shape gadget_shape(uint32_t kind, uint32_t num_bits, uint32_t flags, uint32_t m_bits) {
-    Shape s = {0, 0, 0};
-    const uint32_t g = (num_bits + 7) / 8;
-    switch (kind) {
-    case ZK_GADGET_POLY: s = {1, (flags & ZK_GADGET_COMPUTE_OUT) ? 1u : 0u, 4}; break;
-    case ZK_GADGET_RANGE: s = {g + 2, num_bits / 2, 4 * g + 5}; break;
-    case ZK_GADGET_LOGIC: s = {num_bits / 2 + 1, 2 * num_bits, 2 * num_bits + 4}; break;
-    case ZK_GADGET_CURVE_ADD: s = {2, 3, 8}; break;
-    case ZK_GADGET_FIXED_BASE: s = {m_bits + 5, 4 * m_bits + 3, 4 * (m_bits + 5)}; break;
-    default: break;
-    }
-    return s;
-}
-
-struct SelPtrs {
-    void* p[N_SEL];
-};
-
-ZK_D uint32_t input_id(const zk_gadget_args& a, int w, uint64_t k) {
-    const uint32_t* p = (const uint32_t*)a.inputs[w];
-    return p ? p[k] : 0u;
-}
-template <class Fr>
-ZK_D Fr fr_words(const uint64_t* w) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        r.v[2 * i] = (uint32_t)w[i];
-        r.v[2 * i + 1] = (uint32_t)(w[i] >> 32);
-    }
-    return r;
-}
-template <class Fr>
-ZK_D Fr coeff_of(const zk_gadget_args& a, int j, uint64_t k) {
-    return a.coeff[j] ? ld_fr<Fr>(a.coeff[j], k) : fr_words<Fr>(a.coeff_const + 4 * j);
-}
-ZK_D uint32_t pick4(const uint32_t (&id)[4], uint32_t w) { return w == 0 ? id[0] : w == 1 ? id[1] : w == 2 ? id[2] : id[3]; }
 
 // the four variable ids (Left, Right, Output, Fourth) of row r of call k
 ZK_D void row_ids(const zk_gadget_args& a, const Shape& s, uint32_t m_bits, uint64_t k, uint32_t r, uint32_t (&id)[4]) {
@@ -265,21 +216,6 @@ __global__ void __launch_bounds__(GT) gadget_insertions(zk_gadget_args a, Shape 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- witness helpers
-template <class Fr>
-ZK_D Fr ld_input(const void* values, const zk_gadget_args& a, int w, uint64_t k, uint32_t* flag) {
-    const uint32_t* p = (const uint32_t*)a.inputs[w];
-    if (!p) return Fr::zero();
-    const uint32_t id = p[k];
-    if (id >= a.var0) {
-        atomicOr(flag, FLAG_INPUT);
-        return Fr::zero();
-    }
-    return ld_fr<Fr>(values, id);
-}
-template <class Fr>
-ZK_D void st_value(void* values, uint64_t num_vars, uint64_t id, const Fr& v) {
-    if (id < num_vars) st_fr<Fr>(values, id, v);
-}
 // w >>= s, s < 32 NW: word steps of 1, 2, 4, 8 under selects, then the bit step
 template <int NW>
 ZK_D void shr_words(uint32_t (&w)[NW], uint32_t s) {
@@ -314,33 +250,6 @@ ZK_D Fr prefix_of(const Fr& v, uint32_t bits, uint32_t s) {
     for (int i = 0; i < 8; ++i) r.v[i] = w[i];
     return r;
 }
-// 1 / z for every lane of the block with ONE field inversion: inclusive prefix and suffix products of z over the block in LDS
-// (Hillis-Steele), 1 / z_t = prefix_{t-1} * suffix_{t+1} / total -- the scan of ipa_fold_key.  z must be non-zero in every lane.
-template <class Fr>
-ZK_D Fr block_inverse(const Fr& z, Fr* pre, Fr* suf, Fr* inv_total) {
-    const uint32_t t = threadIdx.x;
-    Fr p = z, s = z;
-    pre[t] = p;
-    suf[t] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < GT; d <<= 1) {
-        const Fr pl = t >= d ? pre[t - d] : Fr::one();
-        const Fr sr = t + d < GT ? suf[t + d] : Fr::one();
-        __syncthreads();
-        if (t >= d) p = Fr::mul(p, pl);
-        if (t + d < GT) s = Fr::mul(s, sr);
-        pre[t] = p;
-        suf[t] = s;
-        __syncthreads();
-    }
-    if (t == 0) *inv_total = Fr::inverse(pre[GT - 1]);
-    __syncthreads();
-    Fr zi = *inv_total;
-    if (t > 0) zi = Fr::mul(zi, pre[t - 1]);
-    if (t + 1 < GT) zi = Fr::mul(zi, suf[t + 1]);
-    return zi;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- witness kernels
 template <class Cv>
 __global__ void __launch_bounds__(GT) gadget_w_poly(zk_gadget_args a, void* values, uint64_t num_vars, uint32_t* flag) {
@@ -562,13 +471,6 @@ __global__ void __launch_bounds__(GT) gadget_w_fixed_norm(zk_gadget_args a, void
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-struct Work {
-    void* base = nullptr;
-    ~Work() {
-        if (base) (void)hipFree(base);                     // waits for the device: nothing queued still reads it
-    }
-};
-
 // what both entry points refuse before anything is launched
 int check_args(const zk_gadget_args& a, const Shape& s) {
     if (a.kind > ZK_GADGET_FIXED_BASE || a.calls == 0 || s.rows == 0) return ZK_ERR_BAD_ARG;
@@ -578,31 +480,7 @@ int check_args(const zk_gadget_args& a, const Shape& s) {
         if (!a.inputs[w]) return ZK_ERR_BAD_ARG;
     if (a.kind == ZK_GADGET_POLY && !(a.flags & ZK_GADGET_COMPUTE_OUT) && !a.inputs[2]) return ZK_ERR_BAD_ARG;
     if (a.kind == ZK_GADGET_FIXED_BASE && !a.table) return ZK_ERR_BAD_ARG;
-    if (a.calls > MAX_ROWS || a.row0 > MAX_ROWS || a.row0 + a.calls * s.rows > MAX_ROWS) return ZK_ERR_UNSUPPORTED;
-    if (a.var0 == 0 || a.var0 > MAX_VARS || a.var0 + a.calls * s.vars > MAX_VARS) return ZK_ERR_UNSUPPORTED;
-    return ZK_OK;
-}
-
-template <class Cv, class Body>
-int run_flagged(zk_ctx* c, size_t work_bytes, Body&& body) {
-    Work wk;
-    if (hipMalloc(&wk.base, 256 + work_bytes) != hipSuccess) {
-        wk.base = nullptr;
-        return ZK_ERR_OOM;
-    }
-    uint32_t* d_flag = (uint32_t*)wk.base;
-    hipStream_t st = c->stream;
-    int rc = [&]() -> int {
-        ZK_HIP_TRY(hipMemsetAsync(d_flag, 0, 256, st));
-        return body(d_flag, (void*)((char*)wk.base + 256));
-    }();
-    uint32_t flag = 0;
-    if (!rc) rc = zk_d2h(c, &flag, d_flag, 4, st);                // the one read-back; also the wait before the buffer is freed
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    return flag ? ZK_ERR_BAD_ARG : ZK_OK;
+    return check_extent(a, s);
 }
 
 template <class Cv>
@@ -629,7 +507,7 @@ int witness_impl(zk_ctx* c, const zk_gadget_args& a, void* d_values, uint64_t nu
     if (rc) return rc;
     if (a.var0 + a.calls * s.vars > num_vars) return ZK_ERR_BAD_ARG;
     if (s.vars == 0) return ZK_OK;
-    const size_t work_bytes = a.kind == ZK_GADGET_FIXED_BASE ? (size_t)96 * (M + 1) * a.calls : 0;
+    const size_t work_bytes = gadget_work_bytes(a.kind, M, a.calls);
     return run_flagged<Cv>(c, work_bytes, [&](uint32_t* d_flag, void* work) -> int {
         hipStream_t st = c->stream;
         switch (a.kind) {
@@ -674,14 +552,15 @@ int witness_impl(zk_ctx* c, const zk_gadget_args& a, void* d_values, uint64_t nu
 // ------------------------------------------------------------------------------------------------------------------------ C ABI
 int zk_gadget_shape(int kind, int curve_id, uint32_t num_bits, uint32_t flags, size_t calls, uint32_t* rows, uint32_t* vars, uint32_t* insertions,
                     size_t* work_bytes) {
-    if (kind < 0 || kind > ZK_GADGET_FIXED_BASE || !zk_curve_ok(curve_id)) return ZK_ERR_BAD_ARG;
+    if (kind < 0 || kind > (int)LAST_KIND || !zk_curve_ok(curve_id)) return ZK_ERR_BAD_ARG;
     if ((kind == ZK_GADGET_RANGE || kind == ZK_GADGET_LOGIC) && (num_bits < 2 || num_bits > 256 || (num_bits & 1u))) return ZK_ERR_BAD_ARG;
     const uint32_t m_bits = zk_on_curve(curve_id, 0u, [&](auto cv) { return (uint32_t) decltype(cv)::FrP::BITS; });
     const Shape s = gadget_shape((uint32_t)kind, num_bits, flags, m_bits);
+    if (s.rows == 0) return ZK_ERR_BAD_ARG;                       // a number between the kinds that names none
     if (rows) *rows = s.rows;
     if (vars) *vars = s.vars;
     if (insertions) *insertions = s.ins;
-    if (work_bytes) *work_bytes = 256 + (kind == ZK_GADGET_FIXED_BASE ? (size_t)96 * (m_bits + 1) * calls : 0);
+    if (work_bytes) *work_bytes = 256 + gadget_work_bytes((uint32_t)kind, m_bits, calls);
     return ZK_OK;
 }
 
@@ -692,6 +571,7 @@ int zk_gadget_layout_dev(zk_ctx* c, int curve_id, const void* args, void* d_wire
     zk_gadget_args a;
     memcpy(&a, args, sizeof a);
     Guard g(c);
+    if (a.kind > ZK_GADGET_FIXED_BASE) return gadget_ext_layout(c, curve_id, a, (uint32_t*)d_wire_ids, d_selectors, (uint32_t*)d_ins_var, (uint32_t*)d_ins_rec);
     return zk_on_curve(curve_id, ZK_ERR_BAD_ARG, [&](auto cv) {
         return layout_impl<decltype(cv)>(c, a, (uint32_t*)d_wire_ids, d_selectors, (uint32_t*)d_ins_var, (uint32_t*)d_ins_rec);
     });
@@ -702,5 +582,6 @@ int zk_gadget_witness_dev(zk_ctx* c, int curve_id, const void* args, void* d_val
     zk_gadget_args a;
     memcpy(&a, args, sizeof a);
     Guard g(c);
+    if (a.kind > ZK_GADGET_FIXED_BASE) return gadget_ext_witness(c, curve_id, a, d_values, (uint64_t)num_vars);
     return zk_on_curve(curve_id, ZK_ERR_BAD_ARG, [&](auto cv) { return witness_impl<decltype(cv)>(c, a, d_values, (uint64_t)num_vars); });
 }

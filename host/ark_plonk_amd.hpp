@@ -416,6 +416,16 @@ inline void gadget_layout(Context& ctx, int curve, const zk_gadget_args& args, v
 inline void gadget_witness(Context& ctx, int curve, const zk_gadget_args& args, DeviceVec& values) {
     check(zk_gadget_witness_dev(ctx.handle(), curve, &args, values.data(), values.size()), "zk_gadget_witness_dev");
 }
+// one insert_multi_* block of a lookup table (lookup/lookup_table.rs:94-152): op 0 add, 1 mul, 2 xor, 3 and; rows (a, b, op(a, b) mod 2^n_bits,
+// tag) for lower_bound <= a, b < 2^n_bits into the four columns from row `at` on (each column holds at least at + (2^n_bits - lower_bound)^2)
+inline void lookup_table_block(Context& ctx, int curve, int op, uint32_t lower_bound, uint32_t n_bits, DeviceVec& a, DeviceVec& b, DeviceVec& c,
+                               DeviceVec& d, size_t at = 0) {
+    const size_t w = n_bits <= 12 && lower_bound < (1u << n_bits) ? (size_t(1) << n_bits) - lower_bound : 0;
+    for (const DeviceVec* v : {&a, &b, &c, &d})
+        if (w == 0 || v->size() < at + w * w) throw Error(ZK_ERR_BAD_ARG, "lookup table block");
+    auto off = [&](DeviceVec& v) { return static_cast<void*>(static_cast<char*>(v.data()) + 32 * at); };
+    check(zk_lookup_table_dev(ctx.handle(), curve, op, lower_bound, n_bits, off(a), off(b), off(c), off(d)), "zk_lookup_table_dev");
+}
 // compute_lookup_permutation_poly up to its ifft (permutation/mod.rs:754-797)
 inline DeviceVec lookup_permutation_evals(Context& ctx, int curve, const DeviceVec& f, const DeviceVec& t, const DeviceVec& h1,
                                           const DeviceVec& h2, const uint64_t* delta_mont, const uint64_t* epsilon_mont) {

@@ -631,7 +631,7 @@ typedef struct zk_circuit_check_summary {
  * Blocks once. */
 int zk_circuit_check_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* args, void* d_mask, void* out);
 
-/* ---- gadget circuits and their witnesses (constraint_system/{arithmetic,boolean,range,logic}.rs, ecc/) -------------------------- */
+/* ---- gadget circuits and their witnesses (constraint_system/{arithmetic,boolean,range,logic,composer,lookup}.rs, ecc/) ----------- */
 /* A SEGMENT is `calls` calls of one gadget with the same parameters: by definition what `StandardComposer` holds after the gadget is
  * called that many times in a row, call k with the k-th input variables -- rows, new variables in `add_input` order and
  * `add_variable_to_map` calls in call order, the cells the reference pushes without mapping (range.rs:185-187) and the logic gate's
@@ -644,6 +644,15 @@ int zk_circuit_check_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* 
  *   ZK_GADGET_LOGIC       xor_gate / and_gate(num_bits)                     bits / 2 + 1       2 bits       2 bits + 4
  *   ZK_GADGET_CURVE_ADD   point_addition_gate                               2                  3            8
  *   ZK_GADGET_FIXED_BASE  fixed_base_scalar_mul                             M + 5              4 M + 3      4 (M + 5)
+ *   ZK_GADGET_CONST_WITNESS add_witness_to_circuit_description(value)       1                  1            4
+ *   ZK_GADGET_IS_ZERO     is_zero_with_output(a)                            2                  2            8
+ *   ZK_GADGET_IS_EQ       is_eq_with_output(a, b)                           3                  3            12
+ *   ZK_GADGET_SELECT      conditional_select(bit, a, b)                     4                  4            16
+ *   ZK_GADGET_POINT_SELECT conditional_point_select(p1, p0, bit)            8                  8            32
+ *   ZK_GADGET_POINT_NEG   conditional_point_neg(bit, p)                     5                  5            20
+ *   ZK_GADGET_VAR_BASE    variable_base_scalar_mul(scalar, point)           8 M + 2            9 M + 257    32 M + 8
+ *   ZK_GADGET_LOOKUP      lookup_gate(a, b, c, d)                           1                  0            4
+ * The kinds from CONST_WITNESS on map every cell of every row, row by row (Left, Right, Output, Fourth).
  * Values (zk_gadget_witness_dev; canonical Montgomery Fr, what zk_fr_gather_dev and the circuit check take):
  *   POLY with ZK_GADGET_COMPUTE_OUT: (q_m a b + q_l a + q_r b + q_c + q_4 d + pi) (-q_o), as arithmetic.rs:144-155 writes it -- a
  *       product with -q_o, NOT a division by it;
@@ -653,7 +662,19 @@ int zk_circuit_check_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* 
  *   CURVE_ADD: x1 y2, then x3 = (x1 y2 + y1 x2) / (1 + d x1 x2 y1 y2), y3 = (y1 y2 - a x1 x2) / (1 - d x1 x2 y1 y2);
  *   FIXED_BASE: the digit of weight 2^j of the width-2 NAF of the scalar e is bit j+1 of 3e minus bit j+1 of e (find_wnaf(2)); row i
  *       uses the digit of weight 2^(M-1-i) and holds the point and scalar accumulators before it and xy_alpha = x y of the addend
- *       +-2^(M-1-i) G, or 0.
+ *       +-2^(M-1-i) G, or 0;
+ *   CONST_WITNESS: the new variable v holds the value, its row is (v, v, v, 0) with q_l = 1, q_c = -value (coeff[5] / coeff_const[20..24)
+ *       is q_c, the value is its negative);
+ *   IS_ZERO: new variables y = 1 / a (1 when a = 0) and b = 1 - a y; rows (a, b, 0, 0) q_m = 1 and (a, y, 0, b) q_m = q_4 = 1, q_c = -1, both
+ *       with q_o = -1.  IS_EQ: the difference a - b on a row of its own (q_l = 1, q_r = -1), then IS_ZERO of it;
+ *   SELECT: bit a; 1 - bit; (1 - bit) b; their sum -- four arithmetic rows, each value the product with -q_o of arithmetic.rs:144-155.
+ *       POINT_SELECT: SELECT(bit, p1.x, p0.x) then SELECT(bit, p1.y, p0.y).  POINT_NEG: -x, then SELECT(bit, -x, x);
+ *   VAR_BASE: variables 0 .. 255 the bits of the canonical scalar e (`to_bits_le` of four 64-bit words; bits M .. 255 appear on no row),
+ *       256 + j (j < M) the accumulator e mod 2^(j+1), 256 + M the constant one of `Point::identity`, then for iteration i (bit M-1-i,
+ *       from the identity (0, 1)) eight values: x1 y2, x3, y3 of the doubling; bit x; 1 - bit + bit y; x1 y2, x3, y3 of the addition, by
+ *       the affine law above.  Rows: M x (boolean row, accumulator row with q_l = 2^j, q_r = 1), the assert_equal with the scalar, the
+ *       row of the one, M x (2 rows of the doubling, select_zero, select_one, 2 rows of the addition).
+ *   LOOKUP: no new variable; the row (a, b, c, d) has q_lookup = 1 alone.
  * ZK_ERR_BAD_ARG, by one flag word read back once per call: an input id that is not smaller than var0 (an undefined variable); a
  * scalar whose NAF has more than M digits (3e >= 2^(M+1); the reference asserts); a zero denominator of the group law.  The outputs
  * of a refused call are unspecified; nothing is read or written outside the buffers. */
@@ -662,6 +683,14 @@ int zk_circuit_check_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* 
 #define ZK_GADGET_LOGIC 2
 #define ZK_GADGET_CURVE_ADD 3
 #define ZK_GADGET_FIXED_BASE 4
+#define ZK_GADGET_CONST_WITNESS 5
+#define ZK_GADGET_IS_ZERO 6
+#define ZK_GADGET_IS_EQ 7
+#define ZK_GADGET_SELECT 8
+#define ZK_GADGET_POINT_SELECT 10                    /* 9 is no kind: it stays refused, as every unknown number is */
+#define ZK_GADGET_POINT_NEG 11
+#define ZK_GADGET_VAR_BASE 12
+#define ZK_GADGET_LOOKUP 13
 #define ZK_GADGET_COMPUTE_OUT 1                      /* flags, POLY: the output wire is a new variable whose value is computed */
 #define ZK_GADGET_XOR 2                              /* flags, LOGIC: q_c = q_logic = -1 (XOR); without it +1 (AND) */
 typedef struct zk_gadget_args {
@@ -677,6 +706,10 @@ typedef struct zk_gadget_args {
                                                       * the witness of a computed output only */
     uint64_t coeff_a[4], coeff_d[4];                 /* P::COEFF_A, P::COEFF_D of the embedded twisted Edwards curve (Montgomery) */
     const void* table;                               /* FIXED_BASE: 3 M Montgomery Fr on the device, row i: x, y, x y of 2^(M-1-i) G */
+    const void* inputs_ext[4];                       /* inputs 4 .. 7, as `inputs`: the kinds from CONST_WITNESS on take, in order --
+                                                      * IS_ZERO: a; IS_EQ: a, b; SELECT: bit, a, b; POINT_SELECT: bit, p1.x, p0.x, p1.y,
+                                                      * p0.y (the fifth is inputs_ext[0]); POINT_NEG: bit, x; VAR_BASE: scalar, x, y of
+                                                      * the point; LOOKUP: a, b, c, d (NULL: the zero variable) */
 } zk_gadget_args;
 /* Host only: the shape of one call and the device bytes a witness of `calls` calls allocates (layout: 256). */
 int zk_gadget_shape(int kind, int curve_id, uint32_t num_bits, uint32_t flags, size_t calls, uint32_t* rows, uint32_t* vars, uint32_t* insertions,
@@ -692,9 +725,16 @@ int zk_gadget_layout_dev(zk_ctx* ctx, int curve_id, const void* args, void* d_wi
                          void* d_ins_rec);
 /* The values of the segment's new variables into d_values[var0 .. var0 + calls * V) (num_vars rows of Montgomery Fr); the inputs'
  * values are read from the same vector, so segments are replayed in build order.  Working memory: one device allocation, freed on
- * every path -- 256 bytes, + 96 (M + 1) calls for FIXED_BASE (the projective accumulators between its two phases).  No buffer of
- * the ctx is used: the call runs inside an open deferred round.  Blocks once. */
+ * every path -- 256 bytes, + 96 (M + 1) calls for FIXED_BASE and + 96 (2 M + 1) calls for VAR_BASE (the projective accumulators
+ * between the two phases of a scalar multiplication: a walk of one lane per call, then a normalisation with one inversion per 256
+ * lanes).  No buffer of the ctx is used: the call runs inside an open deferred round.  Blocks once. */
 int zk_gadget_witness_dev(zk_ctx* ctx, int curve_id, const void* args, void* d_values, size_t num_vars);
+/* One block of a lookup table (lookup/lookup_table.rs:94-152 insert_multi_add / _mul / _xor / _and(lower_bound, n_bits)) on the device:
+ * with w = 2^n_bits - lower_bound, row r < w^2 holds a = lower_bound + r / w, b = lower_bound + r % w, c = op(a, b) mod 2^n_bits and the
+ * tag of the operation -- op 0: add, tag 0; 1: mul, tag 1; 2: xor, tag -1; 3: and, tag 2 -- as Montgomery Fr into the four columns
+ * d_a, d_b, d_c, d_d (w^2 elements each; a caller concatenates blocks by offsetting the pointers).  ZK_ERR_BAD_ARG: a null ctx or
+ * column, an unknown op, n_bits > 12, lower_bound >= 2^n_bits.  Queued on the ctx stream; uses no buffer of the ctx. */
+int zk_lookup_table_dev(zk_ctx* ctx, int curve_id, int op, uint32_t lower_bound, uint32_t n_bits, void* d_a, void* d_b, void* d_c, void* d_d);
 
 /* ---- device self-test ------------------------------------------------------------------------------ */
 /* Runs the quad-cooperative point arithmetic of the bucket-reduction kernels (csrc/ecq.cuh) against the

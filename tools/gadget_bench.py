@@ -6,11 +6,16 @@
     the rest curve additions and arithmetic): building it (every layout call + `description()`), one witness replay (`Composer.assign`), and --
     in the same process, on the same circuit -- `compile`, one `check_circuit` and one `prove`.
 
+  * --ext: the kinds of the second unit (csrc/gadgets_ext.hip) -- `variable_base_scalar_mul` at B = 1, 64, 4096 and `is_zero_with_output`
+    at B = 2^20: layout, witness, the phases of the variable-base witness, and, where the circuit pads to at most 2^--ext-prove-log-n
+    rows, `compile` and one `prove` of the same circuit.
+
 One JSON line per measurement; --out writes them to a file.  Every timed call ends in a device synchronise; the median of --reps calls
 after --warmup calls is reported.  Kernel times for the record come from a separate `rocprofv3 --kernel-trace --stats` run of this
 script (add --no-prove --reps 3 there to keep the trace short).
 
     python tools/gadget_bench.py [--log-n 18 20 22] [--curve 0] [--reps 5] [--warmup 1] [--no-kinds] [--no-prove] [--out FILE]
+                                 [--ext] [--ext-calls 1 64 4096] [--ext-prove-log-n 21]
 """
 from __future__ import annotations
 
@@ -98,6 +103,56 @@ def kinds(zk, ctx, cid, coeffs, G, a, emit):
         emit(line)
 
 
+def ext_kinds(zk, ctx, cid, coeffs, G, a, emit):
+    """the second unit: one segment per case on a fresh composer -- layout, witness, and compile + prove of that circuit"""
+    from ark_plonk_amd import compile as zc
+    from ark_plonk_amd import prover
+    from ark_plonk_amd.curves import fr_to_mont
+    ca_m, cd_m = fr_to_mont(cid, [coeffs[0]])[0], fr_to_mont(cid, [coeffs[1]])[0]
+    gx, gy = (fr_to_mont(cid, [v])[0].view(np.int64) for v in G)
+    cases = [("variable_base", B) for B in a.ext_calls] + [("is_zero", 1 << 20)]
+    for name, B in cases:
+        def build():
+            c = zk.Composer(cid, ctx, coeffs=coeffs)
+            x = c.inputs(B)
+            if name == "variable_base":
+                c.variable_base_scalar_mul(x, (c.inputs(B), c.inputs(B)))
+            else:
+                c.is_zero_with_output(x)
+            return c
+        import torch
+        layout_ms = median_ms(build, a.reps, a.warmup)
+        c = build()
+        ins = [below(ctx, cid, B, 250, 5)]
+        if name == "variable_base":
+            ins += [torch.from_numpy(col).cuda().reshape(1, 4).repeat(B, 1) for col in (gx, gy)]
+        ctx.profile(True)
+        ctx.profile_reset()
+        witness_ms = median_ms(lambda: c.assign(ins), a.reps, a.warmup)
+        line = {"what": "ext_kind", "kind": name, "calls": B, "rows": c.n_gates, "vars": c.num_vars, "layout_ms": layout_ms, "witness_ms": witness_ms}
+        for ph in ("gadget_w_var_bits", "gadget_w_var_walk", "gadget_w_var_norm", "gadget_w_is_zero"):
+            ms, cnt = ctx.profile_get(ph)
+            if cnt:
+                line[ph + "_ms"] = ms / cnt
+        ctx.profile(False)
+        desc = c.description()
+        n = desc.size()
+        if not a.no_prove and 32 <= n <= 1 << a.ext_prove_log_n:
+            ck = make_key(ctx, cid, n, 77)
+            t, (pk, vk, pre) = timed(lambda: zc.compile(desc, ck, b"bench", cid, ctx))
+            line["log_n"], line["compile_ms"] = n.bit_length() - 1, t * 1e3
+            wires = zc.assign(desc, c.assign(ins), ctx)
+            rep = zk.check_circuit(pk, wires, {}, ca_m, cd_m, ctx=ctx)
+            assert rep.ok, str(rep)
+            line["prove_ms"] = median_ms(lambda: prover.prove(pk, ck, wires, {}, pre, ca_m, cd_m), 3, 1)
+            line["witness_share_of_prove"] = witness_ms / line["prove_ms"]
+            ck.close()
+            del pk, vk, wires
+        emit(line)
+        del c, desc, ins
+        torch.cuda.empty_cache()
+
+
 def fill(zk, ctx, cid, coeffs, G, lg):
     """a composer whose circuit pads to 2^lg rows, and its input tensors"""
     n = 1 << lg
@@ -126,6 +181,9 @@ def main():
     ap.add_argument("--no-kinds", action="store_true")
     ap.add_argument("--no-prove", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--ext", action="store_true", help="the kinds of csrc/gadgets_ext.hip")
+    ap.add_argument("--ext-calls", type=int, nargs="*", default=[1, 64, 4096])
+    ap.add_argument("--ext-prove-log-n", type=int, default=21)
     a = ap.parse_args()
     import torch
     import ark_plonk_amd as zk
@@ -146,6 +204,8 @@ def main():
         lines.append(line)
     if not a.no_kinds:
         kinds(zk, ctx, cid, (ca, cd), G, a, emit)
+    if a.ext:
+        ext_kinds(zk, ctx, cid, (ca, cd), G, a, emit)
     ca_m, cd_m = fr_to_mont(cid, [ca])[0], fr_to_mont(cid, [cd])[0]
     for lg in a.log_n:
         build_ms = median_ms(lambda: fill(zk, ctx, cid, (ca, cd), G, lg)[0].description(), a.reps, a.warmup)
