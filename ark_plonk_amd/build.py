@@ -26,7 +26,7 @@ HOST_HDRS = FIELD_HDRS + ["ec.cuh", "ecu.cuh", "ctx.h", "../../include/ark_plonk
 API_HDRS = HOST_HDRS + ["api_internal.h"]
 # helpers with one definition each: Fr / 32-byte element access; the quotient's bounded lazy arithmetic; the MSM's point storage
 FR_IO, ZBOUND, POINT_IO = ["fr_io.cuh"], ["fr_io.cuh", "zbound.cuh"], ["point_io.cuh"]
-GADGET = ["gadget_common.cuh"]            # what the two units of the device composer share
+GADGET = ["gadget_common.cuh"]            # what the two units of the device composer (layout, witness) share
 # the C ABI, one unit per subsystem (api_internal.h is what they share)
 API_UNITS = ("api_ctx", "residency", "srs", "commit", "round", "api_host", "api_poly")
 MSM_UNITS = ("msm_accumulate", "msm_reduce", "msm_sort", "msm_plan")      # heaviest first
@@ -50,10 +50,10 @@ def jobs():
         ("ipa.o", "ipa.hip", [], API_HDRS + FR_IO + POINT_IO),
         ("compile.o", "compile.hip", [], API_HDRS + FR_IO),
         ("check.o", "check.hip", [], API_HDRS + ZBOUND),
-        # the device composer: gadget segments (rows, ids, selectors, insertions) and the values of the variables they create
-        ("gadgets.o", "gadgets.hip", [], API_HDRS + FR_IO + GADGET),
-        # ... its second unit: is_zero / is_eq, the conditional selects, variable-base scalar multiplication, lookup gates and tables
-        ("gadgets_ext.o", "gadgets_ext.hip", [], API_HDRS + FR_IO + GADGET),
+        # the device composer: gadget segments (rows, ids, selectors, insertions) and lookup tables, built once per circuit ...
+        ("gadget_layout.o", "gadget_layout.hip", [], API_HDRS + FR_IO + GADGET),
+        # ... and the values of the variables the segments create, replayed once per proof
+        ("gadget_witness.o", "gadget_witness.hip", [], API_HDRS + FR_IO + GADGET),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

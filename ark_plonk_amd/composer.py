@@ -1,6 +1,6 @@
 """`StandardComposer` (plonk-core/src/constraint_system/) for batched gadget calls, on the device: `Composer` produces what
-`compile.compile` consumes -- the `CircuitDescription`, built once per circuit -- and what `compile.assign` consumes -- the
-(num_vars, 4) value vector, replayed per proof (csrc/gadgets.hip: zk_gadget_layout_dev, zk_gadget_witness_dev).
+`compile.compile` consumes -- the `CircuitDescription`, built once per circuit (csrc/gadget_layout.hip: zk_gadget_layout_dev) -- and
+what `compile.assign` consumes -- the (num_vars, 4) value vector, replayed per proof (csrc/gadget_witness.hip: zk_gadget_witness_dev).
 
 A SEGMENT is B calls of one gadget with the same parameters; by definition it is what the reference's composer holds after that gadget
 is called B times in a row, call k with the k-th input variables: rows, new variables in `add_input` order and `add_variable_to_map`
@@ -24,7 +24,7 @@ range_gate(bits)        ceil(bits/8) + 2     bits / 2          4 ceil(bits/8) + 
 xor_gate / and_gate     bits / 2 + 1         2 bits            2 bits + 4
 point_addition_gate     2                    3                 8
 fixed_base_scalar_mul   M + 5                4 M + 3           4 (M + 5)         M = bits of the scalar field (255 / 254)
-add_witness_to_circuit_description  1        1                 4                 (csrc/gadgets_ext.hip from here on)
+add_witness_to_circuit_description  1        1                 4
 is_zero_with_output     2                    2                 8
 is_eq_with_output       3                    3                 12
 conditional_select      4                    4                 16
@@ -283,6 +283,11 @@ class Composer:
         self._program.append(("segment", seg))
         return seg
 
+    def _gadget(self, kind, handles, B=None, **kw):
+        """the segment of one gadget over its input handles (None: an input the call does not have), batched to a common B"""
+        B = self._batch([h for h in handles if h is not None], B)
+        return self._segment(kind, B, [None if h is None else self._handle(h, B) for h in handles], **kw)
+
     def _new_vars(self, seg, offset: int):
         """the handle of new variable `offset` of every call of the segment"""
         import torch
@@ -295,11 +300,9 @@ class Composer:
         integer or B integers (host values given at build time, replaceable per row at assign time).  With c=None the output is a new
         variable whose value is (q_m a b + q_l a + q_r b + q_c + q_4 d + pi) (-q_o), exactly as arithmetic.rs:144-155 writes it: it
         MULTIPLIES by -q_o, it does not divide -- the row is satisfied for q_o = -1 (the default) and q_o = 1 only.  Returns c."""
-        B = self._batch([h for h in (a, b, c, d) if h is not None], B)
-        hs = [self._handle(a, B), self._handle(b, B), None if c is None else self._handle(c, B), self._handle(0 if d is None else d, B)]
-        seg = self._segment(_lib.ZK_GADGET_POLY, B, hs, flags=_lib.ZK_GADGET_COMPUTE_OUT if c is None else 0,
-                            coeff=(q_m, q_l, q_r, q_o, q_4, q_c), pi=pi)
-        return self._new_vars(seg, 0) if c is None else self._own(hs[2])
+        seg = self._gadget(_lib.ZK_GADGET_POLY, [a, b, c, 0 if d is None else d], B, flags=_lib.ZK_GADGET_COMPUTE_OUT if c is None else 0,
+                           coeff=(q_m, q_l, q_r, q_o, q_4, q_c), pi=pi)
+        return self._new_vars(seg, 0) if c is None else self._own(seg["inputs"][2])
 
     def poly_gate(self, a, b, c, q_m=0, q_l=0, q_r=0, q_o=0, q_c=0, pi=None, B=None):
         """`poly_gate` (composer.rs:269-312)"""
@@ -330,14 +333,11 @@ class Composer:
 
     def range_gate(self, x, num_bits: int):
         """`range_gate` (range.rs:27-195); the closing assert_equal row is satisfied iff the value is below 2^num_bits"""
-        num_bits = self._check_bits(num_bits)
-        B = self._batch([x])
-        self._segment(_lib.ZK_GADGET_RANGE, B, [self._handle(x, B)], num_bits=num_bits)
+        self._gadget(_lib.ZK_GADGET_RANGE, [x], num_bits=self._check_bits(num_bits))
 
     def _logic(self, a, b, num_bits, flags):
         num_bits = self._check_bits(num_bits)
-        B = self._batch([a, b])
-        seg = self._segment(_lib.ZK_GADGET_LOGIC, B, [self._handle(a, B), self._handle(b, B)], num_bits=num_bits, flags=flags)
+        seg = self._gadget(_lib.ZK_GADGET_LOGIC, [a, b], num_bits=num_bits, flags=flags)
         return self._new_vars(seg, 4 * (num_bits // 2 - 1) + 3)
 
     def xor_gate(self, a, b, num_bits: int):
@@ -351,9 +351,7 @@ class Composer:
 
     def point_addition_gate(self, p1, p2):
         """`point_addition_gate` (variable_base_gate.rs:24-93): points are (x, y) pairs of handles; returns (x3, y3)"""
-        hs = [p1[0], p1[1], p2[0], p2[1]]
-        B = self._batch(hs)
-        seg = self._segment(_lib.ZK_GADGET_CURVE_ADD, B, [self._handle(h, B) for h in hs])
+        seg = self._gadget(_lib.ZK_GADGET_CURVE_ADD, [p1[0], p1[1], p2[0], p2[1]])
         return self._new_vars(seg, 1), self._new_vars(seg, 2)
 
     def fixed_base_table(self, base):
@@ -370,14 +368,8 @@ class Composer:
     def fixed_base_scalar_mul(self, scalar, base):
         """`fixed_base_scalar_mul` (fixed_base.rs:51-160): base an affine point (x, y) of the embedded curve as integers; returns the
         handles (acc_x, acc_y) of the product.  A scalar whose width-2 NAF has more than M digits is refused at assign time."""
-        B = self._batch([scalar])
-        seg = self._segment(_lib.ZK_GADGET_FIXED_BASE, B, [self._handle(scalar, B)], table=self.fixed_base_table(base))
+        seg = self._gadget(_lib.ZK_GADGET_FIXED_BASE, [scalar], table=self.fixed_base_table(base))
         return self._new_vars(seg, 4 * self.m_bits), self._new_vars(seg, 4 * self.m_bits + 1)
-
-    # ------------------------------------------------------------------------------------------------------------ csrc/gadgets_ext.hip
-    def _ext(self, kind, handles, B=None, **kw):
-        B = self._batch([h for h in handles if h is not None], B)
-        return self._segment(kind, B, [None if h is None else self._handle(h, B) for h in handles], **kw)
 
     def add_witness_to_circuit_description(self, value, B=None):
         """`add_witness_to_circuit_description` (composer.rs:192-196): a new variable fixed to `value` -- an integer (B calls of it) or
@@ -385,40 +377,40 @@ class Composer:
         r = self.curve.r
         neg = (-int(value)) % r if isinstance(value, (int, np.integer)) else [(-int(v)) % r for v in value]
         B = (1 if B is None else int(B)) if isinstance(neg, int) else len(neg)
-        seg = self._segment(_lib.ZK_GADGET_CONST_WITNESS, B, [], coeff=(0, 0, 0, 0, 0, neg))
+        seg = self._gadget(_lib.ZK_GADGET_CONST_WITNESS, [], B, coeff=(0, 0, 0, 0, 0, neg))
         return self._new_vars(seg, 0)
 
     def is_zero_with_output(self, a):
         """`is_zero_with_output` (composer.rs:355-383): the variable b = (a == 0), with y = 1 / a (1 when a = 0) beside it"""
-        return self._new_vars(self._ext(_lib.ZK_GADGET_IS_ZERO, [a]), 1)
+        return self._new_vars(self._gadget(_lib.ZK_GADGET_IS_ZERO, [a]), 1)
 
     def is_eq_with_output(self, a, b):
         """`is_eq_with_output` (composer.rs:387-392): is_zero of the difference a - b"""
-        return self._new_vars(self._ext(_lib.ZK_GADGET_IS_EQ, [a, b]), 2)
+        return self._new_vars(self._gadget(_lib.ZK_GADGET_IS_EQ, [a, b]), 2)
 
     def conditional_select(self, bit, choice_a, choice_b):
         """`conditional_select` (composer.rs:404-433): bit == 1 => choice_a, bit == 0 => choice_b; four rows"""
-        return self._new_vars(self._ext(_lib.ZK_GADGET_SELECT, [bit, choice_a, choice_b]), 3)
+        return self._new_vars(self._gadget(_lib.ZK_GADGET_SELECT, [bit, choice_a, choice_b]), 3)
 
     def conditional_point_select(self, point_1, point_0, bit):
         """`conditional_point_select` (ecc/mod.rs:145-155): bit == 1 => point_1, bit == 0 => point_0"""
-        seg = self._ext(_lib.ZK_GADGET_POINT_SELECT, [bit, point_1[0], point_0[0], point_1[1], point_0[1]])
+        seg = self._gadget(_lib.ZK_GADGET_POINT_SELECT, [bit, point_1[0], point_0[0], point_1[1], point_0[1]])
         return self._new_vars(seg, 3), self._new_vars(seg, 7)
 
     def conditional_point_neg(self, bit, point):
         """`conditional_point_neg` (ecc/mod.rs:165-182): bit == 1 => (-x, y), bit == 0 => (x, y)"""
-        seg = self._ext(_lib.ZK_GADGET_POINT_NEG, [bit, point[0]])
+        seg = self._gadget(_lib.ZK_GADGET_POINT_NEG, [bit, point[0]])
         return self._new_vars(seg, 4), point[1]
 
     def variable_base_scalar_mul(self, scalar, point):
         """`variable_base_scalar_mul` (ecc/scalar_mul/variable_base.rs:27-95): scalar a variable, point a pair of variables; returns
         the handles of the product.  8 M + 2 rows per call; a zero denominator of the group law on the way is refused at assign time."""
-        seg = self._ext(_lib.ZK_GADGET_VAR_BASE, [scalar, point[0], point[1]])
+        seg = self._gadget(_lib.ZK_GADGET_VAR_BASE, [scalar, point[0], point[1]])
         return self._new_vars(seg, seg["V"] - 2), self._new_vars(seg, seg["V"] - 1)
 
     def lookup_gate(self, a, b, c, d=None, pi=None, B=None):
         """`lookup_gate` (lookup.rs:18-65): the row (a, b, c, d) must be a row of `self.lookup_table`; d=None is the zero variable"""
-        seg = self._ext(_lib.ZK_GADGET_LOOKUP, [a, b, c, d], B, pi=pi)
+        seg = self._gadget(_lib.ZK_GADGET_LOOKUP, [a, b, c, d], B, pi=pi)
         return self._own(seg["inputs"][2])
 
     # ---- compositions of the rows above, with the reference's names

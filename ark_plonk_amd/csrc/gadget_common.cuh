@@ -1,6 +1,11 @@
-// What the two units of the device composer (gadgets.hip, gadgets_ext.hip) share, each helper defined once: the shape table of every
-// gadget kind, the access to a segment's inputs and coefficients, the guarded value store, the shared block inversion and the flagged
-// launch (one working-memory allocation per call, one flag word read back once).  Not part of the C ABI.
+// What the two units of the device composer share -- gadget_layout.hip, the circuit description built once per circuit, and
+// gadget_witness.hip, the values replayed once per proof -- each helper defined once: the shape table of every gadget kind, what both
+// entry points refuse before anything is launched, the access to a segment's inputs and coefficients, the guarded value store, the
+// shared block inversion and the flagged launch (one working-memory allocation per call, one flag word read back once).  A SEGMENT is
+// B calls of one gadget with the same parameters; every gadget has a fixed shape per call (R rows, V new variables, I insertions:
+// gadget_shape), so call k owns rows row0 + k R ..., variables var0 + k V ... and insertions k I ... and no kernel loops over calls or
+// rows on the host.  Errors are one flag word, OR-ed, read back once per call.  No buffer of the ctx is used, so both calls run
+// inside an open deferred round.  Not part of the C ABI.
 #pragma once
 #include "api_internal.h"
 #include "fr_io.cuh"
@@ -48,13 +53,12 @@ inline size_t gadget_work_bytes(uint32_t kind, uint32_t m_bits, uint64_t calls) 
     return 0;
 }
 
-struct SelPtrs {
-    void* p[N_SEL];
-};
-
-// input w of call k: inputs[0 .. 4), then inputs_ext
+// the handles of input w: inputs[0 .. 4), then inputs_ext; null where the segment has no such input
+constexpr int MAX_INPUTS = 5;
+ZK_HD const uint32_t* input_ptr(const zk_gadget_args& a, int w) { return (const uint32_t*)(w < 4 ? a.inputs[w] : a.inputs_ext[w - 4]); }
+// input w of call k; an input the segment does not have reads as the zero variable
 ZK_D uint32_t input_id(const zk_gadget_args& a, int w, uint64_t k) {
-    const uint32_t* p = (const uint32_t*)(w < 4 ? a.inputs[w] : a.inputs_ext[w - 4]);
+    const uint32_t* p = input_ptr(a, w);
     return p ? p[k] : 0u;
 }
 template <class Fr>
@@ -71,12 +75,11 @@ template <class Fr>
 ZK_D Fr coeff_of(const zk_gadget_args& a, int j, uint64_t k) {
     return a.coeff[j] ? ld_fr<Fr>(a.coeff[j], k) : fr_words<Fr>(a.coeff_const + 4 * j);
 }
-ZK_D uint32_t pick4(const uint32_t (&id)[4], uint32_t w) { return w == 0 ? id[0] : w == 1 ? id[1] : w == 2 ? id[2] : id[3]; }
 
 // ---------------------------------------------------------------------------------------------------------------- witness helpers
 template <class Fr>
 ZK_D Fr ld_input(const void* values, const zk_gadget_args& a, int w, uint64_t k, uint32_t* flag) {
-    const uint32_t* p = (const uint32_t*)(w < 4 ? a.inputs[w] : a.inputs_ext[w - 4]);
+    const uint32_t* p = input_ptr(a, w);
     if (!p) return Fr::zero();
     const uint32_t id = p[k];
     if (id >= a.var0) {
@@ -92,7 +95,12 @@ ZK_D void st_value(void* values, uint64_t num_vars, uint64_t id, const Fr& v) {
 // 1 / z for every lane of the block with ONE field inversion: inclusive prefix and suffix products of z over the block in LDS
 // (Hillis-Steele), 1 / z_t = prefix_{t-1} * suffix_{t+1} / total -- the scan of ipa_fold_key.  z must be non-zero in every lane.
 template <class Fr>
-ZK_D Fr block_inverse(const Fr& z, Fr* pre, Fr* suf, Fr* inv_total) {
+struct alignas(16) InverseLds {                    // declared __shared__ once in every kernel that calls block_inverse; 16: 128-bit LDS access
+    Fr pre[GT], suf[GT], inv_total;
+};
+template <class Fr>
+ZK_D Fr block_inverse(const Fr& z, InverseLds<Fr>& lds) {
+    Fr *const pre = lds.pre, *const suf = lds.suf, *const inv_total = &lds.inv_total;
     const uint32_t t = threadIdx.x;
     Fr p = z, s = z;
     pre[t] = p;
@@ -124,9 +132,41 @@ struct Work {
     }
 };
 
-// the limits on rows and variables every kind shares
-inline int check_extent(const zk_gadget_args& a, const Shape& s) {
-    if (a.calls == 0 || s.rows == 0) return ZK_ERR_BAD_ARG;
+inline int inputs_needed(uint32_t kind) {
+    switch (kind) {
+    case ZK_GADGET_POLY: return 2;                         // and the output, unless it is computed
+    case ZK_GADGET_RANGE: return 1;
+    case ZK_GADGET_LOGIC: return 2;
+    case ZK_GADGET_CURVE_ADD: return 4;
+    case ZK_GADGET_FIXED_BASE: return 1;                   // and the table
+    case ZK_GADGET_IS_ZERO: return 1;
+    case ZK_GADGET_IS_EQ: return 2;
+    case ZK_GADGET_SELECT: return 3;
+    case ZK_GADGET_POINT_SELECT: return 5;
+    case ZK_GADGET_POINT_NEG: return 2;
+    case ZK_GADGET_VAR_BASE: return 3;
+    case ZK_GADGET_LOOKUP: return 3;
+    default: return 0;
+    }
+}
+// num_bits of the kinds that take one: even, 2 .. 256
+inline bool bits_ok(uint32_t kind, uint32_t num_bits) {
+    return (kind != ZK_GADGET_RANGE && kind != ZK_GADGET_LOGIC) || (num_bits >= 2 && num_bits <= 256 && !(num_bits & 1u));
+}
+// what both entry points refuse before anything is launched; a number between the kinds that names none has a shape of no rows
+inline int check_args(const zk_gadget_args& a, const Shape& s) {
+    if (a.kind > LAST_KIND || a.calls == 0 || s.rows == 0 || !bits_ok(a.kind, a.num_bits)) return ZK_ERR_BAD_ARG;
+    for (int w = 0; w < inputs_needed(a.kind); ++w)
+        if (!input_ptr(a, w)) return ZK_ERR_BAD_ARG;
+    switch (a.kind) {
+    case ZK_GADGET_POLY:
+        if (!(a.flags & ZK_GADGET_COMPUTE_OUT) && !a.inputs[2]) return ZK_ERR_BAD_ARG;
+        break;
+    case ZK_GADGET_FIXED_BASE:
+        if (!a.table) return ZK_ERR_BAD_ARG;
+        break;
+    default: break;
+    }
     if (a.calls > MAX_ROWS || a.row0 > MAX_ROWS || a.row0 + a.calls * s.rows > MAX_ROWS) return ZK_ERR_UNSUPPORTED;
     if (a.var0 == 0 || a.var0 > MAX_VARS || a.var0 + a.calls * s.vars > MAX_VARS) return ZK_ERR_UNSUPPORTED;
     return ZK_OK;
@@ -155,7 +195,3 @@ int run_flagged(zk_ctx* c, size_t work_bytes, Body&& body) {
 }
 
 }  // namespace
-
-// ---- gadgets_ext.hip: the kinds after ZK_GADGET_FIXED_BASE; ctx lock held, args already copied, buffers checked for null
-int gadget_ext_layout(zk_ctx* c, int curve_id, const zk_gadget_args& a, uint32_t* d_ids, void* const* d_sel, uint32_t* d_ins_var, uint32_t* d_ins_rec);
-int gadget_ext_witness(zk_ctx* c, int curve_id, const zk_gadget_args& a, void* d_values, uint64_t num_vars);

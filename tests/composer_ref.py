@@ -3,8 +3,8 @@ definitions in plonk-core/src/constraint_system/ -- composer.rs:186-350,580-648 
 blinding rows), arithmetic.rs:103-168, boolean.rs:25-51, range.rs:27-195, logic.rs:36-345, ecc/curve_addition/variable_base_gate.rs:
 24-93, ecc/curve_addition/fixed_base_gate.rs:77-107, ecc/scalar_mul/fixed_base.rs:19-160 -- one call at a time, with the loops the
 reference has.  It records rows (four variable ids, twelve selector values), the `add_variable_to_map` calls in call order, the
-public inputs and the value of every variable.  Independent of ark_plonk_amd/composer.py and csrc/gadgets.hip: no closed form is used
-here (the accumulators are accumulated, the NAF is `find_wnaf(2)`'s loop, the point accumulator is a running affine sum)."""
+public inputs and the value of every variable.  Independent of ark_plonk_amd/composer.py, csrc/gadget_layout.hip and
+csrc/gadget_witness.hip: no closed form is used here (the accumulators are accumulated, the NAF is `find_wnaf(2)`'s loop, the point accumulator is a running affine sum)."""
 
 SELECTORS = ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_arith", "q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add", "q_lookup")
 L, R, O, F = 0, 1, 2, 3                         # WireData::Left, Right, Output, Fourth

@@ -4,7 +4,7 @@ constraint_system/composer.rs:192-196 (add_witness_to_circuit_description), 355-
 (conditional_select, _zero, _one), ecc/mod.rs:58-206 (Point::identity, add_affine ..., conditional_point_select, conditional_point_neg,
 conditional_select_identity), ecc/scalar_mul/variable_base.rs:27-95, constraint_system/lookup.rs:18-65 and lookup/lookup_table.rs:
 32-204 -- with the loops the reference has: the scalar's accumulators are accumulated, the point is doubled and added bit by bit in
-affine coordinates.  Independent of ark_plonk_amd/composer.py and csrc/gadgets_ext.hip."""
+affine coordinates.  Independent of ark_plonk_amd/composer.py, csrc/gadget_layout.hip and csrc/gadget_witness.hip."""
 from tests import composer_ref as cr
 from tests.composer_ref import te_add
 

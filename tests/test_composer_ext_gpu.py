@@ -1,4 +1,6 @@
-"""GPU suite of the device composer's second unit (ark_plonk_amd/composer.py, csrc/gadgets_ext.hip): is_zero / is_eq, the
+"""GPU suite of the device composer (ark_plonk_amd/composer.py; csrc/gadget_layout.hip: gadget_layout, gadget_insertions,
+lookup_table_fill; csrc/gadget_witness.hip: gadget_w_select, gadget_w_is_zero, gadget_w_var_bits, gadget_w_var_walk, gadget_w_var_norm) for
+the kinds from add_witness_to_circuit_description on: is_zero / is_eq, the
 conditional selects, variable-base scalar multiplication, lookup gates and the lookup-table builders -- descriptions and values
 against the sequential restatement of the reference's composer (tests/composer_ref_ext.py), the reference's own gadget tests end to
 end (compile -> assign -> check_circuit -> prove -> the oracle's verifier), and the refusals.  Every comparison is exact equality."""

@@ -1,4 +1,6 @@
-"""GPU suite of the device composer (ark_plonk_amd/composer.py, csrc/gadgets.hip): descriptions and values against the sequential
+"""GPU suite of the device composer (ark_plonk_amd/composer.py; csrc/gadget_layout.hip: gadget_layout, gadget_insertions;
+csrc/gadget_witness.hip: gadget_w_poly, gadget_w_range, gadget_w_logic, gadget_w_curve, gadget_w_fixed_walk, gadget_w_fixed_norm) for the
+arithmetic family, the range and logic gates, curve addition and the fixed base: descriptions and values against the sequential
 restatement of the reference's composer (tests/composer_ref.py), the reference's own gadget tests end to end (compile -> assign ->
 check_circuit -> prove -> the oracle's verifier), localisation of failing calls, a circuit that fills 2^14 rows, and the refusals.
 Every comparison is exact equality."""

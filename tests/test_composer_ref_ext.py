@@ -1,8 +1,9 @@
 """tests/composer_ref_ext.py -- the sequential restatement of the reference's remaining gadgets (is_zero / is_eq, the conditional
 selects, variable-base scalar multiplication, lookup gates and tables) -- against what the repository already trusts: its circuits
 pass the circuit check's definition (tests/circuit_check_ref.py, lookup rows with their table) with sigma from tests/compile_ref.py,
-the shape table of DESIGN.md 6e holds (and `zk_gadget_shape` returns the same numbers), the closed forms the kernels of
-csrc/gadgets_ext.hip use equal the sequential loops, the table builders equal the reference's own table tests
+the shape table of DESIGN.md 6e holds (and `zk_gadget_shape` returns the same numbers), the closed forms `row_of`
+(csrc/gadget_layout.hip) and the kernels gadget_w_select, gadget_w_is_zero, gadget_w_var_bits, gadget_w_var_walk, gadget_w_var_norm and
+lookup_table_fill use equal the sequential loops, the table builders equal the reference's own table tests
 (lookup/lookup_table.rs:214-326), and the reference's gadget tests (tests/golden/gadget_reference_cases_ext.json, recorded as data)
 come out as the reference says.  Exact integers, both curves, no GPU."""
 import ctypes

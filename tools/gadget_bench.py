@@ -1,14 +1,14 @@
-"""Timings of the device composer (ark_plonk_amd/composer.py, csrc/gadgets.hip) on one GPU:
+"""Timings of the device composer (ark_plonk_amd/composer.py, csrc/gadget_layout.hip, csrc/gadget_witness.hip) on one GPU:
 
   * per gadget kind, one segment of B calls: the layout call (zk_gadget_layout_dev) and the witness call (zk_gadget_witness_dev), the
-    two phases of the fixed-base witness from the ctx's event profile;
+    two phases of the fixed-base witness (gadget_w_fixed_walk, gadget_w_fixed_norm) and gadget_w_curve from the ctx's event profile;
   * a program that fills n = 2^log_n rows with every kind (half of the rows fixed-base products, a quarter range gates, an eighth logic gates,
     the rest curve additions and arithmetic): building it (every layout call + `description()`), one witness replay (`Composer.assign`), and --
     in the same process, on the same circuit -- `compile`, one `check_circuit` and one `prove`.
 
-  * --ext: the kinds of the second unit (csrc/gadgets_ext.hip) -- `variable_base_scalar_mul` at B = 1, 64, 4096 and `is_zero_with_output`
-    at B = 2^20: layout, witness, the phases of the variable-base witness, and, where the circuit pads to at most 2^--ext-prove-log-n
-    rows, `compile` and one `prove` of the same circuit.
+  * --ext: two more kinds -- `variable_base_scalar_mul` at B = 1, 64, 4096 and `is_zero_with_output` at B = 2^20: layout, witness, the
+    kernels of the variable-base witness (gadget_w_var_bits, gadget_w_var_walk, gadget_w_var_norm) and gadget_w_is_zero from the event
+    profile, and, where the circuit pads to at most 2^--ext-prove-log-n rows, `compile` and one `prove` of the same circuit.
 
 One JSON line per measurement; --out writes them to a file.  Every timed call ends in a device synchronise; the median of --reps calls
 after --warmup calls is reported.  Kernel times for the record come from a separate `rocprofv3 --kernel-trace --stats` run of this
@@ -104,7 +104,7 @@ def kinds(zk, ctx, cid, coeffs, G, a, emit):
 
 
 def ext_kinds(zk, ctx, cid, coeffs, G, a, emit):
-    """the second unit: one segment per case on a fresh composer -- layout, witness, and compile + prove of that circuit"""
+    """--ext: one segment per case on a fresh composer -- layout, witness, and compile + prove of that circuit"""
     from ark_plonk_amd import compile as zc
     from ark_plonk_amd import prover
     from ark_plonk_amd.curves import fr_to_mont
@@ -181,7 +181,7 @@ def main():
     ap.add_argument("--no-kinds", action="store_true")
     ap.add_argument("--no-prove", action="store_true")
     ap.add_argument("--out", default="")
-    ap.add_argument("--ext", action="store_true", help="the kinds of csrc/gadgets_ext.hip")
+    ap.add_argument("--ext", action="store_true", help="also time variable_base_scalar_mul (at --ext-calls) and is_zero_with_output")
     ap.add_argument("--ext-calls", type=int, nargs="*", default=[1, 64, 4096])
     ap.add_argument("--ext-prove-log-n", type=int, default=21)
     a = ap.parse_args()
