@@ -15,6 +15,16 @@
 #pragma once
 #include "fields.cuh"
 
+// A condition the compiler cannot see through.  Steps that exclude one another, written as `if (zk_apart(a)) A; if (zk_apart(b)) B;`,
+// stay two blocks that a lane enters or walks past.  As alternatives (if / else) the device code lays them out one after the other
+// with the values of one side alive across the other, and what both sides assign is moved into place at the join by every lane.
+ZK_HD bool zk_apart(uint32_t flag) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(flag));
+#endif
+    return flag != 0;
+}
+
 template <class F>
 struct AffineU {
     F x, y;  // residues in (-p, p), strict limbs, R' Montgomery domain; x = y = 0 limbs encodes "no point"
@@ -97,6 +107,42 @@ struct XYZZu {
         o.y = F::dot2(r_, F::sub16(qq, o.x), F::neg16(p.y), ppp);   // r*(qq - x3) - y1*ppp, one reduction
         o.zzz = F::mul(p.zzz, ppp);
         return o;
+    }
+
+    // The addition of the MSM accumulation loop in two halves, the sum written over p: p += q for p NOT infinity and q not null.
+    // q's coordinates are read in madd_begin alone, so between the halves the caller can request the next point into q's own
+    // registers, with four fifths of the addition in front of its first use.  madd_finish returns MADD_SUM (p holds the sum), or
+    // MADD_SAME (p == q: the caller doubles q) / MADD_OPPOSITE (p == -q: the sum is infinity) with p left undefined -- neither needs
+    // it, and ZZ3 can then be written over ZZ1 before it is tested.  The full compare of ZZ3 is reached only by lanes whose limb 0
+    // is that of 0 or +-p (fields.cuh); the arithmetic is madd's, instruction for instruction.
+    enum : int { MADD_SUM = 0, MADD_SAME = 1, MADD_OPPOSITE = 2 };
+    struct MaddHalf {
+        F u2, s2;
+    };
+    ZK_HD static MaddHalf madd_begin(const XYZZu& p, const AffineU<F>& q) {
+        MaddHalf h;
+        h.u2 = F::mul(q.x, p.zz);
+        h.s2 = F::mul(q.y, p.zzz);
+        return h;
+    }
+    ZK_HD static int madd_finish(XYZZu& p, const MaddHalf& h) {
+        F pp_ = F::sub16(h.u2, p.x);
+        F r_ = F::sub16(h.s2, p.y);
+        F pp = F::sqr(pp_);
+        F rr = F::sqr(r_);
+        p.zz = F::mul(p.zz, pp);
+        int how = MADD_SUM;
+        if (p.zz.limb0_of_zero_mod()) {
+            if (p.zz.is_zero_mod_reduced()) how = rr.is_zero_mod_reduced() ? MADD_SAME : MADD_OPPOSITE;
+        }
+        if (zk_apart(how == MADD_SUM)) {
+            F ppp = F::mul(pp_, pp);
+            F qq = F::mul(p.x, pp);
+            p.x = F::sub_sum3(rr, ppp, qq, qq);
+            p.y = F::dot2(r_, F::sub16(qq, p.x), F::neg16(p.y), ppp);   // r*(qq - x3) - y1*ppp, one reduction
+            p.zzz = F::mul(p.zzz, ppp);
+        }
+        return how;
     }
 
     // this + q, both XYZZ; handles infinities, doubling and cancellation

@@ -262,6 +262,8 @@ struct Fs {
         return r;
     }
 
+    // necessary for is_zero_mod_reduced(): limb 0 is that of 0, p or -p (one in 2^30 values that are not zero pass it too)
+    ZK_HD bool limb0_of_zero_mod() const { return v[0] == 0 || v[0] == (uint32_t)P::MOD(0) || v[0] == (uint32_t)P::NMOD(0); }
     // exact "== 0 mod p" for a mul / sqr / dot2 output: strict limbs, value in (-2p, 2p), so it is 0, p or -p
     ZK_HD bool is_zero_mod_reduced() const {
         if (v[0] != 0 && v[0] != (uint32_t)P::MOD(0) && v[0] != (uint32_t)P::NMOD(0)) return false;

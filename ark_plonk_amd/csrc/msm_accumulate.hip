@@ -29,44 +29,76 @@ ZK_D void accumulate_chunk(const uint32_t t, const uint32_t* entries, const uint
     uint32_t bend = offsets[b + 1];
     const bool head_partial = offsets[b] < (uint32_t)e0;
     bool first_run = true;
+    // The sum of the current run.  `inf` says that it is the point at infinity; acc's limbs are then whatever they were (a run's first
+    // point is written over them), and a store of such a run writes the zero limbs of infinity instead.
     XYZZu<F> acc = XYZZu<F>::infinity();
-    // software pipeline: the reference and the 128-byte point of iteration e+1 are requested before the
-    // mixed addition of iteration e (two dependent HBM/L2 round trips otherwise sit in front of every add)
+    bool inf = true;
+    auto store_run = [&](void* arr, uint64_t slot) {
+        if (inf) acc = XYZZu<F>::infinity();
+        st_xyzz<F>(arr, slot, acc);
+    };
     auto point_index = [&](uint32_t ref) -> uint64_t {
         return PRE ? (uint64_t)((ref >> 26) & 31u) * tab_stride + tab_off + (ref & 0x3ffffffu) : (uint64_t)(ref & 0x7fffffffu);
     };
-    uint32_t ref_n = entries[(uint32_t)e0];
-    AffineU<F> p_n = ld_affine<F>(bases, point_index(ref_n));
+    // Software pipeline: the reference of iteration e+1 is requested at the top of iteration e and its 128-byte point between the two
+    // halves of the addition of iteration e, straight into p -- the addition has read p for the last time by then, and four fifths of
+    // it are still in front of the point's first use.  (The last iteration requests its own row again: no condition around the load.)
+    // Every step that is not an addition is a block of its own that a lane either enters or walks past: the run's end (store), the
+    // run's first point (it is written over acc), P == +-Q (after the addition).  Written as alternatives of one another they would
+    // be laid out one after the other with the values of one side alive across the other, and every reference would pay for moving
+    // the sum into acc's registers at the join; zk_apart (ecu.cuh) keeps the compiler from merging them back into such alternatives.
+    uint32_t ref = entries[(uint32_t)e0];
+    AffineU<F> p = ld_affine<F>(bases, point_index(ref));
     for (uint32_t e = (uint32_t)e0; e < e1; ++e) {
-        const uint32_t ref = ref_n;
-        AffineU<F> p = p_n;
-        if (e + 1 < e1) {
-            ref_n = entries[e + 1];
-            p_n = ld_affine<F>(bases, point_index(ref_n));
-        }
+        const uint32_t ref_n = entries[e + 1 < e1 ? e + 1 : e];
         if (e == bend) {
-            if (first_run && head_partial) st_xyzz<F>(part_pt, 2ull * t, acc);
-            else st_xyzz<F>(buckets, b, acc);
+            if (first_run && head_partial) store_run(part_pt, 2ull * t);
+            else store_run(buckets, b);
             first_run = false;
-            acc = XYZZu<F>::infinity();
+            inf = true;
             do {
                 ++b;
                 bend = offsets[b + 1];
             } while (bend <= e);
         }
-        if (p.is_null()) continue;
-        if (ref >> 31) p.y = F::neg_canonical(p.y);
-        acc = XYZZu<F>::madd(acc, p);
+        const bool point = !p.is_null();
+        const bool add = zk_apart(point && !inf);
+        if (zk_apart(point && inf)) {
+            acc.x = p.x;
+            acc.y = (ref >> 31) ? F::neg_canonical(p.y) : p.y;
+            acc.zz = F::one();
+            acc.zzz = F::one();
+            inf = false;
+        }
+        typename XYZZu<F>::MaddHalf h;
+        if (add) {
+            if (ref >> 31) p.y = F::neg_canonical(p.y);
+            h = XYZZu<F>::madd_begin(acc, p);
+        }
+        p = ld_affine<F>(bases, point_index(ref_n));
+        int how = XYZZu<F>::MADD_SUM;
+        if (zk_apart(add)) how = XYZZu<F>::madd_finish(acc, h);
+        if (zk_apart(how != XYZZu<F>::MADD_SUM)) {
+            // P == +-Q: the row of THIS reference is read again (p holds the next point by now)
+            if (how == XYZZu<F>::MADD_SAME) {
+                AffineU<F> q = ld_affine<F>(bases, point_index(ref));
+                if (ref >> 31) q.y = F::neg_canonical(q.y);
+                acc = XYZZu<F>::dbl_affine(q);
+            } else {
+                inf = true;
+            }
+        }
+        ref = ref_n;
     }
     // Slot convention (msm_combine relies on it): a run that is the FIRST run of its chunk and is
     // not a whole bucket goes to slot 2t, a trailing incomplete run that is not the first goes to 2t+1.
     const bool tail_complete = (e1 == bend);
     if (first_run) {
-        if (head_partial || !tail_complete) st_xyzz<F>(part_pt, 2ull * t, acc);
-        else st_xyzz<F>(buckets, b, acc);
+        if (head_partial || !tail_complete) store_run(part_pt, 2ull * t);
+        else store_run(buckets, b);
     } else {
-        if (tail_complete) st_xyzz<F>(buckets, b, acc);
-        else st_xyzz<F>(part_pt, 2ull * t + 1, acc);
+        if (tail_complete) store_run(buckets, b);
+        else store_run(part_pt, 2ull * t + 1);
     }
 }
 
