@@ -109,7 +109,23 @@ struct RJobs {
     uint32_t lanes[MAX_RJOBS];      // ... its lanes, and the bucket count (offsets[nbk] = references in the list): see chunk_len
     uint32_t nbk[MAX_RJOBS];
 };
-
+// job k of a reduction launch over the work buffers of one set: the combine queues q_off words into part_key, (run | acc) of n_seg
+// level-1 segments in seg; win_s / win_t: where the window sums go (win_t may be null on the per-window path)
+template <class F>
+void set_rjob(RJobs& jobs, uint32_t k, const MsmBufs& mb, uint32_t q_off, size_t n_seg, uint32_t* win_s, uint32_t* win_t, uint32_t L, uint32_t lanes,
+              uint32_t nbk) {
+    jobs.part_pt[k] = mb.part_pt.p;
+    jobs.offsets[k] = (const uint32_t*)mb.offsets.p;
+    jobs.buckets[k] = mb.buckets.p;
+    jobs.q[k] = (uint32_t*)mb.part_key.p + q_off;
+    jobs.seg_run[k] = mb.seg.p;
+    jobs.seg_acc[k] = (char*)mb.seg.p + n_seg * Store<F>::POINT_BYTES;
+    jobs.win_s[k] = win_s;
+    jobs.win_t[k] = win_t;
+    jobs.L[k] = L;
+    jobs.lanes[k] = lanes;
+    jobs.nbk[k] = nbk;
+}
 
 constexpr uint32_t PS_PARTS = 256;    // partitions of the two-pass sort (msm_sort.hip): the high 8 of a table window's c - 1 bucket bits;
                                       // the low lob = c - 9 bits are ordered inside a partition
@@ -162,6 +178,21 @@ uint32_t modulus_minus_one_bits(uint32_t shift) {
     return (uint32_t)v;
 }
 
+// The geometry of one reduction level: W windows of B buckets in segments of 2^logG, and what follows from them -- nb, the segments
+// per window and how many of them a lane of msm_win_finish takes (one, the quad forms' case, up to 256 per window).  `g`: what the
+// other fields are.  A level of the wide reduction has none and takes the default: an empty whole-table geometry (c = 0, no fold,
+// Wt = w0 = 0, wstep = 1), with logq derived like everywhere else although the kernels those levels reach read W, B, ns and logG only.
+inline MsmGeom level_geom(uint32_t W, uint32_t B, uint32_t logG, MsmGeom g = MsmGeom()) {
+    g.W = W;
+    g.B = B;
+    g.nb = W * B;
+    g.logG = logG;
+    g.ns = B >> logG;
+    g.logq = 0;
+    while ((256u << g.logq) < g.ns) ++g.logq;
+    return g;
+}
+
 template <class FrP>
 MsmGeom make_geom(uint64_t n, int c_override, uint32_t max_c = 16) {
     const int bits = FrP::BITS;
@@ -208,14 +239,7 @@ MsmGeom make_geom(uint64_t n, int c_override, uint32_t max_c = 16) {
         }
     }
     g.Wt = g.W;
-    g.B = 1u << (c - 1);
-    g.nb = g.W * g.B;
-    g.logG = c - 1 < 4 ? c - 1 : 4;
-    g.ns = g.B >> g.logG;
-    uint32_t per = (g.ns + 255) / 256;
-    g.logq = 0;
-    while ((1u << g.logq) < per) ++g.logq;
-    return g;
+    return level_geom(g.W, 1u << (c - 1), c - 1 < 4 ? c - 1 : 4, g);
 }
 
 struct PrePlan {

@@ -10,7 +10,7 @@
 // msm_reduce queue them (ZK_SYM entry points of msm_common.cuh).  The unit ends with the curve's MsmOps table (ctx.h).
 #include "msm_common.cuh"
 
-#include <chrono>
+#include <array>
 
 namespace {
 
@@ -18,19 +18,38 @@ int ensure_pinned(zk_ctx* c, size_t bytes);
 template <class Fq>
 XYZZ<Fq> jac_to_xyzz(const uint64_t* xyz);
 
+// XYZZ -> Jacobian (X*ZZ, Y*ZZZ, ZZ):  x = X/ZZ = X*ZZ/ZZ^2, y = Y/ZZZ = Y*ZZZ/ZZ^3; infinity as arkworks writes Jacobian zero: (1, 1, 0)
+template <class Fq>
+void put_jacobian(const XYZZ<Fq>& p, uint64_t* out_xyz) {
+    constexpr int L64 = Fq::N / 2;
+    Fq X = Fq::one(), Y = Fq::one(), Z = Fq::zero();
+    if (!p.is_inf()) {
+        X = Fq::mul(p.x, p.zz);
+        Y = Fq::mul(p.y, p.zzz);
+        Z = p.zz;
+    }
+    memcpy(out_xyz, X.v, sizeof(uint64_t) * L64);
+    memcpy(out_xyz + L64, Y.v, sizeof(uint64_t) * L64);
+    memcpy(out_xyz + 2 * L64, Z.v, sizeof(uint64_t) * L64);
+}
+// GroupAffine::zero() = (0, 1, infinity = true)
+template <class Fq>
+void put_affine_zero(uint64_t* out_xy, uint8_t* out_inf) {
+    constexpr int L64 = Fq::N / 2;
+    const Fq zero = Fq::zero(), one = Fq::one();
+    memcpy(out_xy, zero.v, sizeof(uint64_t) * L64);
+    memcpy(out_xy + L64, one.v, sizeof(uint64_t) * L64);
+    if (out_inf) *out_inf = 1;
+}
+
 template <class Cv>
 int msm_run(zk_ctx* c, const void* d_bases, const void* d_scalars, size_t n, uint64_t* out_xyz) {
     typedef typename Cv::Fq Fq;       // host / arkworks-layout arithmetic
     typedef typename Cv::FqU F;       // device arithmetic
     typedef XYZZ<Fq> PH;
-    constexpr int L64 = Fq::N / 2;
-    constexpr size_t PT = (size_t)4 * Store<F>::WORDS * 4;   // bytes of one stored XYZZu
+    constexpr size_t PT = Store<F>::POINT_BYTES;
     if (n == 0) {
-        // Jacobian zero as arkworks writes it: (1, 1, 0)
-        Fq one = Fq::one(), zero = Fq::zero();
-        memcpy(out_xyz, one.v, sizeof(uint64_t) * L64);
-        memcpy(out_xyz + L64, one.v, sizeof(uint64_t) * L64);
-        memcpy(out_xyz + 2 * L64, zero.v, sizeof(uint64_t) * L64);
+        put_jacobian<Fq>(PH::infinity(), out_xyz);
         return ZK_OK;
     }
     if (n >= (1ull << 31)) return ZK_ERR_UNSUPPORTED;
@@ -60,17 +79,7 @@ int msm_run(zk_ctx* c, const void* d_bases, const void* d_scalars, size_t n, uin
     {
         RJobs jobs;
         memset(&jobs, 0, sizeof jobs);
-        jobs.part_pt[0] = mb.part_pt.p;
-        jobs.offsets[0] = (const uint32_t*)mb.offsets.p;
-        jobs.buckets[0] = mb.buckets.p;
-        jobs.q[0] = (uint32_t*)mb.part_key.p;
-        jobs.seg_run[0] = mb.seg.p;
-        jobs.seg_acc[0] = (char*)mb.seg.p + (size_t)g.W * g.ns * PT;
-        jobs.win_s[0] = (uint32_t*)mb.win.p;
-        jobs.win_t[0] = nullptr;
-        jobs.L[0] = CHUNK_L;
-        jobs.lanes[0] = n_lanes;
-        jobs.nbk[0] = g.nb;
+        set_rjob<F>(jobs, 0, mb, 0, (size_t)g.W * g.ns, (uint32_t*)mb.win.p, nullptr, CHUNK_L, n_lanes, g.nb);
         if ((rc = ZK_SYM(queue_reduce)(c, jobs, 1, g.nb, g, st, false, 0u))) return rc;
     }
     // window sums -> host, Horner (high window first), Jacobian out
@@ -82,16 +91,7 @@ int msm_run(zk_ctx* c, const void* d_bases, const void* d_scalars, size_t n, uin
         for (uint32_t k = 0; k < g.c; ++k) total = PH::dbl(total);
         total = PH::add(total, win[w]);
     }
-    // XYZZ -> Jacobian (X*ZZ, Y*ZZZ, ZZ):  x = X/ZZ = X*ZZ/ZZ^2, y = Y/ZZZ = Y*ZZZ/ZZ^3
-    Fq X = Fq::one(), Y = Fq::one(), Z = Fq::zero();
-    if (!total.is_inf()) {
-        X = Fq::mul(total.x, total.zz);
-        Y = Fq::mul(total.y, total.zzz);
-        Z = total.zz;
-    }
-    memcpy(out_xyz, X.v, sizeof(uint64_t) * L64);
-    memcpy(out_xyz + L64, Y.v, sizeof(uint64_t) * L64);
-    memcpy(out_xyz + 2 * L64, Z.v, sizeof(uint64_t) * L64);
+    put_jacobian<Fq>(total, out_xyz);
     return ZK_OK;
 }
 
@@ -104,29 +104,21 @@ int msm_run(zk_ctx* c, const void* d_bases, const void* d_scalars, size_t n, uin
 // the reduction's view of the shared bucket set: a function of the table's window (pl.g.B buckets) and the ctx's options only
 inline void pre_reduce_geom(const zk_ctx* c, PrePlan& pl) {
     pl.wide_red = pl.g.B > (1u << 16);
-    pl.gv = pl.g;                                       // the reduction sees PRE_VW virtual windows (wide: windows of 512 buckets)
-    pl.gv.W = pl.wide_red ? pl.g.B / WIDE_VB : PRE_VW;
-    pl.gv.B = pl.g.B / pl.gv.W;
-    pl.gv.nb = pl.g.B;
+    uint32_t VW = pl.wide_red ? pl.g.B / WIDE_VB : PRE_VW;    // the reduction sees PRE_VW virtual windows (wide: windows of WIDE_VB = 2048 buckets)
     // 64 chains (one wavefront per SIMD) per virtual window: segments of 8 buckets for windows of 512 (c = 16; measured against 4 / 16),
     // of 16 for windows of 1024 (c = 17; 64 x 16 measured against 128 x 8, and against 128 and 32 virtual windows)
-    pl.gv.logG = pl.wide_red ? 2 : pl.gv.B >= 1024 ? 4 : 3;
+    uint32_t logG = pl.wide_red ? 2 : pl.g.B / VW >= 1024 ? 4 : 3;
     if (!pl.wide_red) {                                   // tuning options "pre_vw" / "pre_logg" (profiles/r02/r02_notes.md)
         if (c->tune.pre_vw) {
             const uint32_t v = (uint32_t)c->tune.pre_vw;
-            if (v >= 8 && v <= 512 && (v & (v - 1)) == 0 && pl.g.B % v == 0) {
-                pl.gv.W = v;
-                pl.gv.B = pl.g.B / v;
-            }
+            if (v >= 8 && v <= 512 && (v & (v - 1)) == 0 && pl.g.B % v == 0) VW = v;
         }
         if (c->tune.pre_logg >= 0) {
             const uint32_t v = (uint32_t)c->tune.pre_logg;
-            if (v <= 5 && (pl.gv.B >> v) >= 1) pl.gv.logG = v;
+            if (v <= 5 && ((pl.g.B / VW) >> v) >= 1) logG = v;
         }
     }
-    pl.gv.ns = pl.gv.B >> pl.gv.logG;
-    pl.gv.logq = 0;
-    while ((256u << pl.gv.logq) < pl.gv.ns) ++pl.gv.logq;
+    pl.gv = level_geom(VW, pl.g.B / VW, logG, pl.g);    // VW divides B: nb = B, the shared bucket set
 }
 
 // long_chunks: the job is followed by another one inside a merged accumulation launch (msm_accumulate_batch): one round of
@@ -208,8 +200,7 @@ struct PreSizes {
 
 template <class Cv>
 void pre_sizes(const PrePlan& pl, PreSizes& z) {
-    typedef typename Cv::FqU F;
-    constexpr size_t PT = (size_t)4 * Store<F>::WORDS * 4;
+    constexpr size_t PT = Store<typename Cv::FqU>::POINT_BYTES;
     memset(&z, 0, sizeof z);
     z.counts = (size_t)PS_PARTS * PS_SLABS * 4;                  // slab counts of the sort partitions -> cursors
     z.offsets = (size_t)(pl.g.B + 1) * 4;
@@ -232,34 +223,35 @@ void pre_sizes(const PrePlan& pl, PreSizes& z) {
     z.stage = (size_t)pl.nf * (pl.wide ? 6 : 5);                 // references in partition order + their low bucket bits
 }
 
-// bytes the device would have to give for this job: what pre_ensure would newly allocate in `mb` (and in the ctx's shared staging area)
+// The one list of a job's work buffers and their bytes under a plan (0 bytes: not used -- need_for and ensure then do nothing), in the
+// order they are allocated; the staging area, the job's own or the ctx's shared one, comes last.
+struct PreBuf {
+    DevBuf* buf;
+    size_t bytes;
+};
 template <class Cv>
-size_t pre_need(zk_ctx* c, const PrePlan& pl, const MsmBufs& mb) {
+std::array<PreBuf, 11> pre_bufs(zk_ctx* c, const PrePlan& pl, MsmBufs& mb) {
     PreSizes z;
     pre_sizes<Cv>(pl, z);
-    size_t t = mb.counts.need_for(z.counts) + mb.offsets.need_for(z.offsets) + mb.entries.need_for(z.entries) + mb.buckets.need_for(z.buckets) +
-               mb.part_pt.need_for(z.part_pt) + mb.part_key.need_for(z.part_key) + mb.seg.need_for(z.seg) + mb.win.need_for(z.win);
-    if (z.seg2) t += mb.seg2.need_for(z.seg2) + mb.seg3.need_for(z.seg3);
-    t += pl.shared_stage ? c->stage_shared.need_for(z.stage) : mb.stage.need_for(z.stage);
+    return {{{&mb.counts, z.counts}, {&mb.offsets, z.offsets}, {&mb.entries, z.entries}, {&mb.buckets, z.buckets}, {&mb.part_pt, z.part_pt},
+             {&mb.part_key, z.part_key}, {&mb.seg, z.seg}, {&mb.win, z.win}, {&mb.seg2, z.seg2}, {&mb.seg3, z.seg3},
+             {pl.shared_stage ? &c->stage_shared : &mb.stage, z.stage}}};
+}
+
+// bytes the device would have to give for this job: what pre_ensure would newly allocate in `mb` (and in the ctx's shared staging area)
+template <class Cv>
+size_t pre_need(zk_ctx* c, const PrePlan& pl, MsmBufs& mb) {
+    size_t t = 0;
+    for (const PreBuf& b : pre_bufs<Cv>(c, pl, mb)) t += b.buf->need_for(b.bytes);
     return t;
 }
 
+// (growing a buffer frees the old one: hipFree waits for the device, so kernels of earlier jobs still reading it are safe)
 template <class Cv>
 int pre_ensure(zk_ctx* c, const PrePlan& pl, MsmBufs& mb) {
-    PreSizes z;
-    pre_sizes<Cv>(pl, z);
     int rc;
-    if ((rc = mb.counts.ensure(z.counts))) return rc;
-    if ((rc = mb.offsets.ensure(z.offsets))) return rc;
-    if ((rc = mb.entries.ensure(z.entries))) return rc;
-    if ((rc = mb.buckets.ensure(z.buckets))) return rc;
-    if ((rc = mb.part_pt.ensure(z.part_pt))) return rc;
-    if ((rc = mb.part_key.ensure(z.part_key))) return rc;
-    if ((rc = mb.seg.ensure(z.seg))) return rc;
-    if ((rc = mb.win.ensure(z.win))) return rc;
-    if (z.seg2 && ((rc = mb.seg2.ensure(z.seg2)) || (rc = mb.seg3.ensure(z.seg3)))) return rc;
-    // (growing a buffer frees the old one: hipFree waits for the device, so kernels of earlier jobs still reading it are safe)
-    if ((rc = (pl.shared_stage ? c->stage_shared : mb.stage).ensure(z.stage))) return rc;
+    for (const PreBuf& b : pre_bufs<Cv>(c, pl, mb))
+        if ((rc = b.buf->ensure(b.bytes))) return rc;
     return ZK_OK;
 }
 
@@ -289,9 +281,8 @@ template <class Cv>
 void jacobian_to_partial_host(const uint64_t* xyz, void* out) {
     typedef typename Cv::Fq Fq;
     typedef typename Cv::FqU F;
-    constexpr size_t PT = (size_t)4 * Store<F>::WORDS * 4;
     constexpr int L64 = Fq::N / 2;
-    memset(out, 0, PT);
+    memset(out, 0, Store<F>::POINT_BYTES);
     Fq Z;
     memcpy(Z.v, xyz + 2 * L64, sizeof(uint64_t) * L64);
     if (Z.is_zero()) return;                       // infinity: all limbs zero
@@ -310,20 +301,11 @@ template <class Cv>
 void pre_host_wide(const void* h, uint32_t log_bv, uint64_t* out_xyz) {
     typedef typename Cv::Fq Fq;
     typedef XYZZ<Fq> PH;
-    constexpr int L64 = Fq::N / 2;
     const PH* w = (const PH*)h;
     PH d = PH::add(w[2], PH::neg(w[3]));
     for (uint32_t k = 0; k < log_bv; ++k) d = PH::dbl(d);
     PH total = PH::add(w[1], d);
-    Fq X = Fq::one(), Y = Fq::one(), Z = Fq::zero();
-    if (!total.is_inf()) {
-        X = Fq::mul(total.x, total.zz);
-        Y = Fq::mul(total.y, total.zzz);
-        Z = total.zz;
-    }
-    memcpy(out_xyz, X.v, sizeof(uint64_t) * L64);
-    memcpy(out_xyz + L64, Y.v, sizeof(uint64_t) * L64);
-    memcpy(out_xyz + 2 * L64, Z.v, sizeof(uint64_t) * L64);
+    put_jacobian<Fq>(total, out_xyz);
 }
 
 // host: S = sum_v S_v + B_v * sum_v v * T_v   (bucket j of virtual window v has weight v*B_v + local index).
@@ -355,7 +337,6 @@ template <class Cv>
 void pre_host_final(const HostPartial<typename Cv::Fq>* part, uint32_t VW, uint32_t VB, uint64_t* out_xyz) {
     typedef typename Cv::Fq Fq;
     typedef XYZZ<Fq> PH;
-    constexpr int L64 = Fq::N / 2;
     // sum_c c * t_c by running sums, then times the chunk length (a power of two), plus the local weights
     PH total = PH::infinity(), run = PH::infinity(), ct = PH::infinity(), wsum = PH::infinity();
     for (int c = (int)HOST_CHUNKS - 1; c >= 0; --c) {
@@ -370,15 +351,7 @@ void pre_host_final(const HostPartial<typename Cv::Fq>* part, uint32_t VW, uint3
     wsum = PH::add(wsum, ct);
     for (uint32_t k = 0; (1u << k) < VB; ++k) wsum = PH::dbl(wsum);
     total = PH::add(total, wsum);
-    Fq X = Fq::one(), Y = Fq::one(), Z = Fq::zero();
-    if (!total.is_inf()) {
-        X = Fq::mul(total.x, total.zz);
-        Y = Fq::mul(total.y, total.zzz);
-        Z = total.zz;
-    }
-    memcpy(out_xyz, X.v, sizeof(uint64_t) * L64);
-    memcpy(out_xyz + L64, Y.v, sizeof(uint64_t) * L64);
-    memcpy(out_xyz + 2 * L64, Z.v, sizeof(uint64_t) * L64);
+    put_jacobian<Fq>(total, out_xyz);
 }
 template <class Cv>
 void pre_host_combine(const void* h_win, uint32_t VW, uint32_t VB, uint64_t* out_xyz) {
@@ -564,10 +537,11 @@ int msm_batch_pre_reduce(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* 
     return ZK_OK;
 }
 
-// the host tail of a round on the shared-bucket path: n_jobs x (VW pairs S_v | T_v in pinned memory, arkworks layout) -> Jacobian (and affine)
+// the host tail of a round on the shared-bucket path: n_jobs x (VW pairs S_v | T_v in pinned memory, arkworks layout) -> Jacobian (and affine).
+// wide_red: a job's wb bytes are the four sums of the wide reduction instead (pre_host_wide: a handful of additions, one item per job)
 template <class Cv>
-int pre_host_finish_jobs(zk_ctx* c, const char* h_win, size_t wb, uint32_t n_jobs, uint32_t VW, uint32_t VB, uint64_t* out_xyz /* n_jobs x 3L */,
-                         uint64_t* out_xy /* optional */, uint8_t* out_inf /* optional */) {
+int pre_host_finish_jobs(zk_ctx* c, const char* h_win, size_t wb, uint32_t n_jobs, bool wide_red, uint32_t VW, uint32_t VB,
+                         uint64_t* out_xyz /* n_jobs x 3L */, uint64_t* out_xy /* optional */, uint8_t* out_inf /* optional */) {
     typedef typename Cv::Fq Fq;
     constexpr int L64 = Fq::N / 2;
     int rcs[MAX_JOBS] = {0};
@@ -576,13 +550,15 @@ int pre_host_finish_jobs(zk_ctx* c, const char* h_win, size_t wb, uint32_t n_job
     // finishes a job's last range also does that job's final sum and affine normalisation -- one wake-up of the pool per round
     HostPartial<Fq> part[MAX_JOBS * HOST_CHUNKS];
     std::atomic<uint32_t> left[MAX_JOBS];
-    for (uint32_t k = 0; k < n_jobs; ++k) left[k].store(HOST_CHUNKS);
-    c->pool->run(n_jobs * HOST_CHUNKS, [&](uint32_t i) {
-        const uint32_t k = i / HOST_CHUNKS, ch = i % HOST_CHUNKS;
-        pre_host_partial<Cv>(h_win + (size_t)k * wb, VW, ch * (VW / HOST_CHUNKS), (ch + 1) * (VW / HOST_CHUNKS), part[i]);
+    const uint32_t per = wide_red ? 1 : HOST_CHUNKS;       // pool items per job
+    for (uint32_t k = 0; k < n_jobs; ++k) left[k].store(per);
+    c->pool->run(n_jobs * per, [&](uint32_t i) {
+        const uint32_t k = i / per, ch = i % per;
+        if (!wide_red) pre_host_partial<Cv>(h_win + (size_t)k * wb, VW, ch * (VW / HOST_CHUNKS), (ch + 1) * (VW / HOST_CHUNKS), part[k * HOST_CHUNKS + ch]);
         if (left[k].fetch_sub(1, std::memory_order_acq_rel) != 1) return;
         uint64_t* xyz = out_xyz + (size_t)k * 3 * L64;
-        pre_host_final<Cv>(part + k * HOST_CHUNKS, VW, VB, xyz);
+        if (wide_red) pre_host_wide<Cv>(h_win + (size_t)k * wb, ilog2_floor(VB), xyz);
+        else pre_host_final<Cv>(part + k * HOST_CHUNKS, VW, VB, xyz);
         if (out_xy) rcs[k] = jac_to_affine<Fq>(xyz, out_xy + (size_t)k * 2 * L64, out_inf ? out_inf + k : nullptr);
     });
     for (uint32_t k = 0; k < n_jobs; ++k)
@@ -608,14 +584,12 @@ int sum_winsums_dev(zk_ctx* c, zk_srs* s, const void* d_all, size_t ranks, uint3
     if ((rc = ZK_SYM(queue_sum_winsums)(c, d_all, (uint32_t)ranks, n_pts, c->pinned, c->stream))) return rc;
     ZK_HIP_TRY(hipStreamSynchronize(c->stream));
     uint64_t xyz[MAX_JOBS * 3 * L64];
-    return pre_host_finish_jobs<Cv>(c, (const char*)c->pinned, wb, n_jobs, VW, VB, xyz, out_xy, out_inf);
+    return pre_host_finish_jobs<Cv>(c, (const char*)c->pinned, wb, n_jobs, false, VW, VB, xyz, out_xy, out_inf);
 }
 
 template <class Cv>
 int msm_batch_pre_end(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slots, const size_t* lens, uint64_t* out_xyz /* n_jobs x 3L */,
                       uint64_t* out_xy /* optional: n_jobs x 2L affine */, uint8_t* out_inf /* optional flags */) {
-    typedef typename Cv::Fq Fq;
-    constexpr int L64 = Fq::N / 2;
     if (n_jobs == 0) return ZK_OK;
     if (n_jobs > (uint32_t)MAX_JOBS) return ZK_ERR_UNSUPPORTED;
     int rc;
@@ -624,35 +598,9 @@ int msm_batch_pre_end(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slo
     PrePlan pl[MAX_JOBS];
     for (uint32_t k = 0; k < n_jobs; ++k)
         if ((rc = pre_plan_geom<Cv>(c, s, lens[k], pl[k]))) return rc;
-    const size_t wb = pl[0].win_bytes;
-    static const bool host_timing = getenv("ZK_HOST_TIMING") != nullptr;      // diagnostic: where the host tail of a round goes
-    const auto t0 = std::chrono::steady_clock::now();
     ZK_HIP_TRY(hipEventSynchronize(c->round.ev));
-    const auto t1 = std::chrono::steady_clock::now();
-    struct TailTimer {
-        bool on;
-        uint32_t n;
-        std::chrono::steady_clock::time_point t0, t1;
-        ~TailTimer() {
-            if (!on) return;
-            const auto t2 = std::chrono::steady_clock::now();
-            fprintf(stderr, "[zk host tail] jobs %u: wait for the stream %.1f us, combine + affine %.1f us\n", n,
-                    std::chrono::duration<double, std::micro>(t1 - t0).count(), std::chrono::duration<double, std::micro>(t2 - t1).count());
-        }
-    } tail_timer{host_timing, n_jobs, t0, t1};
-    const char* h_win = (const char*)c->pinned;
-    if (pl[0].wide_red) {
-        int rcs[MAX_JOBS] = {0};
-        c->pool->run(n_jobs, [&](uint32_t k) {
-            uint64_t* xyz = out_xyz + (size_t)k * 3 * L64;
-            pre_host_wide<Cv>(h_win + (size_t)k * wb, ilog2_floor(pl[k].gv.B), xyz);
-            if (out_xy) rcs[k] = jac_to_affine<Fq>(xyz, out_xy + (size_t)k * 2 * L64, out_inf ? out_inf + k : nullptr);
-        });
-        for (uint32_t k = 0; k < n_jobs; ++k)
-            if (rcs[k]) return rcs[k];
-        return ZK_OK;
-    }
-    return pre_host_finish_jobs<Cv>(c, h_win, wb, n_jobs, pl[0].gv.W, pl[0].gv.B, out_xyz, out_xy, out_inf);
+    // every job of a round has the geometry of the first (msm_batch_pre_reduce refuses a round otherwise)
+    return pre_host_finish_jobs<Cv>(c, (const char*)c->pinned, pl[0].win_bytes, n_jobs, pl[0].wide_red, pl[0].gv.W, pl[0].gv.B, out_xyz, out_xy, out_inf);
 }
 
 // The blocking form: begin every job, end them together.  Under the memory budget (msm_batch_pre_begin) the call may come in
@@ -705,11 +653,7 @@ int jac_to_affine(const uint64_t* xyz, uint64_t* out_xy, uint8_t* out_inf) {
     memcpy(Y.v, xyz + L64, sizeof(uint64_t) * L64);
     memcpy(Z.v, xyz + 2 * L64, sizeof(uint64_t) * L64);
     if (Z.is_zero()) {
-        // GroupAffine::zero() = (0, 1, infinity = true)
-        Fq zero = Fq::zero(), one = Fq::one();
-        memcpy(out_xy, zero.v, sizeof(uint64_t) * L64);
-        memcpy(out_xy + L64, one.v, sizeof(uint64_t) * L64);
-        if (out_inf) *out_inf = 1;
+        put_affine_zero<Fq>(out_xy, out_inf);
         return ZK_OK;
     }
     Fq zi = Fq::inverse(Z);
@@ -744,10 +688,7 @@ int sum_partials(const uint64_t* partials, size_t count, uint64_t* out_xy, uint8
     Affine<Fq> a;
     bool fin = acc.to_affine(a);
     if (!fin) {
-        Fq one = Fq::one();
-        memset(out_xy, 0, sizeof(uint64_t) * L64);
-        memcpy(out_xy + L64, one.v, sizeof(uint64_t) * L64);
-        if (out_inf) *out_inf = 1;
+        put_affine_zero<Fq>(out_xy, out_inf);
         return ZK_OK;
     }
     memcpy(out_xy, a.x.v, sizeof(uint64_t) * L64);

@@ -10,6 +10,7 @@ template <class F>
 struct Store {
     static constexpr int U4 = (F::NL + 3) / 4;      // uint4 per field element
     static constexpr int WORDS = 4 * U4;
+    static constexpr size_t POINT_BYTES = (size_t)4 * WORDS * 4;    // bytes of one stored XYZZ point
 };
 template <class F>
 ZK_D F ld_fu(const uint4* q) {

@@ -108,7 +108,7 @@ int zk_ctx_set_staging(zk_ctx* ctx, int mode);
  *                         and the computed / uploaded value is used.  A diagnostic mode: it costs what the caches save
  * ZK_ERR_UNSUPPORTED: unknown key; ZK_ERR_BAD_ARG: value out of range; ZK_ERR_PENDING: a deferred round is open (a job's plan must
  * not change between its accumulation and its reduction).  The library reads NO environment variable on a compute path
- * (ZK_VERBOSE and ZK_HOST_TIMING switch diagnostics on stderr only). */
+ * (ZK_VERBOSE switches diagnostics on stderr only). */
 /* Residency cache of the HOST-POINTER entry points (opt-in, per ctx; round 5).  The reference's call structure sends the same
  * vector across PCIe again and again: an `ifft` output goes straight back up as a `PC::commit` input (prover.rs:196-213), then as a
  * `coset_fft` input (quotient_poly.rs:72-120), then into the last round's commitments and openings (prover.rs:569-618) -- about 58 of
