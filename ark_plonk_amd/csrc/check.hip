@@ -38,11 +38,8 @@ constexpr uint32_t CTAB = 48;                     // multiples of r held for the
 constexpr uint32_t BIT_ARITH = 0, BIT_RANGE = 1, BIT_LOGIC = 5, BIT_FIXED = 10, BIT_CURVE = 14, BIT_LOOKUP = 17, BIT_COPY = 18;
 
 // ---------------------------------------------------------------------------------------------------------------- key map
-// A key is W field elements: element k of key i is col[k][i] (W = 4: a table row; W = 1: an identity encoding).
-template <int W>
-struct Key {
-    El e[W];
-};
+// A key is W field elements (Key<W>, key_hash: fr_io.cuh): element k of key i is col[k][i] (W = 4: a table row; W = 1: an identity
+// encoding).
 struct KeyCols {
     const void* col[4];
 };
@@ -59,13 +56,6 @@ ZK_D bool key_eq(const Key<W>& x, const Key<W>& y) {
 #pragma unroll
     for (int j = 0; j < W; ++j) eq = eq && el_eq(x.e[j], y.e[j]);
     return eq;
-}
-template <int W>
-ZK_D uint32_t key_hash(const Key<W>& k) {
-    uint64_t h = 0;
-#pragma unroll
-    for (int j = 0; j < W; ++j) h = el_mix(h, k.e[j]);
-    return (uint32_t)(h ^ (h >> 32));
 }
 // Index of a key of the map equal to `q`, or EMPTY.  Every occupant on the way is compared in full.
 template <int W>
@@ -205,7 +195,7 @@ struct CArgsU {
 template <class F>
 __global__ void __launch_bounds__(CT) check_gates(const CArgsU<F>* __restrict__ Ap, uint64_t n, uint32_t* mask) {
     typedef Z<F, 10> C;      // a constant of the argument block (canonical)
-    typedef Z<F, 12> L;      // a loaded column value
+    typedef Z<F, RP_B> L;      // a loaded column value
     __shared__ uint32_t rtab[CTAB][F::NL];
     const CArgsU<F>& A = *Ap;
     for (uint32_t k = threadIdx.x; k < CTAB * F::NL; k += CT) rtab[k / F::NL][k % F::NL] = A.rtab[k / F::NL][k % F::NL];

@@ -52,6 +52,18 @@ ZK_D uint64_t el_mix(uint64_t h, const El& e) {
     return h;
 }
 ZK_D uint32_t el_hash(const El& e) { return (uint32_t)el_mix(0, e); }
+// a key of W elements (check.hip's maps: W = 4 a table row, W = 1 an identity encoding) and its hash
+template <int W>
+struct Key {
+    El e[W];
+};
+template <int W>
+ZK_D uint32_t key_hash(const Key<W>& k) {
+    uint64_t h = 0;
+#pragma unroll
+    for (int j = 0; j < W; ++j) h = el_mix(h, k.e[j]);
+    return (uint32_t)(h ^ (h >> 32));
+}
 
 // ---- the 29-bit-limb type
 

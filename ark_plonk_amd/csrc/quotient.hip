@@ -48,7 +48,7 @@ struct QArgsU {
 template <class F>
 __global__ void __launch_bounds__(QT, 2) quotient_points(const QArgsU<F>* __restrict__ Ap, uint64_t n4, void* out) {
     typedef Z<F, 10> C;      // a constant of the argument block (canonical)
-    typedef Z<F, 12> L;      // a loaded column value
+    typedef Z<F, RP_B> L;      // a loaded column value
     __shared__ uint32_t rtab[QTAB][F::NL];
     const QArgsU<F>& A = *Ap;
     for (uint32_t k = threadIdx.x; k < QTAB * F::NL; k += QT) rtab[k / F::NL][k % F::NL] = A.rtab[k / F::NL][k % F::NL];

@@ -61,18 +61,26 @@ ZK_D Z<F, 20> delta4(const Z<F, B>& f, const Z<F, 10>& one, const Z<F, 10>& c2, 
     return (f * (f - one)) * ((f - c2) * (f - c3));
 }
 
-// arkworks Montgomery value x * 2^256 (canonical, 8 words) -> x * 2^261 mod r, < 1.2 r:
-// shift left by 5 bits (32 v < 32 r < 2^260), subtract q2 * r with q2 = floor(floor(32 v / 2^BITS) * (2^BITS / r)) <= 32 v / r
-// (leaves < 2.15 r), then r once more if the rest is still >= r.  rtab[q] = q * r, ratio_fx and top_shift: rp_table below.
+// arkworks Montgomery value x * 2^256 (canonical, 8 words) -> x * 2^261 mod r, < RP_B / 10 * r:
+// shift left by 5 bits (32 v < 32 r < 2^260), subtract q2 * r with q2 = floor(T * ratio_fx / 2^13), T = floor(32 v / 2^(BITS - 3)) < 256
+// (three bits below the 2^BITS place, so the truncated top costs < 2^BITS / 8r = 0.17 r), then r once more if the rest is still >= r.
+// ratio_fx / 2^10 < 2^BITS / r by less than 2^-9, so q2 <= 32 v / r (the difference never goes negative) and
+//     32 v / r - q2  <  1 (floor) + 2^BITS / 8r (top) + 256 / 2^12 (ratio)  <  1.23:
+// the rest is < 1.23 r before and < r after the conditional subtraction, on both curves.  Measured by the host harness
+// (tests/test_fieldu.py: the boundary words and 10^5 random ones per curve): the largest result is r - 1 on BLS12-381 and on BN254
+// (rest before the subtraction: 1.155 r and 1.177 r), at most 31 r taken off.  With the top truncated at the 2^BITS place
+// (>> top_shift, >> 10) the same inputs gave 1.083 r and 1.290 r: past the 1.2 r every L below is typed with.
+// RP_B stays at 12: no rule below needs it tighter.  rtab[q] = q * r, ratio_fx and top_shift: rp_table below.
+constexpr int RP_B = 12;      // a loaded value is a Z<F, RP_B>: the L type of quotient.hip and check.hip
 template <class F>
-ZK_D Z<F, 12> to_rp(const El& e, const uint32_t (*rtab)[F::NL], uint32_t ratio_fx, uint32_t top_shift) {
+ZK_D Z<F, RP_B> to_rp(const El& e, const uint32_t (*rtab)[F::NL], uint32_t ratio_fx, uint32_t top_shift) {
     uint32_t w[8] = {e.a.x, e.a.y, e.a.z, e.a.w, e.b.x, e.b.y, e.b.z, e.b.w};
     F l = F::split_words(w);
     F s;
 #pragma unroll
     for (int i = F::NL - 1; i >= 1; --i) s.v[i] = ((l.v[i] << 5) | (l.v[i - 1] >> 24)) & (i == F::NL - 1 ? 0xffffffffu : F::M);
     s.v[0] = (l.v[0] << 5) & F::M;
-    const uint32_t q2 = ((s.v[F::NL - 1] >> top_shift) * ratio_fx) >> 10;
+    const uint32_t q2 = ((s.v[F::NL - 1] >> (top_shift - 3)) * ratio_fx) >> 13;
     F t;
 #pragma unroll
     for (int i = 0; i < F::NL; ++i) t.v[i] = s.v[i] - rtab[q2][i];
@@ -85,10 +93,10 @@ ZK_D Z<F, 12> to_rp(const El& e, const uint32_t (*rtab)[F::NL], uint32_t ratio_f
     F r;
 #pragma unroll
     for (int i = 0; i < F::NL; ++i) r.v[i] = neg ? t.v[i] : d.v[i];
-    return Z<F, 12>(r);
+    return Z<F, RP_B>(r);
 }
 template <class F>
-ZK_D Z<F, 12> ld_rp(const void* base, uint64_t idx, const uint32_t (*rtab)[F::NL], uint32_t ratio_fx, uint32_t top_shift) {
+ZK_D Z<F, RP_B> ld_rp(const void* base, uint64_t idx, const uint32_t (*rtab)[F::NL], uint32_t ratio_fx, uint32_t top_shift) {
     return to_rp<F>(ld_el(base, idx), rtab, ratio_fx, top_shift);
 }
 
@@ -101,7 +109,8 @@ typename Cv::FrU to_rp_host(const typename Cv::Fr& v) {
     return Cv::FrU::split_words(t.v);
 }
 // what to_rp reads: rtab[q] = q * r as 29-bit limbs for q < len, ratio_fx = floor(2^BITS / r * 2^10) - 1 and
-// top_shift = BITS - 29 * (NL - 1).  len must cover the largest q2 (32 v / r < 32, and the estimate never exceeds it).
+// top_shift = BITS - 29 * (NL - 1) (>= 3: to_rp keeps three bits below it).  len must cover the largest q2 (32 v / r < 32, and the
+// estimate never exceeds it).
 template <class Cv>
 void rp_table(uint32_t (*rtab)[Cv::FrU::NL], uint32_t len, uint32_t& ratio_fx, uint32_t& top_shift) {
     typedef typename Cv::FrU FU;
@@ -116,6 +125,7 @@ void rp_table(uint32_t (*rtab)[Cv::FrU::NL], uint32_t len, uint32_t& ratio_fx, u
     long double rv = 0;
     for (int i = Cv::Fr::N - 1; i >= 0; --i) rv = rv * 4294967296.0L + (long double)Cv::FrP::MOD(i);
     ratio_fx = (uint32_t)floorl(ldexpl(1.0L, Cv::FrP::BITS + 10) / rv) - 1;
+    static_assert(Cv::FrP::BITS - 29 * (FU::NL - 1) >= 3, "to_rp reads three bits below the 2^BITS place of the top limb");
     top_shift = (uint32_t)(Cv::FrP::BITS - 29 * (FU::NL - 1));
 }
 

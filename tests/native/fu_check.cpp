@@ -1,11 +1,21 @@
 // Host-side harness for the unsaturated fields / lazy XYZZ code (fieldu.cuh, fields.cuh, ecu.cuh): the same
 // templates the HIP kernels instantiate, compiled with g++ so tests/test_fieldu.py can check them
-// against the big-int oracle without a GPU.
+// against the big-int oracle without a GPU; and for the device-only load conversion of the quotient kernel and the circuit
+// check (zbound.cuh) and the hash of the device key maps (fr_io.cuh).
 #include <cstdint>
 #include <cstring>
 #include "../../ark_plonk_amd/csrc/curve_params.h"
+#include "../../ark_plonk_amd/csrc/field.cuh"
 #include "../../ark_plonk_amd/csrc/fieldu.cuh"
 #include "../../ark_plonk_amd/csrc/ecu.cuh"
+#if !defined(__HIPCC__)
+struct uint4 {                            // the 16-byte vector type of the device headers, for the host build
+    uint32_t x, y, z, w;
+};
+static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
+#endif
+#include "../../ark_plonk_amd/csrc/fr_io.cuh"
+#include "../../ark_plonk_amd/csrc/zbound.cuh"
 
 template <class F>
 static void fs_dot2(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
@@ -68,6 +78,43 @@ typedef Fu<FrBn254UParams> FrN;
 typedef Fs<FqBls12_381SParams> FqBs;     // signed 30-bit limbs (fields.cuh): the base fields
 typedef Fs<FqBn254SParams> FqNs;
 
+// the device-only pieces of the quotient kernel and the circuit check: the load conversion (zbound.cuh) and the hash of the key maps
+// (fr_io.cuh), over the three members of a curve they read
+struct HostBls {
+    typedef Fp<FrBls12_381Params> Fr;
+    typedef FrB FrU;
+    typedef FrBls12_381Params FrP;
+};
+struct HostBn {
+    typedef Fp<FrBn254Params> Fr;
+    typedef FrN FrU;
+    typedef FrBn254Params FrP;
+};
+constexpr uint32_t RP_ROWS = 64;         // multiples of r held by the harness: more than either kernel holds
+static El el_of(const uint32_t* w) {
+    El e;
+    e.a = make_uint4(w[0], w[1], w[2], w[3]);
+    e.b = make_uint4(w[4], w[5], w[6], w[7]);
+    return e;
+}
+template <class Cv>
+static void to_rp_many(const uint32_t* words_in, uint32_t* limbs_out, uint64_t n) {
+    typedef typename Cv::FrU FU;
+    static uint32_t rtab[RP_ROWS][FU::NL];
+    uint32_t ratio_fx, top_shift;
+    rp_table<Cv>(rtab, RP_ROWS, ratio_fx, top_shift);
+    for (uint64_t k = 0; k < n; ++k) {
+        const Z<FU, RP_B> z = to_rp<FU>(el_of(words_in + 8 * k), rtab, ratio_fx, top_shift);
+        for (int i = 0; i < FU::NL; ++i) limbs_out[FU::NL * k + i] = z.v.v[i];
+    }
+}
+template <int W>
+static uint32_t key_hash_of(const uint32_t* words) {
+    Key<W> k;
+    for (int j = 0; j < W; ++j) k.e[j] = el_of(words + 8 * j);
+    return key_hash<W>(k);
+}
+
 // raw signed-limb operands (no conversion on the way in): the worst-case limb patterns of the column bounds of fields.cuh.
 // op 0: mul(a, b)   1: sqr(a)   2: dot2(a, b, c, d)   3: sub_sum3(a, b, c, d) (strict operands)   4: add3 / sub chains
 template <class F>
@@ -104,6 +151,15 @@ void fu_op(int field, int op, const uint32_t* a, const uint32_t* b, uint32_t* ou
     case 3: fu_binop<FrN>(op, a, b, out); break;
     }
 }
+// field: 1 Fr-BLS, 3 Fr-BN.  n stored words (8 x 32 bits each, canonical) -> the limbs to_rp returns (FrU::NL each), as they are
+void fu_to_rp(int field, const uint32_t* words_in, uint32_t* limbs_out, uint64_t n) {
+    if (field == 1) to_rp_many<HostBls>(words_in, limbs_out, n);
+    else to_rp_many<HostBn>(words_in, limbs_out, n);
+}
+int fu_rp_bound() { return RP_B; }        // a loaded value is < RP_B / 10 * r
+int fu_rp_limbs() { return FrB::NL; }
+uint64_t fu_el_mix(uint64_t h, const uint32_t* words) { return el_mix(h, el_of(words)); }
+uint32_t fu_key_hash(int w, const uint32_t* words) { return w == 1 ? key_hash_of<1>(words) : key_hash_of<4>(words); }
 int fu_xyzz_chain(int curve, const uint32_t* pts_xy, const uint8_t* flags, int n, uint32_t* out_xy) {
     return curve == 0 ? xyzz_chain<FqBs>(pts_xy, flags, n, out_xy) : xyzz_chain<FqNs>(pts_xy, flags, n, out_xy);
 }

@@ -1,14 +1,19 @@
 """CPU check of the unsaturated fields (29-bit limbs for the scalar fields: fieldu.cuh; signed 30-bit limbs for the base
 fields: fields.cuh) and of the lazy XYZZ group law (ecu.cuh) that the HIP kernels use, compiled for the host and compared
-with big-int arithmetic."""
+with big-int arithmetic; and of two device-only pieces: the load conversion of the quotient kernel and the circuit check (to_rp,
+zbound.cuh) on boundary and random stored words, and the hash of the device key maps (fr_io.cuh) against its Python restatement
+(tests/edge_values.py), on which the crafted collisions of the GPU suite rest."""
 import ctypes
 import os
+import random
+import re
 import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import bigint_oracle as bo
+from tests import edge_values as ev
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "fu_check.cpp")
@@ -17,13 +22,19 @@ SO = os.path.join(ROOT, "tests", "native", "libfu_check.so")
 
 @pytest.fixture(scope="module")
 def fu():
-    deps = [SRC] + [os.path.join(ROOT, "ark_plonk_amd", "csrc", f) for f in ("fieldu.cuh", "fields.cuh", "ecu.cuh", "curve_params.h", "zk_common.h")]
+    deps = [SRC] + [os.path.join(ROOT, "ark_plonk_amd", "csrc", f) for f in ("fieldu.cuh", "fields.cuh", "ecu.cuh", "curve_params.h", "zk_common.h", "field.cuh", "fr_io.cuh", "zbound.cuh")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "c++", SRC, "-o", SO])
     L = ctypes.CDLL(SO)
     L.fu_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.fu_xyzz_chain.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     L.fs_raw_op.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+    L.fu_to_rp.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    L.fu_to_rp.restype = None
+    L.fu_el_mix.argtypes = [ctypes.c_uint64, ctypes.c_void_p]
+    L.fu_el_mix.restype = ctypes.c_uint64
+    L.fu_key_hash.argtypes = [ctypes.c_int, ctypes.c_void_p]
+    L.fu_key_hash.restype = ctypes.c_uint32
     return L
 
 
@@ -173,3 +184,91 @@ def test_signed_limbs_at_the_edge_of_the_column_bound(field, fu):
         b = np.array([sb] * (nl - 1) + [-3], dtype=np.int32)
         fu.fs_raw_op(field, 3, a.ctypes.data, b.ctypes.data, b.ctypes.data, b.ctypes.data, out.ctypes.data)
         assert val(out) == val(a) - 3 * val(b) and all(abs(int(v)) <= E for v in out[:-1]), (sa, sb)
+
+
+# ---- the load conversion of the quotient kernel and the circuit check (zbound.cuh)
+def _table_rows():
+    """QTAB and CTAB: the multiples of r the two kernels hold"""
+    out = []
+    for unit, name in (("quotient.hip", "QTAB"), ("check.hip", "CTAB")):
+        text = open(os.path.join(ROOT, "ark_plonk_amd", "csrc", unit)).read()
+        out.append(int(re.search(r"constexpr uint32_t %s = (\d+);" % name, text).group(1)))
+    return out
+
+
+@pytest.mark.parametrize("field", [1, 3])
+def test_to_rp_is_32v_below_its_bound(field, fu):
+    """to_rp(v) for the stored word v: congruent to 32 v, normalised limbs, below RP_B / 10 * r -- the premise of every Z<F, B> rule
+    the two kernels compile under -- and never past the multiples of r either kernel holds.  Boundary words (where the true quotient
+    and the truncated top the estimate starts from step) and 10^5 random canonical words.  The multiple of r that was taken off,
+    (32 v - result) / r, is q2 or q2 + 1: it bounds q2 from above."""
+    r = FIELDS[field][0]
+    rng = random.Random(0x70 + field)
+    vs = ev.to_rp_boundary_words(r) + [rng.randrange(r) for _ in range(100000)]
+    nl, bound = fu.fu_rp_limbs(), fu.fu_rp_bound()
+    win = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vs), dtype="<u4").copy()
+    out = np.zeros(nl * len(vs), dtype="<u4")
+    fu.fu_to_rp(field, win.ctypes.data, out.ctypes.data, len(vs))
+    assert int(out.max()) < 1 << 29, "limbs not normalised"
+    limbs = out.reshape(len(vs), nl).astype(object)
+    got = [int(sum(int(l[i]) << (29 * i) for i in range(nl))) for l in limbs]
+    worst, worst_q = 0, 0
+    for v, g in zip(vs, got):
+        assert (g - 32 * v) % r == 0, hex(v)
+        worst, worst_q = max(worst, g), max(worst_q, (32 * v - g) // r)
+    print(f"to_rp field {field}: largest result {worst / r:.6f} r, largest multiple of r taken off {worst_q}")
+    assert 10 * worst < bound * r, f"{worst / r:.4f} r against a bound of {bound / 10} r"
+    assert worst_q < min(_table_rows())
+
+
+# ---- the hash of the device key maps (fr_io.cuh) and its restatement
+def _w8(v):
+    return np.frombuffer(int(v).to_bytes(32, "little"), dtype="<u4").copy()
+
+
+def test_hash_restatement_and_crafted_collisions(fu):
+    """tests/edge_values.py restates el_mix / key_hash; the crafted collisions of the GPU suite collide under the restatement, so it
+    has to BE the compiled hash: on random words and chains, on every colliding pair (equal el_mix from any chained state, distinct
+    words, both canonical on both curves) and on every member of a slot cluster."""
+    rng = random.Random(0xE1)
+    for _ in range(2000):
+        v, h = rng.getrandbits(256), rng.getrandbits(64)
+        assert fu.fu_el_mix(h, _w8(v).ctypes.data) == ev.el_mix(h, v)
+        assert fu.fu_el_mix(0, _w8(v).ctypes.data) & 0xFFFFFFFF == ev.el_hash(v)
+        key = [rng.getrandbits(256) for _ in range(4)]
+        buf = np.concatenate([_w8(k) for k in key])
+        assert fu.fu_key_hash(4, buf.ctypes.data) == ev.key_hash(key)
+        assert fu.fu_key_hash(1, buf.ctypes.data) == ev.key_hash(key[:1])
+    small_r = min(bo.BLS12_381.r, bo.BN254.r)
+    for _ in range(500):
+        a, b = ev.colliding_pair(rng)
+        h = rng.getrandbits(64)
+        assert a != b and a < small_r and b < small_r and a >> 252 == 0 and b >> 252 == 0
+        assert fu.fu_el_mix(h, _w8(a).ctypes.data) == fu.fu_el_mix(h, _w8(b).ctypes.data) == ev.el_mix(h, a)
+        pre = [rng.getrandbits(256) for _ in range(3)]
+        ka, kb = np.concatenate([_w8(k) for k in pre + [a]]), np.concatenate([_w8(k) for k in pre + [b]])
+        assert fu.fu_key_hash(4, ka.ctypes.data) == fu.fu_key_hash(4, kb.ctypes.data) == ev.key_hash(pre + [a])
+    for cv in (bo.BLS12_381, bo.BN254):                    # a partner of a given word (an identity encoding of the copy map)
+        v = ev.stored_word(cv, 7 * cv.root_of_unity(3) % cv.r)
+        p = ev.colliding_partner(v, rng)
+        assert p != v and fu.fu_key_hash(1, _w8(p).ctypes.data) == fu.fu_key_hash(1, _w8(v).ctypes.data)
+        assert ev.stored_word(cv, ev.field_value(cv, p % cv.r)) == p % cv.r
+    for mask, slot in ((1023, 1023), (1023, 1022), (511, 511)):
+        pre = [rng.getrandbits(256) for _ in range(3)]
+        for v in ev.slot_cluster(mask, slot, 8, ev.el_hash, seed=1):
+            assert fu.fu_el_mix(0, _w8(v).ctypes.data) & mask == slot
+        wide = ev.slot_cluster(mask, slot, 8, lambda v: ev.key_hash(pre + [v]), seed=2)
+        assert len(set(wide)) == 8
+        for v in wide:
+            assert fu.fu_key_hash(4, np.concatenate([_w8(k) for k in pre + [v]]).ctypes.data) & mask == slot
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_edge_elements_are_what_they_say(cid):
+    cv = bo.CURVES[cid]
+    e = ev.edge_elements(cv)
+    assert len(set(e)) == len(e) and all(0 <= x < cv.r for x in e)
+    for x in (0, 1, 2, 3, cv.r - 1, cv.r - 2, cv.r - 3, (cv.r - 1) // 2, (cv.r + 1) // 2, 1 << 29, (1 << 232) - 1, 1 << 192, (1 << 64) - 1):
+        assert x in e
+    words = ev.to_rp_boundary_words(cv.r)
+    assert all(ev.field_value(cv, v) in e for v in words) and len(words) > 150

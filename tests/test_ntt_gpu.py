@@ -5,6 +5,7 @@ import pytest
 
 import ark_plonk_amd as zk
 from oracle import bigint_oracle as bo
+from tests import edge_values as ev
 
 pytestmark = pytest.mark.gpu
 
@@ -83,6 +84,47 @@ def test_vs_cpu_oracle_all_kinds(cid, log_n, ctx, oracle_cpu):
             exp = oracle_cpu.ntt(cid, kind, log_n, x)
             got = run_kind(dom, kind, x)
             assert np.array_equal(got, exp), (log_n, kind, in_len)
+
+
+def _edge_limbs(oracle_cpu, cid):
+    return oracle_cpu.convert(cid, "fr", True, oracle_cpu.ints_to_limbs(ev.edge_elements(bo.CURVES[cid]), 4))
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+@pytest.mark.parametrize("log_n", [4, 6, 15, 18, 19])
+def test_vs_cpu_oracle_edge_inputs(cid, log_n, ctx, oracle_cpu):
+    """The sizes the matrix above skips -- 18 and 19 are the (9, 9) and (7, 6, 6) decompositions, 15 the (8, 7) one -- on inputs no
+    seeded draw gives: the edge set of tests/edge_values.py tiled (all four kinds), and a single one at position 0, 1 and n - 1 and
+    0 / r - 1 alternating (two kinds each, in turn)."""
+    cv = bo.CURVES[cid]
+    n = 1 << log_n
+    e = _edge_limbs(oracle_cpu, cid)
+    one, minus_one = oracle_cpu.convert(cid, "fr", True, oracle_cpu.ints_to_limbs([1, cv.r - 1], 4))
+    inputs = [("edges", np.tile(e, (-(-n // e.shape[0]), 1))[:n].copy(), (0, 1, 2, 3))]
+    for j, pos in enumerate((0, 1, n - 1)):
+        x = np.zeros((n, 4), dtype=np.uint64)
+        x[pos] = one
+        inputs.append((f"one at {pos}", x, (j % 4, (j + 2) % 4)))
+    x = np.zeros((n, 4), dtype=np.uint64)
+    x[1::2] = minus_one
+    inputs.append(("0 / r-1", x, (3, 1)))
+    dom = zk.Radix2EvaluationDomain.new(n, cid, ctx)
+    for name, x, kinds in inputs:
+        for kind in kinds:
+            assert np.array_equal(run_kind(dom, kind, x), oracle_cpu.ntt(cid, kind, log_n, x)), (name, kind)
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+@pytest.mark.parametrize("log_n", [0, 1, 2])
+def test_smallest_domains_on_the_edge_set(cid, log_n, ctx, oracle_cpu):
+    """n = 1, 2, 4: the whole edge set, n values at a time, all four kinds."""
+    n = 1 << log_n
+    e = _edge_limbs(oracle_cpu, cid)
+    dom = zk.Radix2EvaluationDomain.new(n, cid, ctx)
+    for lo in range(0, e.shape[0] - n + 1, n):
+        x = e[lo:lo + n].copy()
+        for kind in range(4):
+            assert np.array_equal(run_kind(dom, kind, x), oracle_cpu.ntt(cid, kind, log_n, x)), (lo, kind)
 
 
 @pytest.mark.parametrize("cid", [0, 1])
