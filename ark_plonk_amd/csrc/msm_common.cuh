@@ -262,10 +262,23 @@ constexpr uint32_t PRE_BIG_ROUNDS = 8;
 
 // The compact form of the wide partition sort (csort_* in msm_sort.hip): a whole table of folded 17-bit windows whose job owns its
 // staging area.  The folded scalar (< 2^254, the fold's sign in bit 255) waits in the job's set instead of the int32 digits, and the
-// staged record is ONE word: sign << 31 | window << 27 | index inside the slab << 8 | low bucket bits, so at most 16 windows and
-// slabs below 2^19 scalars (nf < 2^31 keeps them below 2^18); from 8 windows on the scalars fit where the references will be.  Every other geometry keeps psort_*.
+// staged record is ONE word (cs_pack below), so at most 16 windows and slabs below 2^19 scalars (nf < 2^31 keeps them below 2^18);
+// from 8 windows on the scalars fit where the references will be.  Every other geometry keeps psort_*.
 constexpr uint32_t CS_C = 17;
 constexpr uint32_t CS_LOB = CS_C - 9;
+
+// The two word layouts of the table path's sort, side by side.
+//   reference       sign << 31 | window << 26 | point index         what `entries` holds (the per-window path: window 0, 31 bits of
+//                                                                   index); its reader is point_index of msm_accumulate.hip
+//   compact record  sign << 31 | window << 27 | index inside the slab << 8 | low CS_LOB bucket bits        what csort_scatter stages
+ZK_HD uint32_t make_ref(uint32_t neg, uint32_t window, uint32_t index) { return (neg << 31) | (window << 26) | index; }
+ZK_HD uint32_t cs_pack(uint32_t neg, uint32_t window, uint32_t rel, uint32_t low) { return ((rel << 8) | low) | (window << 27) | (neg << 31); }
+// the reference of compact record v, staged by slab `slab` of a job of n scalars in slabs of sp
+ZK_HD uint32_t cs_ref(uint32_t v, uint32_t slab, uint32_t sp, uint32_t n) {
+    const uint32_t first = slab * sp < n ? slab * sp : n;
+    return (v & 0x80000000u) | (((v >> 27) & 15u) << 26) | (first + ((v >> 8) & 0x7ffffu));
+}
+
 inline bool pre_compact(const PrePlan& pl) {
     return pl.wide && pl.g.c == CS_C && pl.g.neg && pl.g.W == pl.g.Wt && pl.g.w0 == 0 && pl.g.wstep == 1 && pl.g.W >= 8 && pl.g.W <= 16 && !pl.shared_stage;
 }

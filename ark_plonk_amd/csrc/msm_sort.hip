@@ -8,8 +8,11 @@
 //                           proof): the folded scalar waits instead of the digits, one staged word per reference
 //   else          psort_*   every other geometry (16 .. 21 bits; window-sharded or shared-stage tables): a digit array, and a staged
 //                           reference with its low bucket bits beside it.  One digit kernel for all of them (int16 digits at
-//                           c = 16, int32 above: PrePlan::wide) and one scan; the scatter and the placement kernel take lob as an
-//                           argument above 16 bits, and the 16-bit table keeps bodies with lob = 7 built in (psort_*16)
+//                           c = 16, int32 above: PrePlan::wide), one scan, and one scatter and one placement kernel: templates
+//                           over LOB, which is 0 where lob is a run-time argument (above 16 bits) and 7 for the 16-bit table
+// The steps the kernels share have one definition each: ld_scalar, recode (the signed digits), the workgroup scans, tile_offsets256 /
+// advance_cursors256 (between counting a tile and placing it), count_keys, and the word layouts make_ref / cs_pack / cs_ref
+// (msm_common.cuh).
 // The per-window path (zk_msm_g1 over caller bases, vectors below 2^13 or beyond 2^26 points, SRS without a table) keeps round 1's
 // LDS COUNTING sort (msm_hist / msm_scan1-3 / msm_scatter): its windows are 3 .. 16 bits -- the window is a measured step function
 // of the length (make_geom) -- and a partition needs at least 2^7 buckets, and its references carry 31 bits of point index where the
@@ -75,28 +78,48 @@ ZK_D bool scalar_fold(uint32_t (&k)[8], const MsmGeom& g) {
     return true;
 }
 
+// scalar i of the caller's vector as canonical limbs; into_repr of a commit's Montgomery coefficient is fused in (MONT)
+template <class Fr, bool MONT>
+ZK_D Fr ld_scalar(const uint32_t* scalars, uint64_t i) {
+    const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * i;
+    const uint4 a = q[0], b = q[1];
+    Fr x;
+    x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
+    x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
+    if (MONT) x = Fr::from_mont(x);
+    return x;
+}
+
+// The signed-digit recode, one window at a time: raw = bits + carry; raw >= 2^(c-1) -> digit raw - 2^c (negative), carry 1.
+// `flip`: the scalar was folded (scalar_fold), so every digit changes its sign; the bucket |digit| - 1 does not move.
+struct Digit {
+    uint32_t mag, neg;      // |digit| and its sign; mag == 0: no reference
+    ZK_D int32_t value() const { return neg ? -(int32_t)mag : (int32_t)mag; }
+};
+ZK_D Digit recode(uint32_t bits, uint32_t& carry, uint32_t c, uint32_t flip = 0) {
+    const uint32_t raw = bits + carry;
+    carry = raw >= (1u << (c - 1)) ? 1u : 0u;
+    return {carry ? (1u << c) - raw : raw, carry ^ flip};
+}
+
 // ---- counting sort of the (point, sign) references by (window, bucket), without global atomics ----
-// K0  msm_digits : signed c-bit digits of every scalar, stored window-major as int16 (c <= 16)
+// K0  msm_digits : signed c-bit digits of every scalar (recode), stored window-major as int16 (c <= 16)
 // K1  msm_hist   : one workgroup per (window, slab of scalars): LDS histogram -> hist[w][slab][bucket]
 // K2  msm_scan1/2/3 : exclusive scan in (window, bucket, slab) order -> bucket offsets + per-slab cursors
 // K3  msm_scatter: same grid as K1, LDS cursors, writes the references to their sorted position
-// digit convention: raw = bits + carry; raw >= 2^(c-1) -> digit raw - 2^c (negative), carry 1.
 __global__ void msm_digits(const uint32_t* scalars, uint64_t n, MsmGeom g, int16_t* dig) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * i;
     const uint4 a = q[0], b = q[1];
     uint32_t s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const bool flip = scalar_fold(s, g);
+    const uint32_t flip = scalar_fold(s, g);
     uint32_t carry = 0;
-    const uint32_t half = 1u << (g.c - 1);
     for (uint32_t w = 0; w < g.Wt; ++w) {
-        uint32_t raw = scalar_bits(s, w * g.c, g.c) + carry;
-        carry = raw >= half ? 1u : 0u;
-        int32_t d = carry ? (int32_t)raw - (int32_t)(1u << g.c) : (int32_t)raw;
+        const Digit d = recode(scalar_bits(s, w * g.c, g.c), carry, g.c, flip);
         uint32_t row;
         // (the int16 store cannot hold -(-32768): make_geom never folds scalars at c = 16, see the assert there)
-        if (g.owns(w, row)) dig[(uint64_t)row * n + i] = (int16_t)(flip ? -d : d);
+        if (g.owns(w, row)) dig[(uint64_t)row * n + i] = (int16_t)d.value();
     }
 }
 
@@ -186,7 +209,7 @@ __global__ void msm_scan3(uint32_t* hist, MsmGeom g, uint32_t S, const uint32_t*
 }
 
 // n_real != 0: dig is the flattened [W][n_real] array sorted as ONE window (shared bucket set); the
-// reference written is sign<<31 | window<<26 | index.
+// reference written is the table path's (make_ref).  Otherwise its window field is 0 and the index has 31 bits.
 __global__ void msm_scatter(const int16_t* dig, uint64_t n, MsmGeom g, uint32_t S, const uint32_t* cursors, uint32_t* entries,
                             uint32_t n_real) {
     extern __shared__ uint32_t lh[];
@@ -205,7 +228,7 @@ __global__ void msm_scatter(const int16_t* dig, uint64_t n, MsmGeom g, uint32_t 
         uint32_t ref = (uint32_t)i;
         if (n_real) {
             const uint32_t wq = (uint32_t)i / n_real;
-            ref = (wq << 26) | ((uint32_t)i - wq * n_real);
+            ref = make_ref(0, wq, (uint32_t)i - wq * n_real);
         }
         entries[pos] = ref | (neg << 31);
     }
@@ -252,25 +275,16 @@ __global__ void __launch_bounds__(256) psort_digits_hist(const uint32_t* scalars
     lc[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
-    const uint32_t half = 1u << (g.c - 1), cmask = (1u << g.c) - 1u;
     for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) {
-        const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * i;
-        uint4 a = q[0], b = q[1];
-        Fr x;
-        x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
-        x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
-        if (MONT) x = Fr::from_mont(x);
-        const bool flip = scalar_fold(x.v, g);
+        Fr x = ld_scalar<Fr, MONT>(scalars, i);
+        const uint32_t flip = scalar_fold(x.v, g);
         uint32_t carry = 0;
         for (uint32_t w = 0; w < g.Wt; ++w) {
-            const uint32_t raw = (scalar_bits(x.v, w * g.c, g.c) & cmask) + carry;
-            carry = raw >= half ? 1u : 0u;
-            int32_t d = carry ? (int32_t)raw - (int32_t)(1u << g.c) : (int32_t)raw;
-            if (flip) d = -d;
+            const Digit d = recode(scalar_bits(x.v, w * g.c, g.c), carry, g.c, flip);
             uint32_t row;
             if (!g.owns(w, row)) continue;
-            dig[(uint64_t)row * n + i] = (Dig)d;
-            if (d != 0) atomicAdd(&lc[(uint32_t)((d < 0 ? -d : d) - 1) >> lob], 1u);
+            dig[(uint64_t)row * n + i] = (Dig)d.value();
+            if (d.mag != 0) atomicAdd(&lc[(d.mag - 1) >> lob], 1u);
         }
     }
     __syncthreads();
@@ -278,7 +292,8 @@ __global__ void __launch_bounds__(256) psort_digits_hist(const uint32_t* scalars
 }
 
 // The fast path of a whole 16-bit table (c = 16, W = Wt = 16, no fold) over an even number of scalars: two scalars per lane, digit w
-// is half-word w of the scalar, 32-byte vector loads and one 4-byte store per window instead of two 2-byte ones.
+// is half-word w of the scalar, 32-byte vector loads and one 4-byte store per window instead of two 2-byte ones.  The recode is
+// written out in its half-word form: raw & 0xffff IS the int16 digit, which is the point of this kernel.
 template <class Fr, bool MONT>
 __global__ void __launch_bounds__(256) psort_digits_hist_pairs16(const uint32_t* scalars, uint64_t n, uint32_t sp, int16_t* dig,
                                                                  uint32_t* hist /* [PS_PARTS][PS_SLABS] */, uint32_t* scan_counter, uint32_t* combine_q) {
@@ -293,12 +308,7 @@ __global__ void __launch_bounds__(256) psort_digits_hist_pairs16(const uint32_t*
         uint32_t sc[2][8];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * (i0 + h);
-            uint4 a = q[0], b = q[1];
-            Fr x;
-            x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
-            x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
-            if (MONT) x = Fr::from_mont(x);
+            const Fr x = ld_scalar<Fr, MONT>(scalars, i0 + h);
 #pragma unroll
             for (int k = 0; k < 8; ++k) sc[h][k] = x.v[k];
         }
@@ -332,14 +342,62 @@ ZK_D uint32_t wave_scan_incl(uint32_t v, uint32_t t) {
 }
 // The workgroup scans (scan128_excl, scan256_excl, scan1024_excl) stay three functions: their barriers differ (128: none behind its
 // LDS read; 256: one behind its LDS read; 1024: one in front of its LDS write, as it is called twice in a row on one tmp).
-ZK_D uint32_t scan1024_excl(uint32_t v, uint32_t t, uint32_t* tmp);
+
+// exclusive scan of 128 values held by lanes 0..127 of a workgroup (every lane calls it); tmp: one LDS word
+ZK_D uint32_t scan128_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
+    uint32_t inc = wave_scan_incl(v, t);
+    if (t == 63) *tmp = inc;
+    __syncthreads();
+    if (t >= 64 && t < 128) inc += *tmp;
+    return inc - v;
+}
+// exclusive scan of 256 values held by lanes 0..255 of a workgroup (every lane calls it); tmp: 4 LDS words
+ZK_D uint32_t scan256_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
+    uint32_t inc = wave_scan_incl(v, t);
+    if (t < 256 && (t & 63) == 63) tmp[t >> 6] = inc;
+    __syncthreads();
+    uint32_t add = 0;
+    for (uint32_t w = 0; w < (t >> 6) && w < 4; ++w) add += tmp[w];
+    __syncthreads();
+    return inc + add - v;
+}
+// exclusive scan of one value per lane over a 1024-lane workgroup; tmp: 16 LDS words
+ZK_D uint32_t scan1024_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
+    uint32_t inc = wave_scan_incl(v, t);
+    __syncthreads();
+    if ((t & 63) == 63) tmp[t >> 6] = inc;
+    __syncthreads();
+    uint32_t add = 0;
+    for (uint32_t w = 0; w < (t >> 6); ++w) add += tmp[w];
+    return inc + add - v;
+}
+
+// The step between counting a tile and placing it, for 256 counters (the partitions of a scatter, the buckets of a compact
+// partition): cnt[0 .. 256) holds the tile's counts on entry; on return toff[0 .. 256] is their exclusive scan (toff[256] = the
+// tile's total) and cnt[] a copy of it, the running positions the placement advances.  Every lane calls it; the barriers in front of
+// the read of cnt and behind the write of it are inside.  stmp: 4 LDS words.
+ZK_D void tile_offsets256(uint32_t* cnt, uint32_t* toff, uint32_t* stmp, uint32_t t) {
+    __syncthreads();
+    {
+        const uint32_t c = t < 256 ? cnt[t] : 0u;
+        const uint32_t ex = scan256_excl(c, t, stmp);
+        if (t < 256) toff[t] = ex;
+        if (t == 255) toff[256] = ex + c;
+    }
+    __syncthreads();
+    if (t < 256) cnt[t] = toff[t];
+    __syncthreads();
+}
+// ... and the step behind the placement: the 256 cursors move past the tile's runs
+ZK_D void advance_cursors256(uint32_t* cur, const uint32_t* toff, uint32_t t) {
+    if (t < 256) cur[t] += toff[t + 1] - toff[t];
+}
 
 // per partition: exclusive scan of its PS_SLABS slab counts in place (coalesced); the workgroup that finishes
-// last (a counter, no waiting) then scans the P partition totals into part_start[0..P].  P is always PS_PARTS: it stays an argument
-// here, and in csort_final / csort_final_long, only so that the code these kernels compile to does not move.
+// last (a counter, no waiting) then scans the PS_PARTS partition totals into part_start[0 .. PS_PARTS].
 // `counter` must be 0 on entry (the job's digit kernel clears it: reset_job_counters) and is left 0.  Both scans are wave shuffles plus one LDS step
 // (scan1024_excl): as twenty-barrier Hillis-Steele loops over LDS this kernel was 13 us of every MSM's sort.
-__global__ void __launch_bounds__(PS_SLABS) psort_scan(SJobs jobs, uint32_t P) {
+__global__ void __launch_bounds__(PS_SLABS) psort_scan(SJobs jobs) {
     static_assert(PS_SLABS == 1024, "scan1024_excl");
     uint32_t* hist = jobs.j[blockIdx.y].hist;
     uint32_t* part_total = jobs.j[blockIdx.y].part_total;
@@ -355,37 +413,33 @@ __global__ void __launch_bounds__(PS_SLABS) psort_scan(SJobs jobs, uint32_t P) {
     if (t == PS_SLABS - 1) {
         part_total[blockIdx.x] = ex + v;
         __threadfence();
-        last_block = atomicAdd(counter, 1u) == P - 1 ? 1u : 0u;
+        last_block = atomicAdd(counter, 1u) == PS_PARTS - 1 ? 1u : 0u;
     }
     __syncthreads();
     if (!last_block) return;
-    const uint32_t tv = t < P ? ((volatile uint32_t*)part_total)[t] : 0u;
+    const uint32_t tv = t < PS_PARTS ? ((volatile uint32_t*)part_total)[t] : 0u;
     const uint32_t ex2 = scan1024_excl(tv, t, tmp);
-    if (t < P) part_start[t] = ex2;
+    if (t < PS_PARTS) part_start[t] = ex2;
     if (t == PS_SLABS - 1) {
-        part_start[P] = ex2 + tv;
+        part_start[PS_PARTS] = ex2 + tv;
         *counter = 0;
     }
 }
 
-// exclusive scan of 256 values held by lanes 0..255 of a workgroup (every lane calls it); tmp: 4 LDS words
-ZK_D uint32_t scan256_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
-    uint32_t inc = wave_scan_incl(v, t);
-    if (t < 256 && (t & 63) == 63) tmp[t >> 6] = inc;
-    __syncthreads();
-    uint32_t add = 0;
-    for (uint32_t w = 0; w < (t >> 6) && w < 4; ++w) add += tmp[w];
-    __syncthreads();
-    return inc + add - v;
-}
+// The scatter and the placement kernel are one family over the low bucket bits.  LOB = 0: lob = c - 9 is the run-time argument (the
+// windows above 16 bits, Lo = uint16_t).  LOB != 0: lob = LOB at compile time (the 16-bit table, LOB = 7, Lo = uint8_t, which every
+// table below 2^19 points runs): the low bits ride in the record word of the scatter's tile instead of an LDS array beside it, and
+// the placement kernel scans its 2^LOB = 128 counters with one wavefront pair (scan128_excl), in static LDS.
 
-// references (sign<<31 | window<<26 | index, as msm_scatter writes them) + their low bucket bits -> partition order.
+// references (make_ref) + their low bucket bits -> partition order.
 // A tile of PS_STILE digits is ordered by partition in LDS first, so the records (4 bytes + a Lo) leave as runs of consecutive
 // addresses, one run per partition and tile.
-template <class Dig, class Lo>
-__global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, uint32_t lob) {
-    static_assert(PS_PARTS == 256, "scan256_excl");
-    constexpr uint32_t PER = PS_STILE / PS_T;
+template <class Dig, class Lo, uint32_t LOB>
+__global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, uint32_t lob_arg) {
+    static_assert(PS_PARTS == 256, "tile_offsets256");
+    static_assert(15 + LOB + 8 <= 32, "position, sign, low bits and partition in one record word");
+    constexpr uint32_t PER = PS_STILE / PS_T, PSH = 15 + LOB;
+    const uint32_t lob = LOB ? LOB : lob_arg;
     const SJob& J = jobs.j[blockIdx.y];
     const Dig* dig = (const Dig*)J.dig;
     const uint64_t n = J.n;
@@ -396,13 +450,13 @@ __global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, ui
     Lo* stage_lo = (Lo*)J.stage_lo;
     const uint32_t LOM = (1u << lob) - 1u;
     __shared__ uint32_t cnt[PS_PARTS], toff[PS_PARTS + 1], gcur[PS_PARTS], stmp[4];
-    __shared__ uint32_t rec[PS_STILE];       // k (14 bits) | neg << 14 | partition << 15
-    __shared__ Lo rlo[PS_STILE];             // low bucket bits of the record at the same position
+    __shared__ uint32_t rec[PS_STILE];       // k (14 bits) | neg << 14 | LOB low bucket bits << 15 | partition << PSH
+    __shared__ Lo rlo[LOB ? 1 : PS_STILE];   // LOB = 0: the low bucket bits of the record at the same position
     const uint32_t t = threadIdx.x;
     if (t < PS_PARTS) gcur[t] = part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x];
     const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
     const uint32_t len = (uint32_t)(hi - lo);
-    const uint32_t total_digits = W * len;
+    const uint32_t total_digits = W * len;           // the slab: W windows x len scalars, visited window-major
     // the digits of the tile after the current one are requested while the current one is counted and placed
     int32_t nd[PER];
     auto fetch = [&](uint32_t base) {
@@ -436,45 +490,36 @@ __global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, ui
             if (d != 0) {
                 const uint32_t neg = d < 0 ? 1u : 0u;
                 const uint32_t b = (uint32_t)((neg ? -d : d) - 1);
-                pk[k] = i | (neg << 14) | ((b >> lob) << 15);
-                pl[k] = (Lo)(b & LOM);
+                pk[k] = i | (neg << 14) | ((b >> lob) << PSH);
+                if (LOB) pk[k] |= (b & LOM) << 15;
+                else pl[k] = (Lo)(b & LOM);
                 atomicAdd(&cnt[b >> lob], 1u);
             }
         }
-        __syncthreads();
-        {
-            const uint32_t c = t < PS_PARTS ? cnt[t] : 0u;
-            const uint32_t ex = scan256_excl(c, t, stmp);
-            if (t < PS_PARTS) toff[t] = ex;
-            if (t == PS_PARTS - 1) toff[PS_PARTS] = ex + c;
-        }
-        __syncthreads();
-        if (t < PS_PARTS) cnt[t] = toff[t];
-        __syncthreads();
+        tile_offsets256(cnt, toff, stmp, t);
 #pragma unroll
         for (uint32_t k = 0; k < PER; ++k)
             if (pk[k] != 0xffffffffu) {
-                const uint32_t at = atomicAdd(&cnt[pk[k] >> 15], 1u);
+                const uint32_t at = atomicAdd(&cnt[pk[k] >> PSH], 1u);
                 rec[at] = pk[k];
-                rlo[at] = pl[k];
+                if (!LOB) rlo[at] = pl[k];
             }
         __syncthreads();
         const uint32_t total = toff[PS_PARTS];
 #pragma unroll
         for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t qq = k * PS_T + t;
+            const uint32_t qq = k * PS_T + t;   // consecutive lanes -> consecutive records of a partition's run
             if (qq < total) {
                 const uint32_t r = rec[qq];
-                const uint32_t pp = r >> 15;
+                const uint32_t pp = r >> PSH;
                 const uint32_t q = base + (r & 0x3fffu), w = q / len, ii = q - w * len;
-                const uint32_t ref = (w << 26) | (uint32_t)(lo + ii) | (((r >> 14) & 1u) << 31);
                 const uint32_t dst = gcur[pp] + (qq - toff[pp]);
-                stage_ref[dst] = ref;
-                stage_lo[dst] = rlo[qq];
+                stage_ref[dst] = make_ref((r >> 14) & 1u, w, (uint32_t)(lo + ii));
+                stage_lo[dst] = LOB ? (Lo)((r >> 15) & LOM) : rlo[qq];
             }
         }
         __syncthreads();
-        if (t < PS_PARTS) gcur[t] += toff[t + 1] - toff[t];
+        advance_cursors256(gcur, toff, t);
     }
 }
 
@@ -483,38 +528,33 @@ __global__ void __launch_bounds__(PS_T) psort_scatter(SJobs jobs, uint32_t W, ui
 // of consecutive addresses (one run per bucket and tile) instead of 64 different cache lines per wave-store.
 // (Wave-private counters were tried for the counting: 16 x 128 write streams per workgroup made it slower.)
 
-// counts of the keys key[i], i = first, first + PS_T, ... < end, into the LDS table cnt.  Eight loads in flight per lane: written
-// as a plain loop the compiler keeps ONE (load, wait, LDS atomic) per iteration, and the pass over a partition's ~60 keys per
-// lane was sixty memory round trips in a row -- most of the kernel's time.
+// counts of the keys key[i] & mask, i = first, first + PS_T, ... < end, into the LDS table cnt.  Eight loads in flight per lane:
+// written as a plain loop the compiler keeps ONE (load, wait, LDS atomic) per iteration, and the pass over a partition's ~60 keys
+// per lane was sixty memory round trips in a row -- most of the kernel's time.
 template <class K>
-ZK_D void count_keys(const K* key, uint32_t first, uint32_t end, uint32_t* cnt) {
+ZK_D void count_keys(const K* key, uint32_t first, uint32_t end, uint32_t* cnt, uint32_t mask = 0xffffffffu) {
     uint32_t i = first;
     for (; i + 7 * PS_T < end; i += 8 * PS_T) {
         uint32_t v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = key[i + k * PS_T];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) atomicAdd(&cnt[v[k]], 1u);
+        for (int k = 0; k < 8; ++k) atomicAdd(&cnt[v[k] & mask], 1u);
     }
-    for (; i < end; i += PS_T) atomicAdd(&cnt[key[i]], 1u);
+    for (; i < end; i += PS_T) atomicAdd(&cnt[key[i] & mask], 1u);
 }
 
-// exclusive scan of one value per lane over a 1024-lane workgroup; tmp: 16 LDS words
-ZK_D uint32_t scan1024_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
-    uint32_t inc = wave_scan_incl(v, t);
-    __syncthreads();
-    if ((t & 63) == 63) tmp[t >> 6] = inc;
-    __syncthreads();
-    uint32_t add = 0;
-    for (uint32_t w = 0; w < (t >> 6); ++w) add += tmp[w];
-    return inc + add - v;
-}
-
-// dynamic LDS: cnt[NB] | cur[NB] | toff[NB + 1] | tmp[16] | sorted[PS_TILE] | skey[PS_TILE] (Lo), NB = 2^lob buckets
+// LDS: cnt[NB] | cur[NB] | toff[NB + 1] | tmp[16] | sorted[PS_TILE] | skey[PS_TILE] (Lo), NB = 2^lob buckets.  Dynamic where lob is
+// a run-time argument; where it is LOB the array is static and the prefetched keys wait as 32-bit registers -- measured: with
+// dynamic LDS and uint8 key registers the 16-bit table's sort was 1 % slower (profiles/sort_tile_steps/notes.md).
 constexpr size_t psort_final_lds(uint32_t lob, size_t lo_bytes) { return ((size_t)3 * (1u << lob) + 1 + 16 + PS_TILE) * 4 + PS_TILE * lo_bytes; }
-template <class Lo>
-__global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t lob) {
-    extern __shared__ uint32_t lds[];
+template <class Lo, uint32_t LOB>
+__global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t lob_arg) {
+    static_assert(LOB == 0 || LOB == 7, "scan_counts: 2^LOB = 128 counters, scan128_excl");
+    extern __shared__ uint32_t dyn_lds[];
+    __shared__ uint32_t st_lds[LOB ? psort_final_lds(LOB, sizeof(Lo)) / 4 : 1];
+    uint32_t* lds = LOB ? st_lds : dyn_lds;
+    typedef typename std::conditional<LOB != 0, uint32_t, Lo>::type Key;      // a key in registers
     const SJob& J = jobs.j[blockIdx.y];
     const uint32_t* stage_ref = J.stage_ref;
     const Lo* stage_lo = (const Lo*)J.stage_lo;
@@ -522,6 +562,7 @@ __global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t lob) {
     uint32_t* entries = J.entries;
     uint32_t* offsets = J.offsets;
     constexpr uint32_t PER = PS_TILE / PS_T;
+    const uint32_t lob = LOB ? LOB : lob_arg;
     const uint32_t NB = 1u << lob;
     const uint32_t K = NB > PS_T ? NB / PS_T : 1u;       // counters per lane in the scans
     uint32_t* cnt = lds;
@@ -536,8 +577,17 @@ __global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t lob) {
     __syncthreads();
     count_keys(stage_lo, s + t, e, cnt);
     __syncthreads();
-    // exclusive scan of cnt[0 .. NB): lane t owns counters [t*K, (t+1)*K)
+    // dst[0 .. NB) = add + the exclusive scan of cnt[0 .. NB), dst[NB] = add + their sum (with_total); a barrier behind it.
+    // Lane t owns counters [t*K, (t+1)*K); the 128 counters of LOB = 7 are one per lane of a wavefront pair
     auto scan_counts = [&](uint32_t* dst, uint32_t add, bool with_total) {
+        if (LOB == 7) {
+            const uint32_t c = t < NB ? cnt[t] : 0u;
+            const uint32_t ex = scan128_excl(c, t, tmp);
+            if (t < NB) dst[t] = add + ex;
+            if (with_total && t == NB - 1) dst[NB] = add + ex + c;
+            __syncthreads();
+            return;
+        }
         uint32_t mine = 0;
         if (t * K < NB)
             for (uint32_t k = 0; k < K; ++k) mine += cnt[t * K + k];
@@ -558,7 +608,7 @@ __global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t lob) {
     // the tile after the current one is requested while the current one is counted, scanned and placed: its 16 references and
     // keys per lane sit in registers across the barriers instead of costing a memory round trip at the top of every tile
     uint32_t nr[PER];
-    Lo nk[PER];
+    Key nk[PER];
     auto fetch = [&](uint32_t base) {
         const uint32_t m = e - base < PS_TILE ? e - base : PS_TILE;
 #pragma unroll
@@ -577,7 +627,7 @@ __global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t lob) {
         for (uint32_t j = t; j < NB; j += PS_T) cnt[j] = 0;
         __syncthreads();
         uint32_t vr[PER];
-        Lo vk[PER];
+        Key vk[PER];
 #pragma unroll
         for (uint32_t k = 0; k < PER; ++k) {
             vr[k] = nr[k];
@@ -599,7 +649,7 @@ __global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t lob) {
             if (i < m) {
                 const uint32_t q = atomicAdd(&cnt[vk[k]], 1u);
                 sorted[q] = vr[k];
-                skey[q] = vk[k];
+                skey[q] = (Lo)vk[k];
             }
         }
         __syncthreads();
@@ -616,201 +666,16 @@ __global__ void __launch_bounds__(PS_T) psort_final(SJobs jobs, uint32_t lob) {
     }
 }
 
-
-// ---- the 16-bit table's own scatter and placement kernels -----------------------------------------------------------------------
-// The same two passes as psort_scatter<Dig, Lo> / psort_final<Lo> with lob a constant: the 7 low bits ride in the record word of the
-// scatter's tile, the 128 counters of a partition are scanned by one wavefront pair (scan128_excl) and the LDS is static.  Every
-// table below 2^19 points runs them; P is always PS_PARTS and stays an argument for the reason psort_scan gives.
-constexpr uint32_t PS_LOB = PRE_C - 9;      // lob = c - 9, as for every table window
-
-// references (sign<<31 | window<<26 | index, as msm_scatter writes them) + their low bucket bits -> partition order.
-// A tile of PS_STILE digits is ordered by partition in LDS first (packed: position in the tile, sign, low bits,
-// partition), so the 8-byte records leave as runs of consecutive addresses, one run per partition and tile.
-__global__ void __launch_bounds__(PS_T) psort_scatter16(SJobs jobs, uint32_t W, uint32_t P) {
-    constexpr uint32_t PER = PS_STILE / PS_T, LOM = (1u << PS_LOB) - 1u;
-    const SJob& J = jobs.j[blockIdx.y];
-    const int16_t* dig = (const int16_t*)J.dig;
-    const uint64_t n = J.n;
-    const uint32_t sp = J.sp;
-    const uint32_t* cursors = J.hist;
-    const uint32_t* part_start = J.part_start;
-    uint32_t* stage_ref = J.stage_ref;
-    uint8_t* stage_lo = (uint8_t*)J.stage_lo;
-    __shared__ uint32_t cnt[PS_PARTS], toff[PS_PARTS + 1], gcur[PS_PARTS], stmp[4];
-    __shared__ uint32_t rec[PS_STILE];       // k (14 bits) | neg << 14 | low bits << 15 | partition << 22
-    const uint32_t t = threadIdx.x;
-    if (t < PS_PARTS) gcur[t] = t < P ? part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x] : 0u;
-    const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
-    const uint32_t len = (uint32_t)(hi - lo);
-    const uint32_t total_digits = W * len;           // the slab: W windows x len scalars, visited window-major
-    // the digits of the tile after the current one are requested while the current one is counted and placed
-    int32_t nd[PER];
-    auto fetch = [&](uint32_t base) {
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t q = base + k * PS_T + t;
-            nd[k] = 0;
-            if (q < total_digits) {
-                const uint32_t w = q / len, ii = q - w * len;
-                nd[k] = dig[(uint64_t)w * n + lo + ii];
-            }
-        }
-    };
-    if (total_digits) fetch(0);
-    for (uint32_t base = 0; base < total_digits; base += PS_STILE) {
-        __syncthreads();
-        if (t < PS_PARTS) cnt[t] = 0;
-        __syncthreads();
-        int32_t vd[PER];
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) vd[k] = nd[k];
-        if (base + PS_STILE < total_digits) fetch(base + PS_STILE);
-        uint32_t pk[PER];
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;
-            pk[k] = 0xffffffffu;
-            const int32_t d = vd[k];      // 0 past the end of the slab
-            if (d != 0) {
-                const uint32_t neg = d < 0 ? 1u : 0u;
-                const uint32_t b = (uint32_t)((neg ? -d : d) - 1);
-                pk[k] = i | (neg << 14) | ((b & LOM) << 15) | ((b >> PS_LOB) << 22);
-                atomicAdd(&cnt[b >> PS_LOB], 1u);
-            }
-        }
-        __syncthreads();
-        {
-            const uint32_t c = t < PS_PARTS ? cnt[t] : 0u;
-            const uint32_t ex = scan256_excl(c, t, stmp);
-            if (t < PS_PARTS) toff[t] = ex;
-            if (t == PS_PARTS - 1) toff[PS_PARTS] = ex + c;
-        }
-        __syncthreads();
-        if (t < PS_PARTS) cnt[t] = toff[t];
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k)
-            if (pk[k] != 0xffffffffu) rec[atomicAdd(&cnt[pk[k] >> 22], 1u)] = pk[k];
-        __syncthreads();
-        const uint32_t total = toff[PS_PARTS];
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t qq = k * PS_T + t;   // consecutive lanes -> consecutive records of a partition's run
-            if (qq < total) {
-                const uint32_t r = rec[qq];
-                const uint32_t pp = r >> 22;
-                const uint32_t q = base + (r & 0x3fffu), w = q / len, ii = q - w * len;
-                const uint32_t ref = (w << 26) | (uint32_t)(lo + ii) | (((r >> 14) & 1u) << 31);
-                const uint32_t dst = gcur[pp] + (qq - toff[pp]);
-                stage_ref[dst] = ref;
-                stage_lo[dst] = (uint8_t)((r >> 15) & LOM);
-            }
-        }
-        __syncthreads();
-        if (t < PS_PARTS) gcur[t] += toff[t + 1] - toff[t];
-    }
-}
-
-// exclusive scan of 128 values held by lanes 0..127 of a workgroup (every lane calls it); tmp: one LDS word
-ZK_D uint32_t scan128_excl(uint32_t v, uint32_t t, uint32_t* tmp) {
-    uint32_t inc = wave_scan_incl(v, t);
-    if (t == 63) *tmp = inc;
-    __syncthreads();
-    if (t >= 64 && t < 128) inc += *tmp;
-    return inc - v;
-}
-__global__ void __launch_bounds__(PS_T) psort_final16(SJobs jobs, uint32_t P) {
-    constexpr uint32_t NB = 1u << PS_LOB, PER = PS_TILE / PS_T;
-    const SJob& J = jobs.j[blockIdx.y];
-    const uint32_t* stage_ref = J.stage_ref;
-    const uint8_t* stage_lo = (const uint8_t*)J.stage_lo;
-    const uint32_t* part_start = J.part_start;
-    uint32_t* entries = J.entries;
-    uint32_t* offsets = J.offsets;
-    __shared__ uint32_t cnt[NB], cur[NB], toff[NB + 1], stmp;
-    __shared__ uint32_t sorted[PS_TILE];
-    __shared__ uint8_t skey[PS_TILE];
-    const uint32_t p = blockIdx.x, t = threadIdx.x;
-    const uint32_t s = part_start[p], e = part_start[p + 1];
-    if (t < NB) cnt[t] = 0;
-    __syncthreads();
-    count_keys(stage_lo, s + t, e, cnt);
-    __syncthreads();
-    {
-        const uint32_t ex = scan128_excl(t < NB ? cnt[t] : 0u, t, &stmp);
-        if (t < NB) cur[t] = s + ex;
-    }
-    __syncthreads();
-    if (t < NB) offsets[p * NB + t] = cur[t];
-    if (p == P - 1 && t == 0) offsets[P * NB] = e;
-    // the tile after the current one is requested while the current one is counted, scanned and placed
-    uint2 nv[PER];
-    auto fetch = [&](uint32_t base) {
-        const uint32_t m = e - base < PS_TILE ? e - base : PS_TILE;
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;
-            if (i < m) nv[k] = make_uint2(stage_ref[base + i], stage_lo[base + i]);
-        }
-    };
-    if (s < e) fetch(s);
-    for (uint32_t base = s; base < e; base += PS_TILE) {
-        const uint32_t m = e - base < PS_TILE ? e - base : PS_TILE;   // references in this tile
-        __syncthreads();
-        if (t < NB) cnt[t] = 0;
-        __syncthreads();
-        uint2 v[PER];
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) v[k] = nv[k];
-        if (base + PS_TILE < e) fetch(base + PS_TILE);
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;
-            if (i < m) atomicAdd(&cnt[v[k].y], 1u);
-        }
-        __syncthreads();
-        {
-            const uint32_t c = t < NB ? cnt[t] : 0u;
-            const uint32_t ex = scan128_excl(c, t, &stmp);
-            if (t < NB) toff[t] = ex;
-            if (t == NB - 1) toff[NB] = ex + c;
-        }
-        __syncthreads();
-        if (t < NB) cnt[t] = toff[t];      // running position inside the tile
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;
-            if (i < m) {
-                const uint32_t q = atomicAdd(&cnt[v[k].y], 1u);
-                sorted[q] = v[k].x;
-                skey[q] = (uint8_t)v[k].y;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            const uint32_t i = k * PS_T + t;   // consecutive lanes -> consecutive positions of a bucket's run
-            if (i < m) {
-                const uint32_t j = skey[i];
-                entries[cur[j] + (i - toff[j])] = sorted[i];
-            }
-        }
-        __syncthreads();
-        if (t < NB) cur[t] += toff[t + 1] - toff[t];
-    }
-}
-
 // ---- the compact form of the wide sort: whole tables of folded 17-bit windows (pre_compact, msm_common.cuh) ---------------------
 // What every MSM of a 2^19 .. 2^21 proof runs.  The int32 digit array of psort_* is a 4 W-byte expansion of a 32-byte scalar that
 // is written once and read once, and its staged record is 6 bytes.  Here
 //   csort_fold_hist  (at submission, the only reader of the caller's vector) leaves the folded canonical scalar in the job's
 //                    `entries` buffer -- it is below 2^254, so bit 255 carries the fold's sign -- and counts the partitions;
 //   csort_scatter    cuts the W digits of its slab's scalars itself (one scalar per lane: a tile is 1024 scalars = 1024 W records,
-//                    so a (tile, partition) run is ~4 W records of 4 bytes) and stages ONE word per reference:
-//                    sign << 31 | window << 27 | index inside the slab << 8 | low 8 bucket bits;
+//                    so a (tile, partition) run is ~4 W records of 4 bytes) and stages ONE word per reference (cs_pack,
+//                    msm_common.cuh);
 //   csort_final      recovers the slab of a staged record from its place in the partition (the slab cursors of psort_scan are the
-//                    starts of the slabs' runs) and writes the references in today's format; it reads a partition once.
+//                    starts of the slabs' runs) and writes the references (cs_ref); it reads a partition once.
 // 32 + 32 + 4 W (scatter) + 2 * 4 W + 4 W (final) bytes per scalar instead of 32 + 4 W + 4 W + 6 W + 2 W + 6 W + 4 W.
 
 // 17-bit field w of the scalar (w is a constant after unrolling: plain shifts)
@@ -830,22 +695,14 @@ __global__ void __launch_bounds__(256, 8) csort_fold_hist(const uint32_t* scalar
     lc[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t lo = slab_lo(n, sp), hi = slab_hi(lo, n, sp);
-    constexpr uint32_t half = 1u << (CS_C - 1);
     for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) {
-        const uint4* q = reinterpret_cast<const uint4*>(scalars) + 2 * i;
-        uint4 a = q[0], b = q[1];
-        Fr x;
-        x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
-        x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
-        if (MONT) x = Fr::from_mont(x);
+        Fr x = ld_scalar<Fr, MONT>(scalars, i);
         const bool flip = scalar_fold(x.v, g);        // now x <= (r - 1) / 2 < 2^254
         uint32_t carry = 0;
 #pragma unroll
         for (uint32_t w = 0; w < 16; ++w) {
             if (w < g.W) {
-                const uint32_t raw = cs_bits(x.v, w) + carry;
-                carry = raw >= half ? 1u : 0u;
-                const uint32_t mag = carry ? (1u << CS_C) - raw : raw;      // |digit|: the sign does not move the bucket
+                const uint32_t mag = recode(cs_bits(x.v, w), carry, CS_C).mag;      // the sign does not move the bucket
                 if (mag != 0) atomicAdd(&lc[(mag - 1) >> CS_LOB], 1u);
             }
         }
@@ -868,7 +725,7 @@ __global__ void __launch_bounds__(PS_T, 8) csort_scatter(SJobs jobs, uint32_t W)
     const uint32_t* cursors = J.hist;
     const uint32_t* part_start = J.part_start;
     uint32_t* stage = J.stage_ref;
-    constexpr uint32_t LOM = (1u << CS_LOB) - 1u, half = 1u << (CS_C - 1);
+    constexpr uint32_t LOM = (1u << CS_LOB) - 1u;
     __shared__ uint32_t cnt[PS_PARTS], toff[PS_PARTS + 1], gcur[PS_PARTS], stmp[4];
     const uint32_t t = threadIdx.x;
     if (t < 256) gcur[t] = part_start[t] + cursors[(uint64_t)t * PS_SLABS + blockIdx.x];
@@ -897,26 +754,15 @@ __global__ void __launch_bounds__(PS_T, 8) csort_scatter(SJobs jobs, uint32_t W)
         for (uint32_t w = 0; w < 16; ++w) {
             pk[w] = 0xffffffffu;
             if (have && w < W) {
-                const uint32_t raw = cs_bits(s, w) + carry;
-                carry = raw >= half ? 1u : 0u;
-                const uint32_t mag = carry ? (1u << CS_C) - raw : raw;
-                if (mag != 0) {
-                    const uint32_t b = mag - 1;
-                    pk[w] = ((b >> CS_LOB) << 23) | ((carry ^ flip) << 22) | (w << 18) | (t << 8) | (b & LOM);
+                const Digit d = recode(cs_bits(s, w), carry, CS_C, flip);
+                if (d.mag != 0) {
+                    const uint32_t b = d.mag - 1;
+                    pk[w] = ((b >> CS_LOB) << 23) | (d.neg << 22) | (w << 18) | (t << 8) | (b & LOM);
                     atomicAdd(&cnt[b >> CS_LOB], 1u);
                 }
             }
         }
-        __syncthreads();
-        {
-            const uint32_t c = t < 256 ? cnt[t] : 0u;
-            const uint32_t ex = scan256_excl(c, t, stmp);
-            if (t < 256) toff[t] = ex;
-            if (t == 255) toff[256] = ex + c;
-        }
-        __syncthreads();
-        if (t < 256) cnt[t] = toff[t];
-        __syncthreads();
+        tile_offsets256(cnt, toff, stmp, t);
 #pragma unroll
         for (uint32_t w = 0; w < 16; ++w)
             if (pk[w] != 0xffffffffu) rec[atomicAdd(&cnt[pk[w] >> 23], 1u)] = pk[w];
@@ -929,11 +775,11 @@ __global__ void __launch_bounds__(PS_T, 8) csort_scatter(SJobs jobs, uint32_t W)
                 const uint32_t r = rec[qq];
                 const uint32_t pp = r >> 23;
                 const uint32_t rel = tb + ((r >> 8) & (PS_T - 1u));        // index inside the slab
-                stage[gcur[pp] + (qq - toff[pp])] = (((r >> 22) & 1u) << 31) | (((r >> 18) & 15u) << 27) | (rel << 8) | (r & LOM);
+                stage[gcur[pp] + (qq - toff[pp])] = cs_pack((r >> 22) & 1u, (r >> 18) & 15u, rel, r & LOM);
             }
         }
         __syncthreads();
-        if (t < 256) gcur[t] += toff[t + 1] - toff[t];
+        advance_cursors256(gcur, toff, t);
     }
 }
 
@@ -944,7 +790,7 @@ __global__ void __launch_bounds__(PS_T, 8) csort_scatter(SJobs jobs, uint32_t W)
 // barriers, not by memory (one workgroup per CU): two atomics per reference and two barriers per tile instead of psort_final's
 // three and eight.  Longer partitions are left to csort_final_long (two kernels: in one, the two paths' registers do not overlay).
 constexpr uint32_t CS_RT = 4;
-__global__ void __launch_bounds__(PS_T) csort_final(SJobs jobs, uint32_t P) {
+__global__ void __launch_bounds__(PS_T) csort_final(SJobs jobs) {
     extern __shared__ uint32_t lds[];
     const SJob& J = jobs.j[blockIdx.y];
     const uint32_t* stage = J.stage_ref;
@@ -1022,7 +868,7 @@ __global__ void __launch_bounds__(PS_T) csort_final(SJobs jobs, uint32_t P) {
         pos[t] = in_tile;
         dst[t] = start + before - in_tile;
         if (r == 0) offsets[p * NB + j] = start;
-        if (p == P - 1 && t == 0) offsets[P * NB] = e;
+        if (p == PS_PARTS - 1 && t == 0) offsets[PS_PARTS * NB] = e;
     }
     // The slab that staged a record is the one whose run holds the record's place in the partition.  Lane t writes slab t's number
     // over the part of its run inside the tile (~60 places for ~270 of the lanes); a run longer than a wavefront (a slab of equal
@@ -1054,9 +900,8 @@ __global__ void __launch_bounds__(PS_T) csort_final(SJobs jobs, uint32_t P) {
             if (i < m) {
                 const uint32_t v = all[r][k];
                 const uint32_t slab = slab_of[i];
-                const uint32_t first = slab * sp < n ? slab * sp : n;
                 const uint32_t q = atomicAdd(&pos[r * NB + (v & LOM)], 1u);
-                sorted[q] = (v & 0x80000000u) | (((v >> 27) & 15u) << 26) | (first + ((v >> 8) & 0x7ffffu));
+                sorted[q] = cs_ref(v, slab, sp, n);
                 skey[q] = (uint8_t)(v & LOM);
             }
         }
@@ -1074,7 +919,7 @@ __global__ void __launch_bounds__(PS_T) csort_final(SJobs jobs, uint32_t P) {
 // The partitions csort_final leaves: longer than CS_RT tiles (skewed scalars: a handful of values repeated; jobs beyond 2^20 points).
 // Read twice, as psort_final reads them -- a counting pass, then tile by tile with the next tile requested ahead -- and the slab of
 // a record found by a 10-step search over the cursors.  dynamic LDS: curs[PS_SLABS] | sorted[PS_TILE] | skey[PS_TILE] (u8)
-__global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P) {
+__global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs) {
     extern __shared__ uint32_t lds[];
     const SJob& J = jobs.j[blockIdx.y];
     const uint32_t* stage = J.stage_ref;
@@ -1083,7 +928,7 @@ __global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P)
     uint32_t* offsets = J.offsets;
     const uint32_t n = (uint32_t)J.n, sp = J.sp;         // table path: n <= 2^26
     constexpr uint32_t PER = PS_TILE / PS_T, NB = 1u << CS_LOB, LOM = NB - 1u;
-    static_assert(NB == 256 && PS_SLABS == 1024 && PS_T == PS_SLABS, "scan256_excl; one slab cursor per lane; 10-step search");
+    static_assert(NB == 256 && PS_SLABS == 1024 && PS_T == PS_SLABS, "tile_offsets256; one slab cursor per lane; 10-step search");
     __shared__ uint32_t cnt[NB], cur[NB], toff[NB + 1], stmp[4];
     uint32_t* curs = lds;                    // start of every slab's run, relative to the partition's
     uint32_t* sorted = curs + PS_SLABS;
@@ -1094,17 +939,7 @@ __global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P)
     curs[t] = J.hist[(uint64_t)p * PS_SLABS + t];
     if (t < NB) cnt[t] = 0;
     __syncthreads();
-    {   // count the low bits: eight loads in flight per lane (count_keys)
-        uint32_t i = s + t;
-        for (; i + 7 * PS_T < e; i += 8 * PS_T) {
-            uint32_t v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = stage[i + k * PS_T];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) atomicAdd(&cnt[v[k] & LOM], 1u);
-        }
-        for (; i < e; i += PS_T) atomicAdd(&cnt[stage[i] & LOM], 1u);
-    }
+    count_keys(stage, s + t, e, cnt, LOM);
     __syncthreads();
     {
         const uint32_t ex = scan256_excl(t < NB ? cnt[t] : 0u, t, stmp);
@@ -1112,7 +947,7 @@ __global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P)
     }
     __syncthreads();
     if (t < NB) offsets[p * NB + t] = cur[t];
-    if (p == P - 1 && t == 0) offsets[P * NB] = e;
+    if (p == PS_PARTS - 1 && t == 0) offsets[PS_PARTS * NB] = e;
     // the tile after the current one is requested while the current one is counted, scanned and placed
     uint32_t nr[PER];
     auto fetch = [&](uint32_t base) {
@@ -1138,16 +973,7 @@ __global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P)
             const uint32_t i = k * PS_T + t;
             if (i < m) atomicAdd(&cnt[vr[k] & LOM], 1u);
         }
-        __syncthreads();
-        {
-            const uint32_t c = t < NB ? cnt[t] : 0u;
-            const uint32_t ex = scan256_excl(c, t, stmp);
-            if (t < NB) toff[t] = ex;
-            if (t == NB - 1) toff[NB] = ex + c;
-        }
-        __syncthreads();
-        if (t < NB) cnt[t] = toff[t];      // running position inside the tile
-        __syncthreads();
+        tile_offsets256(cnt, toff, stmp, t);
 #pragma unroll
         for (uint32_t k = 0; k < PER; ++k) {
             const uint32_t i = k * PS_T + t;
@@ -1159,10 +985,8 @@ __global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P)
                 for (uint32_t step = PS_SLABS / 2; step >= 1; step >>= 1)
                     if (curs[slab + step] <= at) slab += step;
                 const uint32_t r = vr[k];
-                const uint32_t first = slab * sp < n ? slab * sp : n;
-                const uint32_t ref = (r & 0x80000000u) | (((r >> 27) & 15u) << 26) | (first + ((r >> 8) & 0x7ffffu));
                 const uint32_t q = atomicAdd(&cnt[r & LOM], 1u);
-                sorted[q] = ref;
+                sorted[q] = cs_ref(r, slab, sp, n);
                 skey[q] = (uint8_t)(r & LOM);
             }
         }
@@ -1176,7 +1000,7 @@ __global__ void __launch_bounds__(PS_T) csort_final_long(SJobs jobs, uint32_t P)
             }
         }
         __syncthreads();
-        if (t < NB) cur[t] += toff[t + 1] - toff[t];
+        advance_cursors256(cur, toff, t);
     }
 }
 
@@ -1260,14 +1084,14 @@ int pre_queue_digits(zk_ctx* c, const PrePlan& pl, MsmBufs& mb, const void* d_sc
     return ZK_OK;
 }
 
-// partition scatter and final placement of a round's jobs with lob = c - 9 as an argument: the windows above 16 bits
-template <class Dig, class Lo>
+// partition scatter and final placement of a round's jobs; LOB = 0: lob = c - 9 goes as an argument (the windows above 16 bits)
+template <class Dig, class Lo, uint32_t LOB>
 int queue_psort_passes(const SJobs& sj, uint32_t n_jobs, const MsmGeom& g, hipStream_t st) {
-    const uint32_t lob = g.c - 9;
-    const size_t lds = psort_final_lds(lob, sizeof(Lo));
-    hipLaunchKernelGGL((psort_scatter<Dig, Lo>), dim3(PS_SLABS, n_jobs), dim3(PS_T), 0, st, sj, g.W, lob);
-    ZK_HIP_TRY(hipFuncSetAttribute((const void*)psort_final<Lo>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((psort_final<Lo>), dim3(PS_PARTS, n_jobs), dim3(PS_T), lds, st, sj, lob);
+    const uint32_t lob = g.c - 9;      // (= LOB where that is not 0: PrePlan::wide is c > PRE_C, and no table window is below PRE_C)
+    const size_t lds = LOB ? 0 : psort_final_lds(lob, sizeof(Lo));      // (LOB != 0: static)
+    hipLaunchKernelGGL((psort_scatter<Dig, Lo, LOB>), dim3(PS_SLABS, n_jobs), dim3(PS_T), 0, st, sj, g.W, lob);
+    if (lds) ZK_HIP_TRY(hipFuncSetAttribute((const void*)psort_final<Lo, LOB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((psort_final<Lo, LOB>), dim3(PS_PARTS, n_jobs), dim3(PS_T), lds, st, sj, lob);
     return ZK_OK;
 }
 
@@ -1307,21 +1131,19 @@ int pre_queue_sort_rest(zk_ctx* c, const PrePlan* pls, MsmBufs* const* mbs, cons
         J.entries = (uint32_t*)mb.entries.p;
         J.offsets = (uint32_t*)mb.offsets.p;
     }
-    hipLaunchKernelGGL(psort_scan, dim3(PS_PARTS, n_jobs), dim3(PS_SLABS), 0, st, sj, PS_PARTS);
+    hipLaunchKernelGGL(psort_scan, dim3(PS_PARTS, n_jobs), dim3(PS_SLABS), 0, st, sj);
     if (pre_compact(p0)) {                                // (all jobs of a launch share the table's geometry and own their staging)
         const size_t lds_s = (size_t)p0.g.W * PS_T * 4, lds_f = ((size_t)PS_SLABS + 1 + PS_TILE) * 4 + (size_t)PS_TILE * 3,
                      lds_l = ((size_t)PS_SLABS + PS_TILE) * 4 + PS_TILE;
         ZK_HIP_TRY(hipFuncSetAttribute((const void*)csort_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
         hipLaunchKernelGGL(csort_scatter, dim3(PS_SLABS, n_jobs), dim3(PS_T), lds_s, st, sj, p0.g.W);
         ZK_HIP_TRY(hipFuncSetAttribute((const void*)csort_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-        hipLaunchKernelGGL(csort_final, dim3(PS_PARTS, n_jobs), dim3(PS_T), lds_f, st, sj, PS_PARTS);
+        hipLaunchKernelGGL(csort_final, dim3(PS_PARTS, n_jobs), dim3(PS_T), lds_f, st, sj);
         ZK_HIP_TRY(hipFuncSetAttribute((const void*)csort_final_long, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l));
-        hipLaunchKernelGGL(csort_final_long, dim3(PS_PARTS, n_jobs), dim3(PS_T), lds_l, st, sj, PS_PARTS);
-    } else if (!p0.wide) {
-        hipLaunchKernelGGL(psort_scatter16, dim3(PS_SLABS, n_jobs), dim3(PS_T), 0, st, sj, p0.g.W, PS_PARTS);
-        hipLaunchKernelGGL(psort_final16, dim3(PS_PARTS, n_jobs), dim3(PS_T), 0, st, sj, PS_PARTS);
+        hipLaunchKernelGGL(csort_final_long, dim3(PS_PARTS, n_jobs), dim3(PS_T), lds_l, st, sj);
     } else {
-        const int rc = queue_psort_passes<int32_t, uint16_t>(sj, n_jobs, p0.g, st);
+        const int rc = p0.wide ? queue_psort_passes<int32_t, uint16_t, 0>(sj, n_jobs, p0.g, st)
+                               : queue_psort_passes<int16_t, uint8_t, PRE_C - 9>(sj, n_jobs, p0.g, st);      // the 16-bit table
         if (rc) return rc;
     }
     ZK_HIP_TRY(hipGetLastError());

@@ -43,8 +43,8 @@ def test_msm_kernels_registers_and_spills():
     fin = find("msm_win_finish_q", "Li512E")
     assert fin["VGPRs Spill"] == 0 and fin["VGPRs"] <= 256, fin
     # Itanium mangling inside the anonymous namespace: <length><name>E for a plain function, <length><name>I<args>E for a template
-    # (s = int16, i = int32 digits; h = uint8, t = uint16 low bucket bits)
-    for name in ("10psort_scanE", "15psort_scatter16E", "13psort_scatterIitE", "13psort_final16E", "11psort_finalItE"):
+    # (s = int16, i = int32 digits; h = uint8, t = uint16 low bucket bits; Lj7E / Lj0E = LOB: 7 at 16 bits, 0 = a run-time lob)
+    for name in ("10psort_scanE", "13psort_scatterIshLj7EE", "13psort_scatterIitLj0EE", "11psort_finalIhLj7EE", "11psort_finalItLj0EE"):
         k = find(name)
         assert k["VGPRs Spill"] == 0 and k["ScratchSize"] == 0, (name, k)
 

@@ -4,7 +4,9 @@ recovery of the placement kernel or a run boundary.  Geometries the form does no
 window-sharded table: `pre_compact` in csrc/msm_common.cuh refuses them, so they run the psort_* family -- int16 digits and uint8
 low bucket bits at 16 bits, int32 and uint16 above) agree with the same oracle.  The 16-bit cases reach every digit kernel of that
 window: the two-scalars-per-lane kernel of even lengths over a whole table, and the generic kernel with int16 digits for odd
-lengths and window-sharded tables.  Several expected points are the point at infinity or a single multiple of one base: that is intended."""
+lengths and window-sharded tables.  Tables of 18, 20 and 21 bits and the window-sharded 17-bit table take skewed scalars too: one
+partition holds every reference, so the placement kernel with lob at run time walks several tiles and scans one, two and four
+counters per lane.  Several expected points are the point at infinity or a single multiple of one base: that is intended."""
 import numpy as np
 import pytest
 
@@ -265,6 +267,57 @@ def test_twenty_bit_table_and_window_sharded_rows_keep_their_kernels_and_agree(c
     ck = zk.CommitterKey(bases, 0, ctx).precompute(17)
     _assert_point(ck.msm(_dev(scal)), exp_xy, exp_inf, "c=17 whole")
     ck.close()
+
+
+@pytest.fixture(scope="module")
+def bases14(ctx):
+    """2^14 points k_i G on BLS12-381, shared by the tables below"""
+    return _small_key(ctx, 0, 1 << 14, 1821)
+
+
+# What make_geom (csrc/msm_common.cuh) gives for the 255-bit r of BLS12-381: 255 // c + 1 windows -- the top bits of r - 1 plus a carry
+# stay far below 2^(c-1) in the last one -- and the fold to 254 bits would need ceil(254 / c) windows, which is no fewer at these
+# widths (15, 13, 13), so it is not taken.  NB = 2^(c-9) buckets per partition: 512, 2048, 4096 for the 1024 lanes of psort_final.
+WIDE_TABLE_WINDOWS = {18: 15, 20: 13, 21: 13}
+
+
+@pytest.fixture(scope="module", params=[18, 20, 21])
+def key_wide(request, ctx, bases14):
+    c = request.param
+    bases, bases_h = bases14
+    ck = zk.CommitterKey(bases, 0, ctx).precompute(c)
+    assert ck.table_windows() == WIDE_TABLE_WINDOWS[c] == 255 // c + 1
+    yield c, ck, bases_h
+    ck.close()
+
+
+@pytest.mark.parametrize("n", [1 << 13, (1 << 13) + 1])
+def test_wide_tables_with_skewed_partitions_against_the_oracle(n, key_wide, oracle_cpu):
+    """psort_scatter / psort_final with lob at run time beyond the few hundred references per partition that random scalars give at
+    2^14 points: one counter per lane with idle lanes (c = 18), two (20) and four (21, the 144 KiB LDS maximum), and with
+    one_partition ~12 * n references in partition 0 -- six tiles of PS_TILE, the multi-tile loop of the placement kernel."""
+    c, ck, bases_h = key_wide
+    cases = scalar_cases(zk.get_curve(0), n, seed=c * n, c=c)
+    for name in ("one_partition", "last_partition", "all_equal", "random_with_edges"):
+        exp_xy, exp_inf = oracle_cpu.msm_g1(0, bases_h[:n], cases[name])
+        _assert_point(ck.msm(_dev(cases[name])), exp_xy, exp_inf, f"{name} n={n} c={c}")
+
+
+@pytest.mark.parametrize("name", ["one_partition", "last_partition"])
+def test_window_sharded_seventeen_bit_rows_with_skewed_partitions(name, ctx, bases14, oracle_cpu):
+    """The window-sharded 17-bit table (rows (g, 2): not the compact form, so psort_* with uint16 low bits and lob = 8) with all the
+    references of the owned rows in the first or the last partition."""
+    bases, bases_h = bases14
+    n = (1 << 13) + 1
+    scal = scalar_cases(zk.get_curve(0), n, seed=1702)[name]
+    exp_xy, exp_inf = oracle_cpu.msm_g1(0, bases_h[:n], scal)
+    parts = []
+    for g in range(2):
+        ckw = zk.CommitterKey(bases[:n], 0, ctx).precompute(17, rows=(g, 2))
+        assert ckw.table_rows() == (g, 2, 8 - g) and ckw.table_windows() == 15
+        parts.append(ckw.commit_batch_partial([_dev(scal)], canonical=[True]))
+        ckw.close()
+    _assert_point(zk.sum_partials_batch(np.stack(parts), 0)[0], exp_xy, exp_inf, f"{name}, c=17, rows (g, 2)")
 
 
 @pytest.fixture(scope="module", params=[0, 1], ids=["bls12_381", "bn254"])

@@ -1,10 +1,11 @@
 """Compile-time guard on the kernels of the table sort (csrc/msm_sort.hip; gfx950 device code, hipcc's own
 `-Rpass-analysis=kernel-resource-usage` remarks; no GPU needed).  The compact form (csort_*): no register spill, no scratch, and at
 least as many workgroups of the launch shape resident per CU as the psort_* kernel (int32 digits, uint16 low bits) each replaces.
-The 16-bit table: the generic digit kernel on int16 digits neither spills nor uses scratch, nor do psort_scatter16 / psort_final16;
-the scatter keeps two workgroups of 1024 lanes per CU.  The placement kernel holds ONE (115 registers = 4 wavefronts per SIMD, and
-83472 bytes of LDS): its sorted tile and keys alone are 80 KiB, half a CU's LDS, so a second one cannot fit at PS_TILE = 16384
-whatever the counters beside them take.  The test pins that one."""
+The 16-bit table: the generic digit kernel on int16 digits neither spills nor uses scratch, nor do its instantiations of the scatter
+and the placement kernel (psort_scatter<int16_t, uint8_t, 7> / psort_final<uint8_t, 7>); the scatter keeps two workgroups of 1024
+lanes per CU.  The placement kernel holds ONE (at most 128 registers = 4 wavefronts per SIMD, and 83524 bytes of static LDS): its
+sorted tile and keys alone are 80 KiB, half a CU's LDS, so a second one cannot fit at PS_TILE = 16384 whatever the counters beside
+them take.  The test pins that one."""
 import os
 import re
 import subprocess
@@ -21,7 +22,7 @@ W, NB17 = 15, 256                                                   # the flagsh
 
 
 def psort_final_lds(lob, lo_bytes):
-    """dynamic LDS of psort_final<Lo>: psort_final_lds in csrc/msm_sort.hip, which its launch uses"""
+    """LDS of psort_final<Lo, LOB>: psort_final_lds in csrc/msm_sort.hip -- dynamic, set by the launch, at LOB = 0; static at LOB = 7"""
     return (3 * (1 << lob) + 1 + 16 + PS_TILE) * 4 + PS_TILE * lo_bytes
 
 
@@ -64,21 +65,23 @@ def test_compact_sort_kernels_registers_spills_and_residency():
     old_digits = workgroups_per_cu(find("psort_digits_hist", "Lb1EiE"), 256, 0)
     assert workgroups_per_cu(new["fold_t"], 256, 0) >= old_digits, (new["fold_t"], old_digits)
     assert workgroups_per_cu(new["fold_f"], 256, 0) >= workgroups_per_cu(find("psort_digits_hist", "Lb0EiE"), 256, 0)
-    old_scatter = workgroups_per_cu(find("psort_scatter", "IitE"), PS_T, 0)
+    old_scatter = workgroups_per_cu(find("psort_scatter", "IitLj0EE"), PS_T, 0)
     assert workgroups_per_cu(new["scatter"], PS_T, W * PS_T * 4) >= old_scatter, (new["scatter"], old_scatter)
     assert psort_final_lds(8, 2) == (3 * NB17 + 1 + 16 + PS_TILE) * 4 + PS_TILE * 2
-    old_final = workgroups_per_cu(find("psort_final", "ItE"), PS_T, psort_final_lds(8, 2))
+    old_final = workgroups_per_cu(find("psort_final", "ItLj0EE"), PS_T, psort_final_lds(8, 2))
     assert workgroups_per_cu(new["final"], PS_T, (PS_SLABS + 1 + PS_TILE) * 4 + PS_TILE * 3) >= old_final, (new["final"], old_final)
     assert workgroups_per_cu(new["long"], PS_T, (PS_SLABS + PS_TILE) * 4 + PS_TILE) >= old_final, (new["long"], old_final)
     # the 16-bit instantiations: lob = 16 - 9
     for mont in ("Lb1EsE", "Lb0EsE"):
         k = find("psort_digits_hist", mont)
         assert k["VGPRs Spill"] == 0 and k["ScratchSize"] == 0, (mont, k)
-    narrow_scatter = find("psort_scatter16")
-    narrow_final = find("psort_final16")
+    narrow_scatter = find("psort_scatter", "IshLj7EE")
+    narrow_final = find("psort_final", "IhLj7EE")
     for k in (narrow_scatter, narrow_final):
         assert k["VGPRs Spill"] == 0 and k["ScratchSize"] == 0, k
     assert workgroups_per_cu(narrow_scatter, PS_T, 0) >= 2, narrow_scatter
     # one workgroup by LDS whatever the registers; 128 registers is what a 1024-lane workgroup can have at all without spilling
     assert narrow_final["VGPRs"] <= 128, narrow_final
+    # (its LDS of psort_final_lds(7, 1) bytes is static, so "LDS Size" holds it and the launch adds none)
+    assert psort_final_lds(7, 1) == 83524 and narrow_final["LDS Size"] >= psort_final_lds(7, 1), narrow_final
     assert workgroups_per_cu(narrow_final, PS_T, 0) == 1, narrow_final
