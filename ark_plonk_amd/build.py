@@ -21,8 +21,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
          "-mllvm", "-pragma-unroll-threshold=1000000", "-Wpass-failed"]
 
-FIELD_HDRS = ["field.cuh", "fieldu.cuh", "fields.cuh", "curve_params.h", "zk_common.h"]
-HOST_HDRS = FIELD_HDRS + ["ec.cuh", "ecu.cuh", "ctx.h", "../../include/ark_plonk_amd.h"]
+FIELD_HDRS = ["field_common.cuh", "field.cuh", "fieldu.cuh", "fields.cuh", "curve_params.h", "zk_common.h"]
+HOST_HDRS = FIELD_HDRS + ["ecu.cuh", "ctx.h", "g1_host.h", "../../include/ark_plonk_amd.h"]
 API_HDRS = HOST_HDRS + ["api_internal.h"]
 # helpers with one definition each: Fr / 32-byte element access; the quotient's bounded lazy arithmetic; the MSM's point storage
 FR_IO, ZBOUND, POINT_IO = ["fr_io.cuh"], ["fr_io.cuh", "zbound.cuh"], ["point_io.cuh"]

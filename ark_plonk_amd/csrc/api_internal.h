@@ -5,15 +5,6 @@
 
 #include <cstring>
 
-// Montgomery one of the base field, arkworks layout (u64 limbs)
-inline void fq_one_sat(int curve, uint64_t* out) {
-    zk_on_curve(curve, 0, [&](auto cv) {
-        const typename decltype(cv)::Fq o = decltype(cv)::Fq::one();
-        memcpy(out, o.v, sizeof o.v);
-        return 0;
-    });
-}
-
 // offsets inside one working-memory allocation, and the grid of a one-lane-per-item launch
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline unsigned blocks_of(uint64_t n, uint64_t t) { return (unsigned)((n + t - 1) / t); }

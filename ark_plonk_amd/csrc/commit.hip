@@ -1,6 +1,7 @@
 // MSM and KZG commitment entry points over device inputs that block until the result is on the host, and the ctx's commitment cache
 // (zk_ctx::CommitCache, ctx.h): every function that writes its state.
 #include "api_internal.h"
+#include "g1_host.h"
 
 static int ensure_pinned_small(zk_ctx* c) {
     if (c->pinned_small) return ZK_OK;
@@ -24,12 +25,7 @@ static int msm_partial_locked(zk_ctx* c, zk_srs* s, size_t base_offset, const vo
     if (s->pre_wstep > 1 && s->pre_w0 != 0) {
         // window-sharded table: what the MSM entry points of this SRS return is the rank's PARTIAL, and the ranks' partials add up, so a
         // vector that does not take the table path is computed (whole, per-window path) by the owner of window 0 only; here: infinity
-        const int L = fq_limbs64(s->curve);
-        uint64_t one[ZK_MAX_FQ64];
-        fq_one_sat(s->curve, one);
-        memcpy(out_xyz, one, sizeof(uint64_t) * L);
-        memcpy(out_xyz + L, one, sizeof(uint64_t) * L);
-        memset(out_xyz + 2 * L, 0, sizeof(uint64_t) * L);
+        st_jacobian_inf(s->curve, out_xyz);
         return ZK_OK;
     }
     return msm_ops(s->curve)->run(c, d_bases, d_scalars, n, out_xyz);

@@ -18,7 +18,6 @@
 
 #include "../../include/ark_plonk_amd.h"
 #include "curve_params.h"
-#include "ec.cuh"
 #include "fieldu.cuh"
 #include "ecu.cuh"
 

@@ -71,7 +71,7 @@ ZK_D F qadd(const F& p, const F& q, uint32_t role) {
     // round 1: role0 U1 = X1*ZZ2, role1 S1 = Y1*ZZZ2, role2 U2 = ZZ1*X2, role3 S2 = ZZZ1*Y2
     const F m1 = F::mul(p, quad_xor(q, 2));
     // d: role0 P_ = U2 - U1, role1 R_ = S2 - S1 (roles 2, 3: unused)
-    const F d = F::sub8(quad_xor(m1, 2), m1);
+    const F d = F::sub(quad_xor(m1, 2), m1);
     // round 2: role0 PP = P_^2, role1 RR = R_^2, role2 ZZ1*ZZ2, role3 ZZZ1*ZZZ2
     const bool lo = role < 2;
     const F m2 = F::mul(fsel(lo, d, p), fsel(lo, d, q));
@@ -82,7 +82,7 @@ ZK_D F qadd(const F& p, const F& q, uint32_t role) {
     const F bc_ppp = quad_bcast(m3, 0);
     const F x3 = F::sub_sum3(m2, bc_ppp, m3, m3);
     const bool r1 = role == 1;
-    const F m4 = F::dot2(fsel(r1, d, m2), fsel(r1, F::sub16(m3, x3), bc_ppp), fsel(r1, F::neg16(m1), F::zero()), bc_ppp);
+    const F m4 = F::dot2(fsel(r1, d, m2), fsel(r1, F::sub(m3, x3), bc_ppp), fsel(r1, F::neg(m1), F::zero()), bc_ppp);
     const F x3_from_role1 = quad_xor(x3, 1);      // shuffles stay outside role-dependent control flow
     F res = role == 0 ? x3_from_role1 : role == 2 ? m3 : m4;
     // ZZ3 == 0 mod p  <=>  same x.  Then RR == 0 mod p <=> same y: P == Q, the sum is 2P; otherwise P == -Q and the
@@ -115,8 +115,8 @@ ZK_D F qdbl(const F& p, uint32_t role) {
     const bool r0 = role == 0;
     const F m3 = F::mul(fsel(r0, mm, p), fsel(r0, mm, bc_w));
     // round 4 (role0): X3 = M^2 - 2S, Y3 = M*(S - X3) - W*Y
-    const F x3 = F::sub8(m3, F::dbl(m2));
-    const F m4 = F::dot2(mm, F::sub16(m2, x3), bc_w, F::neg16(quad_bcast(p, 1)));
+    const F x3 = F::sub(m3, F::dbl(m2));
+    const F m4 = F::dot2(mm, F::sub(m2, x3), bc_w, F::neg(quad_bcast(p, 1)));
     const F y3_from_role0 = quad_xor(m4, 1);
     F res = role == 0 ? x3 : role == 1 ? y3_from_role0 : role == 2 ? m2 : m3;
     if (p_inf) res = p;

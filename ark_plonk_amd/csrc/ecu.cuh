@@ -1,7 +1,14 @@
-// G1 group law (a = 0) over the signed-limb base field Fs (fields.cuh) -- the device form of ec.cuh.
+// The G1 group law (short Weierstrass, a = 0): the one definition, taken by the signed-limb Fs (fields.cuh) on the device and by the
+// saturated Fp (field.cuh) on the host.
 //
-// Same formulas as ec.cuh (madd-2008-s / add-2008-s / dbl-2008-s-1, XYZZ coordinates) with the lazy
-// reduction calculus of fields.cuh: limbs are signed, so a difference is just a difference, and
+// Stands behind ark-ec 0.3 `GroupProjective::{add_assign_mixed, add_assign, double_in_place, into_affine}` as used by
+// `VariableBaseMSM::multi_scalar_mul` (reference call sites: plonk-core/src/commitment.rs:45, every PC::commit in
+// proof_system/prover.rs).  The reference accumulates in Jacobian coordinates; here points are kept in extended-Jacobian XYZZ
+// (x = X/ZZ, y = Y/ZZZ, ZZ^3 = ZZZ^2; infinity <=> ZZ = 0) because the mixed addition is 8M + 2S with no field inversion and fewer
+// live registers than Jacobian madd.  The formulas are madd-2008-s / add-2008-s / dbl-2008-s-1.  Results are compared after affine
+// normalisation, where the group element has a single representation.
+//
+// Over Fs the law is written for the lazy reduction calculus of fields.cuh: limbs are signed, so a difference is just a difference, and
 //   * products and squares come out in (-p, p) with strict limbs; stored coordinates are |X| < 4p (a
 //     sum of four products, almost-balanced limbs) and Y, ZZ, ZZZ products;
 //   * every operand of a product is a product, a stored coordinate or ONE sum / difference of those
@@ -9,10 +16,11 @@
 //   * Y3 = R*(Q - X3) - Y1*PPP is ONE double product with one Montgomery reduction (dot2 against -Y1);
 //   * P == +-Q is detected on the *result*: ZZ3 = ZZ1*PP is a product, so ZZ3 == 0 mod p iff its strict
 //     limbs are those of 0 (or +-p) -- compares on one limb in the common path.
-// The names sub8 / sub16 / neg16 are kept from the unsigned form (they said which multiple of p kept a
-// difference positive there); over Fs they are all plain limb-wise differences.
-// Infinity is ZZ = 0 with all limbs zero (only ever created explicitly).
+// Over Fp every value is canonical, so none of these bounds is needed: add3 / sub_sum3 / dot2 are the plain sums, limbs_zero and
+// is_zero_mod_reduced are both the exact zero test, and the law computes the same group elements with the same formulas.
+// Infinity is ZZ = 0 with all limbs zero (only ever created explicitly, or read as such from a device sum).
 #pragma once
+#include "field.cuh"
 #include "fields.cuh"
 
 // A condition the compiler cannot see through.  Steps that exclude one another, written as `if (zk_apart(a)) A; if (zk_apart(b)) B;`,
@@ -27,7 +35,7 @@ ZK_HD bool zk_apart(uint32_t flag) {
 
 template <class F>
 struct AffineU {
-    F x, y;  // residues in (-p, p), strict limbs, R' Montgomery domain; x = y = 0 limbs encodes "no point"
+    F x, y;  // over Fs: residues in (-p, p), strict limbs, R' Montgomery domain.  x = y = 0 limbs encodes "no point"
     ZK_HD bool is_null() const { return x.limbs_zero() && y.limbs_zero(); }
 };
 
@@ -63,8 +71,8 @@ struct XYZZu {
         F xx = F::sqr(p.x);
         F m = F::add3(xx, xx, xx);
         XYZZu r;
-        r.x = F::sub8(F::sqr(m), F::dbl(s));
-        r.y = F::dot2(m, F::sub16(s, r.x), w, F::neg16(p.y));   // m*(s - x3) - w*y, one reduction
+        r.x = F::sub(F::sqr(m), F::dbl(s));
+        r.y = F::dot2(m, F::sub(s, r.x), w, F::neg(p.y));   // m*(s - x3) - w*y, one reduction
         r.zz = v;
         r.zzz = w;
         return r;
@@ -79,8 +87,8 @@ struct XYZZu {
         F xx = F::sqr(p.x);
         F m = F::add3(xx, xx, xx);
         XYZZu r;
-        r.x = F::sub8(F::sqr(m), F::dbl(s));
-        r.y = F::dot2(m, F::sub16(s, r.x), w, F::neg16(p.y));
+        r.x = F::sub(F::sqr(m), F::dbl(s));
+        r.y = F::dot2(m, F::sub(s, r.x), w, F::neg(p.y));
         r.zz = F::mul(v, p.zz);
         r.zzz = F::mul(w, p.zzz);
         return r;
@@ -91,8 +99,8 @@ struct XYZZu {
         if (p.is_inf()) return from_affine(q);
         F u2 = F::mul(q.x, p.zz);
         F s2 = F::mul(q.y, p.zzz);
-        F pp_ = F::sub16(u2, p.x);
-        F r_ = F::sub16(s2, p.y);
+        F pp_ = F::sub(u2, p.x);
+        F r_ = F::sub(s2, p.y);
         F pp = F::sqr(pp_);
         F rr = F::sqr(r_);
         XYZZu o;
@@ -104,7 +112,7 @@ struct XYZZu {
         F ppp = F::mul(pp_, pp);
         F qq = F::mul(p.x, pp);
         o.x = F::sub_sum3(rr, ppp, qq, qq);
-        o.y = F::dot2(r_, F::sub16(qq, o.x), F::neg16(p.y), ppp);   // r*(qq - x3) - y1*ppp, one reduction
+        o.y = F::dot2(r_, F::sub(qq, o.x), F::neg(p.y), ppp);   // r*(qq - x3) - y1*ppp, one reduction
         o.zzz = F::mul(p.zzz, ppp);
         return o;
     }
@@ -126,8 +134,8 @@ struct XYZZu {
         return h;
     }
     ZK_HD static int madd_finish(XYZZu& p, const MaddHalf& h) {
-        F pp_ = F::sub16(h.u2, p.x);
-        F r_ = F::sub16(h.s2, p.y);
+        F pp_ = F::sub(h.u2, p.x);
+        F r_ = F::sub(h.s2, p.y);
         F pp = F::sqr(pp_);
         F rr = F::sqr(r_);
         p.zz = F::mul(p.zz, pp);
@@ -139,7 +147,7 @@ struct XYZZu {
             F ppp = F::mul(pp_, pp);
             F qq = F::mul(p.x, pp);
             p.x = F::sub_sum3(rr, ppp, qq, qq);
-            p.y = F::dot2(r_, F::sub16(qq, p.x), F::neg16(p.y), ppp);   // r*(qq - x3) - y1*ppp, one reduction
+            p.y = F::dot2(r_, F::sub(qq, p.x), F::neg(p.y), ppp);   // r*(qq - x3) - y1*ppp, one reduction
             p.zzz = F::mul(p.zzz, ppp);
         }
         return how;
@@ -153,8 +161,8 @@ struct XYZZu {
         F u2 = F::mul(q.x, p.zz);
         F s1 = F::mul(p.y, q.zzz);
         F s2 = F::mul(q.y, p.zzz);
-        F pp_ = F::sub8(u2, u1);
-        F r_ = F::sub8(s2, s1);
+        F pp_ = F::sub(u2, u1);
+        F r_ = F::sub(s2, s1);
         F pp = F::sqr(pp_);
         F rr = F::sqr(r_);
         XYZZu o;
@@ -166,9 +174,15 @@ struct XYZZu {
         F ppp = F::mul(pp_, pp);
         F qq = F::mul(u1, pp);
         o.x = F::sub_sum3(rr, ppp, qq, qq);
-        o.y = F::dot2(r_, F::sub16(qq, o.x), F::neg16(s1), ppp);
+        o.y = F::dot2(r_, F::sub(qq, o.x), F::neg(s1), ppp);
         o.zzz = F::mul(F::mul(p.zzz, q.zzz), ppp);
         return o;
+    }
+
+    ZK_HD static XYZZu neg(const XYZZu& p) {
+        XYZZu r = p;
+        r.y = F::neg(p.y);
+        return r;
     }
 
     // affine normalisation; returns false for infinity.  Output coordinates are products (< 2p).

@@ -1,15 +1,18 @@
-// Montgomery prime-field arithmetic on 32-bit limbs, shared by gfx950 device code and the host
-// side of the C ABI (final MSM window combine, domain constants).
+// Montgomery prime-field arithmetic on saturated 32-bit limbs, shared by gfx950 device code (the scalar field where a kernel wants
+// canonical values) and the host side of the C ABI (the MSM's window combine, the IPA and wire-format point arithmetic, domain constants).
 //
 // Replaces (behind the C ABI) ark-ff 0.3 Fp256/Fp384 as used by the reference's hot path
 // (plonk-core/src/proof_system/prover.rs:196-203 fft inputs, commitment.rs:33-48 scalars/points).
 // Host layout is arkworks': little-endian 64-bit limbs, Montgomery form with R = 2^(64*limbs);
 // a little-endian u64 limb array is byte-identical to the u32 limb array used here.
 //
+// Every value is canonical (in [0, p)), so every zero test is exact.  Fp<Fq> is the host's field under the G1 group law of ecu.cuh: the
+// names that law calls (add3, sub_sum3, dot2, limbs_zero, is_zero_mod_reduced, limb0_of_zero_mod) are one-line members here.
+//
 // Device mapping: one field element per lane, limbs in VGPRs; 32x32->64 multiply-accumulate
 // lowers to v_mad_u64_u32 on gfx950 (no MFMA: there is no dense contraction on this path).
 #pragma once
-#include "zk_common.h"
+#include "field_common.cuh"
 
 template <class P>
 struct Fp {
@@ -195,6 +198,14 @@ struct Fp {
     }
     ZK_HD static Fp sqr(const Fp& a) { return mul(a, a); }
 
+    // what the group law of ecu.cuh asks of its field beyond add / sub / neg / dbl / mul / sqr (fields.cuh has the lazy forms)
+    ZK_HD static Fp add3(const Fp& a, const Fp& b, const Fp& c) { return add(add(a, b), c); }
+    ZK_HD static Fp sub_sum3(const Fp& a, const Fp& b, const Fp& c, const Fp& d) { return sub(sub(sub(a, b), c), d); }
+    ZK_HD static Fp dot2(const Fp& a, const Fp& b, const Fp& c, const Fp& d) { return add(mul(a, b), mul(c, d)); }
+    ZK_HD bool limbs_zero() const { return is_zero(); }
+    ZK_HD bool is_zero_mod_reduced() const { return is_zero(); }
+    ZK_HD bool limb0_of_zero_mod() const { return v[0] == 0; }
+
     ZK_HD Fp operator+(const Fp& b) const { return add(*this, b); }
     ZK_HD Fp operator-(const Fp& b) const { return sub(*this, b); }
     ZK_HD Fp operator*(const Fp& b) const { return mul(*this, b); }
@@ -219,34 +230,18 @@ struct Fp {
         return to_mont(c);
     }
 
-    // a^e for a little-endian 32-bit-limb exponent (square-and-multiply, MSB first)
-    ZK_HD static Fp pow_limbs(const Fp& a, const uint32_t* e, int n) {
-        Fp r = one();
-        bool started = false;
-        for (int i = n - 1; i >= 0; --i)
-            for (int b = 31; b >= 0; --b) {
-                if (started) r = sqr(r);
-                if ((e[i] >> b) & 1u) {
-                    r = mul(r, a);
-                    started = true;
-                }
-            }
-        return r;
-    }
+    // a^e for a little-endian 32-bit-limb exponent
+    ZK_HD static Fp pow_limbs(const Fp& a, const uint32_t* e, int n) { return zk_pow_words(a, e, n); }
     ZK_HD static Fp pow_u64(const Fp& a, uint64_t e) {
         uint32_t l[2] = {(uint32_t)e, (uint32_t)(e >> 32)};
-        return pow_limbs(a, l, 2);
+        return zk_pow_words(a, l, 2);
     }
     // Fermat inverse a^(p-2); inverse(0) = 0
     ZK_HD static Fp inverse(const Fp& a) {
         uint32_t e[N];
-        uint32_t borrow = 2;
 #pragma unroll
-        for (int i = 0; i < N; ++i) {
-            uint64_t t = (uint64_t)P::MOD(i) - borrow;
-            e[i] = (uint32_t)t;
-            borrow = (uint32_t)(t >> 32) & 1u;
-        }
-        return pow_limbs(a, e, N);
+        for (int i = 0; i < N; ++i) e[i] = P::MOD(i);
+        zk_words_minus_two(e);
+        return zk_pow_words(a, e, N);
     }
 };

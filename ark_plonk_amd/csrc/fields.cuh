@@ -14,12 +14,14 @@
 //               what mul / sqr / dot2 / from_sat / canonical_lt2p return;
 //   "almost"  : |v[i]| <= 2^29 + 2 -- what add / sub / dbl / add3 return (one carry step, no ripple).
 // Inputs of mul / sqr / dot2: almost-balanced limbs, |value| < 12p.
-// The interface (names included) is the one of Fu<>, so the group law templates take either.
+// A difference is a plain limb-wise difference and a negation a limb-wise negation: no multiple of p is added, so `sub` and `neg` are
+// the only names.  The group law of ecu.cuh is written against this interface; the host instantiates it over the saturated Fp of
+// field.cuh, which carries the same names with canonical values.
 //
 // Stands behind ark-ff 0.3 Fp384 / Fp256 arithmetic inside VariableBaseMSM (commitment.rs:45); arkworks-format
 // values cross in / out through from_sat / to_sat.
 #pragma once
-#include "zk_common.h"
+#include "field_common.cuh"
 
 template <class P>
 struct Fs {
@@ -135,17 +137,12 @@ struct Fs {
         normalize_wide(t);
         return t;
     }
-    // the names the group law uses with Fu (there they say which multiple of p keeps the difference positive)
-    ZK_HD static Fs sub2(const Fs& a, const Fs& b) { return sub(a, b); }
-    ZK_HD static Fs sub8(const Fs& a, const Fs& b) { return sub(a, b); }
-    ZK_HD static Fs sub16(const Fs& a, const Fs& b) { return sub(a, b); }
-    ZK_HD static Fs neg16(const Fs& a) {                  // limb-wise: stays almost balanced
+    ZK_HD static Fs neg(const Fs& a) {                    // limb-wise: stays almost balanced
         Fs t;
 #pragma unroll
         for (int i = 0; i < NL; ++i) t.v[i] = 0u - a.v[i];
         return t;
     }
-    ZK_HD static Fs neg_canonical(const Fs& a) { return neg16(a); }
 
     // Montgomery product a*b/R': interleaved product scanning, one signed 64-bit accumulator per column (the
     // compiler merges the three partial sums below into one v_mad_i64_i32 chain per column, two columns interleaved).
@@ -352,49 +349,16 @@ struct Fs {
         return t;
     }
     // floor limbs of a non-negative value below 2^(32 SAT) -> words
-    ZK_HD void pack_words(uint32_t* w) const {
-#pragma unroll
-        for (int j = 0; j < SAT; ++j) {
-            const int lo_bit = 32 * j;
-            uint64_t acc = 0;
-#pragma unroll
-            for (int i = 0; i < NL; ++i) {
-                const int lb = 30 * i;
-                if (lb + 30 <= lo_bit || lb >= lo_bit + 32) continue;
-                if (lb >= lo_bit) acc |= (uint64_t)v[i] << (lb - lo_bit);
-                else acc |= (uint64_t)v[i] >> (lo_bit - lb);
-            }
-            w[j] = (uint32_t)acc;
-        }
-    }
+    ZK_HD void pack_words(uint32_t* w) const { zk_pack_words<30>(*this, w); }
 
-    // a^e, e little-endian 32-bit words (square-and-multiply)
-    ZK_HD static Fs pow_words(const Fs& a, const uint32_t* e, int n) {
-        Fs r = one();
-        bool started = false;
-        for (int i = n - 1; i >= 0; --i)
-            for (int b = 31; b >= 0; --b) {
-                if (started) r = sqr(r);
-                if ((e[i] >> b) & 1u) {
-                    r = mul(r, a);
-                    started = true;
-                }
-            }
-        return r;
-    }
+    // a^e, e little-endian 32-bit words
+    ZK_HD static Fs pow_words(const Fs& a, const uint32_t* e, int n) { return zk_pow_words(a, e, n); }
     // Fermat inverse; inverse(0) = 0
     ZK_HD static Fs inverse(const Fs& a) {
         uint32_t e[SAT];
 #pragma unroll
         for (int i = 0; i < SAT; ++i) e[i] = P::MODW(i);
-        uint64_t t = (uint64_t)e[0] - 2u;      // p - 2: p is odd and > 2
-        e[0] = (uint32_t)t;
-        uint32_t borrow = (uint32_t)(t >> 32) & 1u;
-        for (int i = 1; i < SAT && borrow; ++i) {
-            t = (uint64_t)e[i] - borrow;
-            e[i] = (uint32_t)t;
-            borrow = (uint32_t)(t >> 32) & 1u;
-        }
-        return pow_words(a, e, SAT);
+        zk_words_minus_two(e);
+        return zk_pow_words(a, e, SAT);
     }
 };

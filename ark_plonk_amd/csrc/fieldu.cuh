@@ -16,7 +16,7 @@
 // Stands behind ark-ff 0.3 Fp256 arithmetic in the NTT butterflies (prover.rs:196-203) and the polynomial
 // kernels; arkworks-format values cross in/out through from_sat/to_sat.
 #pragma once
-#include "zk_common.h"
+#include "field_common.cuh"
 
 template <class P>
 struct Fu {
@@ -309,7 +309,7 @@ struct Fu {
         Fu t = canonical_lt2p(mul(*this, c));
         t.pack_words(w);
     }
-    // plain integer (no Montgomery factor change): 32-bit words -> 29-bit limbs
+    // plain integer (no Montgomery factor change): 32-bit words -> 29-bit limbs, and back
     ZK_HD static Fu split_words(const uint32_t* w) {
         Fu t;
 #pragma unroll
@@ -322,54 +322,18 @@ struct Fu {
         }
         return t;
     }
-    ZK_HD void pack_words(uint32_t* w) const {
-#pragma unroll
-        for (int j = 0; j < SAT; ++j) {
-            // word j holds bits [32j, 32j+32): pieces of up to three limbs
-            const int lo_bit = 32 * j;
-            uint64_t acc = 0;
-#pragma unroll
-            for (int i = 0; i < NL; ++i) {
-                const int lb = 29 * i;
-                if (lb + 29 <= lo_bit || lb >= lo_bit + 32) continue;
-                if (lb >= lo_bit) acc |= (uint64_t)v[i] << (lb - lo_bit);
-                else acc |= (uint64_t)v[i] >> (lo_bit - lb);
-            }
-            w[j] = (uint32_t)acc;
-        }
-    }
+    ZK_HD void pack_words(uint32_t* w) const { zk_pack_words<29>(*this, w); }
 
-    // a^e, e little-endian 32-bit words (square-and-multiply)
-    ZK_HD static Fu pow_words(const Fu& a, const uint32_t* e, int n) {
-        Fu r = one();
-        bool started = false;
-        for (int i = n - 1; i >= 0; --i)
-            for (int b = 31; b >= 0; --b) {
-                if (started) r = sqr(r);
-                if ((e[i] >> b) & 1u) {
-                    r = mul(r, a);
-                    started = true;
-                }
-            }
-        return r;
-    }
+    // a^e, e little-endian 32-bit words
+    ZK_HD static Fu pow_words(const Fu& a, const uint32_t* e, int n) { return zk_pow_words(a, e, n); }
     // Fermat inverse (inputs < 64p); inverse(0) = 0
     ZK_HD static Fu inverse(const Fu& a) {
-        // exponent p - 2 as 32-bit words
         Fu pm;
 #pragma unroll
         for (int i = 0; i < NL; ++i) pm.v[i] = P::MOD(i);
         uint32_t e[SAT];
         pm.pack_words(e);
-        // p is odd and > 2: subtracting 2 only touches the low word unless it underflows
-        uint64_t t = (uint64_t)e[0] - 2u;
-        e[0] = (uint32_t)t;
-        uint32_t borrow = (uint32_t)(t >> 32) & 1u;
-        for (int i = 1; i < SAT && borrow; ++i) {
-            t = (uint64_t)e[i] - borrow;
-            e[i] = (uint32_t)t;
-            borrow = (uint32_t)(t >> 32) & 1u;
-        }
-        return pow_words(a, e, SAT);
+        zk_words_minus_two(e);
+        return zk_pow_words(a, e, SAT);
     }
 };

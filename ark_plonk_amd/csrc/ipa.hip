@@ -10,6 +10,7 @@
 //   a' = a_l + xi^-1 a_r, b' = b_l + xi b_r   (ipa_scalar_pass: also the canonical copy of a' and the next round's inner products)
 // Round 0 reads the registered key itself (SRS window-table path); later rounds run the per-window MSM over the folded key.
 #include "api_internal.h"
+#include "g1_host.h"
 #include "fr_io.cuh"
 #include "point_io.cuh"
 
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(FOLD_T) ipa_fold_key(const void* src, void* ds
                 if (dp || dn) {
                     AffineU<F> qq;
                     qq.x = q.x;
-                    qq.y = dn ? F::neg16(q.y) : q.y;
+                    qq.y = dn ? F::neg(q.y) : q.y;
                     acc = P::madd(acc, qq);
                 }
             }
@@ -299,42 +300,12 @@ int launch_scalar_pass(zk_ctx* c, void* a, void* b, size_t mo, const typename Cv
 // host: affine out = P + k * Q (P Jacobian as the MSM returns it, Q affine Montgomery, k Montgomery Fr)
 template <class Cv>
 void add_scaled(const uint64_t* xyz, const uint64_t* q_xy, const typename Cv::Fr& k_mont, uint64_t* out_xy, uint8_t* out_inf) {
-    typedef typename Cv::Fq Fq;
+    typedef G1Host<typename Cv::Fq> H;
     typedef typename Cv::Fr Fr;
-    typedef XYZZ<Fq> PH;
-    constexpr int L64 = Fq::N / 2;
-    PH p;
-    Fq Z;
-    memcpy(p.x.v, xyz, 8 * L64);
-    memcpy(p.y.v, xyz + L64, 8 * L64);
-    memcpy(Z.v, xyz + 2 * L64, 8 * L64);
-    p.zz = Fq::sqr(Z);
-    p.zzz = Fq::mul(p.zz, Z);
-    Affine<Fq> q;
-    memcpy(q.x.v, q_xy, 8 * L64);
-    memcpy(q.y.v, q_xy + L64, 8 * L64);
-    const bool q_inf = q.x.is_zero() && (q.y.is_zero() || q.y == Fq::one());
-    if (!q_inf) {
-        const Fr k = Fr::from_mont(k_mont);
-        PH acc = PH::infinity();
-        for (int w = 7; w >= 0; --w)
-            for (int bit = 31; bit >= 0; --bit) {
-                acc = PH::dbl(acc);
-                if ((k.v[w] >> bit) & 1u) acc = PH::madd(acc, q);
-            }
-        p = PH::add(p, acc);
-    }
-    Affine<Fq> a;
-    if (!p.to_affine(a)) {
-        const Fq one = Fq::one();
-        memset(out_xy, 0, 8 * L64);
-        memcpy(out_xy + L64, one.v, 8 * L64);
-        if (out_inf) *out_inf = 1;
-        return;
-    }
-    memcpy(out_xy, a.x.v, 8 * L64);
-    memcpy(out_xy + L64, a.y.v, 8 * L64);
-    if (out_inf) *out_inf = 0;
+    typename H::P p = H::ld_jacobian(xyz);
+    const typename H::A q = H::ld_affine(q_xy);
+    if (!H::affine_is_inf(q)) p = H::P::add(p, H::scalar_mul(q, Fr::from_mont(k_mont).v, Fr::N));
+    H::st_normalised(out_xy, out_inf, p);
 }
 
 // NULL handles, a key of another device, a key length that is not a power of two: ZK_ERR_BAD_ARG
@@ -353,7 +324,7 @@ template <class Cv>
 int round_impl(zk_ctx* c, zk_srs* s, int first_round, size_t m, void* d_a, void* d_b, void* d_work, const uint64_t* h_prime_xy,
                uint64_t* out_lr_xy, uint8_t* out_lr_inf) {
     typedef typename Cv::Fr Fr;
-    constexpr int L64 = Cv::Fq::N / 2;
+    constexpr int L64 = G1Host<typename Cv::Fq>::L;
     const Layout ly = layout(s->curve, s->n);
     char* w = (char*)d_work;
     void* a_can = w + ly.a_can;
@@ -447,24 +418,17 @@ int to_abi(zk_ctx* c, const void* src, size_t n, void* d_out_xy, uint8_t* d_out_
 template <class Cv>
 void internal_to_abi_host(const void* pt, uint64_t* out_xy, uint8_t* out_inf) {
     typedef typename Cv::FqU F;
-    typedef typename Cv::Fq Fq;
-    constexpr int L64 = Fq::N / 2;
+    typedef G1Host<typename Cv::Fq> H;
     const uint32_t* w = (const uint32_t*)pt;
-    F x, y;
+    AffineU<F> p;
     for (int k = 0; k < F::NL; ++k) {
-        x.v[k] = w[k];
-        y.v[k] = w[4 * Store<F>::U4 + k];
+        p.x.v[k] = w[k];
+        p.y.v[k] = w[4 * Store<F>::U4 + k];
     }
-    const bool inf = x.limbs_zero() && y.limbs_zero();
-    if (inf) {
-        const Fq one = Fq::one();
-        memset(out_xy, 0, 8 * L64);
-        memcpy(out_xy + L64, one.v, 8 * L64);
-    } else {
-        x.to_sat((uint32_t*)out_xy);
-        y.to_sat((uint32_t*)(out_xy + L64));
-    }
-    if (out_inf) *out_inf = inf ? 1 : 0;
+    if (p.is_null()) return H::st_affine_inf(out_xy, out_inf);
+    p.x.to_sat((uint32_t*)out_xy);
+    p.y.to_sat((uint32_t*)(out_xy + H::L));
+    if (out_inf) *out_inf = 0;
 }
 
 }  // namespace

@@ -65,14 +65,14 @@ ZK_D void accumulate_chunk(const uint32_t t, const uint32_t* entries, const uint
         const bool add = zk_apart(point && !inf);
         if (zk_apart(point && inf)) {
             acc.x = p.x;
-            acc.y = (ref >> 31) ? F::neg_canonical(p.y) : p.y;
+            acc.y = (ref >> 31) ? F::neg(p.y) : p.y;
             acc.zz = F::one();
             acc.zzz = F::one();
             inf = false;
         }
         typename XYZZu<F>::MaddHalf h;
         if (add) {
-            if (ref >> 31) p.y = F::neg_canonical(p.y);
+            if (ref >> 31) p.y = F::neg(p.y);
             h = XYZZu<F>::madd_begin(acc, p);
         }
         p = ld_affine<F>(bases, point_index(ref_n));
@@ -82,7 +82,7 @@ ZK_D void accumulate_chunk(const uint32_t t, const uint32_t* entries, const uint
             // P == +-Q: the row of THIS reference is read again (p holds the next point by now)
             if (how == XYZZu<F>::MADD_SAME) {
                 AffineU<F> q = ld_affine<F>(bases, point_index(ref));
-                if (ref >> 31) q.y = F::neg_canonical(q.y);
+                if (ref >> 31) q.y = F::neg(q.y);
                 acc = XYZZu<F>::dbl_affine(q);
             } else {
                 inf = true;

@@ -9,47 +9,22 @@
 // the host combine of the window sums and the affine normalisation.  No kernel is defined here: the units msm_sort / msm_accumulate /
 // msm_reduce queue them (ZK_SYM entry points of msm_common.cuh).  The unit ends with the curve's MsmOps table (ctx.h).
 #include "msm_common.cuh"
+#include "g1_host.h"
 
 #include <array>
 
 namespace {
 
 int ensure_pinned(zk_ctx* c, size_t bytes);
-template <class Fq>
-XYZZ<Fq> jac_to_xyzz(const uint64_t* xyz);
-
-// XYZZ -> Jacobian (X*ZZ, Y*ZZZ, ZZ):  x = X/ZZ = X*ZZ/ZZ^2, y = Y/ZZZ = Y*ZZZ/ZZ^3; infinity as arkworks writes Jacobian zero: (1, 1, 0)
-template <class Fq>
-void put_jacobian(const XYZZ<Fq>& p, uint64_t* out_xyz) {
-    constexpr int L64 = Fq::N / 2;
-    Fq X = Fq::one(), Y = Fq::one(), Z = Fq::zero();
-    if (!p.is_inf()) {
-        X = Fq::mul(p.x, p.zz);
-        Y = Fq::mul(p.y, p.zzz);
-        Z = p.zz;
-    }
-    memcpy(out_xyz, X.v, sizeof(uint64_t) * L64);
-    memcpy(out_xyz + L64, Y.v, sizeof(uint64_t) * L64);
-    memcpy(out_xyz + 2 * L64, Z.v, sizeof(uint64_t) * L64);
-}
-// GroupAffine::zero() = (0, 1, infinity = true)
-template <class Fq>
-void put_affine_zero(uint64_t* out_xy, uint8_t* out_inf) {
-    constexpr int L64 = Fq::N / 2;
-    const Fq zero = Fq::zero(), one = Fq::one();
-    memcpy(out_xy, zero.v, sizeof(uint64_t) * L64);
-    memcpy(out_xy + L64, one.v, sizeof(uint64_t) * L64);
-    if (out_inf) *out_inf = 1;
-}
 
 template <class Cv>
 int msm_run(zk_ctx* c, const void* d_bases, const void* d_scalars, size_t n, uint64_t* out_xyz) {
-    typedef typename Cv::Fq Fq;       // host / arkworks-layout arithmetic
-    typedef typename Cv::FqU F;       // device arithmetic
-    typedef XYZZ<Fq> PH;
+    typedef G1Host<typename Cv::Fq> H;   // host / arkworks-layout arithmetic
+    typedef typename Cv::FqU F;          // device arithmetic
+    typedef typename H::P PH;
     constexpr size_t PT = Store<F>::POINT_BYTES;
     if (n == 0) {
-        put_jacobian<Fq>(PH::infinity(), out_xyz);
+        H::st_jacobian(out_xyz, PH::infinity());
         return ZK_OK;
     }
     if (n >= (1ull << 31)) return ZK_ERR_UNSUPPORTED;
@@ -91,7 +66,7 @@ int msm_run(zk_ctx* c, const void* d_bases, const void* d_scalars, size_t n, uin
         for (uint32_t k = 0; k < g.c; ++k) total = PH::dbl(total);
         total = PH::add(total, win[w]);
     }
-    put_jacobian<Fq>(total, out_xyz);
+    H::st_jacobian(out_xyz, total);
     return ZK_OK;
 }
 
@@ -126,8 +101,7 @@ inline void pre_reduce_geom(const zk_ctx* c, PrePlan& pl) {
 // pre_plan_geom derives the plan and allocates nothing; pre_sizes / pre_need / pre_ensure are its buffers.
 template <class Cv>
 int pre_plan_geom(const zk_ctx* c, const zk_srs* s, size_t n, PrePlan& pl, bool long_chunks = false) {
-    typedef typename Cv::Fq Fq;
-    typedef XYZZ<Fq> PH;
+    typedef XYZZu<typename Cv::Fq> PH;
     if (n > zk_pre_max_n(c)) return ZK_ERR_UNSUPPORTED;      // the callers (api.hip) send longer vectors down the per-window path
     pl.g = make_geom<typename Cv::FrP>(n, (int)s->pre_c, PRE_C_MAX);
     if (pl.g.W != s->pre_W || pl.g.W > 32) return ZK_ERR_UNSUPPORTED;
@@ -279,15 +253,12 @@ bool partial_dev_supported(zk_ctx* c, zk_srs* s, uint32_t* vw, uint32_t* vb) {
 // were computed at submission (vectors too short for the table path)
 template <class Cv>
 void jacobian_to_partial_host(const uint64_t* xyz, void* out) {
-    typedef typename Cv::Fq Fq;
+    typedef G1Host<typename Cv::Fq> H;
     typedef typename Cv::FqU F;
-    constexpr int L64 = Fq::N / 2;
     memset(out, 0, Store<F>::POINT_BYTES);
-    Fq Z;
-    memcpy(Z.v, xyz + 2 * L64, sizeof(uint64_t) * L64);
-    if (Z.is_zero()) return;                       // infinity: all limbs zero
-    const XYZZ<Fq> p = jac_to_xyzz<Fq>(xyz);
-    const Fq* co[4] = {&p.x, &p.y, &p.zz, &p.zzz};
+    if (H::jacobian_is_inf(xyz)) return;           // infinity: all limbs zero
+    const typename H::P p = H::ld_jacobian(xyz);
+    const typename Cv::Fq* co[4] = {&p.x, &p.y, &p.zz, &p.zzz};
     for (int r = 0; r < 4; ++r) {
         const F v = F::canonical_lt2p(F::from_sat((const uint32_t*)co[r]->v));
         uint32_t* w = (uint32_t*)out + (size_t)r * Store<F>::WORDS;
@@ -299,13 +270,12 @@ void jacobian_to_partial_host(const uint64_t* xyz, void* out) {
 // wide reduction: h = [sum_v S_v (as win: unused), sum_v S_v (tot) | K = sum_v (v+1) T_v, sum_v T_v]; buckets per virtual window = 2^log_bv
 template <class Cv>
 void pre_host_wide(const void* h, uint32_t log_bv, uint64_t* out_xyz) {
-    typedef typename Cv::Fq Fq;
-    typedef XYZZ<Fq> PH;
+    typedef G1Host<typename Cv::Fq> H;
+    typedef typename H::P PH;
     const PH* w = (const PH*)h;
     PH d = PH::add(w[2], PH::neg(w[3]));
     for (uint32_t k = 0; k < log_bv; ++k) d = PH::dbl(d);
-    PH total = PH::add(w[1], d);
-    put_jacobian<Fq>(total, out_xyz);
+    H::st_jacobian(out_xyz, PH::add(w[1], d));
 }
 
 // host: S = sum_v S_v + B_v * sum_v v * T_v   (bucket j of virtual window v has weight v*B_v + local index).
@@ -315,11 +285,11 @@ void pre_host_wide(const void* h, uint32_t log_bv, uint64_t* out_xyz) {
 constexpr uint32_t HOST_CHUNKS = 4;
 template <class Fq>
 struct HostPartial {
-    XYZZ<Fq> s, t, w;
+    XYZZu<Fq> s, t, w;
 };
 template <class Cv>
 void pre_host_partial(const void* h_win, uint32_t VW, uint32_t lo, uint32_t hi, HostPartial<typename Cv::Fq>& out) {
-    typedef XYZZ<typename Cv::Fq> PH;
+    typedef XYZZu<typename Cv::Fq> PH;
     const PH* win = (const PH*)h_win;
     PH s = PH::infinity(), run = PH::infinity(), w = PH::infinity();
     for (int v = (int)hi - 1; v >= (int)lo; --v) {
@@ -335,8 +305,8 @@ void pre_host_partial(const void* h_win, uint32_t VW, uint32_t lo, uint32_t hi, 
 }
 template <class Cv>
 void pre_host_final(const HostPartial<typename Cv::Fq>* part, uint32_t VW, uint32_t VB, uint64_t* out_xyz) {
-    typedef typename Cv::Fq Fq;
-    typedef XYZZ<Fq> PH;
+    typedef G1Host<typename Cv::Fq> H;
+    typedef typename H::P PH;
     // sum_c c * t_c by running sums, then times the chunk length (a power of two), plus the local weights
     PH total = PH::infinity(), run = PH::infinity(), ct = PH::infinity(), wsum = PH::infinity();
     for (int c = (int)HOST_CHUNKS - 1; c >= 0; --c) {
@@ -350,8 +320,7 @@ void pre_host_final(const HostPartial<typename Cv::Fq>* part, uint32_t VW, uint3
     for (uint32_t k = 0; (1u << k) < VW / HOST_CHUNKS; ++k) ct = PH::dbl(ct);
     wsum = PH::add(wsum, ct);
     for (uint32_t k = 0; (1u << k) < VB; ++k) wsum = PH::dbl(wsum);
-    total = PH::add(total, wsum);
-    put_jacobian<Fq>(total, out_xyz);
+    H::st_jacobian(out_xyz, PH::add(total, wsum));
 }
 template <class Cv>
 void pre_host_combine(const void* h_win, uint32_t VW, uint32_t VB, uint64_t* out_xyz) {
@@ -393,8 +362,12 @@ int msm_run_pre(zk_ctx* c, zk_srs* s, size_t base_offset, const void* d_scalars,
     return ZK_OK;
 }
 
+// Jacobian -> affine (one field inversion)
 template <class Fq>
-int jac_to_affine(const uint64_t* xyz, uint64_t* out_xy, uint8_t* out_inf);
+int jac_to_affine(const uint64_t* xyz, uint64_t* out_xy, uint8_t* out_inf) {
+    G1Host<Fq>::st_normalised(out_xy, out_inf, G1Host<Fq>::ld_jacobian(xyz));
+    return ZK_OK;
+}
 
 // A batch of commitments over the same SRS (the polynomials of one prover round): Montgomery
 // coefficients in, Jacobian results out.  Every job has its own buffer set and every step is ONE launch per kernel
@@ -543,7 +516,7 @@ template <class Cv>
 int pre_host_finish_jobs(zk_ctx* c, const char* h_win, size_t wb, uint32_t n_jobs, bool wide_red, uint32_t VW, uint32_t VB,
                          uint64_t* out_xyz /* n_jobs x 3L */, uint64_t* out_xy /* optional */, uint8_t* out_inf /* optional */) {
     typedef typename Cv::Fq Fq;
-    constexpr int L64 = Fq::N / 2;
+    constexpr int L64 = G1Host<Fq>::L;
     int rcs[MAX_JOBS] = {0};
     // ~200 point additions + one field inversion per job (measured: 200 us on one host thread, the GPU idle meanwhile): every
     // job's virtual windows are cut into HOST_CHUNKS ranges that go to the pool as separate items, and whichever thread
@@ -571,8 +544,8 @@ int pre_host_finish_jobs(zk_ctx* c, const char* h_win, size_t wb, uint32_t n_job
 template <class Cv>
 int sum_winsums_dev(zk_ctx* c, zk_srs* s, const void* d_all, size_t ranks, uint32_t n_jobs, uint64_t* out_xy, uint8_t* out_inf) {
     typedef typename Cv::Fq Fq;
-    typedef XYZZ<Fq> PH;
-    constexpr int L64 = Fq::N / 2;
+    typedef XYZZu<Fq> PH;
+    constexpr int L64 = G1Host<Fq>::L;
     if (n_jobs == 0) return ZK_OK;
     if (ranks == 0 || ranks > 4096 || n_jobs > (uint32_t)MAX_JOBS) return ZK_ERR_BAD_ARG;
     uint32_t VW = 0, VB = 0;
@@ -608,7 +581,7 @@ int msm_batch_pre_end(zk_ctx* c, zk_srs* s, uint32_t n_jobs, const uint32_t* slo
 template <class Cv>
 int msm_batch_pre(zk_ctx* c, zk_srs* s, uint32_t n_polys, const void* const* d_coeffs, const size_t* lens, uint64_t* out_xyz /* n_polys x 3L */,
                   const uint8_t* kinds, uint64_t* out_xy, uint8_t* out_inf, const std::function<int(uint32_t)>* before_job) {
-    constexpr int L64 = Cv::Fq::N / 2;
+    constexpr int L64 = G1Host<typename Cv::Fq>::L;
     if (n_polys == 0) return ZK_OK;
     if (n_polys > (uint32_t)MAX_JOBS) return ZK_ERR_UNSUPPORTED;
     for (int k = 0; k < MAX_JOBS; ++k) c->mb[k].stage_of_job = 0;     // no round is open (the callers refuse otherwise): every set is free
@@ -646,54 +619,11 @@ int msm_batch_pre(zk_ctx* c, zk_srs* s, uint32_t n_polys, const void* const* d_c
 }
 
 template <class Fq>
-int jac_to_affine(const uint64_t* xyz, uint64_t* out_xy, uint8_t* out_inf) {
-    constexpr int L64 = Fq::N / 2;
-    Fq X, Y, Z;
-    memcpy(X.v, xyz, sizeof(uint64_t) * L64);
-    memcpy(Y.v, xyz + L64, sizeof(uint64_t) * L64);
-    memcpy(Z.v, xyz + 2 * L64, sizeof(uint64_t) * L64);
-    if (Z.is_zero()) {
-        put_affine_zero<Fq>(out_xy, out_inf);
-        return ZK_OK;
-    }
-    Fq zi = Fq::inverse(Z);
-    Fq zi2 = Fq::sqr(zi);
-    Fq x = Fq::mul(X, zi2);
-    Fq y = Fq::mul(Y, Fq::mul(zi2, zi));
-    memcpy(out_xy, x.v, sizeof(uint64_t) * L64);
-    memcpy(out_xy + L64, y.v, sizeof(uint64_t) * L64);
-    if (out_inf) *out_inf = 0;
-    return ZK_OK;
-}
-
-// Jacobian (X, Y, Z) -> XYZZ (X, Y, Z^2, Z^3)
-template <class Fq>
-XYZZ<Fq> jac_to_xyzz(const uint64_t* xyz) {
-    constexpr int L64 = Fq::N / 2;
-    XYZZ<Fq> p;
-    Fq Z;
-    memcpy(p.x.v, xyz, sizeof(uint64_t) * L64);
-    memcpy(p.y.v, xyz + L64, sizeof(uint64_t) * L64);
-    memcpy(Z.v, xyz + 2 * L64, sizeof(uint64_t) * L64);
-    p.zz = Fq::sqr(Z);
-    p.zzz = Fq::mul(p.zz, Z);
-    return p;
-}
-
-template <class Fq>
 int sum_partials(const uint64_t* partials, size_t count, uint64_t* out_xy, uint8_t* out_inf) {
-    constexpr int L64 = Fq::N / 2;
-    XYZZ<Fq> acc = XYZZ<Fq>::infinity();
-    for (size_t i = 0; i < count; ++i) acc = XYZZ<Fq>::add(acc, jac_to_xyzz<Fq>(partials + i * 3 * L64));
-    Affine<Fq> a;
-    bool fin = acc.to_affine(a);
-    if (!fin) {
-        put_affine_zero<Fq>(out_xy, out_inf);
-        return ZK_OK;
-    }
-    memcpy(out_xy, a.x.v, sizeof(uint64_t) * L64);
-    memcpy(out_xy + L64, a.y.v, sizeof(uint64_t) * L64);
-    if (out_inf) *out_inf = 0;
+    typedef G1Host<Fq> H;
+    typename H::P acc = H::P::infinity();
+    for (size_t i = 0; i < count; ++i) acc = H::P::add(acc, H::ld_jacobian(partials + i * 3 * H::L));
+    H::st_normalised(out_xy, out_inf, acc);
     return ZK_OK;
 }
 

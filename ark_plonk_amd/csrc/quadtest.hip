@@ -11,8 +11,8 @@ template <class F>
 ZK_D bool same_point(const XYZZu<F>& a, const XYZZu<F>& b) {
     if (a.is_inf() || b.is_inf()) return a.is_inf() && b.is_inf();
     // x_a/zz_a == x_b/zz_b and y_a/zzz_a == y_b/zzz_b
-    const F dx = F::sub8(F::mul(a.x, b.zz), F::mul(b.x, a.zz));
-    const F dy = F::sub8(F::mul(a.y, b.zzz), F::mul(b.y, a.zzz));
+    const F dx = F::sub(F::mul(a.x, b.zz), F::mul(b.x, a.zz));
+    const F dy = F::sub(F::mul(a.y, b.zzz), F::mul(b.y, a.zzz));
     return dx.is_zero_mod() && dy.is_zero_mod();
 }
 
@@ -45,7 +45,7 @@ __global__ void __launch_bounds__(256) quad_selftest(uint32_t n_quads, uint32_t*
     if (kind == 1) Q = P;
     if (kind == 2) {
         Q = P;
-        Q.y = F::neg16(Q.y);
+        Q.y = F::neg(Q.y);
     }
     if (kind == 3 || kind == 5) P = XYZZu<F>::infinity();
     if (kind == 4 || kind == 5) Q = XYZZu<F>::infinity();

@@ -13,7 +13,7 @@
 //    circuit_domain_sep = ("dom-sep","circuit_size") + append_u64("n").
 // merlin, ark-serialize and ark-ff are crates.io dependencies absent from /root/reference (plonk-core/Cargo.toml:51-65):
 // this file restates their published behaviour; tests pin it on merlin's published conformance vector.
-#include "ctx.h"
+#include "g1_host.h"
 
 namespace {
 
@@ -152,6 +152,7 @@ struct Wire {
     typedef typename Cv::Fr Fr;
     typedef typename Cv::FqP FqP;
     typedef typename Cv::FrP FrP;
+    typedef G1Host<Fq> H;
     static constexpr size_t FQ_BYTES = (FqP::BITS + 2 + 7) / 8;   // serialize_with_flags::<SWFlags>: 2 flag bits
     static constexpr size_t FR_BYTES = (FrP::BITS + 7) / 8;
 
@@ -167,59 +168,34 @@ struct Wire {
         memcpy(mont, x.v, 32);
         return ZK_OK;
     }
-    static void load_xy(const uint64_t* xy, Fq& x, Fq& y) {
-        memcpy(x.v, xy, sizeof x.v);
-        memcpy(y.v, xy + Fq::N / 2, sizeof y.v);
-    }
-    static bool is_inf(const uint64_t* xy, uint8_t inf) {
-        if (inf) return true;
-        Fq x, y;
-        load_xy(xy, x, y);
-        return x.is_zero() && (y.is_zero() || y == Fq::one());
-    }
     static int g1_ser_c(const uint64_t* xy, uint8_t inf, uint8_t* out) {
-        if (is_inf(xy, inf)) {
+        const typename H::A a = H::ld_affine(xy);
+        if (H::affine_is_inf(a, inf)) {
             memset(out, 0, FQ_BYTES);
             out[FQ_BYTES - 1] |= 1u << 6;
             return ZK_OK;
         }
-        Fq x, y;
-        load_xy(xy, x, y);
-        fp_to_le_bytes<Fq>(x, out, FQ_BYTES);
-        if (fp_gt<Fq>(y, Fq::neg(y))) out[FQ_BYTES - 1] |= 1u << 7;
+        fp_to_le_bytes<Fq>(a.x, out, FQ_BYTES);
+        if (fp_gt<Fq>(a.y, Fq::neg(a.y))) out[FQ_BYTES - 1] |= 1u << 7;
         return ZK_OK;
     }
     static int g1_ser_u(const uint64_t* xy, uint8_t inf, uint8_t* out) {
-        if (is_inf(xy, inf)) {
+        const typename H::A a = H::ld_affine(xy);
+        if (H::affine_is_inf(a, inf)) {
             memset(out, 0, 2 * FQ_BYTES);
             out[2 * FQ_BYTES - 1] |= 1u << 6;
             return ZK_OK;
         }
-        Fq x, y;
-        load_xy(xy, x, y);
-        fp_to_le_bytes<Fq>(x, out, FQ_BYTES);
-        fp_to_le_bytes<Fq>(y, out + FQ_BYTES, FQ_BYTES);
+        fp_to_le_bytes<Fq>(a.x, out, FQ_BYTES);
+        fp_to_le_bytes<Fq>(a.y, out + FQ_BYTES, FQ_BYTES);
         return ZK_OK;
     }
     static Fq curve_rhs(const Fq& x) { return Fq::add(Fq::mul(Fq::sqr(x), x), Fq::from_u32(FqP::COEFF_B)); }
     // r * P == O ?  (ark's is_in_correct_subgroup_assuming_on_curve)
     static bool in_subgroup(const Fq& x, const Fq& y) {
-        typedef XYZZ<Fq> PH;
-        Affine<Fq> a;
-        a.x = x;
-        a.y = y;
-        PH acc = PH::infinity();
-        for (int i = Fr::N - 1; i >= 0; --i)
-            for (int b = 31; b >= 0; --b) {
-                acc = PH::dbl(acc);
-                if ((FrP::MOD(i) >> b) & 1u) acc = PH::madd(acc, a);
-            }
-        return acc.is_inf();
-    }
-    static void store_xy(uint64_t* xy, uint8_t* inf, const Fq& x, const Fq& y, bool infinity) {
-        memcpy(xy, x.v, sizeof x.v);
-        memcpy(xy + Fq::N / 2, y.v, sizeof y.v);
-        if (inf) *inf = infinity ? 1 : 0;
+        uint32_t r[Fr::N];
+        for (int i = 0; i < Fr::N; ++i) r[i] = FrP::MOD(i);
+        return H::scalar_mul(typename H::A{x, y}, r, Fr::N).is_inf();
     }
     static int g1_de_c(const uint8_t* in, uint64_t* xy, uint8_t* inf) {
         uint8_t buf[FQ_BYTES];
@@ -230,7 +206,7 @@ struct Wire {
         Fq x;
         if (!fp_from_le_bytes<Fq, FqP>(buf, FQ_BYTES, x)) return ZK_ERR_BAD_ARG;
         if (flags & 0x40) {                                  // infinity: GroupAffine::zero() = (0, 1)
-            store_xy(xy, inf, Fq::zero(), Fq::one(), true);
+            H::st_affine_inf(xy, inf);
             return ZK_OK;
         }
         // both base fields are 3 mod 4: sqrt(a) = a^((p+1)/4)
@@ -250,7 +226,7 @@ struct Wire {
         const bool want_greatest = (flags & 0x80) != 0;
         if (fp_gt<Fq>(y, ny) != want_greatest) y = ny;
         if (!in_subgroup(x, y)) return ZK_ERR_BAD_ARG;
-        store_xy(xy, inf, x, y, false);
+        H::st_affine(xy, inf, typename H::A{x, y});
         return ZK_OK;
     }
     static int g1_de_u(const uint8_t* in, uint64_t* xy, uint8_t* inf) {
@@ -262,11 +238,11 @@ struct Wire {
         Fq x, y;
         if (!fp_from_le_bytes<Fq, FqP>(in, FQ_BYTES, x) || !fp_from_le_bytes<Fq, FqP>(buf, FQ_BYTES, y)) return ZK_ERR_BAD_ARG;
         if (flags & 0x40) {
-            store_xy(xy, inf, Fq::zero(), Fq::one(), true);
+            H::st_affine_inf(xy, inf);
             return ZK_OK;
         }
         if (Fq::sqr(y) != curve_rhs(x) || !in_subgroup(x, y)) return ZK_ERR_BAD_ARG;
-        store_xy(xy, inf, x, y, false);
+        H::st_affine(xy, inf, typename H::A{x, y});
         return ZK_OK;
     }
     // transcript.rs:35-46: size = size_in_bits / 8 challenge bytes -> F::from_random_bytes

@@ -1,9 +1,10 @@
-// Host-side harness for the unsaturated fields / lazy XYZZ code (fieldu.cuh, fields.cuh, ecu.cuh): the same
-// templates the HIP kernels instantiate, compiled with g++ so tests/test_fieldu.py can check them
-// against the big-int oracle without a GPU; and for the device-only load conversion of the quotient kernel and the circuit
+// Host-side harness for the unsaturated fields / the XYZZ group law (fieldu.cuh, fields.cuh, ecu.cuh): the same
+// templates the HIP kernels instantiate, and the law's host instantiation over the saturated field (field.cuh), compiled with g++ so
+// tests/test_fieldu.py can check them against the big-int oracle without a GPU; and for the device-only load conversion of the quotient kernel and the circuit
 // check (zbound.cuh) and the hash of the device key maps (fr_io.cuh).
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 #include "../../ark_plonk_amd/csrc/curve_params.h"
 #include "../../ark_plonk_amd/csrc/field.cuh"
 #include "../../ark_plonk_amd/csrc/fieldu.cuh"
@@ -18,10 +19,31 @@ static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
 #include "../../ark_plonk_amd/csrc/zbound.cuh"
 
 template <class F>
+struct is_fs : std::false_type {};
+template <class P>
+struct is_fs<Fs<P>> : std::true_type {};
+template <class F>
+struct is_fp : std::false_type {};
+template <class P>
+struct is_fp<Fp<P>> : std::true_type {};
+
+// x - y and -x as each field names them: Fu says which multiple of p keeps the value positive (8p, or 16p for `wide`), Fs has one of each
+template <class F>
+static F f_sub(const F& x, const F& y, bool wide) {
+    if constexpr (is_fs<F>::value) return F::sub(x, y);
+    else return wide ? F::sub16(x, y) : F::sub8(x, y);
+}
+template <class F>
+static F f_neg(const F& x) {
+    if constexpr (is_fs<F>::value) return F::neg(x);
+    else return F::neg_canonical(x);
+}
+
+template <class F>
 static void fs_dot2(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
     F x = F::from_sat(a), y = F::from_sat(b), r;
-    if (op == 9) r = F::dot2(x, y, F::sub16(x, y), F::add3(x, x, y));       // x*y + (x - y)(2x + y) with one reduction
-    else if (op == 10) r = F::dot2(x, y, F::neg16(y), y);                   // x*y - y*y through the negated operand
+    if (op == 9) r = F::dot2(x, y, F::sub(x, y), F::add3(x, x, y));         // x*y + (x - y)(2x + y) with one reduction
+    else if (op == 10) r = F::dot2(x, y, F::neg(y), y);                     // x*y - y*y through the negated operand
     else r = F::sub_sum3(F::mul(x, y), F::sqr(x), F::sqr(y), F::mul(x, x));  // xy - 2x^2 - y^2, one carry step
     r.to_sat(out);
 }
@@ -32,15 +54,15 @@ static void fu_binop(int op, const uint32_t* a, const uint32_t* b, uint32_t* out
     switch (op) {
     case 0: r = F::mul(x, y); break;
     case 1: r = F::add(x, y); break;
-    case 2: r = F::sub8(x, y); break;
-    case 3: r = F::sub16(x, y); break;
+    case 2: r = f_sub(x, y, false); break;
+    case 3: r = f_sub(x, y, true); break;
     case 4: r = F::sqr(x); break;
     case 5: r = F::inverse(x); break;
-    case 6: r = F::neg_canonical(x); break;
+    case 6: r = f_neg(x); break;
     case 7: r = F::dbl(x); break;
     case 8: {  // a long lazy chain: ((x - y + 16p) * (x + x + y) - x*y + 8p)^2
-        F t = F::mul(F::sub16(x, y), F::add3(x, x, y));
-        r = F::sqr(F::sub8(t, F::mul(x, y)));
+        F t = F::mul(f_sub(x, y, true), F::add3(x, x, y));
+        r = F::sqr(f_sub(t, F::mul(x, y), false));
         break;
     }
     default: r = F::zero();
@@ -48,28 +70,50 @@ static void fu_binop(int op, const uint32_t* a, const uint32_t* b, uint32_t* out
     r.to_sat(out);
 }
 
+// a coordinate in / out of the law's field: Fp holds the arkworks words themselves, Fs converts (stored coordinates are canonical)
+template <class F>
+constexpr int sat_words() {
+    if constexpr (is_fp<F>::value) return F::N;
+    else return F::SAT;
+}
+template <class F>
+static F coord_in(const uint32_t* w) {
+    if constexpr (is_fp<F>::value) {
+        F f;
+        memcpy(f.v, w, sizeof f.v);
+        return f;
+    } else {
+        return F::canonical_lt2p(F::from_sat(w));
+    }
+}
+template <class F>
+static void coord_out(const F& f, uint32_t* w) {
+    if constexpr (is_fp<F>::value) memcpy(w, f.v, sizeof f.v);
+    else f.to_sat(w);
+}
+
 // acc (affine or infinity) + sequence of affine points with signs -> affine result
 template <class F>
 static int xyzz_chain(const uint32_t* pts_xy, const uint8_t* flags /* bit0 negate, bit1 use full add, bit2 double acc first */, int n,
                       uint32_t* out_xy) {
-    constexpr int W = F::SAT;
+    constexpr int W = sat_words<F>();
     XYZZu<F> acc = XYZZu<F>::infinity();
     for (int i = 0; i < n; ++i) {
         AffineU<F> p;
-        p.x = F::canonical_lt2p(F::from_sat(pts_xy + (2 * i) * W));
-        p.y = F::canonical_lt2p(F::from_sat(pts_xy + (2 * i + 1) * W));
+        p.x = coord_in<F>(pts_xy + (2 * i) * W);
+        p.y = coord_in<F>(pts_xy + (2 * i + 1) * W);
         bool null = true;
         for (int k = 0; k < 2 * W; ++k) null = null && pts_xy[2 * i * W + k] == 0;
         if (null) continue;
-        if (flags[i] & 1) p.y = F::neg_canonical(p.y);
+        if (flags[i] & 1) p.y = F::neg(p.y);
         if (flags[i] & 4) acc = XYZZu<F>::dbl(acc);
         if (flags[i] & 2) acc = XYZZu<F>::add(acc, XYZZu<F>::from_affine(p));
         else acc = XYZZu<F>::madd(acc, p);
     }
     AffineU<F> a;
     bool fin = acc.to_affine(a);
-    a.x.to_sat(out_xy);
-    a.y.to_sat(out_xy + W);
+    coord_out(a.x, out_xy);
+    coord_out(a.y, out_xy + W);
     return fin ? 0 : 1;
 }
 
@@ -131,7 +175,7 @@ static void fs_raw(int op, const int32_t* a, const int32_t* b, const int32_t* c,
     case 1: r = F::sqr(x); break;
     case 2: r = F::dot2(x, y, z, w); break;
     case 3: r = F::sub_sum3(x, y, z, w); break;
-    default: r = F::sub16(F::add3(x, y, z), w); break;
+    default: r = F::sub(F::add3(x, y, z), w); break;
     }
     for (int i = 0; i < F::NL; ++i) out[i] = (int32_t)r.v[i];
 }
@@ -160,7 +204,14 @@ int fu_rp_bound() { return RP_B; }        // a loaded value is < RP_B / 10 * r
 int fu_rp_limbs() { return FrB::NL; }
 uint64_t fu_el_mix(uint64_t h, const uint32_t* words) { return el_mix(h, el_of(words)); }
 uint32_t fu_key_hash(int w, const uint32_t* words) { return w == 1 ? key_hash_of<1>(words) : key_hash_of<4>(words); }
-int fu_xyzz_chain(int curve, const uint32_t* pts_xy, const uint8_t* flags, int n, uint32_t* out_xy) {
-    return curve == 0 ? xyzz_chain<FqBs>(pts_xy, flags, n, out_xy) : xyzz_chain<FqNs>(pts_xy, flags, n, out_xy);
+// law: 0 BLS12-381, 1 BN254 over the signed-limb field (the device's instantiation); 2, 3 the same curves over the saturated field (the host's)
+int fu_xyzz_chain(int law, const uint32_t* pts_xy, const uint8_t* flags, int n, uint32_t* out_xy) {
+    switch (law) {
+    case 0: return xyzz_chain<FqBs>(pts_xy, flags, n, out_xy);
+    case 1: return xyzz_chain<FqNs>(pts_xy, flags, n, out_xy);
+    case 2: return xyzz_chain<Fp<FqBls12_381Params>>(pts_xy, flags, n, out_xy);
+    case 3: return xyzz_chain<Fp<FqBn254Params>>(pts_xy, flags, n, out_xy);
+    }
+    return -1;
 }
 }

@@ -1,6 +1,6 @@
 """CPU check of the unsaturated fields (29-bit limbs for the scalar fields: fieldu.cuh; signed 30-bit limbs for the base
-fields: fields.cuh) and of the lazy XYZZ group law (ecu.cuh) that the HIP kernels use, compiled for the host and compared
-with big-int arithmetic; and of two device-only pieces: the load conversion of the quotient kernel and the circuit check (to_rp,
+fields: fields.cuh) and of the XYZZ group law (ecu.cuh) -- over the signed-limb field as the HIP kernels use it and over the saturated
+field (field.cuh) as the host code does -- compiled for the host and compared with big-int arithmetic; and of two device-only pieces: the load conversion of the quotient kernel and the circuit check (to_rp,
 zbound.cuh) on boundary and random stored words, and the hash of the device key maps (fr_io.cuh) against its Python restatement
 (tests/edge_values.py), on which the crafted collisions of the GPU suite rest."""
 import ctypes
@@ -22,7 +22,7 @@ SO = os.path.join(ROOT, "tests", "native", "libfu_check.so")
 
 @pytest.fixture(scope="module")
 def fu():
-    deps = [SRC] + [os.path.join(ROOT, "ark_plonk_amd", "csrc", f) for f in ("fieldu.cuh", "fields.cuh", "ecu.cuh", "curve_params.h", "zk_common.h", "field.cuh", "fr_io.cuh", "zbound.cuh")]
+    deps = [SRC] + [os.path.join(ROOT, "ark_plonk_amd", "csrc", f) for f in ("field_common.cuh", "fieldu.cuh", "fields.cuh", "ecu.cuh", "curve_params.h", "zk_common.h", "field.cuh", "fr_io.cuh", "zbound.cuh")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "c++", SRC, "-o", SO])
     L = ctypes.CDLL(SO)
@@ -90,8 +90,8 @@ def test_xyzz_chain_matches_affine_group_law(cid, fu):
     pts = [bo.ec_mul(cv, k, G) for k in (1, 2, 3, 5, 7, 1, 11, 7, 13, 5)]
     rng = np.random.default_rng(cid + 10)
 
-    def run(seq):
-        """seq: list of (point or None, flags)"""
+    def run(seq, law):
+        """seq: list of (point or None, flags); law: the harness's id of the curve and of the field the law is instantiated over"""
         arr = np.zeros((len(seq), 2 * W), dtype="<u4")
         fl = np.zeros(len(seq), dtype=np.uint8)
         for i, (pt, f) in enumerate(seq):
@@ -100,7 +100,7 @@ def test_xyzz_chain_matches_affine_group_law(cid, fu):
                 arr[i, W:] = words(pt[1] * R % cv.q, W)
             fl[i] = f
         out = np.zeros(2 * W, dtype="<u4")
-        inf = fu.fu_xyzz_chain(cid, arr.ctypes.data, fl.ctypes.data, len(seq), out.ctypes.data)
+        inf = fu.fu_xyzz_chain(law, arr.ctypes.data, fl.ctypes.data, len(seq), out.ctypes.data)
         if inf:
             return None
         rinv = pow(R, -1, cv.q)
@@ -128,8 +128,9 @@ def test_xyzz_chain_matches_affine_group_law(cid, fu):
         [(pts[4], 0), (None, 0), (pts[5], 4), (pts[6], 5), (pts[7], 6)],
         [(p, int(rng.integers(0, 8))) for p in pts] * 3,  # long mixed chain: lazy bounds hold over many ops
     ]
-    for seq in cases:
-        assert run(seq) == expect(seq), seq
+    for law in (cid, cid + 2):            # the signed-limb field (device), the saturated field (host)
+        for seq in cases:
+            assert run(seq, law) == expect(seq), (law, seq)
 
 
 @pytest.mark.parametrize("field", [0, 1])
