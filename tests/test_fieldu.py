@@ -59,6 +59,13 @@ def test_field_ops(field, fu):
     # limb patterns at the edges of the digit ranges: every 29- / 30-bit digit all ones, 2^29 or 2^29 - 1 in every 30-bit digit
     specials += [v % p for v in ((1 << (32 * n)) - 1, sum(1 << (30 * i + 29) for i in range(13)), sum(((1 << 29) - 1) << (30 * i) for i in range(13)),
                                  sum(((1 << 29) + 1) << (30 * i) for i in range(13)), (p + 1) // 2, (1 << (p.bit_length() - 1)) - 1)]
+    if field in (0, 2):
+        # the edge targets of the curve points (tests/edge_values.py) as field elements: the values whose stored word t * R^-1, and
+        # whose internal form t * R'^-1 (R' = 2^(30 NL): strict limbs at the ends of their range), is the target
+        cv = bo.CURVES[field // 2]
+        ts = [t for t, _ in ev.fq_targets(p)]
+        specials += [t * Rinv % p for t in ts]
+        specials += [t * pow(ev.form_factor(cv, "internal"), -1, p) % p for t in ts + [ev.limbs_value(l) for l, _ in ev.internal_patterns(cv)]]
     vals = specials + [int.from_bytes(rng.bytes(4 * n + 8), "little") % p for _ in range(40)]
     out = np.zeros(n, dtype="<u4")
     for i, x in enumerate(vals):
@@ -130,6 +137,21 @@ def test_xyzz_chain_matches_affine_group_law(cid, fu):
     ]
     for law in (cid, cid + 2):            # the signed-limb field (device), the saturated field (host)
         for seq in cases:
+            assert run(seq, law) == expect(seq), (law, seq)
+    # the same law on points whose coordinates are base-field edges (tests/edge_values.py): every point alone, so that the output
+    # -- to_sat of canon_floor -- is the edge; P + P; P + Q - Q, an edge as the result of real arithmetic; every point against a
+    # strided partner under all flag combinations; long mixed chains
+    edge = [tuple(e) for e in ev.edge_points(cv)]
+    m = len(edge)
+    crng = random.Random(0xC4A1 + cid)
+    ecases = []
+    for i, P in enumerate(edge):
+        Q = edge[(7 * i + 3) % m]
+        ecases += [[(P, 0)], [(P, 2)], [(P, 0), (P, 0)], [(P, 2), (P, 2)], [(P, 0), (Q, 2 * (i & 1)), (Q, 1 + 2 * (i >> 1 & 1))]]
+        ecases += [[(P, f), (Q, g)] for f in range(8) for g in range(8)]
+    ecases += [[(edge[crng.randrange(m)], crng.randrange(8)) for _ in range(60)] for _ in range(20)]
+    for law in (cid, cid + 2):
+        for seq in ecases:
             assert run(seq, law) == expect(seq), (law, seq)
 
 
@@ -273,3 +295,62 @@ def test_edge_elements_are_what_they_say(cid):
         assert x in e
     words = ev.to_rp_boundary_words(cv.r)
     assert all(ev.field_value(cv, v) in e for v in words) and len(words) > 150
+
+
+# ---- curve points with base-field edges as coordinates (tests/edge_values.py)
+@pytest.mark.parametrize("cid", [0, 1])
+def test_edge_points_are_what_they_say(cid, fu):
+    cv = bo.CURVES[cid]
+    q, nl = cv.q, ev.FS_LIMBS[cid]
+    assert nl == fu.fs_limbs(cid)
+    pts = ev.edge_points(cv)
+    assert len(pts) >= 100 and len(set(tuple(e) for e in pts)) == len(pts)
+    assert all(0 <= e[0] < q and 0 < e[1] < q and bo.on_curve(cv, tuple(e)) for e in pts)
+    worst = max(e.dist for e in pts)
+    print(f"{cv.name}: {len(pts)} edge points, largest search distance {worst}")
+    assert worst < 32
+    patterned = 0
+    for e in pts:
+        c = e[1] if e.side == "y" else e[0]                     # the coordinate that was aimed
+        got = c * ev.form_factor(cv, e.form) % q
+        assert abs(got - e.target) == e.dist, (e.form, e.side, hex(e.target))
+        if e.pattern is not None:                               # the walk moved limb 0 alone
+            limbs = ev.strict_limbs(got, nl)
+            assert ev.limbs_value(limbs) == got and limbs[1:nl - 1] == e.pattern[1:nl - 1] and limbs[nl - 1] == e.pattern[nl - 1], e.pattern
+            assert abs(limbs[0] - e.pattern[0]) == e.dist
+            patterned += 1
+    assert patterned >= 10
+    for form in ("value", "stored", "internal"):                # the ends of the field, in every form, are in
+        have = {e[0] * ev.form_factor(cv, form) % q for e in pts}
+        assert any(t in have for t in range(0, 16)) and any(q - t in have for t in range(1, 16)), form
+    if cid == 0:
+        assert (0, 2) in pts and bo.ec_mul(cv, 3, (0, 2)) is None
+    else:
+        assert (cv.gx, cv.gy) in pts
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_references_agree_on_edge_points(cid, oracle_cpu):
+    """The pure-Python group law and the C++ restatement of the arkworks Pippenger give the same MSM over the whole edge set -- the
+    vector of tests/test_edge_points_gpu.py, with its repeated and opposite points, the point of order 3 and the infinities -- so the
+    GPU tests may take the restatement alone: scalars in [0, (r - 1) / 2] on both curves and the whole range on BN254, as the MSMs
+    of the GPU tests take them (a BLS12-381 edge point is outside the r-torsion subgroup); and the two-point sums L + xi R of the
+    key-fold test, where the scalar is an integer on both sides, with xi up to r - 1 on both curves."""
+    cv = bo.CURVES[cid]
+    for top in ((cv.r - 1) // 2,) + ((cv.r - 1,) if cid == 1 else ()):
+        rows = ev.edge_msm_rows(cv, top)
+        sc = [s for _, s, _ in rows]
+        assert {0, 1, top} <= set(sc) and max(sc) <= top
+        assert {tuple(e) for e in ev.edge_points(cv)} <= {p for p, _, _ in rows} and {e for _, _, e in rows} == {0, 1, 2, 3}
+        want = bo.msm(cv, [p for p, _, _ in rows], sc)
+        bases, scal, _, flags = ev.rows_arrays(cv, rows)
+        xy, inf = oracle_cpu.msm_g1(cid, bases, scal, inf=flags)
+        assert want is not None and not inf
+        assert np.array_equal(xy, ev.points_to_limbs(cv, [want])[0]), hex(top)
+    pts = [tuple(e) for e in ev.edge_points(cv)]
+    for i in range(0, len(pts), 9):
+        pair = [pts[i], pts[(i + 37) % len(pts)]]
+        for xi in (0, 1, 2, cv.r - 1):
+            want = bo.ec_add(cv, pair[0], bo.ec_mul(cv, xi, pair[1]))
+            xy, inf = oracle_cpu.msm_g1(cid, ev.points_to_limbs(cv, pair), oracle_cpu.ints_to_limbs([1, xi], 4), threads=1)
+            assert not inf and np.array_equal(xy, ev.points_to_limbs(cv, [want])[0]), (i, hex(xi))
