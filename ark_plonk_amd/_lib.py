@@ -216,6 +216,13 @@ SYMBOLS = {
     "zk_transcript_append_public_inputs": (c_int, [c_void_p, c_int, ctypes.c_char_p, c_size_t, c_void_p, c_void_p, c_size_t]),
     "zk_proof_serialized_size": (c_size_t, [c_int, c_u32, ctypes.POINTER(c_u32)]),
     "zk_proof_serialize": (c_int, [c_int, ctypes.POINTER(ZkProof), ctypes.c_char_p, c_size_t, ctypes.POINTER(c_size_t)]),
+    # batch verification: device decode of compressed points; host parse + transcript replay of a batch of proofs
+    "zk_g1_decompress_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "zk_proof_replay_batch": (c_int, [c_void_p, c_int, c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_size_t), c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_verify_scalars_dev": (c_int, [c_void_p, c_int, c_u32, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_fr_column_sum_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_u32, c_void_p]),
 }
 
 _lib = None

@@ -54,6 +54,9 @@ def jobs():
         ("gadget_layout.o", "gadget_layout.hip", [], API_HDRS + FR_IO + GADGET),
         # ... and the values of the variables the segments create, replayed once per proof
         ("gadget_witness.o", "gadget_witness.hip", [], API_HDRS + FR_IO + GADGET),
+        # the verifier's device side: batch decoding of compressed G1 points, per-proof scalars, the column sum of a fold (its host
+        # side, parse and replay, is in wire.hip)
+        ("verify.o", "verify.hip", [], API_HDRS + FR_IO),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

@@ -447,3 +447,166 @@ int zk_proof_serialize(int curve_id, const zk_proof* p, uint8_t* out, size_t cap
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------ the verifier's parse and replay
+namespace {
+
+// the seven custom evaluations the verifier reads by label (proof.rs:488-611), in the order of the evaluation row
+const char* const VERIFY_CUSTOM[7] = {"a_next_eval", "b_next_eval", "d_next_eval", "q_arith_eval", "q_c_eval", "q_l_eval", "q_r_eval"};
+
+uint64_t le_u64(const uint8_t* p) {
+    uint64_t v = 0;
+    for (int b = 0; b < 8; ++b) v |= (uint64_t)p[b] << (8 * b);
+    return v;
+}
+
+// One proof: walk proof.rs:41-103, then replay proof.rs:128-300, 343-378 on a copy of the seeded transcript.
+// points_out (optional): the 13 commitments and the two openings, FQ_BYTES each, as they stand in the proof.
+template <class Cv>
+uint8_t replay_one(const zk_transcript& seeded, const uint8_t* data, size_t len, const uint64_t* pi_pos, const uint64_t* pi_val, size_t n_pi,
+                   uint64_t* ch_out, uint64_t* ev_out, uint8_t* points_out) {
+    typedef Wire<Cv> W;
+    constexpr size_t G = W::FQ_BYTES, F = W::FR_BYTES;
+    constexpr int CID = Cv::ID;
+    size_t pos = 0;
+    const uint8_t* pts[15];
+    for (int i = 0; i < 15; ++i) {
+        if (len - pos < G) return ZK_PROOF_TRUNCATED;
+        pts[i] = data + pos;
+        pos += G;
+        if (i >= 13) {                                       // kzg10::Proof { w, random_v }: random_v is None in every proof of this scheme
+            if (len - pos < 1) return ZK_PROOF_TRUNCATED;
+            if (data[pos] != 0) return ZK_PROOF_BAD_OPTION;
+            pos += 1;
+        }
+    }
+    if (points_out) {
+        for (int i = 0; i < 15; ++i) memcpy(points_out + i * G, pts[i], G);
+    }
+    for (int i = 0; i < ZK_PROOF_N_EVALS; ++i) {
+        if (len - pos < F) return ZK_PROOF_TRUNCATED;
+        if (W::fr_de(data + pos, ev_out + 4 * i)) return ZK_PROOF_FR_NOT_REDUCED;
+        pos += F;
+    }
+    if (len - pos < 8) return ZK_PROOF_TRUNCATED;
+    const uint64_t k = le_u64(data + pos);
+    pos += 8;
+    if (k > (len - pos) / (8 + F)) return ZK_PROOF_BAD_COUNT;       // more entries than bytes: also bounds the loop below
+    struct Custom {
+        const uint8_t* label;
+        size_t label_len;
+        uint64_t v[4];
+    };
+    std::vector<Custom> custom((size_t)k);
+    for (uint64_t i = 0; i < k; ++i) {
+        if (pos == len) return ZK_PROOF_BAD_COUNT;                  // the bytes end on an entry boundary with entries still announced
+        if (len - pos < 8) return ZK_PROOF_TRUNCATED;
+        const uint64_t ll = le_u64(data + pos);
+        pos += 8;
+        if (ll > len - pos || len - pos - ll < F) return ZK_PROOF_TRUNCATED;
+        Custom& c = custom[(size_t)i];
+        c.label = data + pos;
+        c.label_len = (size_t)ll;
+        pos += (size_t)ll;
+        if (W::fr_de(data + pos, c.v)) return ZK_PROOF_FR_NOT_REDUCED;
+        pos += F;
+    }
+    if (pos != len) return ZK_PROOF_TRAILING;
+    for (int j = 0; j < 7; ++j) {
+        const size_t ll = strlen(VERIFY_CUSTOM[j]);
+        const Custom* hit = nullptr;
+        for (const Custom& c : custom)
+            if (c.label_len == ll && memcmp(c.label, VERIFY_CUSTOM[j], ll) == 0) hit = &c;     // a repeated label: the last one counts
+        if (!hit) return ZK_PROOF_MISSING_LABEL;
+        memcpy(ev_out + 4 * (ZK_PROOF_N_EVALS + j), hit->v, 32);
+    }
+
+    zk_transcript t(seeded);
+    if (zk_transcript_append_public_inputs(&t, CID, (const uint8_t*)"pi", 2, pi_pos, pi_val, n_pi)) return ZK_PROOF_BAD_PUBLIC_INPUTS;
+    // ark appends the re-serialised point: for a decodable encoding that is the proof's own bytes, except that infinity is written with x = 0
+    auto put_g1 = [&](const char* label, int i) {
+        uint8_t buf[G];
+        memcpy(buf, pts[i], G);
+        if ((buf[G - 1] & 0xC0) == 0x40) {
+            memset(buf, 0, G);
+            buf[G - 1] = 0x40;
+        }
+        transcript_append(t.st, (const uint8_t*)label, strlen(label), buf, G);
+    };
+    auto put_fr = [&](const char* label, const uint64_t* mont) {
+        uint8_t buf[F];
+        W::fr_ser(mont, buf);
+        transcript_append(t.st, (const uint8_t*)label, strlen(label), buf, F);
+    };
+    int slot = 0;
+    auto draw = [&](const char* label, const char* put) {
+        uint64_t* c = ch_out + 4 * slot++;
+        W::challenge(t.st, (const uint8_t*)label, strlen(label), c);
+        if (put) put_fr(put, c);
+    };
+    // indices into pts: a b c d z f h_1 h_2 z_2 t_1 t_2 t_3 t_4
+    put_g1("w_l", 0), put_g1("w_r", 1), put_g1("w_o", 2), put_g1("w_4", 3);
+    draw("zeta", "zeta");
+    put_g1("f", 5), put_g1("h1", 6), put_g1("h2", 7);
+    draw("beta", "beta"), draw("gamma", "gamma"), draw("delta", "delta"), draw("epsilon", "epsilon");
+    put_g1("z", 4);
+    draw("alpha", "alpha");
+    draw("range separation challenge", "range seperation challenge");
+    draw("logic separation challenge", "logic seperation challenge");
+    draw("fixed base separation challenge", "fixed base separation challenge");
+    draw("variable base separation challenge", "variable base separation challenge");
+    draw("lookup separation challenge", "lookup separation challenge");
+    put_g1("t_1", 9), put_g1("t_2", 10), put_g1("t_3", 11), put_g1("t_4", 12);
+    draw("z", "z");
+    // the 14 evaluations proof.rs:253-300 appends, by their index in the proof's evaluation block
+    static const struct {
+        const char* label;
+        int idx;
+    } EV[14] = {{"a_eval", 0}, {"b_eval", 1}, {"c_eval", 2}, {"d_eval", 3}, {"left_sig_eval", 4}, {"right_sig_eval", 5}, {"out_sig_eval", 6},
+                {"perm_eval", 7}, {"f_eval", 13}, {"q_lookup_eval", 8}, {"lookup_perm_eval", 9}, {"h_1_eval", 10}, {"h_1_next_eval", 11},
+                {"h_2_eval", 12}};
+    for (const auto& e : EV) put_fr(e.label, ev_out + 4 * e.idx);
+    for (const Custom& c : custom) {
+        uint8_t buf[F];
+        W::fr_ser(c.v, buf);
+        transcript_append(t.st, c.label, c.label_len, buf, F);
+    }
+    draw("aggregate_witness", nullptr);
+    draw("aggregate_witness", nullptr);
+    return ZK_PROOF_OK;
+}
+
+}  // namespace
+
+extern "C" int zk_proof_replay_batch(const zk_transcript* seeded, int curve_id, size_t n_proofs, const uint8_t* const* proofs, const size_t* proof_lens,
+                                     const uint64_t* pi_offsets, const uint64_t* pi_positions, const uint64_t* pi_values_mont,
+                                     uint64_t* out_challenges_mont, uint64_t* out_evals_mont, uint8_t* out_points, uint8_t* out_status) {
+    if (!seeded || !zk_curve_ok(curve_id)) return ZK_ERR_BAD_ARG;
+    if (n_proofs && (!proofs || !proof_lens || !pi_offsets || !out_challenges_mont || !out_evals_mont || !out_status)) return ZK_ERR_BAD_ARG;
+    for (size_t j = 0; j < n_proofs; ++j) {
+        if (!proofs[j] && proof_lens[j]) return ZK_ERR_BAD_ARG;
+        if (pi_offsets[j + 1] < pi_offsets[j]) return ZK_ERR_BAD_ARG;
+    }
+    if (n_proofs && pi_offsets[n_proofs] && (!pi_positions || !pi_values_mont)) return ZK_ERR_BAD_ARG;
+    const size_t g = zk_g1_compressed_size(curve_id);
+    for (size_t j = 0; j < n_proofs; ++j) {
+        uint64_t* ch = out_challenges_mont + j * 4 * ZK_VERIFY_N_CHALLENGES;
+        uint64_t* ev = out_evals_mont + j * 4 * ZK_VERIFY_N_EVALS;
+        uint8_t* pt = out_points ? out_points + j * 15 * g : nullptr;
+        const uint64_t o = pi_offsets[j];
+        const size_t n_pi = (size_t)(pi_offsets[j + 1] - o);
+        out_status[j] = zk_on_curve(curve_id, (uint8_t)ZK_PROOF_TRUNCATED, [&](auto cv) {
+            return replay_one<decltype(cv)>(*seeded, proofs[j], proof_lens[j], n_pi ? pi_positions + o : nullptr, n_pi ? pi_values_mont + 4 * o : nullptr,
+                                            n_pi, ch, ev, pt);
+        });
+        if (out_status[j] != ZK_PROOF_OK) {                 // a rejected proof leaves no half-written rows behind
+            memset(ch, 0, 32 * ZK_VERIFY_N_CHALLENGES);
+            memset(ev, 0, 32 * ZK_VERIFY_N_EVALS);
+            if (pt) {                                        // ... and its points decode as infinity: stage 1 has nothing to report for them
+                memset(pt, 0, 15 * g);
+                for (int i = 0; i < 15; ++i) pt[i * g + g - 1] = 0x40;
+            }
+        }
+    }
+    return ZK_OK;
+}

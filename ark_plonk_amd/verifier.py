@@ -1,0 +1,333 @@
+"""Batch verification of proofs of one circuit, up to the two pairing inputs.
+
+`Proof::verify` (proof_system/proof.rs:110-425) ends in two KZG checks, e(C - v G, H) = e(W, tau H - z H) each.  Everything in front of
+them is G1 and Fr arithmetic, and with unpredictable weights it folds across proofs: B proofs of one verifier key go in, TWO points
+come out,
+
+    L = sum_j (u_j W_aw,j + u'_j W_saw,j)
+    R = sum_j (u_j (sum_k chi^k (C_k - v_k G) + z W_aw) + u'_j (sum_k chi'^k (C'_k - v'_k G) + z w W_saw))_j
+
+and every proof of the batch is valid iff e(L, [tau]H) = e(R, H), except with probability about 2^-128 over the weights.  The pairing
+is the caller's: this library has none.  Stages, each one entry point of the C ABI:
+
+  1  zk_g1_decompress_batch_dev   the 15 points of every proof decoded and checked on the device (one lane per point)
+  2  zk_proof_replay_batch        host: bytes parsed, the transcript replayed -> 14 challenges and 23 evaluations per proof
+  3  zk_verify_scalars_dev        per proof: 20 scalars over the verifier key's bases and G, 15 over its own points, 2 for L
+  4  zk_fr_column_sum_dev + the existing MSM over the decoded points (zk_srs_register_dev, zk_msm_g1_srs_partial_dev,
+     zk_g1_sum_partials), over any range [lo, hi) of the batch: the per-proof rows stay resident, another range costs only this stage
+
+Field elements are 4 x uint64 Montgomery limbs and points `G1Affine`, as everywhere in this package.
+"""
+from __future__ import annotations
+
+import ctypes
+import secrets
+
+import numpy as np
+
+from ._lib import check, lib
+from .context import Context, default_context, ptr_of
+from .curves import fq_to_mont, get_curve, ints_to_limbs
+from .msm import CommitterKey, G1Affine, sum_partials
+
+N_CHALLENGES, N_EVALS, N_KEY_BASES, N_PROOF_BASES = 14, 23, 20, 15
+CHALLENGES = ("zeta", "beta", "gamma", "delta", "epsilon", "alpha", "range", "logic", "fixed", "var", "lookup", "z", "aw", "saw")
+# the evaluation row: the proof's 16 in its own order (transcript.PROOF_EVAL_FIELDS), then the seven custom ones the verifier reads
+EVALS = ("a_eval", "b_eval", "c_eval", "d_eval", "left_sigma_eval", "right_sigma_eval", "out_sigma_eval", "permutation_eval",
+         "q_lookup_eval", "z2_next_eval", "h1_eval", "h1_next_eval", "h2_eval", "f_eval", "table_eval", "table_next_eval",
+         "a_next_eval", "b_next_eval", "d_next_eval", "q_arith_eval", "q_c_eval", "q_l_eval", "q_r_eval")
+# the verifier key's commitments behind the key-base row (names of ProverKey.verifier_key); the 20th base is the generator G
+KEY_BASES = ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add", "q_lookup",
+             "left_sigma", "right_sigma", "out_sigma", "fourth_sigma", "table_1", "table_2", "table_3", "table_4")
+# the proof-base row: the commitments in the proof's order (transcript.PROOF_COMMITMENTS), then the two openings
+PROOF_BASES = ("a_comm", "b_comm", "c_comm", "d_comm", "z_comm", "f_comm", "h_1_comm", "h_2_comm", "z_2_comm", "t_1_comm", "t_2_comm",
+               "t_3_comm", "t_4_comm", "aw_opening", "saw_opening")
+
+# stage 1 (per point), stage 2 (per proof), and the per-proof status stage 3 leaves
+G1_OK, G1_BAD_FLAGS, G1_X_NOT_REDUCED, G1_NOT_ON_CURVE, G1_NOT_IN_SUBGROUP = range(5)
+(PROOF_OK, PROOF_TRUNCATED, PROOF_TRAILING, PROOF_BAD_OPTION, PROOF_FR_NOT_REDUCED, PROOF_MISSING_LABEL, PROOF_BAD_COUNT,
+ PROOF_BAD_PUBLIC_INPUTS) = range(8)
+VERIFY_OK, VERIFY_BAD_POINT, VERIFY_Z_ON_DOMAIN = 0, 16, 32
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def decompress_batch(encodings, curve="bls12_381", ctx: Context | None = None):
+    """Stage 1.  encodings: n compressed G1 points as bytes / a (n, g) uint8 array or device tensor.  Returns device tensors
+    (points (n, 2L) int64 Montgomery affine, infinity flags (n,) uint8, status (n,) uint8 of G1_*); queued, not waited for."""
+    torch = _torch()
+    cv = get_curve(curve)
+    g = lib().zk_g1_compressed_size(cv.curve_id)
+    ctx = ctx or default_context(0)
+    if isinstance(encodings, (bytes, bytearray)):
+        encodings = np.frombuffer(bytes(encodings), dtype=np.uint8)
+    if not torch.is_tensor(encodings):
+        encodings = torch.from_numpy(np.array(encodings, dtype=np.uint8))        # a copy: the caller's buffer may be read-only
+    dev = torch.device("cuda", ctx.device)
+    d_in = encodings.to(dev).contiguous().view(-1)
+    if d_in.dtype != torch.uint8 or d_in.numel() % g:
+        raise ValueError(f"expected uint8 encodings of {g} bytes each")
+    n = d_in.numel() // g
+    pts = torch.empty((n, 2 * cv.fq_limbs), dtype=torch.int64, device=dev)
+    inf = torch.empty((n,), dtype=torch.uint8, device=dev)
+    st = torch.empty((n,), dtype=torch.uint8, device=dev)
+    ctx.use_torch_stream()
+    check(lib().zk_g1_decompress_batch_dev(ctx.handle, cv.curve_id, ptr_of(d_in), n, ptr_of(pts), ptr_of(inf), ptr_of(st)),
+          "zk_g1_decompress_batch_dev")
+    return pts, inf, st
+
+
+def _flatten_public_inputs(public_inputs, n_proofs):
+    """[{position: 4 Montgomery limbs}] -> (offsets (B + 1,), positions, values (m, 4)), positions ascending inside a proof"""
+    if public_inputs is None:
+        public_inputs = [{}] * n_proofs
+    if len(public_inputs) != n_proofs:
+        raise ValueError("one public-input map per proof")
+    off = np.zeros(n_proofs + 1, dtype=np.uint64)
+    pos, vals = [], []
+    for j, pi in enumerate(public_inputs):
+        for k in sorted(pi):
+            pos.append(int(k))
+            vals.append(np.asarray(pi[k], dtype=np.uint64).reshape(4))
+        off[j + 1] = len(pos)
+    p = np.array(pos, dtype=np.uint64) if pos else np.zeros(1, dtype=np.uint64)
+    v = np.ascontiguousarray(np.stack(vals), dtype=np.uint64) if vals else np.zeros((1, 4), dtype=np.uint64)
+    return off, p, v
+
+
+def replay_batch(seeded, proofs, public_inputs=None, curve="bls12_381", with_points=False):
+    """Stage 2 (host).  seeded: the `transcript.Transcript` after the verifier key was seeded into it (left untouched); proofs: B byte
+    strings; public_inputs: B maps {position: 4 Montgomery limbs}.  Returns (challenges (B, 14, 4), evaluations (B, 23, 4), status (B,)
+    of PROOF_*) -- rows in the order of CHALLENGES / EVALS, Montgomery -- and with with_points the (B, 15, g) uint8 encodings too."""
+    cv = get_curve(curve)
+    B = len(proofs)
+    g = lib().zk_g1_compressed_size(cv.curve_id)
+    off, pos, vals = _flatten_public_inputs(public_inputs, B)
+    bufs = [bytes(p) for p in proofs]
+    ptrs = (ctypes.c_char_p * max(B, 1))(*bufs)
+    lens = (ctypes.c_size_t * max(B, 1))(*[len(b) for b in bufs])
+    ch = np.zeros((B, N_CHALLENGES, 4), dtype=np.uint64)
+    ev = np.zeros((B, N_EVALS, 4), dtype=np.uint64)
+    st = np.zeros(max(B, 1), dtype=np.uint8)
+    pts = np.zeros((B, N_PROOF_BASES, g), dtype=np.uint8) if with_points else None
+    check(lib().zk_proof_replay_batch(seeded._h, cv.curve_id, B, ptrs, lens, ptr_of(off), ptr_of(pos), ptr_of(vals), ptr_of(ch), ptr_of(ev),
+                                      None if pts is None else ptr_of(pts), ptr_of(st)), "zk_proof_replay_batch")
+    return (ch, ev, st[:B], pts) if with_points else (ch, ev, st[:B])
+
+
+def proof_point_bytes(proofs, curve="bls12_381") -> np.ndarray:
+    """The 15 compressed points of every proof, (B, 15, g) uint8, by their fixed offsets (proof.rs:41-103: 13 commitments, then two
+    openings followed by an Option byte each) -- no parsing, so stage 1 can start before stage 2.  A proof too short to hold them gets
+    infinity encodings: stage 2 reports it."""
+    cv = get_curve(curve)
+    g = lib().zk_g1_compressed_size(cv.curve_id)
+    out = np.zeros((len(proofs), N_PROOF_BASES, g), dtype=np.uint8)
+    for j, p in enumerate(proofs):
+        if len(p) < 15 * g + 2:
+            out[j, :, g - 1] = 0x40
+            continue
+        a = np.frombuffer(bytes(p[:15 * g + 2]), dtype=np.uint8)
+        out[j, :14] = a[:14 * g].reshape(14, g)
+        out[j, 14] = a[14 * g + 1:15 * g + 1]
+    return out
+
+
+def scalar_rows(log_n, challenges, evals, public_inputs, coeff_a, coeff_d, weights, parse_status=None, point_status=None,
+                curve="bls12_381", ctx: Context | None = None):
+    """Stage 3.  challenges / evals: stage 2's rows (host arrays or device tensors); weights: B pairs (u, u') of integers;
+    parse_status (B,), point_status (B * 15,): uint8, host or device, or None.  Returns device tensors (key rows (B, 20, 4), proof rows
+    (B, 15, 4), opening rows (B, 2, 4) -- canonical scalars, int64 -- and status (B,) uint8); queued, not waited for."""
+    torch = _torch()
+    cv = get_curve(curve)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+
+    def up(x, dtype=None):
+        if x is None:
+            return None
+        if not torch.is_tensor(x):
+            a = np.ascontiguousarray(x)
+            x = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a)
+        return x.to(dev).contiguous()
+
+    d_ch, d_ev = up(challenges), up(evals)
+    B = d_ch.numel() // (4 * N_CHALLENGES)
+    if d_ev.numel() != B * 4 * N_EVALS or len(weights) != B:
+        raise ValueError("challenge rows, evaluation rows and weights must describe the same number of proofs")
+    off, pos, vals = _flatten_public_inputs(public_inputs, B)
+    d_off, d_pos, d_vals = up(off), up(pos), up(vals)
+    w = ints_to_limbs([int(x) % cv.r for pair in weights for x in pair], 4) if B else np.zeros((1, 4), dtype=np.uint64)
+    d_w = up(w)
+    d_ps, d_pts = up(parse_status), up(point_status)
+    key = torch.empty((B, N_KEY_BASES, 4), dtype=torch.int64, device=dev)
+    prf = torch.empty((B, N_PROOF_BASES, 4), dtype=torch.int64, device=dev)
+    opn = torch.empty((B, 2, 4), dtype=torch.int64, device=dev)
+    st = torch.empty((B,), dtype=torch.uint8, device=dev)
+    ca = np.ascontiguousarray(coeff_a, dtype=np.uint64).reshape(4)
+    cd = np.ascontiguousarray(coeff_d, dtype=np.uint64).reshape(4)
+    ctx.use_torch_stream()
+    check(lib().zk_verify_scalars_dev(ctx.handle, cv.curve_id, int(log_n), B, ptr_of(d_ch), ptr_of(d_ev), ptr_of(d_off), ptr_of(d_pos), ptr_of(d_vals),
+                                      ptr_of(ca), ptr_of(cd), ptr_of(d_w), None if d_ps is None else ptr_of(d_ps),
+                                      None if d_pts is None else ptr_of(d_pts), ptr_of(key), ptr_of(prf), ptr_of(opn), ptr_of(st)),
+          "zk_verify_scalars_dev")
+    return key, prf, opn, st
+
+
+def column_sum(rows, curve="bls12_381", ctx: Context | None = None):
+    """Stage 4's kernel: (n_rows, n_cols, 4) device scalars -> (n_cols, 4), the sum of every column mod r."""
+    torch = _torch()
+    cv = get_curve(curve)
+    ctx = ctx or default_context(rows.device.index)
+    n_rows, n_cols = rows.shape[0], rows.shape[1]
+    out = torch.empty((n_cols, 4), dtype=torch.int64, device=rows.device)
+    ctx.use_torch_stream()
+    check(lib().zk_fr_column_sum_dev(ctx.handle, cv.curve_id, ptr_of(rows.contiguous()), n_rows, n_cols, ptr_of(out)), "zk_fr_column_sum_dev")
+    return out
+
+
+class _Resident:
+    """what one batch leaves on the device: the decoded points as MSM bases and the scalar rows"""
+
+    def __init__(self, n, key_rows, proof_rows, open_rows, proof_ck, open_ck, status):
+        self.n, self.key_rows, self.proof_rows, self.open_rows = n, key_rows, proof_rows, open_rows
+        self.proof_ck, self.open_ck, self.status = proof_ck, open_ck, status
+
+    def close(self):
+        for ck in (self.proof_ck, self.open_ck):
+            if ck is not None:
+                ck.close()
+        self.proof_ck = self.open_ck = None
+
+
+class BatchVerifier:
+    """B proofs of ONE circuit -> the two pairing inputs (L, R) and a status per proof.
+
+    vk: the dict `ProverKey.verifier_key` returns (name -> G1Affine); n: the circuit's domain size; seeded_transcript: the
+    `transcript.Transcript` after `seed_transcript(vk, n)`; coeff_a, coeff_d: the embedded curve's coefficients (4 Montgomery limbs).
+    The pairing check e(L, [tau]H) = e(R, H) is the caller's."""
+
+    def __init__(self, vk: dict, n: int, seeded_transcript, coeff_a, coeff_d, curve="bls12_381", ctx: Context | None = None):
+        torch = _torch()
+        self.curve = get_curve(curve)
+        self.ctx = ctx or default_context(0)
+        if n <= 0 or n & (n - 1):
+            raise ValueError("the domain size is a power of two")
+        self.n, self.log_n = n, n.bit_length() - 1
+        self.seeded = seeded_transcript
+        self.coeff_a = np.ascontiguousarray(coeff_a, dtype=np.uint64).reshape(4).copy()
+        self.coeff_d = np.ascontiguousarray(coeff_d, dtype=np.uint64).reshape(4).copy()
+        cv = self.curve
+        pts = [vk[k] for k in KEY_BASES]
+        g = fq_to_mont(cv, [cv.gx, cv.gy]).reshape(-1)
+        xy = np.stack([np.asarray(p.xy(), dtype=np.uint64) for p in pts] + [g])
+        inf = np.array([1 if p.infinity else 0 for p in pts] + [0], dtype=np.uint8)
+        dev = torch.device("cuda", self.ctx.device)
+        self._key_ck = CommitterKey(torch.from_numpy(xy.view(np.int64)).to(dev), cv, self.ctx, infinity=torch.from_numpy(inf).to(dev))
+        self._res = None
+
+    def close(self):
+        if self._res is not None:
+            self._res.close()
+            self._res = None
+        if self._key_ck is not None:
+            self._key_ck.close()
+            self._key_ck = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def random_weights(n_proofs: int) -> list:
+        """128-bit non-zero weights from the operating system's randomness: what the soundness of the fold rests on"""
+        return [(secrets.randbits(128) or 1, secrets.randbits(128) or 1) for _ in range(n_proofs)]
+
+    def prepare(self, proofs, public_inputs=None, weights=None):
+        """Stages 1-3 for a batch; the rows and the decoded points stay resident for `fold_range`.  Returns the statuses (B,) uint8."""
+        torch = _torch()
+        cv, ctx = self.curve, self.ctx
+        B = len(proofs)
+        if weights is None:
+            weights = self.random_weights(B)
+        if self._res is not None:
+            self._res.close()
+            self._res = None
+        if B == 0:
+            self._res = _Resident(0, None, None, None, None, None, np.zeros(0, dtype=np.uint8))
+            return self._res.status
+        # stage 1 first: the decode runs on the stream while the host replays the transcripts
+        pts, inf, pst = decompress_batch(proof_point_bytes(proofs, cv), cv, ctx)
+        ch, ev, parse_st = replay_batch(self.seeded, proofs, public_inputs, cv)
+        key, prf, opn, st = scalar_rows(self.log_n, ch, ev, public_inputs, self.coeff_a, self.coeff_d, weights, parse_st, pst, cv, ctx)
+        L2 = 2 * cv.fq_limbs
+        proof_ck = CommitterKey(pts, cv, ctx, infinity=inf)                       # proof-major: proof j owns bases [15 j, 15 j + 15)
+        o_pts = pts.view(B, N_PROOF_BASES, L2)[:, 13:15].contiguous().view(2 * B, L2)
+        o_inf = inf.view(B, N_PROOF_BASES)[:, 13:15].contiguous().view(2 * B)
+        open_ck = CommitterKey(o_pts, cv, ctx, infinity=o_inf)                    # the openings again, stride 2: the bases of L
+        self._res = _Resident(B, key, prf, opn, proof_ck, open_ck, st.cpu().numpy())
+        return self._res.status
+
+    def rows(self):
+        """The prepared batch's resident scalar rows: device tensors (key (B, 20, 4), proof (B, 15, 4), openings (B, 2, 4)), canonical."""
+        if self._res is None:
+            raise RuntimeError("prepare a batch first")
+        return self._res.key_rows, self._res.proof_rows, self._res.open_rows
+
+    def fold_range(self, lo: int = 0, hi: int | None = None):
+        """Stage 4 over the proofs [lo, hi) of the prepared batch: (L, R) as G1Affine.  Proofs with a non-zero status contribute
+        nothing (their rows are zero)."""
+        res = self._res
+        if res is None:
+            raise RuntimeError("prepare a batch first")
+        hi = res.n if hi is None else hi
+        if not 0 <= lo <= hi <= res.n:
+            raise ValueError("range outside the batch")
+        cv = self.curve
+        if lo == hi:
+            zero = np.zeros(cv.fq_limbs, dtype=np.uint64)
+            one = fq_to_mont(cv, [1]).reshape(-1)
+            return G1Affine(zero, one, True, cv.name), G1Affine(zero.copy(), one.copy(), True, cv.name)
+        key_sum = column_sum(res.key_rows[lo:hi], cv, self.ctx)
+        parts = [self._key_ck.msm_partial(key_sum),
+                 res.proof_ck.msm_partial(res.proof_rows[lo:hi].reshape(-1, 4), N_PROOF_BASES * lo)]
+        l_part = res.open_ck.msm_partial(res.open_rows[lo:hi].reshape(-1, 4), 2 * lo)
+        return sum_partials(l_part.reshape(1, -1), cv), sum_partials(np.stack(parts), cv)
+
+    def fold(self, proofs, public_inputs=None, weights=None, lo: int = 0, hi: int | None = None):
+        """(L, R, statuses) of the proofs [lo, hi) of the batch.  weights: B pairs (u, u') of integers; None draws 128-bit non-zero
+        values from the operating system -- never fix them: a prover who knows the weights can make invalid proofs cancel."""
+        st = self.prepare(proofs, public_inputs, weights)
+        L, R = self.fold_range(lo, hi)
+        return L, R, st
+
+    def locate_invalid(self, proofs, public_inputs, accepts, weights=None) -> list:
+        """Indices of the proofs that do not verify: those with a non-zero status, and those a bisection over ranges finds with the
+        caller's `accepts(L, R) -> bool` (its pairing check).  The rows stay resident, so a range costs one fold; `accepts` is called at
+        most 1 + 2 k ceil(log2 B) times for k failing proofs."""
+        st = self.prepare(proofs, public_inputs, weights)
+        bad = {int(j) for j in np.nonzero(st)[0]}
+        B = len(proofs)
+
+        def ok(lo, hi):
+            return bool(accepts(*self.fold_range(lo, hi)))
+
+        def search(lo, hi):                      # [lo, hi) is known to fail
+            if hi - lo == 1:
+                bad.add(lo)
+                return
+            mid = (lo + hi) // 2
+            if ok(lo, mid):                      # then the failure is on the right: no check needed there
+                search(mid, hi)
+                return
+            search(lo, mid)
+            if not ok(mid, hi):
+                search(mid, hi)
+
+        if B and not ok(0, B):
+            search(0, B)
+        return sorted(bad)

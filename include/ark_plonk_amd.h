@@ -532,6 +532,76 @@ typedef struct zk_proof {
 size_t zk_proof_serialized_size(int curve_id, uint32_t n_custom_evals, const uint32_t* label_lens);
 int zk_proof_serialize(int curve_id, const zk_proof* proof, uint8_t* out, size_t cap, size_t* written);
 
+/* ---- batch verification, the stages in front of the two pairing inputs ----------------------------------------- */
+/* Stage 1, general (not tied to proofs): n compressed G1 encodings in device memory -> affine Montgomery points in the layout
+ * zk_srs_register_dev takes (2L limbs each), one infinity flag and one status byte per point.  The rules are those of
+ * zk_g1_deserialize_compressed (ark's GroupAffine::deserialize); where that returns ZK_ERR_BAD_ARG this reports which rule failed,
+ * in the order they are applied.  Infinity is written as (0, 1) with flag 1; a rejected encoding as all-zero words, flag 0.
+ * One lane per point, queued on the ctx stream, no working memory. */
+#define ZK_G1_OK 0
+#define ZK_G1_BAD_FLAGS 1        /* both flag bits set */
+#define ZK_G1_X_NOT_REDUCED 2    /* x >= q (checked before the infinity flag is honoured, as ark does) */
+#define ZK_G1_NOT_ON_CURVE 3     /* x^3 + b is no square */
+#define ZK_G1_NOT_IN_SUBGROUP 4  /* r * P != O */
+int zk_g1_decompress_batch_dev(zk_ctx* ctx, int curve_id, const void* d_in, size_t n, void* d_out_xy, void* d_out_inf, void* d_status);
+
+/* Stage 2, host only: parse n_proofs serialised proofs (the layout of zk_proof above) and replay the verifier's transcript traffic
+ * (proof.rs:128-300, 343-378) for each on a copy of `seeded` -- the transcript after VerifierKey::seed_transcript -- which is left
+ * untouched.  Proof j has the public inputs pi_positions / pi_values_mont [pi_offsets[j], pi_offsets[j + 1]) (strictly ascending
+ * positions; zero values are not part of the message, as in zk_transcript_append_public_inputs).
+ *   out_challenges_mont  n_proofs x ZK_VERIFY_N_CHALLENGES x 4 limbs: zeta beta gamma delta epsilon alpha range logic fixed var lookup
+ *                        z aw saw
+ *   out_evals_mont       n_proofs x ZK_VERIFY_N_EVALS x 4 limbs: the 16 evaluations in the proof's order, then a_next b_next d_next
+ *                        q_arith q_c q_l q_r (found by label among the custom evaluations; a repeated label: the last one)
+ *   out_points           optional, n_proofs x 15 compressed encodings (13 commitments, aw and saw opening): the input of stage 1
+ *   out_status           one ZK_PROOF_* per proof; a rejected proof has all-zero rows and infinity encodings
+ * The transcript takes a commitment's own bytes (an infinity-flagged one in canonical form, as ark re-serialises it), so the replay
+ * does not wait for the points to be decoded: whether they decode is stage 1's status.  Malformed bytes are a status, never a
+ * return code: ZK_ERR_BAD_ARG is for null arguments, an unknown curve and descending pi_offsets. */
+#define ZK_VERIFY_N_CHALLENGES 14
+#define ZK_VERIFY_N_EVALS 23
+#define ZK_PROOF_OK 0
+#define ZK_PROOF_TRUNCATED 1          /* the bytes end inside a field */
+#define ZK_PROOF_TRAILING 2           /* bytes are left after the last custom evaluation */
+#define ZK_PROOF_BAD_OPTION 3         /* an opening's random_v is not None */
+#define ZK_PROOF_FR_NOT_REDUCED 4     /* an evaluation >= r */
+#define ZK_PROOF_MISSING_LABEL 5      /* one of the seven custom evaluations the verifier reads is absent */
+#define ZK_PROOF_BAD_COUNT 6          /* the custom-evaluation count names more entries than the bytes hold */
+#define ZK_PROOF_BAD_PUBLIC_INPUTS 7  /* positions not strictly ascending */
+int zk_proof_replay_batch(const zk_transcript* seeded, int curve_id, size_t n_proofs, const uint8_t* const* proofs, const size_t* proof_lens,
+                          const uint64_t* pi_offsets, const uint64_t* pi_positions, const uint64_t* pi_values_mont, uint64_t* out_challenges_mont,
+                          uint64_t* out_evals_mont, uint8_t* out_points, uint8_t* out_status);
+
+/* Stage 3: the scalars of every proof's share of the two pairing inputs.  With u, u' the proof's two weights (d_weights: n_proofs x 2
+ * canonical scalars), chi / chi' the aw / saw challenges and (C_k, v_k) the pairs of the two openings as Proof::verify forms them
+ * (proof.rs:303-395: C_0 the linearisation commitment of :488-611, v_0 = -r_0 of :427-486),
+ *   R_j = u (sum_k chi^k (C_k - v_k G) + z W_aw) + u' (sum_k chi'^k (C'_k - v'_k G) + z w W_saw),   L_j = u W_aw + u' W_saw,
+ * expanded over the bases:
+ *   d_key_rows    n_proofs x ZK_VERIFY_N_KEY_BASES: q_m q_l q_r q_o q_4 q_c q_range q_logic q_fixed_group_add q_variable_group_add
+ *                 q_lookup | left right out fourth sigma | table_1..4 | G
+ *   d_proof_rows  n_proofs x ZK_VERIFY_N_PROOF_BASES: the 13 commitments in the proof's order, aw_opening, saw_opening
+ *   d_open_rows   n_proofs x 2: u, u' (the scalars of L over aw_opening, saw_opening)
+ * all canonical (the form the MSM entry points take).  Inputs: the rows zk_proof_replay_batch wrote, copied to the device, the public
+ * inputs in the same three arrays, the embedded curve's coefficients (host, 4 limbs each), and the statuses of stages 2 (one per proof;
+ * may be NULL) and 1 (ZK_VERIFY_N_PROOF_BASES per proof; may be NULL).  d_status: one byte per proof -- 0, the stage-2 status, ZK_VERIFY_BAD_POINT + the
+ * stage-1 status of its first rejected point, or ZK_VERIFY_Z_ON_DOMAIN (z = w^pos for a public input's position or z = 1: the
+ * barycentric form has no value there).  Every row of a proof with a non-zero status is zero, so it drops out of any sum over the
+ * batch.  One 64-lane workgroup per proof striding over its public inputs; one field inversion per 64 denominators.  Queued on the
+ * ctx stream, no working memory.  ZK_ERR_DOMAIN_TOO_LARGE: log_n beyond the field's two-adicity. */
+#define ZK_VERIFY_N_KEY_BASES 20
+#define ZK_VERIFY_N_PROOF_BASES 15
+#define ZK_VERIFY_OK 0
+#define ZK_VERIFY_BAD_POINT 16
+#define ZK_VERIFY_Z_ON_DOMAIN 32
+int zk_verify_scalars_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, size_t n_proofs, const void* d_challenges_mont, const void* d_evals_mont,
+                          const void* d_pi_offsets, const void* d_pi_positions, const void* d_pi_values_mont, const uint64_t* coeff_a_mont,
+                          const uint64_t* coeff_d_mont, const void* d_weights, const void* d_parse_status, const void* d_point_status,
+                          void* d_key_rows, void* d_proof_rows, void* d_open_rows, void* d_status);
+/* Stage 4's one kernel: d_out[c] = sum_r d_rows[r][c] over n_rows rows of n_cols Fr each (either form: a sum does not care), e.g. the
+ * key-scalar rows of a range [lo, hi) of the batch -> 20 scalars.  The fold itself is the existing MSM over the decoded points
+ * registered with zk_srs_register_dev (proof-major: base_offset = 15 lo, n = 15 (hi - lo)) and zk_g1_sum_partials. */
+int zk_fr_column_sum_dev(zk_ctx* ctx, int curve_id, const void* d_rows, size_t n_rows, uint32_t n_cols, void* d_out);
+
 /* ---- inner-product-argument commitment (IPA) -------------------------------------------------------------------------------- */
 /* The reference's second HomomorphicCommitment (plonk-core/src/commitment.rs:50-91: ark-poly-commit 0.3 ipa_pc::InnerProductArgPC),
  * without hiding and degree bounds, as ark-plonk uses it (prover.rs:582-618).  The committer key is a zk_srs of d1 = d + 1 = 2^k
