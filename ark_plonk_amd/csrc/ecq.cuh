@@ -11,6 +11,9 @@
 //
 // Formulas and bounds are those of ecu.cuh (add-2008-s / dbl-2008-s-1 with the lazy calculus of
 // fields.cuh); the rare P = +-Q case is resolved with the quad doubling / infinity.
+// That the operands, as they move between lanes by role, honour those bounds in every lane is checked by
+// tests/test_fieldu.py (test_quad_law_is_closed_under_the_signed_limb_contract): this file, unmodified,
+// over the checked field of tests/native/fb_field.h, four host threads per quad.
 #pragma once
 #include "ecu.cuh"
 

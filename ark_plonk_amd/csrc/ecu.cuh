@@ -16,6 +16,10 @@
 //   * Y3 = R*(Q - X3) - Y1*PPP is ONE double product with one Montgomery reduction (dot2 against -Y1);
 //   * P == +-Q is detected on the *result*: ZZ3 = ZZ1*PP is a product, so ZZ3 == 0 mod p iff its strict
 //     limbs are those of 0 (or +-p) -- compares on one limb in the common path.
+// These bullets are enforced, not only argued: tests/test_fieldu.py (test_g1_law_is_closed_under_the_signed_limb_contract) runs every
+// function below once per branch outcome over a field that checks the preconditions of fields.cuh at each call (tests/native/fb_field.h),
+// with the inputs widened to the class invariant -- X: |limb| <= 2^29 + 2, |X| < 4p; Y: |limb| <= 2^29, |Y| < p; ZZ, ZZZ: strict,
+// below p in magnitude; affine x strict, affine y |limb| <= 2^29, both below p -- and demands that the outputs are inside it again.
 // Over Fp every value is canonical, so none of these bounds is needed: add3 / sub_sum3 / dot2 are the plain sums, limbs_zero and
 // is_zero_mod_reduced are both the exact zero test, and the law computes the same group elements with the same formulas.
 // Infinity is ZZ = 0 with all limbs zero (only ever created explicitly, or read as such from a device sum).

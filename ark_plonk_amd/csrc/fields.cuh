@@ -14,6 +14,9 @@
 //               what mul / sqr / dot2 / from_sat / canonical_lt2p return;
 //   "almost"  : |v[i]| <= 2^29 + 2 -- what add / sub / dbl / add3 return (one carry step, no ripple).
 // Inputs of mul / sqr / dot2: almost-balanced limbs, |value| < 12p.
+// These preconditions, and the ones stated at each operator below, are restated once as a rule table in tests/native/fb_field.h (a
+// field that checks them at every call); tests/test_fieldu.py holds each rule against big integers at the extreme of its precondition
+// and runs the group law over that field, so a call site that leaves the contract fails there.
 // A difference is a plain limb-wise difference and a negation a limb-wise negation: no multiple of p is added, so `sub` and `neg` are
 // the only names.  The group law of ecu.cuh is written against this interface; the host instantiates it over the saturated Fp of
 // field.cuh, which carries the same names with canonical values.
@@ -129,7 +132,8 @@ struct Fs {
         normalize(t);
         return t;
     }
-    // a - (b + c + d) with one carry step.  Strict operands: a limb of the raw result is in [-2^31 + 3, 2^31 - 1].
+    // a - (b + c + d) with one carry step.  Strict operands: a limb of the raw result is in [-2^31 + 3, 2^31 - 1].  What it needs, like
+    // add3, is the raw limb sum inside int32 (one past it wraps: tests/test_fieldu.py shows both); negated strict operands still fit.
     ZK_HD static Fs sub_sum3(const Fs& a, const Fs& b, const Fs& c, const Fs& d) {
         Fs t;
 #pragma unroll
@@ -185,7 +189,9 @@ struct Fs {
         r.v[NL - 1] = (uint32_t)carry;
         return r;
     }
-    // (a*b + c*d)/R' with ONE Montgomery reduction.  |a||b| + |c||d| < 288 p^2 keeps the result in (-p, p).
+    // (a*b + c*d)/R' with ONE Montgomery reduction, for |a||b| + |c||d| < 288 p^2 (all that four operands below 12p can give).  The
+    // result is below (|a||b| + |c||d|)/R' + p/2 in magnitude: inside (-p, p) up to 256 p^2 at the R' >= 512 p every modulus has, and
+    // up to the whole 288 p^2 at R' >= 576 p, which both moduli in use have (gen_constants.py asserts either); always in (-2p, 2p).
     ZK_HD static Fs dot2(const Fs& a, const Fs& b, const Fs& c, const Fs& d) {
         int32_t m[NL];
         Fs r;

@@ -1,7 +1,8 @@
 // Host-side harness for the unsaturated fields / the XYZZ group law (fieldu.cuh, fields.cuh, ecu.cuh): the same
 // templates the HIP kernels instantiate, and the law's host instantiation over the saturated field (field.cuh), compiled with g++ so
 // tests/test_fieldu.py can check them against the big-int oracle without a GPU; and for the device-only load conversion of the quotient kernel and the circuit
-// check (zbound.cuh) and the hash of the device key maps (fr_io.cuh).
+// check (zbound.cuh) and the hash of the device key maps (fr_io.cuh).  The group law is instantiated a third time over Fb (fb_field.h), the
+// signed-limb field with the preconditions of fields.cuh checked at every call, and with it the quad-cooperative law of ecq.cuh (fb_laws.h).
 #include <cstdint>
 #include <cstring>
 #include <type_traits>
@@ -17,6 +18,8 @@ static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
 #endif
 #include "../../ark_plonk_amd/csrc/fr_io.cuh"
 #include "../../ark_plonk_amd/csrc/zbound.cuh"
+#include "fb_field.h"                     // the checked signed-limb field Fb: the contract of fields.cuh at every call
+#include "fb_laws.h"                      // ecu.cuh and ecq.cuh over Fb, one run per branch (brings in ecq.cuh with host wave primitives)
 
 template <class F>
 struct is_fs : std::false_type {};
@@ -121,6 +124,8 @@ typedef Fu<FrBls12_381UParams> FrB;      // 29-bit limbs (fieldu.cuh): the scala
 typedef Fu<FrBn254UParams> FrN;
 typedef Fs<FqBls12_381SParams> FqBs;     // signed 30-bit limbs (fields.cuh): the base fields
 typedef Fs<FqBn254SParams> FqNs;
+typedef Fb<FqBls12_381SParams> FqBb;     // the same, with the preconditions of fields.cuh checked at every call (fb_field.h)
+typedef Fb<FqBn254SParams> FqNb;
 
 // the device-only pieces of the quotient kernel and the circuit check: the load conversion (zbound.cuh) and the hash of the key maps
 // (fr_io.cuh), over the three members of a curve they read
@@ -161,6 +166,8 @@ static uint32_t key_hash_of(const uint32_t* words) {
 
 // raw signed-limb operands (no conversion on the way in): the worst-case limb patterns of the column bounds of fields.cuh.
 // op 0: mul(a, b)   1: sqr(a)   2: dot2(a, b, c, d)   3: sub_sum3(a, b, c, d) (strict operands)   4: add3 / sub chains
+// and every operator alone, for the rule table of fb_field.h: 5 add(a, b)   6 sub(a, b)   7 dbl(a)   8 add3(a, b, c)   9 neg(a)
+// 10 canonical_lt2p(a)   11 is_zero_mod_reduced(a) and 12 limb0_of_zero_mod(a), the flag in out[0]
 template <class F>
 static void fs_raw(int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out) {
     F x, y, z, w, r;
@@ -175,6 +182,14 @@ static void fs_raw(int op, const int32_t* a, const int32_t* b, const int32_t* c,
     case 1: r = F::sqr(x); break;
     case 2: r = F::dot2(x, y, z, w); break;
     case 3: r = F::sub_sum3(x, y, z, w); break;
+    case 5: r = F::add(x, y); break;
+    case 6: r = F::sub(x, y); break;
+    case 7: r = F::dbl(x); break;
+    case 8: r = F::add3(x, y, z); break;
+    case 9: r = F::neg(x); break;
+    case 10: r = F::canonical_lt2p(x); break;
+    case 11: r = F::zero(); r.v[0] = x.is_zero_mod_reduced(); break;
+    case 12: r = F::zero(); r.v[0] = x.limb0_of_zero_mod(); break;
     default: r = F::sub(F::add3(x, y, z), w); break;
     }
     for (int i = 0; i < F::NL; ++i) out[i] = (int32_t)r.v[i];
@@ -211,7 +226,40 @@ int fu_xyzz_chain(int law, const uint32_t* pts_xy, const uint8_t* flags, int n, 
     case 1: return xyzz_chain<FqNs>(pts_xy, flags, n, out_xy);
     case 2: return xyzz_chain<Fp<FqBls12_381Params>>(pts_xy, flags, n, out_xy);
     case 3: return xyzz_chain<Fp<FqBn254Params>>(pts_xy, flags, n, out_xy);
+    case 4: return xyzz_chain<FqBb>(pts_xy, flags, n, out_xy);      // the signed-limb field, checked: violations go to the record
+    case 5: return xyzz_chain<FqNb>(pts_xy, flags, n, out_xy);
     }
     return -1;
+}
+// ---- the checked field (fb_field.h, fb_laws.h).  field / cid: 0 BLS12-381, 1 BN254
+// the rule table: operation (fb::Op) and operand envelopes (lo, hi, V in units of 2^-16 p each) in; ok flag and result envelope out
+int fb_units() { return (int)fb::VU; }
+int fb_op_count() { return fb::OP_COUNT; }
+const char* fb_op_name(int op) { return fb::op_name(op); }
+int fb_op_arity(int op) { return fb::op_arity(op); }
+int fb_rule(int field, int op, const int64_t* operands, int64_t* result) {
+    fb::Env e[4] = {};
+    for (int i = 0; i < fb::op_arity(op); ++i) e[i] = fb::Env{operands[3 * i], operands[3 * i + 1], operands[3 * i + 2]};
+    const fb::RuleOut r = field == 0 ? fb::rule(op, e, FqBb::tp(), FqBb::words_v()) : fb::rule(op, e, FqNb::tp(), FqNb::words_v());
+    result[0] = r.res.lo;
+    result[1] = r.res.hi;
+    result[2] = r.res.V;
+    return r.ok ? 1 : 0;
+}
+// the records since the last call, one per line, then forgotten; returns their number
+int fb_log_take(char* out, int cap) {
+    std::lock_guard<std::mutex> g(fb::log_mutex());
+    std::string s;
+    for (const fb::Record& r : fb::log()) s += fb::record_text(r) + "\n";
+    const int n = (int)fb::log().size();
+    fb::log().clear();
+    snprintf(out, (size_t)cap, "%s", s.c_str());
+    return n;
+}
+// which: 0 the single-lane law of ecu.cuh, 1 qadd / qdbl of ecq.cuh.  words: two affine points P, Q (x, y, x, y; arkworks words).
+// Writes "CASE name" per case run, "FAIL ..." / "VIOLATION ..." per failure, "QUADVIOLATION ..." per record of a quad lane; returns
+// the failures other than quad records
+int fb_closure(int cid, int which, const uint32_t* words, char* out, int cap) {
+    return cid == 0 ? fbl::closure<FqBls12_381SParams>(which, words, out, cap) : fbl::closure<FqBn254SParams>(which, words, out, cap);
 }
 }

@@ -2,7 +2,9 @@
 fields: fields.cuh) and of the XYZZ group law (ecu.cuh) -- over the signed-limb field as the HIP kernels use it and over the saturated
 field (field.cuh) as the host code does -- compiled for the host and compared with big-int arithmetic; and of two device-only pieces: the load conversion of the quotient kernel and the circuit check (to_rp,
 zbound.cuh) on boundary and random stored words, and the hash of the device key maps (fr_io.cuh) against its Python restatement
-(tests/edge_values.py), on which the crafted collisions of the GPU suite rest."""
+(tests/edge_values.py), on which the crafted collisions of the GPU suite rest.  And of the call sites of the group law (ecu.cuh, ecq.cuh):
+instantiated over a field that checks the preconditions of fields.cuh at every call (tests/native/fb_field.h), the law must stay inside
+the contract on every branch, from inputs anywhere in its class invariant."""
 import ctypes
 import os
 import random
@@ -22,10 +24,16 @@ SO = os.path.join(ROOT, "tests", "native", "libfu_check.so")
 
 @pytest.fixture(scope="module")
 def fu():
-    deps = [SRC] + [os.path.join(ROOT, "ark_plonk_amd", "csrc", f) for f in ("field_common.cuh", "fieldu.cuh", "fields.cuh", "ecu.cuh", "curve_params.h", "zk_common.h", "field.cuh", "fr_io.cuh", "zbound.cuh")]
+    deps = [SRC] + [os.path.join(ROOT, "tests", "native", f) for f in ("fb_field.h", "fb_laws.h")]
+    deps += [os.path.join(ROOT, "ark_plonk_amd", "csrc", f) for f in ("field_common.cuh", "fieldu.cuh", "fields.cuh", "ecu.cuh", "ecq.cuh", "curve_params.h", "zk_common.h", "field.cuh", "fr_io.cuh", "zbound.cuh")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "c++", SRC, "-o", SO])
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", SRC, "-o", SO])
     L = ctypes.CDLL(SO)
+    L.fb_rule.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.fb_op_name.argtypes = [ctypes.c_int]
+    L.fb_op_name.restype = ctypes.c_char_p
+    L.fb_log_take.argtypes = [ctypes.c_char_p, ctypes.c_int]
+    L.fb_closure.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
     L.fu_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.fu_xyzz_chain.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     L.fs_raw_op.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
@@ -135,7 +143,11 @@ def test_xyzz_chain_matches_affine_group_law(cid, fu):
         [(pts[4], 0), (None, 0), (pts[5], 4), (pts[6], 5), (pts[7], 6)],
         [(p, int(rng.integers(0, 8))) for p in pts] * 3,  # long mixed chain: lazy bounds hold over many ops
     ]
-    for law in (cid, cid + 2):            # the signed-limb field (device), the saturated field (host)
+    # the signed-limb field (device), the saturated field (host), and the signed-limb field with the contract of fields.cuh checked
+    # at every call and the concrete limbs held against the envelope after every operation (tests/native/fb_field.h)
+    log = ctypes.create_string_buffer(1 << 16)
+    fu.fb_log_take(log, len(log))
+    for law in (cid, cid + 2, cid + 4):
         for seq in cases:
             assert run(seq, law) == expect(seq), (law, seq)
     # the same law on points whose coordinates are base-field edges (tests/edge_values.py): every point alone, so that the output
@@ -150,9 +162,11 @@ def test_xyzz_chain_matches_affine_group_law(cid, fu):
         ecases += [[(P, 0)], [(P, 2)], [(P, 0), (P, 0)], [(P, 2), (P, 2)], [(P, 0), (Q, 2 * (i & 1)), (Q, 1 + 2 * (i >> 1 & 1))]]
         ecases += [[(P, f), (Q, g)] for f in range(8) for g in range(8)]
     ecases += [[(edge[crng.randrange(m)], crng.randrange(8)) for _ in range(60)] for _ in range(20)]
-    for law in (cid, cid + 2):
-        for seq in ecases:
-            assert run(seq, law) == expect(seq), (law, seq)
+    ewant = [expect(seq) for seq in ecases]               # the big-integer reference once, shared by the three laws
+    for law in (cid, cid + 2, cid + 4):
+        for seq, want in zip(ecases, ewant):
+            assert run(seq, law) == want, (law, seq)
+    assert fu.fb_log_take(log, len(log)) == 0, log.value.decode()
 
 
 @pytest.mark.parametrize("field", [0, 1])
@@ -207,6 +221,187 @@ def test_signed_limbs_at_the_edge_of_the_column_bound(field, fu):
         b = np.array([sb] * (nl - 1) + [-3], dtype=np.int32)
         fu.fs_raw_op(field, 3, a.ctypes.data, b.ctypes.data, b.ctypes.data, b.ctypes.data, out.ctypes.data)
         assert val(out) == val(a) - 3 * val(b) and all(abs(int(v)) <= E for v in out[:-1]), (sa, sb)
+
+
+# ---- the contract of fields.cuh at every call site of the G1 law (tests/native/fb_field.h, fb_laws.h)
+H29 = 1 << 29
+STRICT = (-H29, H29 - 1)            # fields.cuh "strict"
+ALMOST = (-H29 - 2, H29 + 2)        # fields.cuh "almost"
+NEGATED = (-H29 + 1, H29)           # a strict element negated limb-wise
+Y_RANGE = (-H29, H29)               # a stored Y: strict or negated
+# operation -> its code in fs_raw_op, and operand envelopes (limb range, |value| < V p) AT the extreme of the precondition fields.cuh
+# states for it: the rule table must accept each, and the operator must then keep what the table predicts
+RULE_CASES = {
+    "mul": (0, [[(ALMOST, 12), (ALMOST, 12)], [(ALMOST, 12), (STRICT, 1)]]),
+    "sqr": (1, [[(ALMOST, 12)]]),
+    "dot2": (2, [[(ALMOST, 12)] * 4, [(ALMOST, 2), (ALMOST, 5), (NEGATED, 1), (STRICT, 1)]]),
+    "add": (5, [[((-2 * H29, 2 * H29), 6), ((-H29 + 1, H29 - 1), 6)], [(ALMOST, 4), (ALMOST, 4)]]),
+    "sub": (6, [[((-2 * H29, 2 * H29), 6), ((-H29 + 1, H29 - 1), 6)], [(STRICT, 1), (ALMOST, 4)]]),
+    "dbl": (7, [[((-3 * H29 // 2 + 1, 3 * H29 // 2 - 1), 6)], [(Y_RANGE, 1)]]),
+    "add3": (8, [[((-2 * H29, 2 * H29 - 1), 4), (Y_RANGE, 4), (Y_RANGE, 4)], [(STRICT, 1)] * 3]),
+    "sub_sum3": (3, [[(STRICT, 4), (Y_RANGE, 4), (Y_RANGE, 4), (Y_RANGE, 4)], [(STRICT, 1)] * 4]),
+    "neg": (9, [[(STRICT, 4)], [(ALMOST, 12)]]),
+    "canonical_lt2p": (10, [[(ALMOST, 2)], [(STRICT, 2)]]),
+}
+# one step past the precondition: the table must refuse each.  (operation, operand envelopes)
+RULE_REFUSALS = [
+    ("mul", [(ALMOST, 12), ((-H29 - 3, H29 + 2), 12)]), ("mul", [(ALMOST, 12 + 2 ** -16), (ALMOST, 12)]), ("sqr", [((-H29 - 2, H29 + 3), 12)]),
+    ("dot2", [(ALMOST, 12), (ALMOST, 12), (ALMOST, 12 + 2 ** -16), (ALMOST, 12)]),
+    ("add", [((-2 * H29, 2 * H29), 6), ((-H29 + 1, H29), 6)]), ("sub", [((-2 * H29, 2 * H29), 6), ((-H29, H29 - 1), 6)]),
+    ("dbl", [((-3 * H29 // 2, 3 * H29 // 2 - 1), 6)]),
+    ("add3", [((-2 * H29, 2 * H29), 4), (Y_RANGE, 4), (Y_RANGE, 4)]), ("add3", [((-2 * H29 - 1, 2 * H29 - 1), 4), (Y_RANGE, 4), (Y_RANGE, 4)]),
+    ("sub_sum3", [(Y_RANGE, 4), (Y_RANGE, 4), (Y_RANGE, 4), (Y_RANGE, 4)]), ("sub_sum3", [(STRICT, 4), (ALMOST, 4), (STRICT, 4), (STRICT, 4)]),
+    ("is_zero_mod_reduced", [(Y_RANGE, 1)]), ("is_zero_mod_reduced", [(STRICT, 2 + 2 ** -16)]), ("limb0_of_zero_mod", [(ALMOST, 1)]),
+    ("canonical_lt2p", [(STRICT, 2 + 2 ** -16)]),
+]
+
+
+def _rule(fu, field, name, envs):
+    """the rule table of fb_field.h: (ok, (lo, hi), V as a fraction of 2^-16 p)"""
+    ops = {fu.fb_op_name(i).decode(): i for i in range(fu.fb_op_count())}
+    unit = fu.fb_units()
+    arg = np.array([[lo, hi, round(V * unit)] for (lo, hi), V in envs], dtype=np.int64).reshape(-1)
+    res = np.zeros(3, dtype=np.int64)
+    ok = fu.fb_rule(field, ops[name], arg.ctypes.data, res.ctypes.data)
+    return bool(ok), (int(res[0]), int(res[1])), int(res[2])
+
+
+@pytest.mark.parametrize("field", [0, 1])
+def test_rule_table_is_sound(field, fu):
+    """Every rule of the checked field (tests/native/fb_field.h: precondition on the operand envelopes -> envelope of the result) against
+    the real operator and big integers.  Operand envelopes at the extreme of each precondition; inside them the limb patterns of the
+    column-bound test (every limb at the upper end, at the lower end, alternating both ways, random) with the top limb at +-V p.  The
+    result must lie in the predicted envelope and be the exact result: sums as integers, products modulo p after R'.  One step past a
+    precondition the table must refuse; for add3 / sub_sum3, whose rule is stated on the raw int32 sum, one step past is shown to be
+    wrong as well, so the rule is necessary and not only sufficient.  Prints, per operation, the largest |limb| and |value| / p seen
+    against what the rule predicts."""
+    p = bo.BLS12_381.q if field == 0 else bo.BN254.q
+    nl = fu.fs_limbs(field)
+    B, Rp, unit = 1 << (30 * (nl - 1)), 1 << (30 * nl), fu.fb_units()
+    rng = random.Random(0xFB + field)
+
+    def val(l):
+        return sum(int(v) << (30 * i) for i, v in enumerate(l))
+
+    def operand(env, kind):
+        (lo, hi), V = env
+        low = {0: [hi] * (nl - 1), 1: [lo] * (nl - 1), 2: [hi if i % 2 == 0 else lo for i in range(nl - 1)],
+               3: [lo if i % 2 == 0 else hi for i in range(nl - 1)]}.get(kind) or [rng.randint(lo, hi) for _ in range(nl - 1)]
+        lv, edge = val(low), V * p - 1                       # the top limb puts the value at the end of (-V p, V p)
+        tmax, tmin = (edge - lv) // B, -((edge + lv) // B)
+        top = tmax if kind in (0, 2) else tmin if kind in (1, 3) else rng.randint(tmin, tmax)
+        l = np.array(low + [top], dtype=np.int32)
+        assert abs(val(l)) < V * p
+        return l
+
+    def call(code, ls):
+        ls = list(ls) + [ls[-1]] * (4 - len(ls))
+        out = np.zeros(nl, dtype=np.int32)
+        fu.fs_raw_op(field, code, *[l.ctypes.data for l in ls], out.ctypes.data)
+        return out
+
+    exact = {
+        "add": lambda v: v[0] + v[1], "sub": lambda v: v[0] - v[1], "dbl": lambda v: 2 * v[0], "add3": lambda v: v[0] + v[1] + v[2],
+        "sub_sum3": lambda v: v[0] - v[1] - v[2] - v[3], "neg": lambda v: -v[0],
+    }
+    modular = {"mul": lambda v: v[0] * v[1], "sqr": lambda v: v[0] * v[0], "dot2": lambda v: v[0] * v[1] + v[2] * v[3]}
+    kinds = [0, 1, 2, 3, 4, 4, 4]
+    for name, (code, cases) in RULE_CASES.items():
+        seen_l, seen_v, pred_l, pred_v = 0, 0, 0, 0
+        for envs in cases:
+            ok, (lo, hi), V = _rule(fu, field, name, envs)
+            assert ok, (name, envs)
+            pred_l, pred_v = max(pred_l, -lo, hi), max(pred_v, V / unit)
+            for ka in kinds:
+                for kb in kinds:
+                    ks = [ka, kb, kb if ka < 4 else 4, ka if kb < 4 else 4][:len(envs)]
+                    ls = [operand(e, k) for e, k in zip(envs, ks)]
+                    vs = [val(l) for l in ls]
+                    out = call(code, ls)
+                    got = val(out)
+                    assert all(lo <= int(x) <= hi for x in out[:-1]), (name, ks)
+                    assert abs(got) * unit < V * p, (name, ks, abs(got) / p, V / unit)
+                    if name in exact:
+                        assert got == exact[name](vs), (name, ks)
+                    elif name in modular:
+                        assert (got * Rp - modular[name](vs)) % p == 0, (name, ks)
+                    else:
+                        assert 0 <= got < p and (got - vs[0]) % p == 0, (name, ks)
+                    seen_l, seen_v = max([seen_l] + [abs(int(x)) for x in out[:-1]]), max(seen_v, abs(got) / p)
+        print(f"field {field} {name}: |limb| seen {seen_l} against {pred_l} predicted, |value|/p seen {seen_v:.6f} against {pred_v:.6f} predicted")
+        assert seen_l <= pred_l and seen_v <= pred_v
+    # the constants without operands
+    assert _rule(fu, field, "zero", []) == (True, (0, 0), 0)
+    assert _rule(fu, field, "one", []) == (True, STRICT, unit) and 0 < Rp % p < p
+    for name, envs in RULE_REFUSALS:
+        assert not _rule(fu, field, name, envs)[0], (name, envs)
+    # add3 / sub_sum3 one past int32: the raw sum wraps and the operator is wrong, so their rule cannot be any looser
+    big = [np.array([v] * (nl - 1) + [1], dtype=np.int32) for v in (2 * H29, H29, H29, -H29)]
+    assert val(call(8, big[:3])) != sum(val(l) for l in big[:3])
+    assert val(call(3, [big[3], big[1], big[1], big[1] + 1])) != val(big[3]) - 2 * val(big[1]) - val(big[1] + 1)
+    # the zero tests: exact on strict limbs in (-2p, 2p), which their rule demands
+    ok, env, V = _rule(fu, field, "is_zero_mod_reduced", [(STRICT, 2)])
+    assert ok and env == STRICT and V == 2 * unit and _rule(fu, field, "limb0_of_zero_mod", [(STRICT, 2)])[0]
+    for v in [k * p + d for k in (-1, 0, 1) for d in (-1, 0, 1)] + [-2 * p + 1, 2 * p - 1] + [rng.randrange(-2 * p + 1, 2 * p) for _ in range(200)]:
+        l = np.array(ev.strict_limbs(v, nl), dtype=np.int32)
+        assert val(l) == v and all(STRICT[0] <= int(x) <= STRICT[1] for x in l[:-1])
+        assert bool(call(11, [l])[0]) == (v % p == 0), hex(v)
+        assert call(12, [l])[0] or v % p != 0, hex(v)
+
+
+# function / branch outcome: what the closure runs must be exactly this list (ecu.cuh; the issue names every entry)
+SINGLE_LANE_CASES = ["setup", "from_affine", "dbl_affine", "dbl/infinity", "dbl/general",
+                     "madd/p infinite", "madd/P = Q", "madd/P = -Q", "madd/general",
+                     "madd_begin + madd_finish/general", "madd_begin + madd_finish/P = Q", "madd_begin + madd_finish/P = -Q",
+                     "add/p infinite", "add/q infinite", "add/P = Q", "add/P = -Q", "add/general", "neg",
+                     "to_affine/infinity", "to_affine/general"]
+# every lane of a quad runs every instruction; the four roles are checked in each case.  "qadd alone" is a wave in which no quad
+# has P = +-Q, so the branch around the quad doubling is not taken; in "qadd" all cases share one wave and every lane takes it
+QUAD_CASES = ["setup", "qadd/inputs", "qadd/general", "qadd/P = Q", "qadd/P = -Q", "qadd/p infinite", "qadd/q infinite", "qadd/both infinite",
+              "qadd alone/inputs", "qadd alone/general", "qdbl/inputs", "qdbl/general", "qdbl/infinity"]
+# Violations in lanes whose value nobody reads: "site|role|operation" -> why the value is unread.  Each entry exempts exactly the
+# records it names and must occur; an entry may never name a role whose result of that operation is selected into `res`.
+# There are none: with inputs inside the class invariant every lane of qadd and qdbl, dead ones included, stays inside the contract
+# (the dead lanes multiply and subtract products and stored coordinates like the live ones).
+DEAD_LANE_EXEMPTIONS = {}
+
+
+def _closure(fu, cid, which):
+    cv = bo.CURVES[cid]
+    W = 2 * cv.fq_limbs
+    G = (cv.gx, cv.gy)
+    P, Q = bo.ec_mul(cv, 3, G), bo.ec_mul(cv, 5, G)          # Q != +-P; 2P, 2Q, 4P, 2P + Q, 2P + 2Q all finite
+    arr = np.concatenate([words(c * cv.fq_R % cv.q, W) for c in P + Q])
+    buf = ctypes.create_string_buffer(1 << 18)
+    failures = fu.fb_closure(cid, which, arr.ctypes.data, buf, len(buf))
+    lines = buf.value.decode().splitlines()
+    return failures, lines
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_g1_law_is_closed_under_the_signed_limb_contract(cid, fu):
+    """XYZZu (ecu.cuh) over the checked field, every function once per branch outcome on a concrete input that takes the branch, the
+    input envelopes widened to the class invariant ("Signed-limb contract of the G1 law"): no precondition of fields.cuh
+    is missed at any call site, every output envelope is inside the invariant again, and the result is the group element the branch
+    gives.  Envelopes do not depend on values, so this is the induction step for every chain of these functions on every input."""
+    failures, lines = _closure(fu, cid, 0)
+    assert failures == 0 and all(l.startswith("CASE ") for l in lines), "\n".join(l for l in lines if not l.startswith("CASE "))
+    assert [l[5:] for l in lines] == SINGLE_LANE_CASES
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_quad_law_is_closed_under_the_signed_limb_contract(cid, fu):
+    """qadd and qdbl of ecq.cuh, the file as the kernels compile it, over the checked field: four host threads per quad in lockstep
+    behind host definitions of the wave primitives, the envelope travelling with every limb through the shuffles.  General case, the
+    P = +-Q slow path and the infinity paths; per role the result envelope is inside the class invariant, and the gathered point is
+    the group element the single-lane law gives.  A violation is tolerated only in a lane listed in DEAD_LANE_EXEMPTIONS."""
+    failures, lines = _closure(fu, cid, 1)
+    recorded = [l[len("QUADVIOLATION "):] for l in lines if l.startswith("QUADVIOLATION ")]
+    rest = [l for l in lines if not l.startswith("QUADVIOLATION ")]
+    assert failures == 0 and all(l.startswith("CASE ") for l in rest), "\n".join(l for l in rest if not l.startswith("CASE "))
+    assert [l[5:] for l in rest] == QUAD_CASES
+    keys = {"|".join(r.split("|")[:3]) for r in recorded}
+    assert keys == set(DEAD_LANE_EXEMPTIONS), "\n".join(recorded)
 
 
 # ---- the load conversion of the quotient kernel and the circuit check (zbound.cuh)

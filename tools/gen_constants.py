@@ -168,6 +168,7 @@ def signed_struct(sname, p, nl, sat_words):
         mp = sum(m[i] * abs(pd[k - i]) for i in range(nl) if 0 <= k - i < nl)
         assert 2 * ab + mp + (1 << 36) < (1 << 63), (sname, k)      # dot2: two products + the reduction + carry + bias
     assert Rp // p >= 512          # |a||b| / R' stays far below p/2 for |a|, |b| < 12 p: products come out in (-p, p)
+    assert Rp // p >= 576          # dot2 at its limit |a||b| + |c||d| < 288 p^2 comes out in (-p, p) as well: 288 / 576 + 1/2
     pinv = (-pow(p, -1, 1 << SB)) % (1 << SB)
     out = [f"struct {sname} {{"]
     out.append(f"    static constexpr int NL = {nl};                 // signed 30-bit limbs")
