@@ -88,7 +88,7 @@ class Context:
 
     # -- tuning options of the MSM planner (zk_ctx_set_option; the ZK_* environment hooks of rounds 2-4 are gone)
     OPTIONS = ("msm_merge", "pre_vw", "pre_logg", "chunk_l", "long_rounds", "combine_sg", "pre_max_log_n", "mem_reserve_mb",
-               "round_mem_limit_mb", "host_workers", "cache_verify")
+               "round_mem_limit_mb", "host_workers", "cache_verify", "ntt_passes")
 
     def set_option(self, key: str, value: int):
         check(lib().zk_ctx_set_option(self.handle, key.encode(), int(value)), f"zk_ctx_set_option({key})")

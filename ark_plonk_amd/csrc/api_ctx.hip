@@ -175,7 +175,7 @@ static int* tune_field(zk_ctx* c, const char* key, int64_t* lo, int64_t* hi) {
         {"pre_logg", &ZkTune::pre_logg, -1, 5},          {"chunk_l", &ZkTune::chunk_l, 0, 1024},
         {"long_rounds", &ZkTune::long_rounds, 1, 16},    {"combine_sg", &ZkTune::combine_sg, 0, 4},
         {"pre_max_log_n", &ZkTune::pre_max_log_n, 0, 25}, {"mem_reserve_mb", &ZkTune::mem_reserve_mb, 0, 1 << 20},
-        {"round_mem_limit_mb", &ZkTune::round_mem_limit_mb, 0, 1 << 20},
+        {"round_mem_limit_mb", &ZkTune::round_mem_limit_mb, 0, 1 << 20}, {"ntt_passes", &ZkTune::ntt_passes, 0, 4},
     };
     for (const Row& r : rows)
         if (strcmp(key, r.key) == 0) {

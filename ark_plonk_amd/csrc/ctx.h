@@ -275,6 +275,10 @@ struct ZkTune {
     int mem_reserve_mb = 1024;
     int round_mem_limit_mb = 0;
     int host_workers = -1;   // helper threads of the ctx's host pool (-1 = min(15, cores / LOCAL_WORLD_SIZE - 1)); read when the pool starts
+    // Passes of an NTT (ntt.hip: decompose).  0: by size (one pass to 2^9, two to 2^18, three to 2^27, four above); 1 .. 4: log_n split
+    // into that many passes by the same balanced rule, refused (ZK_ERR_UNSUPPORTED) where a radix leaves [3, 9].  For tests and A/B
+    // runs: the four-pass chain and the radix-3 / radix-4 passes of a multi-pass plan are otherwise reachable only at >= 2^28 / not at all.
+    int ntt_passes = 0;
 };
 
 struct zk_ctx {
@@ -291,7 +295,7 @@ struct zk_ctx {
     std::vector<hipEvent_t> event_pool;
 
     // NTT state
-    std::map<uint64_t, NttPlan*> plans;          // key = curve<<40 | inverse<<32 | log_n
+    std::map<uint64_t, NttPlan*> plans;          // key = curve<<40 | ntt_passes<<36 | inverse<<32 | log_n
     std::map<uint64_t, void*> inner_tw;          // key = curve<<40 | inverse<<32 | s
     DevBuf ntt_work;                             // N-element scratch between passes
     DevBuf coset_pow[2];                         // per curve: g^j

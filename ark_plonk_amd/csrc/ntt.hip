@@ -146,18 +146,24 @@ int launch_pow_table(zk_ctx* c, void* out, uint64_t n, typename C::Fr base, type
     return ZK_OK;
 }
 
-// pass decomposition: every pass radix in [3, 9] (a wavefront holds 2^9 elements)
-void decompose(uint32_t log_n, int& n_pass, int s[4]) {
+// pass decomposition: every pass radix in [3, 9] (a wavefront holds 2^9 elements).  forced = 0: the pass count follows from the size
+// (one pass to 2^9, two to 2^18, three to 2^27, four above); 1 .. 4 (option "ntt_passes", for tests and A/B runs): that many passes,
+// split by the same balanced rule.  false: a radix of the forced split is outside [3, 9] -- nothing may be launched for it.
+bool decompose(uint32_t log_n, int forced, int& n_pass, int s[4]) {
     s[0] = s[1] = s[2] = s[3] = 0;
-    if (log_n <= 9) {
+    if (forced == 0 && log_n <= 9) {
         n_pass = 1;
         s[0] = (int)log_n;
-        return;
+        return true;
     }
-    n_pass = (int)((log_n + 8) / 9);
+    n_pass = forced ? forced : (int)((log_n + 8) / 9);
+    if (n_pass > 4) return true;             // beyond four passes of 2^9: ntt_run refuses the size
     int base = (int)log_n / n_pass, extra = (int)log_n % n_pass;
     for (int i = 0; i < n_pass; ++i) s[i] = base + (i < extra ? 1 : 0);
+    return forced == 0 || (s[n_pass - 1] >= 3 && s[0] <= 9);
 }
+// the ctx's forced pass count; transforms below 2^3 (ntt_tiny) have no passes to choose
+int forced_passes(const zk_ctx* c, uint32_t log_n) { return log_n < 3 ? 0 : c->tune.ntt_passes; }
 
 template <class C>
 int get_inner_tw(zk_ctx* c, int s, bool inverse, void** out) {
@@ -197,17 +203,22 @@ int get_inner_tw(zk_ctx* c, int s, bool inverse, void** out) {
 template <class C>
 int get_plan(zk_ctx* c, uint32_t log_n, bool inverse, NttPlan** out) {
     typedef typename C::Fr Fr;
-    uint64_t key = ((uint64_t)C::ID << 40) | ((uint64_t)(inverse ? 1 : 0) << 32) | log_n;
+    // the forced pass count is part of the key: a plan built under one setting of "ntt_passes" never serves another
+    const int forced = forced_passes(c, log_n);
+    uint64_t key = ((uint64_t)C::ID << 40) | ((uint64_t)forced << 36) | ((uint64_t)(inverse ? 1 : 0) << 32) | log_n;
     auto it = c->plans.find(key);
     if (it != c->plans.end()) {
         *out = it->second;
         return ZK_OK;
     }
+    int n_pass, s[4];
+    if (!decompose(log_n, forced, n_pass, s)) return ZK_ERR_UNSUPPORTED;    // dispatch_pass's code for such a radix, before any table
     NttPlan* pl = new NttPlan();
     pl->curve = C::ID;
     pl->log_n = log_n;
     pl->inverse = inverse;
-    decompose(log_n, pl->n_pass, pl->s);
+    pl->n_pass = n_pass;
+    for (int i = 0; i < 4; ++i) pl->s[i] = s[i];
     uint32_t log_mprev = log_n;
     for (int p = 0; p < pl->n_pass; ++p) {
         if (log_n >= 3) {
@@ -302,6 +313,10 @@ int ntt_run(zk_ctx* c, int kind, uint32_t log_n, uint32_t n_polys, const void* c
         ZK_HIP_TRY(hipGetLastError());
         return ZK_OK;
     }
+    {   // a forced pass count (option "ntt_passes") that this size cannot take is refused before anything is allocated or launched
+        int np, sp[4];
+        if (!decompose(log_n, forced_passes(c, log_n), np, sp)) return ZK_ERR_UNSUPPORTED;
+    }
     void* pre = nullptr;
     void* post = nullptr;
     if (kind == ZK_NTT_COSET_FFT && in_len > 0) {
@@ -375,6 +390,7 @@ int ntt_run(zk_ctx* c, int kind, uint32_t log_n, uint32_t n_polys, const void* c
         }
         rc = dispatch_pass<C>(c, s, last, a);
         if (rc) return rc;
+        if (c->profiling) c->prof["ntt_passes"].launches += 1;     // the plan as it ran: one per pass launched (a batch is one launch)
     }
     return ZK_OK;
 }

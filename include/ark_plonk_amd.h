@@ -101,6 +101,12 @@ int zk_ctx_set_staging(zk_ctx* ctx, int mode);
  *                         still fits (hipMemGetInfo): default 1024
  *   "round_mem_limit_mb"  test hook, 0 = off: the buffer sets of a round's QUEUED jobs may together hold at most this many MiB, so that
  *                         the early close described at zk_kzg_round_begin_dev can be exercised at small sizes
+ *   "ntt_passes"     passes of an NTT: 0 (default) = by size (one to 2^9, two to 2^18, three to 2^27, four above); 1 .. 4: log_n is
+ *                    split into that many passes by the same balanced rule (the first log_n % k passes get one bit more).  It exists
+ *                    for tests and A/B runs: the four-pass plan is otherwise reached only from 2^28.  A transform whose split would
+ *                    need a radix outside 2^3 .. 2^9 returns ZK_ERR_UNSUPPORTED and leaves its output untouched; transforms below 2^3
+ *                    ignore the option.  Takes effect at the next transform; with profiling on, the counter "ntt_passes"
+ *                    (zk_profile_get: launches) grows by one per pass launched
  *   "host_workers"        helper threads of the ctx's host pool (window-sum combine, affine normalisation, digests): default
  *                         min(15, hardware threads - 1); a launcher with several ranks per host passes cores / LOCAL_WORLD_SIZE - 1
  *   "cache_verify"        0 (default) | 1: every hit of the commitment cache is recomputed and every hit of the residency cache compared

@@ -195,7 +195,48 @@ static void fs_raw(int op, const int32_t* a, const int32_t* b, const int32_t* c,
     for (int i = 0; i < F::NL; ++i) out[i] = (int32_t)r.v[i];
 }
 
+// raw 29-bit-limb operands (no conversion on the way in or out): the limb patterns of lazily reduced intermediates, which no stored
+// word can choose.  The normalising operators of fieldu.cuh: 0 mul(a, b)   1 mul_fenced(a, b)   2 sqr(a)   3 add(a, b)   4 add3(a, b, c)
+// 5 sub2(a, b)   6 sub8(a, b)   7 sub16(a, b)   8 neg16(a); the lazily normalised ones of the NTT butterflies: 9 add_raw(a, b)
+// 10 sub_raw3(a, b)   11 sub_raw8(a, b)   12 sub_raw16(a, b)   13 sweep(a); and 14 canonical_lt2p(a)   15 is_zero_mod_reduced(a), the flag
+// in out[0]
+template <class F>
+static void fu_raw(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out) {
+    F x, y, z, r;
+    for (int i = 0; i < F::NL; ++i) {
+        x.v[i] = a[i];
+        y.v[i] = b[i];
+        z.v[i] = c[i];
+    }
+    switch (op) {
+    case 0: r = F::mul(x, y); break;
+    case 1: r = F::mul_fenced(x, y); break;
+    case 2: r = F::sqr(x); break;
+    case 3: r = F::add(x, y); break;
+    case 4: r = F::add3(x, y, z); break;
+    case 5: r = F::sub2(x, y); break;
+    case 6: r = F::sub8(x, y); break;
+    case 7: r = F::sub16(x, y); break;
+    case 8: r = F::neg16(x); break;
+    case 9: r = F::add_raw(x, y); break;
+    case 10: r = F::sub_raw3(x, y); break;
+    case 11: r = F::sub_raw8(x, y); break;
+    case 12: r = F::sub_raw16(x, y); break;
+    case 13: r = x; F::sweep(r); break;
+    case 14: r = F::canonical_lt2p(x); break;
+    case 15: r = F::zero(); r.v[0] = x.is_zero_mod_reduced(); break;
+    default: r = F::zero();
+    }
+    for (int i = 0; i < F::NL; ++i) out[i] = r.v[i];
+}
+
 extern "C" {
+int fu_limbs(int field) { return field == 1 ? FrB::NL : FrN::NL; }
+// field: 1 Fr-BLS, 3 Fr-BN (as fu_op)
+void fu_raw_op(int field, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out) {
+    if (field == 1) fu_raw<FrB>(op, a, b, c, out);
+    else fu_raw<FrN>(op, a, b, c, out);
+}
 int fs_limbs(int field) { return field == 0 ? FqBs::NL : FqNs::NL; }
 void fs_raw_op(int field, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out) {
     if (field == 0) fs_raw<FqBs>(op, a, b, c, d, out);

@@ -272,7 +272,7 @@ def test_ctx_options_api(ctx):
     v = ctypes.c_int64()
     assert L.zk_ctx_get_option(ctx.handle, b"no_such_key", ctypes.byref(v)) == _lib.ZK_ERR_UNSUPPORTED
     for key, bad in (("pre_vw", 48), ("pre_vw", 4), ("chunk_l", 4), ("combine_sg", 3), ("pre_max_log_n", 12), ("pre_max_log_n", 26), ("long_rounds", 0),
-                     ("msm_merge", 2), ("pre_logg", 6)):
+                     ("msm_merge", 2), ("pre_logg", 6), ("ntt_passes", 5), ("ntt_passes", -1)):
         assert L.zk_ctx_set_option(ctx.handle, key.encode(), bad) == _lib.ZK_ERR_BAD_ARG, (key, bad)
     assert L.zk_ctx_set_option(None, b"pre_vw", 64) == _lib.ZK_ERR_BAD_ARG and L.zk_ctx_set_option(ctx.handle, None, 64) == _lib.ZK_ERR_BAD_ARG
     cv = zk.get_curve(0)

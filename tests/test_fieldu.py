@@ -4,7 +4,9 @@ field (field.cuh) as the host code does -- compiled for the host and compared wi
 zbound.cuh) on boundary and random stored words, and the hash of the device key maps (fr_io.cuh) against its Python restatement
 (tests/edge_values.py), on which the crafted collisions of the GPU suite rest.  And of the call sites of the group law (ecu.cuh, ecq.cuh):
 instantiated over a field that checks the preconditions of fields.cuh at every call (tests/native/fb_field.h), the law must stay inside
-the contract on every branch, from inputs anywhere in its class invariant."""
+the contract on every branch, from inputs anywhere in its class invariant.  And of the scalar field's lazily normalised operators
+(fieldu.cuh: mul_fenced, add_raw, sub_raw3/8/16, sweep, the constants ZB3/8/16) and the numeric rules of zbound.cuh, on raw 29-bit
+limb patterns at the ends of the contracts their comments state."""
 import ctypes
 import os
 import random
@@ -37,6 +39,7 @@ def fu():
     L.fu_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.fu_xyzz_chain.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     L.fs_raw_op.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+    L.fu_raw_op.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
     L.fu_to_rp.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
     L.fu_to_rp.restype = None
     L.fu_el_mix.argtypes = [ctypes.c_uint64, ctypes.c_void_p]
@@ -402,6 +405,263 @@ def test_quad_law_is_closed_under_the_signed_limb_contract(cid, fu):
     assert [l[5:] for l in rest] == QUAD_CASES
     keys = {"|".join(r.split("|")[:3]) for r in recorded}
     assert keys == set(DEAD_LANE_EXEMPTIONS), "\n".join(recorded)
+
+
+# ---- the scalar field's lazily normalised operators (fieldu.cuh) and the numeric rules of zbound.cuh, on raw 29-bit limbs
+U29 = 1 << 29
+FU_OPS = {"mul": 0, "mul_fenced": 1, "sqr": 2, "add": 3, "add3": 4, "sub2": 5, "sub8": 6, "sub16": 7, "neg16": 8, "add_raw": 9,
+          "sub_raw3": 10, "sub_raw8": 11, "sub_raw16": 12, "sweep": 13, "canonical_lt2p": 14, "is_zero_mod_reduced": 15}
+FU_KINDS = [0, 1, 2, 3, 4, 4, 4]
+
+
+def ntt_units_before(t):
+    """ntt_pass.cuh: limb units of a lane's registers before stage t of a pass"""
+    b = 1
+    for _ in range(t):
+        if b > 6:
+            b = 1
+        b += 2
+    return b
+
+
+class RawFu:
+    """Fu<P> of the harness on raw limbs (lists of Python integers in, lists out), for field 1 (Fr of BLS12-381) or 3 (BN254)"""
+
+    def __init__(self, fu, field):
+        self.fu, self.field, self.r = fu, field, FIELDS[field][0]
+        self.nl = fu.fu_limbs(field)
+        self.B, self.Rp = 1 << (29 * (self.nl - 1)), 1 << (29 * self.nl)      # the top limb's weight; the Montgomery radix R'
+        self.rng = random.Random(0xF0 + field)
+        self.zero = [0] * self.nl
+
+    @staticmethod
+    def val(l):
+        return sum(int(v) << (29 * i) for i, v in enumerate(l))
+
+    def limbs(self, v):
+        """the normalised limbs of v"""
+        return [(v >> (29 * i)) & (U29 - 1) for i in range(self.nl - 1)] + [v >> (29 * (self.nl - 1))]
+
+    def swept(self, l):
+        return all(0 <= v < U29 for v in l[:-1]) and 0 <= l[-1] < 1 << 32
+
+    def units(self, l):
+        return max(l[:-1]) // U29 + 1
+
+    def call(self, name, *ls):
+        assert all(0 <= v < 1 << 32 for l in ls for v in l), name
+        arrs = [np.array(l, dtype=np.uint32) for l in ls]
+        arrs += [arrs[-1]] * (3 - len(arrs))
+        out = np.zeros(self.nl, dtype=np.uint32)
+        self.fu.fu_raw_op(self.field, FU_OPS[name], *[a.ctypes.data for a in arrs], out.ctypes.data)
+        return [int(v) for v in out]
+
+    def operand(self, units, bound, kind):
+        """Limbs below the top one in [0, units * 2^29): all at the upper end (kind 0), all zero (1), alternating (2, 3), else random;
+        the top limb puts the value just below `bound` (random kinds: anywhere below it)."""
+        hi, n = units * U29 - 1, self.nl - 1
+        low = {0: [hi] * n, 1: [0] * n, 2: [hi if i % 2 == 0 else 0 for i in range(n)],
+               3: [0 if i % 2 == 0 else hi for i in range(n)]}.get(kind) or [self.rng.randint(0, hi) for _ in range(n)]
+        tmax = (bound - 1 - self.val(low)) // self.B
+        assert 0 <= tmax < 1 << 32
+        l = low + [tmax if kind < 4 else self.rng.randint(0, tmax)]
+        assert self.val(l) < bound and (kind >= 4 or self.val(l) + self.B >= bound)
+        return l
+
+    def product_columns(self, a, b):
+        """Fu::mul / mul_fenced restated on integers: (the largest 64-bit column total, the result limbs)"""
+        nl, M, mod = self.nl, U29 - 1, self.limbs(self.r)
+        pinv = (-pow(self.r, -1, U29)) % U29
+        m, out, carry, worst = [], [], 0, 0
+        for k in range(nl):
+            t = carry + sum(a[i] * b[k - i] for i in range(k + 1)) + sum(m[i] * mod[k - i] for i in range(k))
+            m.append((t * pinv) & M)
+            t += m[k] * mod[0]
+            assert t & M == 0
+            worst, carry = max(worst, t), t >> 29
+        for k in range(nl, 2 * nl - 1):
+            t = carry + sum(a[i] * b[k - i] + m[i] * mod[k - i] for i in range(k - nl + 1, nl))
+            out.append(t & M)
+            worst, carry = max(worst, t), t >> 29
+        return worst, out + [carry]
+
+    def checked_product(self, a, b, what):
+        """mul and mul_fenced of a, b: equal limb for limb, every column inside 64 bits, the result swept, below 2r and a b / R'"""
+        worst, want = self.product_columns(a, b)
+        assert worst < 1 << 64, (what, worst / 2 ** 64)
+        got = self.call("mul", a, b)
+        assert got == self.call("mul_fenced", a, b) == want, what
+        assert self.swept(got) and self.val(got) < 2 * self.r and (self.val(got) * self.Rp - self.val(a) * self.val(b)) % self.r == 0, what
+        return got, worst
+
+    def checked_sub_raw(self, name, a, b, what):
+        """sub_raw3/8/16: limb-wise a + k r - b computed here without wrap; no limb below zero or past 32 bits, at most units(a) + 2"""
+        zb = self.call(name, self.zero, self.zero)
+        want = [x + z - y for x, z, y in zip(a, zb, b)]
+        assert all(0 <= v < 1 << 32 for v in want), (what, want)
+        assert all(v < (self.units(a) + 2) * U29 for v in want[:-1]), what
+        got = self.call(name, a, b)
+        assert got == want and self.val(got) == self.val(a) + self.val(zb) - self.val(b), what
+        return got
+
+
+@pytest.mark.parametrize("field", [1, 3])
+def test_lazy_limbs_at_the_edge_of_the_column_bound(field, fu):
+    """The lazily normalised operators of the NTT butterflies (fieldu.cuh) at the ends of the contracts their comments state, on raw
+    limb patterns: limbs below the top one all at the upper end of their range, all zero, alternating both ways and random, the top limb
+    putting the value just below its bound.
+    mul / mul_fenced: a first operand of 6 units just below 47r (the bound of a pass, ntt_pass.cuh) and just below K r, K the largest
+    multiple with K r b <= 2^261 r, against a swept second operand just below r: every 64-bit column total (restated here on integers)
+    stays below 2^64, the two products agree limb for limb with the restatement, the result is swept, below 2r and a b / 2^261.
+    sub_raw3/8/16: a of 1, 3 and 5 units (below 2r, 5r, 13r: a fresh product, after stage 0, after stage 1 of a pass), b swept and just
+    below 2r / 7r / 15r: the exact integer a + k r - b, no limb below zero or past 32 bits, at most units(a) + 2; one step past the
+    precondition (a b whose top limb exceeds the constant's; an unswept b) the result is wrong, so the bound is necessary.
+    add_raw: the exact sum, units add up to the 8 a limb holds.  sweep: 7 units (the most ntt_units_before reaches) below 47r: same
+    value, swept, the top limb inside 29 bits.  ZB3/8/16: 3r / 8r / 16r with limbs below the top in [2^29, 2^30) and a top limb that covers
+    every swept value below 2r / 7r / 15r.  Then the unit schedule of one radix-9 pass replayed with these operators."""
+    F = RawFu(fu, field)
+    r, Rp = F.r, F.Rp
+    assert F.nl == 9 and 47 * r < Rp
+    # ---- the product
+    worst = 0
+    for kb in [0, 1, 2, 3, 4]:
+        b = F.operand(1, r, kb)
+        K = Rp // F.val(b) if F.val(b) else Rp // r           # a < K r gives a b < 2^261 r
+        assert K >= Rp // r >= 70
+        for bound in (47 * r, min(K * r, 6 * U29 * F.B)):       # the top limb counts among the 6 units as well
+            for ka in FU_KINDS:
+                a = F.operand(6, bound, ka)
+                assert F.val(a) * F.val(b) < Rp * r
+                worst = max(worst, F.checked_product(a, b, (kb, bound // r, ka))[1])
+    # the column argument itself (fieldu.cuh: 9 * 6 * 2^58 + 9 * 2^58 + carry < 2^64, a margin of 1/64) speaks of limbs only: EVERY limb of
+    # the first operand at 6 * 2^29 - 1 and of the second at 2^29 - 1, which no value inside the bounds above has in its top limb.  The
+    # product is then past 2r, but still a b / 2^261, and no column may wrap
+    a, b = [6 * U29 - 1] * F.nl, [U29 - 1] * F.nl
+    full, want = F.product_columns(a, b)
+    got = F.call("mul", a, b)
+    assert got == F.call("mul_fenced", a, b) == want and (F.val(got) * Rp - F.val(a) * F.val(b)) % r == 0
+    print(f"field {field}: largest product column {worst / 2 ** 64:.6f} of 2^64 inside the value bounds, {full / 2 ** 64:.6f} with every limb at its end")
+    assert 48 << 58 < worst < full < 1 << 64 and full > 54 << 58
+    # ---- the constants, and the differences
+    for name, k, cover in (("sub_raw3", 3, 2), ("sub_raw8", 8, 7), ("sub_raw16", 16, 15)):
+        zb = F.call(name, F.zero, F.zero)
+        assert F.val(zb) == k * r and all(U29 <= v < 2 * U29 for v in zb[:-1]), name
+        assert zb[-1] >= (cover * r - 1) // F.B, name                                  # the top limb of any swept value below cover * r
+        for units, abound in ((1, 2), (3, 5), (5, 13)):
+            for ka in FU_KINDS:
+                for kb in FU_KINDS:
+                    a, b = F.operand(units, abound * r, ka), F.operand(1, cover * r, kb)
+                    F.checked_sub_raw(name, a, b, (name, units, ka, kb))
+        # one step past: a swept b whose top limb exceeds the constant's (just below 7r / 16r / 32r); a b that is not swept
+        a, past = F.operand(1, 2 * r, 0), F.operand(1, {3: 7, 8: 16, 16: 32}[k] * r, 0)
+        assert a[-1] + zb[-1] - past[-1] < 0 and F.val(F.call(name, a, past)) != F.val(a) + k * r - F.val(past), name
+        wide = F.operand(3, 2 * r, 0)
+        assert F.val(F.call(name, F.zero, wide)) != k * r - F.val(wide), name
+    # ---- sums without a sweep, and the sweep
+    for ua, ub in ((1, 1), (3, 1), (5, 1), (3, 3), (5, 3), (7, 1)):
+        for ka in FU_KINDS:
+            for kb in FU_KINDS:
+                a, b = F.operand(ua, 47 * r, ka), F.operand(ub, 47 * r, kb)
+                got = F.call("add_raw", a, b)
+                assert got == [x + y for x, y in zip(a, b)] and F.units(got) <= ua + ub <= 8, (ua, ub, ka, kb)
+    for ka in FU_KINDS:
+        a = F.operand(7, 47 * r, ka)
+        got = F.call("sweep", a)
+        assert got == F.limbs(F.val(a)) and F.swept(got) and got[-1] < U29, ka
+    # ---- one radix-9 pass: three windows of three stages on the eight registers of a lane (dit_window), the sweeps where ntt_sweep_at
+    # takes them, the product-free butterflies of the first window; every register's residue followed on integers
+    Rinv = pow(Rp, -1, r)
+    after = [5, 13, 29, 32, 35, 38, 41, 44, 47]                 # value bound in r after stage t: ntt_pass.cuh "the pass still ends below 47r"
+    for run in range(3):
+        if run == 0:                                            # the all-high pattern, just below 2r
+            x = [F.operand(1, 2 * r - e * F.B, 0) for e in range(8)]
+        else:
+            x = [F.operand(1, 2 * r, 4) for _ in range(8)]
+        exp = [F.val(l) % r for l in x]
+        for t in range(9):
+            lb, first = t % 3, t < 3
+            claimed = ntt_units_before(t)
+            assert claimed <= 7 and all(F.units(l) <= claimed for l in x), t
+            if claimed > 6:                                     # ntt_sweep_at(t)
+                x = [F.call("sweep", l) for l in x]
+                assert all(F.swept(l) and F.val(l) % r == v for l, v in zip(x, exp))
+                claimed = 1
+            for e in range(8):
+                if e & (1 << lb):
+                    continue
+                eo = e | (1 << lb)
+                if first and (lb == 0 or e & ((1 << lb) - 1) == 0):       # the twiddle is 1
+                    m = x[eo] if lb == 0 else F.call("sweep", x[eo])
+                    assert F.swept(m) and F.val(m) < (2, 7, 15)[lb] * r, (t, e)
+                    name, tw = ("sub_raw3", "sub_raw8", "sub_raw16")[lb], Rp % r
+                else:
+                    assert F.units(x[eo]) <= claimed <= 5, (t, e)          # at most 5 units into a product
+                    w = F.operand(1, r, (e + t) % 5)
+                    m, _ = F.checked_product(x[eo], w, (t, e))
+                    name, tw = "sub_raw3", F.val(w)
+                te = exp[eo] * tw * Rinv % r
+                x[eo], x[e] = F.checked_sub_raw(name, x[e], m, (t, e)), F.call("add_raw", x[e], m)
+                exp[eo], exp[e] = (exp[e] - te) % r, (exp[e] + te) % r
+            assert all(F.val(l) < after[t] * r and F.val(l) % r == v for l, v in zip(x, exp)), t
+        assert ntt_units_before(9) == 7 and all(F.units(l) <= 7 for l in x)        # the sweep in front of the last product
+        scale = F.operand(1, r, 0)
+        for l, v in zip(x, exp):
+            y, _ = F.checked_product(F.call("sweep", l), scale, "scale")
+            c = F.call("canonical_lt2p", y)
+            assert F.swept(c) and F.val(c) == v * F.val(scale) * Rinv % r
+
+
+@pytest.mark.parametrize("field", [1, 3])
+def test_z_rules_are_sound(field, fu):
+    """The numbers of zbound.cuh (Z<F, B>: a value below B / 10 r) against the operators at the extreme each rule admits, on swept
+    operands in the limb patterns of the test above.  Products with A B <= 6400: (8r, 8r), (64r, r), (32r, 2r) in both orders and the
+    square of 8r come out below 2r and congruent.  Sums up to 600: exact, normalised, the top limb inside 29 bits.  Differences through
+    sub2 / sub8 / sub16 (SubK: 2r / 8r / 16r): subtrahend just below the multiple, minuend 0 and at the most the sum rule leaves: exact,
+    normalised, no negative top limb.  The two tests on values below 2r: exact on 0, r, r +- 1, 2r - 1 and random ones."""
+    F = RawFu(fu, field)
+    r, Rp = F.r, F.Rp
+    text = open(os.path.join(ROOT, "ark_plonk_amd", "csrc", "zbound.cuh")).read()
+    prod_max = int(re.search(r"static_assert\(A \* B <= (\d+),", text).group(1))
+    sum_max = int(re.search(r"static_assert\(A \+ B <= (\d+),", text).group(1))
+    assert re.search(r"K = B <= 20 \? 20 : B <= 80 \? 80 : 160;", text) and "A * A <= %d" % prod_max in text
+    assert (prod_max, sum_max) == (6400, 600) and sum_max * r < 10 * Rp
+
+    def below(tenths, kind):
+        return F.operand(1, tenths * r // 10, kind)
+
+    for A, B in ((80, 80), (640, 10), (320, 20)):
+        assert A * B == prod_max
+        for ka in FU_KINDS:
+            for kb in FU_KINDS:
+                a, b = below(A, ka), below(B, kb)
+                F.checked_product(a, b, (A, B, ka, kb))
+                F.checked_product(b, a, (B, A, kb, ka))
+    for ka in FU_KINDS:
+        a = below(80, ka)
+        got = F.call("sqr", a)
+        assert got == F.call("mul", a, a) and F.swept(got) and F.val(got) < 2 * r and (F.val(got) * Rp - F.val(a) ** 2) % r == 0, ka
+    for A, B in ((300, 300), (590, 10), (10, 590), (400, 200)):
+        assert A + B == sum_max
+        for ka in FU_KINDS:
+            for kb in FU_KINDS:
+                a, b = below(A, ka), below(B, kb)
+                got = F.call("add", a, b)
+                assert got == F.limbs(F.val(a) + F.val(b)) and got[-1] < U29, (A, B, ka, kb)
+                c = below(B // 2, kb)
+                assert F.call("add3", a, c, c) == F.limbs(F.val(a) + 2 * F.val(c)), (A, B, ka, kb)
+    for name, k in (("sub2", 2), ("sub8", 8), ("sub16", 16)):
+        for kb in FU_KINDS:
+            b = F.operand(1, k * r, kb)
+            for a in [F.zero] + [below(sum_max - 10 * k, ka) for ka in FU_KINDS]:
+                got = F.call(name, a, b)
+                assert got == F.limbs(F.val(a) + k * r - F.val(b)) and got[-1] < U29, (name, kb)
+            if k == 16:
+                assert F.call("neg16", b) == F.limbs(16 * r - F.val(b)), kb
+    vs = [0, 1, r - 1, r, r + 1, 2 * r - 1] + [F.rng.randrange(2 * r) for _ in range(300)]
+    for v in vs:
+        l = F.limbs(v)
+        assert bool(F.call("is_zero_mod_reduced", l)[0]) == (v % r == 0), hex(v)
+        assert F.call("canonical_lt2p", l) == F.limbs(v % r), hex(v)
 
 
 # ---- the load conversion of the quotient kernel and the circuit check (zbound.cuh)

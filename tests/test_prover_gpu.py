@@ -311,6 +311,11 @@ def test_proof_bytes_equal_the_cpu_restatement(cid, log_n, ctx, oracle_cpu):
     on integers from the oracle's own pieces (its transforms, grand products, quotient, linearisation, multisets, merlin,
     serialiser; the C++ restatement's Pippenger for the commitments) -- produce the SAME proof bytes for the same circuit,
     including every gate type at 128 rows.  Challenges are compared too, so a difference would be located by round."""
+    assert_proof_bytes_equal_the_cpu_restatement(cid, log_n, ctx, oracle_cpu)
+
+
+def assert_proof_bytes_equal_the_cpu_restatement(cid, log_n, ctx, oracle_cpu):
+    """The comparison of the test above, for callers that run it under another setting of the ctx (tests/test_ntt_pass_shapes_gpu.py)."""
     from oracle import prover_oracle as po
     cv, pk, ck, proof, pub, (ca, cd), wires = run_case(cid, log_n, ctx, oracle_cpu)
     n = 1 << log_n
