@@ -27,6 +27,7 @@ API_HDRS = HOST_HDRS + ["api_internal.h"]
 # helpers with one definition each: Fr / 32-byte element access; the quotient's bounded lazy arithmetic; the MSM's point storage
 FR_IO, ZBOUND, POINT_IO = ["fr_io.cuh"], ["fr_io.cuh", "zbound.cuh"], ["point_io.cuh"]
 GADGET = ["gadget_common.cuh"]            # what the two units of the device composer (layout, witness) share
+BLOCK_INV = ["block_inverse.cuh"]         # one field inversion per workgroup: the key fold, the gadget witnesses, the verifier's scalars
 # the C ABI, one unit per subsystem (api_internal.h is what they share)
 API_UNITS = ("api_ctx", "residency", "srs", "commit", "round", "api_host", "api_poly")
 MSM_UNITS = ("msm_accumulate", "msm_reduce", "msm_sort", "msm_plan")      # heaviest first
@@ -47,16 +48,16 @@ def jobs():
         ("msm_dispatch.o", "msm_dispatch.hip", [], HOST_HDRS),
         # the inner-product-argument commitment; circuit compilation (the wire permutation from the variable map, the witness gather);
         # the circuit check (per-row masks of violated gate, copy and lookup constraints)
-        ("ipa.o", "ipa.hip", [], API_HDRS + FR_IO + POINT_IO),
+        ("ipa.o", "ipa.hip", [], API_HDRS + FR_IO + POINT_IO + BLOCK_INV),
         ("compile.o", "compile.hip", [], API_HDRS + FR_IO),
         ("check.o", "check.hip", [], API_HDRS + ZBOUND),
         # the device composer: gadget segments (rows, ids, selectors, insertions) and lookup tables, built once per circuit ...
         ("gadget_layout.o", "gadget_layout.hip", [], API_HDRS + FR_IO + GADGET),
         # ... and the values of the variables the segments create, replayed once per proof
-        ("gadget_witness.o", "gadget_witness.hip", [], API_HDRS + FR_IO + GADGET),
+        ("gadget_witness.o", "gadget_witness.hip", [], API_HDRS + FR_IO + GADGET + BLOCK_INV),
         # the verifier's device side: batch decoding of compressed G1 points, per-proof scalars, the column sum of a fold (its host
         # side, parse and replay, is in wire.hip)
-        ("verify.o", "verify.hip", [], API_HDRS + FR_IO),
+        ("verify.o", "verify.hip", [], API_HDRS + FR_IO + BLOCK_INV),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

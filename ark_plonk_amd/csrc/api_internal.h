@@ -1,4 +1,5 @@
-// What the units of the C ABI (api_ctx / residency / srs / commit / round / api_host / api_poly .hip, ipa.hip, compile.hip, check.hip) share.
+// What the units of the C ABI (api_ctx / residency / srs / commit / round / api_host / api_poly .hip, ipa.hip, compile.hip, check.hip, the
+// gadget units, verify.hip) share.
 // Every function is listed once, with the locks its caller holds.  Not part of the C ABI.
 #pragma once
 #include "ctx.h"
@@ -35,6 +36,38 @@ inline void copy_affine(uint64_t* dst, size_t kd, const uint64_t* src, size_t ks
 }
 inline void copy_jacobian(uint64_t* dst, size_t kd, const uint64_t* src, size_t ks, int L) {
     memcpy(dst + kd * 3 * L, src + ks * 3 * L, sizeof(uint64_t) * 3 * L);
+}
+
+// the working memory of one call: a device allocation freed on every path out of the call
+struct DeviceAlloc {
+    void* base = nullptr;
+    ~DeviceAlloc() {
+        if (base) (void)hipFree(base);                     // waits for the device: nothing queued still reads it
+    }
+};
+// A call whose kernels report errors through one flag word (compile.hip, gadget_layout.hip, gadget_witness.hip): allocates
+// 256 + work_bytes, clears the 256 of the flag word, runs body(d_flag, work) -- which queues the kernels on the ctx stream and returns
+// a ZK_* code -- and reads the flag back once.  A set flag is ZK_ERR_BAD_ARG.  ctx lock held.
+template <class Body>
+int run_flagged(zk_ctx* c, size_t work_bytes, Body&& body) {
+    DeviceAlloc wk;
+    if (hipMalloc(&wk.base, 256 + work_bytes) != hipSuccess) {
+        wk.base = nullptr;
+        return ZK_ERR_OOM;
+    }
+    uint32_t* d_flag = (uint32_t*)wk.base;
+    hipStream_t st = c->stream;
+    int rc = [&]() -> int {
+        ZK_HIP_TRY(hipMemsetAsync(d_flag, 0, 256, st));
+        return body(d_flag, (void*)((char*)wk.base + 256));
+    }();
+    uint32_t flag = 0;
+    if (!rc) rc = zk_d2h(c, &flag, d_flag, 4, st);                // the one read-back; also the wait before the buffer is freed
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    return flag ? ZK_ERR_BAD_ARG : ZK_OK;
 }
 
 // a deferred round (zk_kzg_round_begin_dev ...) holds the ctx's MSM buffer sets until zk_kzg_round_end.  ctx lock held.

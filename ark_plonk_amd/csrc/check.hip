@@ -277,13 +277,6 @@ __global__ void __launch_bounds__(CT) check_gates(const CArgsU<F>* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-struct Work {
-    void* base = nullptr;
-    ~Work() {
-        if (base) (void)hipFree(base);                     // waits for the device: nothing queued still reads it
-    }
-};
-
 template <class Cv>
 void fill_args(CArgsU<typename Cv::FrU>& A, const zk_circuit_check_args* q) {
     typedef typename Cv::Fr Fr;
@@ -324,7 +317,7 @@ int check_impl(zk_ctx* c, uint32_t log_n, const zk_circuit_check_args* q, uint32
                  o_slots_id = o_keys + up256(4 * n * 32), o_slots_t = o_slots_id + up256(cap_id * 4), o_mask = o_slots_t + up256(cap_t * 4),
                  total = o_mask + (d_mask ? 0 : up256(n * 4));
     static_assert(sizeof(zk_circuit_check_summary) <= HEAD - 256, "the summary shares the head of the buffer with the flag word");
-    Work wk;
+    DeviceAlloc wk;
     if (hipMalloc(&wk.base, total) != hipSuccess) {
         wk.base = nullptr;
         return ZK_ERR_OOM;

@@ -255,13 +255,6 @@ __global__ void __launch_bounds__(256) fr_gather(const void* values, uint64_t nu
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-struct Work {
-    void* base = nullptr;
-    ~Work() {
-        if (base) (void)hipFree(base);                     // waits for the device: nothing queued still reads it
-    }
-};
-
 int scan_in_place(zk_ctx* c, uint32_t* d_data, uint64_t len, uint32_t* d_sums) {
     const uint64_t n_chunks = blocks_of(len, SCAN_CHUNK);
     hipLaunchKernelGGL(scan_sums, dim3((unsigned)n_chunks), dim3(SCAN_T), 0, c->stream, d_data, len, d_sums);
@@ -285,22 +278,16 @@ int sigma_impl(zk_ctx* c, uint32_t log_n, const uint32_t* ins_var, const uint32_
     const uint32_t passes = m ? (bits + 7) / 8 : 0;
     const uint64_t n_tiles = blocks_of(m, SORT_TILE);
     const uint64_t hist_len = passes ? RADIX * n_tiles : 0;
-    const size_t o_consts = 256, o_hist = o_consts + up256(N_CONSTS * 32), o_sums = o_hist + up256(hist_len * 4),
+    // offsets behind the flag word (run_flagged)
+    const size_t o_consts = 0, o_hist = o_consts + up256(N_CONSTS * 32), o_sums = o_hist + up256(hist_len * 4),
                  o_sort = o_sums + up256(blocks_of(hist_len, SCAN_CHUNK) * 4), sort_one = up256(m * 4),
                  o_pos = o_sort + (passes >= 2 ? 4 : passes ? 2 : 0) * sort_one, total = o_pos + (d_sigma_pos ? 0 : up256(n_pos * 4));
-    Work wk;
-    if (hipMalloc(&wk.base, total) != hipSuccess) {
-        wk.base = nullptr;
-        return ZK_ERR_OOM;
-    }
-    char* w = (char*)wk.base;
-    uint32_t* d_flag = (uint32_t*)w;
-    uint32_t* d_hist = (uint32_t*)(w + o_hist);
-    uint32_t* d_sums = (uint32_t*)(w + o_sums);
-    uint32_t* sigma_pos = d_sigma_pos ? d_sigma_pos : (uint32_t*)(w + o_pos);
     hipStream_t st = c->stream;
-    auto body = [&]() -> int {
-        ZK_HIP_TRY(hipMemsetAsync(d_flag, 0, 256, st));
+    return run_flagged(c, total, [&](uint32_t* d_flag, void* work) -> int {
+        char* w = (char*)work;
+        uint32_t* d_hist = (uint32_t*)(w + o_hist);
+        uint32_t* d_sums = (uint32_t*)(w + o_sums);
+        uint32_t* sigma_pos = d_sigma_pos ? d_sigma_pos : (uint32_t*)(w + o_pos);
         ZK_HIP_TRY(hipMemsetAsync(sigma_pos, 0xff, n_pos * 4, st));
         if (m) {
             const uint32_t* var_s = ins_var;
@@ -349,42 +336,18 @@ int sigma_impl(zk_ctx* c, uint32_t log_n, const uint32_t* ins_var, const uint32_
                            (const void*)(w + o_consts), out);
         ZK_HIP_TRY(hipGetLastError());
         return ZK_OK;
-    };
-    int rc = body();
-    uint32_t flag = 0;
-    if (!rc) rc = zk_d2h(c, &flag, d_flag, 4, st);                // the one read-back; also the wait before the buffer is freed
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    return flag ? ZK_ERR_BAD_ARG : ZK_OK;
+    });
 }
 
 template <class Cv>
 int gather_impl(zk_ctx* c, const void* d_values, size_t num_values, const uint32_t* d_index, size_t n, void* d_out) {
-    Work wk;
-    if (hipMalloc(&wk.base, 256) != hipSuccess) {
-        wk.base = nullptr;
-        return ZK_ERR_OOM;
-    }
-    uint32_t* d_flag = (uint32_t*)wk.base;
-    hipStream_t st = c->stream;
-    auto body = [&]() -> int {
-        ZK_HIP_TRY(hipMemsetAsync(d_flag, 0, 256, st));
+    return run_flagged(c, 0, [&](uint32_t* d_flag, void*) -> int {
         ProfScope ps(c, "fr_gather");
-        hipLaunchKernelGGL(fr_gather<Cv>, dim3(blocks_of(n, 256)), dim3(256), 0, st, d_values, (uint64_t)num_values, d_index, (uint64_t)n,
-                           d_out, d_flag);
+        hipLaunchKernelGGL(fr_gather<Cv>, dim3(blocks_of(n, 256)), dim3(256), 0, c->stream, d_values, (uint64_t)num_values, d_index,
+                           (uint64_t)n, d_out, d_flag);
         ZK_HIP_TRY(hipGetLastError());
         return ZK_OK;
-    };
-    int rc = body();
-    uint32_t flag = 0;
-    if (!rc) rc = zk_d2h(c, &flag, d_flag, 4, st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    return flag ? ZK_ERR_BAD_ARG : ZK_OK;
+    });
 }
 
 }  // namespace

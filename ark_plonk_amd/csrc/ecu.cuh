@@ -189,7 +189,18 @@ struct XYZZu {
         return r;
     }
 
-    // affine normalisation; returns false for infinity.  Output coordinates are products (< 2p).
+    // affine normalisation of a finite point from i3 = 1 / ZZZ, a product (for a caller with a batched inversion: the key fold of
+    // ipa.hip after block_inverse.cuh).  ZZ * i3 = 1 / Z.  Output coordinates are products (< 2p).
+    ZK_HD void to_affine_given(const F& i3, AffineU<F>& out) const {
+        F zi = F::mul(zz, i3);
+        F zi2 = F::sqr(zi);
+        out.x = F::mul(x, zi2);
+        out.y = F::mul(y, i3);
+    }
+    // affine normalisation (one field inversion); returns false for infinity.  Output coordinates are products (< 2p).
+    // The three products of to_affine_given stand here a second time: as a call of that member -- in any of the forms tried,
+    // profiles/block_inverse/asm_digests.md -- the device code of msm_accumulate.hip's fixed-base kernel is scheduled differently, and
+    // that unit's code is pinned (profiles/pmc_msm_accumulate.json).
     ZK_HD bool to_affine(AffineU<F>& out) const {
         if (is_inf()) {
             out.x = F::zero();

@@ -1,7 +1,7 @@
 // What the two units of the device composer share -- gadget_layout.hip, the circuit description built once per circuit, and
 // gadget_witness.hip, the values replayed once per proof -- each helper defined once: the shape table of every gadget kind, what both
-// entry points refuse before anything is launched, the access to a segment's inputs and coefficients, the guarded value store, the
-// shared block inversion and the flagged launch (one working-memory allocation per call, one flag word read back once).  A SEGMENT is
+// entry points refuse before anything is launched, the access to a segment's inputs and coefficients and the guarded value store
+// (the flagged launch -- one working-memory allocation per call, one flag word read back once -- is api_internal.h's).  A SEGMENT is
 // B calls of one gadget with the same parameters; every gadget has a fixed shape per call (R rows, V new variables, I insertions:
 // gadget_shape), so call k owns rows row0 + k R ..., variables var0 + k V ... and insertions k I ... and no kernel loops over calls or
 // rows on the host.  Errors are one flag word, OR-ed, read back once per call.  No buffer of the ctx is used, so both calls run
@@ -92,46 +92,7 @@ template <class Fr>
 ZK_D void st_value(void* values, uint64_t num_vars, uint64_t id, const Fr& v) {
     if (id < num_vars) st_fr<Fr>(values, id, v);
 }
-// 1 / z for every lane of the block with ONE field inversion: inclusive prefix and suffix products of z over the block in LDS
-// (Hillis-Steele), 1 / z_t = prefix_{t-1} * suffix_{t+1} / total -- the scan of ipa_fold_key.  z must be non-zero in every lane.
-template <class Fr>
-struct alignas(16) InverseLds {                    // declared __shared__ once in every kernel that calls block_inverse; 16: 128-bit LDS access
-    Fr pre[GT], suf[GT], inv_total;
-};
-template <class Fr>
-ZK_D Fr block_inverse(const Fr& z, InverseLds<Fr>& lds) {
-    Fr *const pre = lds.pre, *const suf = lds.suf, *const inv_total = &lds.inv_total;
-    const uint32_t t = threadIdx.x;
-    Fr p = z, s = z;
-    pre[t] = p;
-    suf[t] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < GT; d <<= 1) {
-        const Fr pl = t >= d ? pre[t - d] : Fr::one();
-        const Fr sr = t + d < GT ? suf[t + d] : Fr::one();
-        __syncthreads();
-        if (t >= d) p = Fr::mul(p, pl);
-        if (t + d < GT) s = Fr::mul(s, sr);
-        pre[t] = p;
-        suf[t] = s;
-        __syncthreads();
-    }
-    if (t == 0) *inv_total = Fr::inverse(pre[GT - 1]);
-    __syncthreads();
-    Fr zi = *inv_total;
-    if (t > 0) zi = Fr::mul(zi, pre[t - 1]);
-    if (t + 1 < GT) zi = Fr::mul(zi, suf[t + 1]);
-    return zi;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host side
-struct Work {
-    void* base = nullptr;
-    ~Work() {
-        if (base) (void)hipFree(base);                     // waits for the device: nothing queued still reads it
-    }
-};
-
 inline int inputs_needed(uint32_t kind) {
     switch (kind) {
     case ZK_GADGET_POLY: return 2;                         // and the output, unless it is computed
@@ -170,28 +131,6 @@ inline int check_args(const zk_gadget_args& a, const Shape& s) {
     if (a.calls > MAX_ROWS || a.row0 > MAX_ROWS || a.row0 + a.calls * s.rows > MAX_ROWS) return ZK_ERR_UNSUPPORTED;
     if (a.var0 == 0 || a.var0 > MAX_VARS || a.var0 + a.calls * s.vars > MAX_VARS) return ZK_ERR_UNSUPPORTED;
     return ZK_OK;
-}
-
-template <class Cv, class Body>
-int run_flagged(zk_ctx* c, size_t work_bytes, Body&& body) {
-    Work wk;
-    if (hipMalloc(&wk.base, 256 + work_bytes) != hipSuccess) {
-        wk.base = nullptr;
-        return ZK_ERR_OOM;
-    }
-    uint32_t* d_flag = (uint32_t*)wk.base;
-    hipStream_t st = c->stream;
-    int rc = [&]() -> int {
-        ZK_HIP_TRY(hipMemsetAsync(d_flag, 0, 256, st));
-        return body(d_flag, (void*)((char*)wk.base + 256));
-    }();
-    uint32_t flag = 0;
-    if (!rc) rc = zk_d2h(c, &flag, d_flag, 4, st);                // the one read-back; also the wait before the buffer is freed
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    return flag ? ZK_ERR_BAD_ARG : ZK_OK;
 }
 
 }  // namespace

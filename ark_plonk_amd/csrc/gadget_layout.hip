@@ -356,7 +356,7 @@ int layout_impl(zk_ctx* c, const zk_gadget_args& a, uint32_t* d_ids, void* const
     if (rc) return rc;
     SelPtrs sel;
     for (int j = 0; j < N_SEL; ++j) sel.p[j] = d_sel[j];
-    return run_flagged<Cv>(c, 0, [&](uint32_t* d_flag, void*) -> int {
+    return run_flagged(c, 0, [&](uint32_t* d_flag, void*) -> int {
         ProfScope ps(c, "gadget_layout");
         hipLaunchKernelGGL(gadget_layout<Cv>, dim3(blocks_of(a.calls * s.rows, GT)), dim3(GT), 0, c->stream, a, s, d_ids, sel, d_flag);
         hipLaunchKernelGGL(gadget_insertions<Cv>, dim3(blocks_of(a.calls * s.ins, GT)), dim3(GT), 0, c->stream, a, s, d_ins_var, d_ins_rec);

@@ -4,7 +4,7 @@
 //   gadget_w_poly        one lane per call: the computed output (q_m a b + q_l a + q_r b + q_c + q_4 d + pi) (-q_o)
 //   gadget_w_range       one lane per (call, accumulator j): (v mod 2^bits) >> (bits - 2 (j + 1)) of the canonical integer v
 //   gadget_w_logic       one lane per (call, quad): both input prefixes, their product quad, the prefix of a ^ b or a & b
-//   gadget_w_curve       one lane per call: x1 y2 and the twisted Edwards sum; ONE field inversion per block (product scans in LDS)
+//   gadget_w_curve       one lane per call: x1 y2 and the twisted Edwards sum; ONE field inversion per block (block_inverse.cuh)
 //   gadget_w_fixed_walk  one lane per call: the width-2 NAF digits in closed form (digit of weight 2^j = bit j+1 of 3e - bit j+1 of e),
 //                        a running sum in extended coordinates against the segment's table of affine multiples, the M + 1
 //                        projective accumulators stored to the call's workspace
@@ -30,6 +30,7 @@
 // Working memory: one allocation per call, freed on every path; 256 bytes, + 96 (M + 1) B for a fixed-base and 96 (2 M + 1) B for a
 // variable-base witness.
 #include "gadget_common.cuh"
+#include "block_inverse.cuh"
 
 namespace {
 
@@ -217,7 +218,7 @@ __global__ void __launch_bounds__(GT) gadget_w_logic(zk_gadget_args a, void* val
 template <class Cv>
 __global__ void __launch_bounds__(GT) gadget_w_curve(zk_gadget_args a, void* values, uint64_t num_vars, uint32_t* flag) {
     typedef typename Cv::Fr Fr;
-    __shared__ InverseLds<Fr> lds;
+    __shared__ BlockInverseLds<Fr, GT> lds;
     const uint64_t k = (uint64_t)blockIdx.x * GT + threadIdx.x;
     const bool active = k < a.calls;
     Fr x1y2 = Fr::zero(), y1x2 = Fr::zero(), num_y = Fr::zero(), den_x = Fr::one(), den_y = Fr::one();
@@ -236,7 +237,7 @@ __global__ void __launch_bounds__(GT) gadget_w_curve(zk_gadget_args a, void* val
         atomicOr(flag, FLAG_DENOM);
         den = Fr::one();
     }
-    const Fr inv = block_inverse<Fr>(den, lds);
+    const Fr inv = block_inverse(den, lds);
     if (!active) return;
     const uint64_t v = a.var0 + 3 * k;
     st_value<Fr>(values, num_vars, v, x1y2);
@@ -285,11 +286,11 @@ template <class Cv>
 __global__ void __launch_bounds__(GT) gadget_w_fixed_norm(zk_gadget_args a, void* values, uint64_t num_vars, const void* work, uint32_t* flag) {
     typedef typename Cv::Fr Fr;
     constexpr uint32_t M = Cv::FrP::BITS;
-    __shared__ InverseLds<Fr> lds;
+    __shared__ BlockInverseLds<Fr, GT> lds;
     const uint64_t g = (uint64_t)blockIdx.x * GT + threadIdx.x;
     const bool active = g < a.calls * (M + 1);
     const Ext<Fr> p = ld_slot<Fr>(work, g, active, flag);
-    const Fr zi = block_inverse<Fr>(p.Z, lds);
+    const Fr zi = block_inverse(p.Z, lds);
     if (!active) return;
     const uint32_t i = (uint32_t)(g / a.calls);
     const uint64_t k = g - (uint64_t)i * a.calls;
@@ -358,7 +359,7 @@ __global__ void __launch_bounds__(GT) gadget_w_select(zk_gadget_args a, uint32_t
 template <class Cv>
 __global__ void __launch_bounds__(GT) gadget_w_is_zero(zk_gadget_args a, void* values, uint64_t num_vars, uint32_t* flag) {
     typedef typename Cv::Fr Fr;
-    __shared__ InverseLds<Fr> lds;
+    __shared__ BlockInverseLds<Fr, GT> lds;
     const uint64_t k = (uint64_t)blockIdx.x * GT + threadIdx.x;
     const bool active = k < a.calls, eq = a.kind == ZK_GADGET_IS_EQ;
     Fr x = Fr::zero();
@@ -367,7 +368,7 @@ __global__ void __launch_bounds__(GT) gadget_w_is_zero(zk_gadget_args a, void* v
         if (eq) x = Fr::sub(x, ld_input<Fr>(values, a, 1, k, flag));
     }
     const bool is_zero = x.is_zero();                      // a zero enters the block's product as 1; its y is 1 by definition
-    const Fr inv = block_inverse<Fr>(is_zero ? Fr::one() : x, lds);
+    const Fr inv = block_inverse(is_zero ? Fr::one() : x, lds);
     if (!active) return;
     const Fr y = is_zero ? Fr::one() : inv;
     uint64_t v = a.var0 + k * (eq ? 3 : 2);
@@ -427,7 +428,7 @@ template <class Cv>
 __global__ void __launch_bounds__(GT) gadget_w_var_norm(zk_gadget_args a, void* values, uint64_t num_vars, const void* work, uint32_t* flag) {
     typedef typename Cv::Fr Fr;
     constexpr uint32_t M = Cv::FrP::BITS;
-    __shared__ InverseLds<Fr> lds;
+    __shared__ BlockInverseLds<Fr, GT> lds;
     const uint64_t g = (uint64_t)blockIdx.x * GT + threadIdx.x;
     const bool active = g < a.calls * M;
     const uint32_t i = active ? (uint32_t)(g / a.calls) : 0u;
@@ -436,7 +437,7 @@ __global__ void __launch_bounds__(GT) gadget_w_var_norm(zk_gadget_args a, void* 
     const Ext<Fr> p1 = ld_slot<Fr>(work, (uint64_t)(2 * i + 1) * a.calls + k, active, flag);
     const Ext<Fr> p2 = ld_slot<Fr>(work, (uint64_t)(2 * i + 2) * a.calls + k, active, flag);
     const Fr z01 = Fr::mul(p0.Z, p1.Z);
-    const Fr zi = block_inverse<Fr>(Fr::mul(z01, p2.Z), lds);
+    const Fr zi = block_inverse(Fr::mul(z01, p2.Z), lds);
     if (!active) return;
     const Fr i2 = Fr::mul(zi, z01), i1 = Fr::mul(zi, Fr::mul(p0.Z, p2.Z)), i0 = Fr::mul(zi, Fr::mul(p1.Z, p2.Z));
     const Fr rx = Fr::mul(p0.X, i0), ry = Fr::mul(p0.Y, i0), dx = Fr::mul(p1.X, i1), dy = Fr::mul(p1.Y, i1);
@@ -463,7 +464,7 @@ int witness_impl(zk_ctx* c, const zk_gadget_args& a, void* d_values, uint64_t nu
     if (rc) return rc;
     if (a.var0 + a.calls * s.vars > num_vars) return ZK_ERR_BAD_ARG;
     if (s.vars == 0) return ZK_OK;
-    return run_flagged<Cv>(c, gadget_work_bytes(a.kind, M, a.calls), [&](uint32_t* d_flag, void* work) -> int {
+    return run_flagged(c, gadget_work_bytes(a.kind, M, a.calls), [&](uint32_t* d_flag, void* work) -> int {
         // one kernel over `lanes` lanes under its own profile scope
         auto launch = [&](const char* name, auto kernel, uint64_t lanes, auto... args) {
             ProfScope ps(c, name);

@@ -11,6 +11,7 @@
 // Round 0 reads the registered key itself (SRS window-table path); later rounds run the per-window MSM over the folded key.
 #include "api_internal.h"
 #include "g1_host.h"
+#include "block_inverse.cuh"
 #include "fr_io.cuh"
 #include "point_io.cuh"
 
@@ -42,15 +43,13 @@ constexpr uint32_t FOLD_T = 128;   // lanes per block of the key fold = points p
 
 // dst[i] = src[i] + xi * src[i + m] for i < m, affine, internal layout.  dst may alias src (lane i alone reads src[i] and src[i + m]
 // and writes dst[i]).  Per lane: the NAF of xi as doublings and mixed additions of +-src[i + m] on the XYZZ law of ecu.cuh, one mixed
-// addition of src[i]; then the block normalises its 128 results with ONE field inversion (Montgomery's trick: product scans over the
-// ZZZ in LDS, 1/ZZZ_i = prefix_{i-1} * suffix_{i+1} / total).
+// addition of src[i]; then the block normalises its 128 results with ONE field inversion of the ZZZ (block_inverse.cuh) and the
+// law's own normalisation from a known 1/ZZZ (XYZZu::to_affine_given).
 template <class Cv>
 __global__ void __launch_bounds__(FOLD_T) ipa_fold_key(const void* src, void* dst, uint64_t m, Naf nf) {
     typedef typename Cv::FqU F;
     typedef XYZZu<F> P;
-    __shared__ F pre[FOLD_T];
-    __shared__ F suf[FOLD_T];
-    __shared__ F inv_total;
+    __shared__ BlockInverseLds<F, FOLD_T> lds;
     const uint32_t t = threadIdx.x;
     const uint64_t i = (uint64_t)blockIdx.x * FOLD_T + t;
     const bool active = i < m;
@@ -76,24 +75,8 @@ __global__ void __launch_bounds__(FOLD_T) ipa_fold_key(const void* src, void* ds
         if (!kl.is_null()) acc = P::madd(acc, kl);
     }
     const bool fin = active && !acc.is_inf();
-    const F z = fin ? acc.zzz : F::one();
-    // inclusive prefix and suffix products of z over the block (Hillis-Steele, log2(FOLD_T) steps each)
-    F p = z, s = z;
-    pre[t] = p;
-    suf[t] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < FOLD_T; d <<= 1) {
-        const F pl = t >= d ? pre[t - d] : F::one();
-        const F sr = t + d < FOLD_T ? suf[t + d] : F::one();
-        __syncthreads();
-        if (t >= d) p = F::mul(p, pl);
-        if (t + d < FOLD_T) s = F::mul(s, sr);
-        pre[t] = p;
-        suf[t] = s;
-        __syncthreads();
-    }
-    if (t == 0) inv_total = F::inverse(pre[FOLD_T - 1]);
-    __syncthreads();
+    if (!fin) acc.zzz = F::one();                        // a lane with no finite result enters the product as 1
+    const F zi3 = block_inverse(acc.zzz, lds);           // 1 / ZZZ_i
     if (!active) return;
     uint4* out = reinterpret_cast<uint4*>(dst) + i * (2 * Store<F>::U4);
     if (!fin) {
@@ -101,14 +84,10 @@ __global__ void __launch_bounds__(FOLD_T) ipa_fold_key(const void* src, void* ds
         st_fu<F>(out + Store<F>::U4, F::zero());
         return;
     }
-    F zi3 = inv_total;                                   // 1 / ZZZ_i
-    if (t > 0) zi3 = F::mul(zi3, pre[t - 1]);
-    if (t + 1 < FOLD_T) zi3 = F::mul(zi3, suf[t + 1]);
-    const F zi = F::mul(acc.zz, zi3);                    // 1 / Z
-    const F x = F::mul(acc.x, F::sqr(zi));
-    const F y = F::mul(acc.y, zi3);
-    st_fu<F>(out, F::canonical_lt2p(x));
-    st_fu<F>(out + Store<F>::U4, F::canonical_lt2p(y));
+    AffineU<F> a;
+    acc.to_affine_given(zi3, a);
+    st_fu<F>(out, F::canonical_lt2p(a.x));
+    st_fu<F>(out + Store<F>::U4, F::canonical_lt2p(a.y));
 }
 
 constexpr uint32_t SP_T = 256;     // lanes per block of the scalar pass

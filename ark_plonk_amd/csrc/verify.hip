@@ -7,6 +7,7 @@
 // (fields.cuh) and the group law is ecu.cuh's, as in g1_fixed_base: nothing is restated here.  Both exponents -- (q + 1) / 4 and r -- are
 // constants of the curve, so every lane that reaches a loop takes the same branches in it.
 #include "api_internal.h"
+#include "block_inverse.cuh"
 #include "fr_io.cuh"
 
 namespace {
@@ -126,7 +127,7 @@ int decompress_impl(zk_ctx* c, const void* d_in, size_t n, void* d_out_xy, void*
 // ------------------------------------------------------------------------------------------------------------ per-proof scalars
 // One 64-lane workgroup per proof.  The lanes stride over the proof's public inputs (the barycentric sum of proof.rs:635-666), one
 // denominator n (z - w^pos) each, with l_1's denominator n (z - 1) as one more item; a round of 64 items is inverted with ONE field
-// inversion (prefix and suffix products in LDS: the scan of gadget_common.cuh's block_inverse at this workgroup's width).  Lane 0 then
+// inversion (block_inverse.cuh at this workgroup's width, computed in Called<Fr> and stored as Fr).  Lane 0 then
 // evaluates r_0, the widget identities and the permutation and lookup terms and writes the rows.  The arithmetic is the canonical
 // Fr of field.cuh: the quotient's widget functions (quotient.hip) carry the bounds of its lazy reduction in their types and are not
 // reusable at a point, so the formulas stand here a second time, on canonical values.
@@ -192,37 +193,13 @@ struct Called : F {
     __device__ Called operator*(const Called& b) const { return mul(*this, b); }
 };
 
+// the kernel's LDS; 16: 128-bit LDS access
 template <class Fr>
 struct alignas(16) WaveLds {
-    Fr pre[VT], suf[VT], inv_total, sum[VT], l1_inv;
+    BlockInverseLds<Fr, VT> inv;
+    Fr sum[VT], l1_inv;
     uint32_t on_domain;
 };
-// 1 / x for every lane with one inversion; x non-zero in every lane
-template <class Fr, class Stored>
-ZK_D Fr wave_inverse(const Fr& x, WaveLds<Stored>& lds) {
-    const uint32_t t = threadIdx.x;
-    Fr p = x, s = x;
-    lds.pre[t] = p;
-    lds.suf[t] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < VT; d <<= 1) {
-        const Fr pl = t >= d ? Fr(lds.pre[t - d]) : Fr::one();
-        const Fr sr = t + d < VT ? Fr(lds.suf[t + d]) : Fr::one();
-        __syncthreads();
-        if (t >= d) p = Fr::mul(p, pl);
-        if (t + d < VT) s = Fr::mul(s, sr);
-        lds.pre[t] = p;
-        lds.suf[t] = s;
-        __syncthreads();
-    }
-    if (t == 0) lds.inv_total = Fr::inverse(Fr(lds.pre[VT - 1]));
-    __syncthreads();
-    Fr xi = Fr(lds.inv_total);
-    if (t > 0) xi = Fr::mul(xi, Fr(lds.pre[t - 1]));
-    if (t + 1 < VT) xi = Fr::mul(xi, Fr(lds.suf[t + 1]));
-    __syncthreads();                                       // the next round writes pre / suf again
-    return xi;
-}
 
 template <class Fr>
 ZK_D Fr fr_packed(const Packed& p) {
@@ -287,9 +264,10 @@ __global__ void __launch_bounds__(VT) verify_scalars(ScalarArgs A) {
                 den = one;
             }
         }
-        const Fr inv = wave_inverse(den, lds);
+        const Fr inv = block_inverse(den, lds.inv);
         if (k < n_pi) sum = sum + ld_fr<Fr>(A.pi_values, o + k) * wp * inv;
         if (k == n_pi) lds.l1_inv = inv;
+        __syncthreads();                                     // the next round writes lds.inv again
     }
     lds.sum[t] = sum;
     __syncthreads();

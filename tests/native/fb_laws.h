@@ -319,6 +319,16 @@ struct Closure {
         out_affine(a);
         want(X::from_affine(a), e2P);
         end();
+        // the normalisation from a known 1 / ZZZ (the key fold of ipa.hip).  i3 is a product at every call site: a Fermat power, or
+        // the product of one with the prefix and suffix products of block_inverse.cuh
+        begin("to_affine_given");
+        {
+            const F i3 = widen(F::inverse(x2P.zzz), inv_zz());
+            widen(x2P).to_affine_given(i3, a);
+            out_affine(a);
+            want(X::from_affine(a), e2P);
+        }
+        end();
     }
 
     // ---- ecq.cuh: one quad per case, every case of a call in one wave (so every lane runs the P = +-Q path as well), four lanes each

@@ -123,6 +123,30 @@ def test_segments_equal_the_reference_composer_ext(cid, B, ctx):
     assert_equal_ext(cid, dev, ref, values)
 
 
+@pytest.mark.parametrize("cid", [0, 1])
+@pytest.mark.parametrize("B", [1, 255, 256, 257])
+def test_block_inversion_at_the_edges_of_a_workgroup(cid, B, ctx):
+    """is_zero_with_output and point_addition_gate share one field inversion per 256-lane workgroup (csrc/block_inverse.cuh): one call,
+    one call short of a workgroup, a whole one, one call into the second.  is_zero's zeros -- which enter the workgroup's product as 1
+    -- stand at lanes 0, 255 and 256.  Description and values equal the sequential composer's exactly."""
+    p, ca, cd, G = setup(cid)
+    rng = random.Random(700 * cid + B)
+    dev, ref = new_pair(cid, ctx)
+    xs = zero_edges(p, rng, B)
+    pool = [cr.te_mul(p, ca, cd, rng.randrange(1, 1 << 16), G) for _ in range(16)]
+    pts = [[pool[rng.randrange(16)] for _ in range(B)] for _ in range(2)]
+    cols = [xs, [q[0] for q in pts[0]], [q[1] for q in pts[0]], [q[0] for q in pts[1]], [q[1] for q in pts[1]]]
+    h = [dev.inputs(B) for _ in cols]
+    rh = [[ref.add_input(v) for v in col] for col in cols]
+    b, rb = dev.is_zero_with_output(h[0]), [ref.is_zero_with_output(rh[0][k]) for k in range(B)]
+    assert b.cpu().tolist() == rb
+    s = dev.point_addition_gate((h[1], h[2]), (h[3], h[4]))
+    rs = [ref.point_addition_gate((rh[1][k], rh[2][k]), (rh[3][k], rh[4][k])) for k in range(B)]
+    assert s[0].cpu().tolist() == [q[0] for q in rs] and s[1].cpu().tolist() == [q[1] for q in rs]
+    values, _ = assign(cid, dev, cols)
+    assert_equal_ext(cid, dev, ref, values)
+
+
 # ---- 2. variable-base scalar multiplication
 def var_base_points(cid):
     p, ca, cd, G = setup(cid)

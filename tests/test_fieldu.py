@@ -357,7 +357,7 @@ SINGLE_LANE_CASES = ["setup", "from_affine", "dbl_affine", "dbl/infinity", "dbl/
                      "madd/p infinite", "madd/P = Q", "madd/P = -Q", "madd/general",
                      "madd_begin + madd_finish/general", "madd_begin + madd_finish/P = Q", "madd_begin + madd_finish/P = -Q",
                      "add/p infinite", "add/q infinite", "add/P = Q", "add/P = -Q", "add/general", "neg",
-                     "to_affine/infinity", "to_affine/general"]
+                     "to_affine/infinity", "to_affine/general", "to_affine_given"]
 # every lane of a quad runs every instruction; the four roles are checked in each case.  "qadd alone" is a wave in which no quad
 # has P = +-Q, so the branch around the quad doubling is not taken; in "qadd" all cases share one wave and every lane takes it
 QUAD_CASES = ["setup", "qadd/inputs", "qadd/general", "qadd/P = Q", "qadd/P = -Q", "qadd/p infinite", "qadd/q infinite", "qadd/both infinite",

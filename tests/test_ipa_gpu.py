@@ -108,6 +108,51 @@ def test_fold_key_matches_the_group_law_incl_edge_cases(ctx, cid):
             assert gi[i] == 0 and zk.curves.fq_from_mont(cid, got[i].reshape(2, L)) == [P[0], P[1]], (m, xi, i)
 
 
+@pytest.mark.parametrize("m", [1, 127, 128, 129])
+@pytest.mark.parametrize("cid", [0, 1])
+def test_fold_key_at_the_edges_of_a_workgroup(ctx, cid, m):
+    """The key fold normalises 128 results with one inversion (block_inverse.cuh); a lane with no finite result enters the products
+    as 1.  Half-lengths around the workgroup: one lane, one lane short of a workgroup, a whole one, one lane into the second.  The
+    three kinds of special lane -- a result at infinity (k_l = -xi k_r), a null k_r, a null k_l -- stand at lane 0, at the last active
+    lane and in the middle (m = 1: one fold per kind), the rest are random; every lane against the oracle's group law, bit for bit."""
+    import torch
+    import ark_plonk_amd as zk
+    from ark_plonk_amd import _lib
+    cv = CURVES[cid]
+    r = cv.r
+    L = zk.get_curve(cid).fq_limbs
+    xi = rand_logs(cv, 1, 40 + m)[0]
+    kinds = ("infinity", "null k_r", "null k_l")
+    places = [{0: k} for k in kinds] if m == 1 else [{0: "infinity", m - 1: "null k_r", m // 2: "null k_l", 1: "null k_r", m - 2: "infinity"}]
+    for place in places:
+        kr = rand_logs(cv, m, 50 + m)
+        kl = rand_logs(cv, m, 60 + m)
+        for i, kind in place.items():
+            if kind == "infinity":
+                kl[i] = (-xi * kr[i]) % r
+            elif kind == "null k_r":
+                kr[i] = 0
+            else:
+                kl[i] = 0
+        key = points_of(ctx, cid, kl + kr)
+        inf = torch.zeros(2 * m, dtype=torch.uint8, device="cuda")
+        out = torch.zeros((m, 2 * L), dtype=torch.int64, device="cuda")
+        oinf = torch.zeros(m, dtype=torch.uint8, device="cuda")
+        xm = zk.curves.fr_to_mont(cid, [xi])
+        _lib.check(_lib.lib().zk_ipa_fold_key_dev(ctx.handle, cid, m, key.data_ptr(), inf.data_ptr(), xm.ctypes.data, out.data_ptr(),
+                                                  oinf.data_ptr()))
+        got = out.cpu().numpy().view(np.uint64)
+        gi = oinf.cpu().numpy()
+        for i in range(m):
+            e = (kl[i] + xi * kr[i]) % r
+            assert (e == 0) == (place.get(i) == "infinity"), (m, i)
+            if e == 0:
+                assert gi[i] == 1, (m, i, place)
+                continue
+            P = bo.ec_mul(cv, e, (cv.gx, cv.gy))
+            assert gi[i] == 0 and zk.curves.fq_from_mont(cid, got[i].reshape(2, L)) == [P[0], P[1]], (m, i, place.get(i))
+
+
 @pytest.mark.parametrize("digest", ["blake2b", "blake2s"])
 @pytest.mark.parametrize("cid", [0, 1])
 @pytest.mark.parametrize("log_d1", range(1, 13))

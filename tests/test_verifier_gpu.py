@@ -235,12 +235,12 @@ def tamper_case(ctx, oracle_cpu):
     return real
 
 
-PI_LOG_N, PI_COUNTS = 8, (0, 1, 2, 65)
+PI_LOG_N, PI_COUNTS = 8, (0, 1, 2, 65, 62, 63, 64)
 
 
 def pi_case(ctx, oracle_cpu):
-    """One circuit with 65 public-input rows -- rows 0 and n - 1 among them -- and four proofs of it whose public inputs are non-zero
-    at 0, 1, 2 and 65 of those rows (a zero value is no entry of the reference's map).  build_circuit's circuit with its own public
+    """One circuit with 65 public-input rows -- rows 0 and n - 1 among them -- and proofs of it whose public inputs are non-zero at 0, 1, 2
+    and 65 of those rows (the first four proofs), then at 62, 63 and 64 (a zero value is no entry of the reference's map).  build_circuit's circuit with its own public
     inputs taken out; the output wire c is in no copy constraint, so adding a public value to an arithmetic row only moves its c."""
     cid, log_n = 0, PI_LOG_N
     cv = bo.CURVES[cid]
@@ -298,6 +298,25 @@ def test_scalar_rows_match_the_expanded_oracle(which, B, reals):
         assert sorted({len(real.proofs[k][1]) for k in ks}) == sorted(set(PI_COUNTS[(j + 3) % 4] for j in range(B)))
         n = 1 << real.log_n
         assert all(0 in real.proofs[k][1] for k in (1, 2, 3)) and all(n - 1 in real.proofs[k][1] for k in (2, 3))
+
+
+def test_scalar_rows_at_the_edges_of_an_inversion_round(reals):
+    """verify_scalars inverts a proof's n_pi + 1 denominators in rounds of 64 with one inversion each (csrc/block_inverse.cuh): 0, 62 and
+    63 public inputs are one round (63: every lane has an item), 64 and 65 go through the loop a second time and write the same LDS
+    again.  One batch that mixes the counts, each of them twice; every row against the expanded oracle, exactly."""
+    import torch
+    real = reals["pi"]
+    counts = (0, 62, 63, 64, 65, 64, 0, 65, 63, 62)
+    ks = [PI_COUNTS.index(c) for c in counts]
+    assert [len(real.proofs[k][1]) for k in ks] == list(counts)
+    ws = weights_for(len(ks), 77)
+    st = real.bv.prepare([real.proofs[k][0] for k in ks], [real.pi(real.proofs[k][1]) for k in ks], ws)
+    torch.cuda.synchronize()
+    assert not st.any()
+    key, prf, opn = (limbs_to_ints(t.cpu().numpy().view(np.uint64).reshape(-1, 4)) for t in real.bv.rows())
+    for j, (k, (u, v)) in enumerate(zip(ks, ws)):
+        wk, wp, wo_ = real.rows(k, u, v)
+        assert (key[20 * j:20 * j + 20], prf[15 * j:15 * j + 15], opn[2 * j:2 * j + 2]) == (wk, wp, wo_), (j, counts[j])
 
 
 def test_a_challenge_on_the_domain_is_a_status(reals, ctx):
