@@ -26,8 +26,13 @@
 #pragma once
 #include "field_common.cuh"
 
-template <class P>
+// Fs<P> is the field every kernel and the host use.  Fs<P, true> is the same field, limb for limb and value for value, whose mul / sqr /
+// dot2 are the chained products (mul_chain ...): the bucket accumulation (msm_accumulate.hip) instantiates its two kernels over it and
+// nothing else does.  In the kernels that run the general doubling and addition in a loop (g1_fixed_base, ipa_fold_key, g1_decompress,
+// msm_win_finish) the chained products spill registers; the plain ones do not (profiles/field_chains/notes.md section 4).
+template <class P, bool CHAIN = false>
 struct Fs {
+    typedef P Params;
     static constexpr int NL = P::NL;
     static constexpr int SAT = P::SAT_WORDS;
     static constexpr uint32_t M = (1u << 30) - 1u;
@@ -35,17 +40,48 @@ struct Fs {
     uint32_t v[NL];
 
     ZK_HD static int32_t sx(uint32_t x) { return (int32_t)(x << 2) >> 2; }   // low 30 bits, sign-extended
-    // The bias 2^29 that starts every high-half column.  On the device it is hidden from the optimiser in a scalar register
-    // pair (an empty asm): as a visible constant it is moved to the end of the column's sum and costs a 64-bit add per
-    // column; as a variable it can be the addend of the column's first multiply-add, whose addend slot is otherwise 0
-    // (the compiler takes that form in about half of the columns; fencing the first partial sum to force it everywhere
-    // cost more registers than it saved instructions).
+    // link(): one step of a column's chain in the chained products (see mul_chain).  On the device the partial sum is handed to an empty asm as an INPUT, which gives
+    // it a second use: the optimiser re-associates a sum only through values used once, so every column stays ONE v_mad_i64_i32 chain
+    // that starts from the carry of the column below.  Left alone, the optimiser forms the a*b products of a column as a chain of
+    // their own and merges it with the carry and the m*p chain afterwards: two v_lshl_add_u64 per column.  The asm defines no
+    // register on purpose: the partial sum passed through an asm OUTPUT (the form of Fu::mul_fenced) costs an s_nop in front of its
+    // consumer, because the compiler's hazard rules assume that an asm's result is forwarded (profiles/field_chains/notes.md §2).
+    ZK_HD static int64_t link(int64_t t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : : "v"(t));
+#endif
+        return t;
+    }
+    // a value the optimiser knows nothing about (no known bits): an empty asm, no instruction
+    ZK_HD static uint32_t opaque(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("" : "+v"(x));
+#endif
+        return x;
+    }
+    // The bias 2^29 of the high-half columns, once per product.  On the device it is hidden from the optimiser in a scalar register
+    // pair (an empty asm).  Plain products: it starts the column, and as a variable it can be the addend of the column's first
+    // multiply-add (as a visible constant it is moved to the end of the sum and costs a 64-bit add per column).  Chained products: it
+    // is added last, and as a visible constant it would be folded with the column's shift and mask at the price of multiply-adds
+    // (profiles/field_chains/notes.md section 2).
     ZK_HD static int64_t column_bias() {
         int64_t h = H;
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" : "+s"(h));
 #endif
         return h;
+    }
+    // the end of a low-half column: the balanced quotient digit m_k makes the column a multiple of 2^30; returns the carry (exact shift)
+    ZK_HD static int64_t finish_low(int64_t t, int32_t& mk) {
+        mk = (int32_t)((uint32_t)t * (P::PINV << 2)) >> 2;      // (t * PINV mod 2^30), sign-extended: the shift rides in the constant
+        return (t + (int64_t)mk * P::MOD(0)) >> 30;
+    }
+    // the end of a high-half column, three instructions: the balanced digit is the sign-extended low 30 bits of the column sum t (one
+    // v_bfe_i32), and its carry (t - digit) / 2^30 is the floor shift of t + 2^29.  The digit is made opaque: a consumer that knows
+    // it to be a sign extension is compiled to unsigned multiply-adds with corrections.
+    ZK_HD static int64_t finish_high(int64_t t, int64_t hb, uint32_t& digit) {
+        digit = opaque((uint32_t)sx((uint32_t)t));
+        return (t + hb) >> 30;
     }
 
     ZK_HD static Fs zero() {
@@ -154,6 +190,7 @@ struct Fs {
     // High half: the column starts from the bias 2^29, so the floor shift is the carry of the BALANCED digit
     // (t + 2^29) mod 2^30 - 2^29.
     ZK_HD static Fs mul(const Fs& a, const Fs& b) {
+        if constexpr (CHAIN) return mul_chain(a, b);
         int32_t m[NL];
         Fs r;
         int64_t carry = 0;
@@ -185,6 +222,39 @@ struct Fs {
             const int64_t t = a0 + a1 + am + carry;
             r.v[k - NL] = ((uint32_t)t & M) - (uint32_t)H;
             carry = t >> 30;
+        }
+        r.v[NL - 1] = (uint32_t)carry;
+        return r;
+    }
+    // The chained product (what mul is in Fs<P, true>): ONE signed 64-bit accumulator per column, no partial sums to merge.  A column's chain starts from
+    // the carry of the column below plus the column's first product and takes every further a*b product and every m*p product in
+    // turn (link); column 0 has no carry.  The sum of a column is the integer it always was -- the same terms of one 64-bit sum in
+    // another order -- so the column bounds that tools/gen_constants.py and tests/test_fieldu.py check hold unchanged, and the host
+    // compile (link, opaque and column_bias do nothing there) computes the same values as the device.
+    // Low half: finish_low.  High half: finish_high.
+    ZK_HD static Fs mul_chain(const Fs& a, const Fs& b) {
+        int32_t m[NL];
+        Fs r;
+        int64_t carry = 0;
+        const int64_t hb = column_bias();
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            int64_t t = (int64_t)(int32_t)a.v[0] * (int32_t)b.v[k];
+            if (k) t = link(carry + t);
+#pragma unroll
+            for (int i = 1; i <= k; ++i) t = link(t + (int64_t)(int32_t)a.v[i] * (int32_t)b.v[k - i]);
+#pragma unroll
+            for (int i = 0; i < k; ++i) t = link(t + (int64_t)m[i] * P::MOD(k - i));
+            carry = finish_low(t, m[k]);
+        }
+#pragma unroll
+        for (int k = NL; k < 2 * NL - 1; ++k) {
+            int64_t t = link(carry + (int64_t)(int32_t)a.v[k - NL + 1] * (int32_t)b.v[NL - 1]);
+#pragma unroll
+            for (int i = k - NL + 2; i < NL; ++i) t = link(t + (int64_t)(int32_t)a.v[i] * (int32_t)b.v[k - i]);
+#pragma unroll
+            for (int i = k - NL + 1; i < NL; ++i) t = link(t + (int64_t)m[i] * P::MOD(k - i));
+            carry = finish_high(t, hb, r.v[k - NL]);
         }
         r.v[NL - 1] = (uint32_t)carry;
         return r;
@@ -193,6 +263,7 @@ struct Fs {
     // result is below (|a||b| + |c||d|)/R' + p/2 in magnitude: inside (-p, p) up to 256 p^2 at the R' >= 512 p every modulus has, and
     // up to the whole 288 p^2 at R' >= 576 p, which both moduli in use have (gen_constants.py asserts either); always in (-2p, 2p).
     ZK_HD static Fs dot2(const Fs& a, const Fs& b, const Fs& c, const Fs& d) {
+        if constexpr (CHAIN) return dot2_chain(a, b, c, d);
         int32_t m[NL];
         Fs r;
         int64_t carry = 0;
@@ -228,8 +299,44 @@ struct Fs {
         r.v[NL - 1] = (uint32_t)carry;
         return r;
     }
+    // chained: both products of a column's first index open its chain
+    ZK_HD static Fs dot2_chain(const Fs& a, const Fs& b, const Fs& c, const Fs& d) {
+        int32_t m[NL];
+        Fs r;
+        int64_t carry = 0;
+        const int64_t hb = column_bias();
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            int64_t t = (int64_t)(int32_t)a.v[0] * (int32_t)b.v[k] + (int64_t)(int32_t)c.v[0] * (int32_t)d.v[k];
+            if (k) t = link(carry + t);
+#pragma unroll
+            for (int i = 1; i <= k; ++i) {
+                t = link(t + (int64_t)(int32_t)a.v[i] * (int32_t)b.v[k - i]);
+                t = link(t + (int64_t)(int32_t)c.v[i] * (int32_t)d.v[k - i]);
+            }
+#pragma unroll
+            for (int i = 0; i < k; ++i) t = link(t + (int64_t)m[i] * P::MOD(k - i));
+            carry = finish_low(t, m[k]);
+        }
+#pragma unroll
+        for (int k = NL; k < 2 * NL - 1; ++k) {
+            int64_t t = link(carry + (int64_t)(int32_t)a.v[k - NL + 1] * (int32_t)b.v[NL - 1]
+                                      + (int64_t)(int32_t)c.v[k - NL + 1] * (int32_t)d.v[NL - 1]);
+#pragma unroll
+            for (int i = k - NL + 2; i < NL; ++i) {
+                t = link(t + (int64_t)(int32_t)a.v[i] * (int32_t)b.v[k - i]);
+                t = link(t + (int64_t)(int32_t)c.v[i] * (int32_t)d.v[k - i]);
+            }
+#pragma unroll
+            for (int i = k - NL + 1; i < NL; ++i) t = link(t + (int64_t)m[i] * P::MOD(k - i));
+            carry = finish_high(t, hb, r.v[k - NL]);
+        }
+        r.v[NL - 1] = (uint32_t)carry;
+        return r;
+    }
     // a*a/R': cross products once, against doubled limbs (|2 a_i| <= 2^30 + 4: the column bound is the one of mul)
     ZK_HD static Fs sqr(const Fs& a) {
+        if constexpr (CHAIN) return sqr_chain(a);
         int32_t m[NL], a2[NL];
         Fs r;
 #pragma unroll
@@ -260,6 +367,39 @@ struct Fs {
             const int64_t t = aa + am + carry;
             r.v[k - NL] = ((uint32_t)t & M) - (uint32_t)H;
             carry = t >> 30;
+        }
+        r.v[NL - 1] = (uint32_t)carry;
+        return r;
+    }
+    // chained: a column's chain opens with its first cross product, or with the square term where it has no cross product (columns 0
+    // and 2 NL - 2)
+    ZK_HD static Fs sqr_chain(const Fs& a) {
+        int32_t m[NL], a2[NL];
+        Fs r;
+#pragma unroll
+        for (int i = 0; i < NL; ++i) a2[i] = (int32_t)(a.v[i] << 1);
+        int64_t carry = 0;
+        const int64_t hb = column_bias();
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            int64_t t = k ? link(carry + (int64_t)a2[0] * (int32_t)a.v[k]) : (int64_t)(int32_t)a.v[0] * (int32_t)a.v[0];
+#pragma unroll
+            for (int i = 1; 2 * i < k; ++i) t = link(t + (int64_t)a2[i] * (int32_t)a.v[k - i]);
+            if (k && (k & 1) == 0) t = link(t + (int64_t)(int32_t)a.v[k / 2] * (int32_t)a.v[k / 2]);
+#pragma unroll
+            for (int i = 0; i < k; ++i) t = link(t + (int64_t)m[i] * P::MOD(k - i));
+            carry = finish_low(t, m[k]);
+        }
+#pragma unroll
+        for (int k = NL; k < 2 * NL - 1; ++k) {
+            const int lo = k - NL + 1;
+            int64_t t = link(carry + (2 * lo < k ? (int64_t)a2[lo] * (int32_t)a.v[k - lo] : (int64_t)(int32_t)a.v[lo] * (int32_t)a.v[lo]));
+#pragma unroll
+            for (int i = lo + 1; 2 * i < k; ++i) t = link(t + (int64_t)a2[i] * (int32_t)a.v[k - i]);
+            if (2 * lo < k && (k & 1) == 0) t = link(t + (int64_t)(int32_t)a.v[k / 2] * (int32_t)a.v[k / 2]);
+#pragma unroll
+            for (int i = lo; i < NL; ++i) t = link(t + (int64_t)m[i] * P::MOD(k - i));
+            carry = finish_high(t, hb, r.v[k - NL]);
         }
         r.v[NL - 1] = (uint32_t)carry;
         return r;

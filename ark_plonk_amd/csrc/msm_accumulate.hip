@@ -305,7 +305,7 @@ int msm_precompute_run(zk_ctx* c, zk_srs* s, uint32_t window_bits, uint32_t w0, 
 // per-window path: one launch over the W windows' lists, CHUNK_L references per lane
 template <class Cv>
 int pw_queue_accumulate(zk_ctx* c, const MsmGeom& g, MsmBufs& mb, const void* d_bases, uint32_t n_lanes, hipStream_t st) {
-    typedef typename Cv::FqU F;
+    typedef Fs<typename Cv::FqU::Params, true> F;       // the accumulation runs the chained products (fields.cuh): same limbs, same values
     ProfScope ps(c, "msm_accumulate", st);
     const int T = 128;
     unsigned blocks = (n_lanes + T - 1) / T;
@@ -319,7 +319,7 @@ int pw_queue_accumulate(zk_ctx* c, const MsmGeom& g, MsmBufs& mb, const void* d_
 template <class Cv>
 int pre_queue_accumulate(zk_ctx* c, const PrePlan* pls, MsmBufs* const* mbs, const size_t* lens, const size_t* tab_offs, uint32_t n_jobs, zk_srs* s,
                          hipStream_t st) {
-    typedef typename Cv::FqU F;
+    typedef Fs<typename Cv::FqU::Params, true> F;       // as in pw_queue_accumulate
     if (n_jobs == 0) return ZK_OK;
     if (n_jobs > (uint32_t)MAX_JOBS) return ZK_ERR_UNSUPPORTED;
     ProfScope ps(c, "msm_accumulate", st);
