@@ -24,7 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 FIELD_HDRS = ["field_common.cuh", "field.cuh", "fieldu.cuh", "fields.cuh", "curve_params.h", "zk_common.h"]
 HOST_HDRS = FIELD_HDRS + ["ecu.cuh", "ctx.h", "g1_host.h", "../../include/ark_plonk_amd.h"]
 API_HDRS = HOST_HDRS + ["api_internal.h"]
-# helpers with one definition each: Fr / 32-byte element access; the quotient's bounded lazy arithmetic; the MSM's point storage
+# helpers with one definition each: Fr / 32-byte element access; bounded lazy arithmetic on the 29-bit Fr type; the MSM's point storage
 FR_IO, ZBOUND, POINT_IO = ["fr_io.cuh"], ["fr_io.cuh", "zbound.cuh"], ["point_io.cuh"]
 GADGET = ["gadget_common.cuh"]            # what the two units of the device composer (layout, witness) share
 BLOCK_INV = ["block_inverse.cuh"]         # one field inversion per workgroup: the key fold, the gadget witnesses, the verifier's scalars
@@ -38,8 +38,8 @@ def jobs():
     out = [(f"{u}.o", f"{u}.hip", [], API_HDRS) for u in API_UNITS] + [
         ("hostio.o", "hostio.hip", [], HOST_HDRS),
         ("wire.o", "wire.hip", [], HOST_HDRS),
-        ("kzg.o", "kzg.hip", [], HOST_HDRS + FR_IO),
-        ("lookup.o", "lookup.hip", [], HOST_HDRS + FR_IO),
+        ("kzg.o", "kzg.hip", [], HOST_HDRS + ZBOUND),
+        ("lookup.o", "lookup.hip", [], HOST_HDRS + ZBOUND),
         ("grand_product.o", "grand_product.hip", [], HOST_HDRS + FR_IO),
         ("quotient.o", "quotient.hip", [], HOST_HDRS + ZBOUND),
         ("quadtest.o", "quadtest.hip", [], HOST_HDRS + ["ecq.cuh"]),

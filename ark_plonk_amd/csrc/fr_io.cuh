@@ -1,7 +1,9 @@
 // Loads / stores of scalar-field elements, defined once for every unit that is free to include it:
 // the 32-byte element as the 8 x 32-bit-word type of field.cuh (ld_fr / st_fr) and as an opaque value (El: equality, zero test,
-// hash mix), and for the kernels that work on the 29-bit-limb Fr type (kzg.hip, lookup.hip): 32-byte arkworks elements <-> limbs
-// with no domain change, lazily reduced limb vectors (48 bytes), and the kernel-argument form of a constant multiplier.
+// hash mix), and for the kernels that work on the 29-bit-limb Fr type: 32-byte arkworks elements <-> limbs with no domain change,
+// lazily reduced limb vectors (48 bytes), and the kernel-argument form of a constant multiplier -- untyped here; kzg.hip and
+// lookup.hip reach them through the typed forms of zbound.cuh.  Host side: the one conversion x R -> x R' behind every such
+// multiplier (and behind the NTT's tables), and the "is a reduced field element" test of the ABI's scalar arguments.
 #pragma once
 #include "zk_common.h"
 
@@ -109,5 +111,28 @@ ZK_D void st_l(void* base, uint64_t idx, const FU& x) {
 }
 template <class FU>
 ZK_D FU unpack(const Packed& p) { return FU::split_words(p.w); }
+
+// ---- host side: the arguments of those kernels
+// x R (arkworks form, R = 2^256) -> x R' mod r, R' = 2^261 the radix of the 29-bit-limb type: five modular doublings, canonical.
+// to_rprime(Fr::one()) is R' mod r itself, the plain integer whose Montgomery product with x R is the same value (ntt.hip's tables).
+template <class Fr>
+Fr to_rprime(const Fr& v) {
+    Fr t = v;
+    for (int k = 0; k < 5; ++k) t = Fr::add(t, t);
+    return t;
+}
+template <class Fr>
+Packed pack_rp(const Fr& v) {                   // the kernel-argument form of the multiplier v
+    Packed p;
+    const Fr t = to_rprime(v);
+    memcpy(p.w, t.v, 32);
+    return p;
+}
+// the 4 x 64-bit words of an ABI argument as a field element; false when they are not a reduced one (the caller's ZK_ERR_BAD_ARG)
+template <class Fr>
+bool fr_reduced(const uint64_t* m, Fr& out) {
+    memcpy(out.v, m, 32);
+    return Fr::reduce_once(out) == out;
+}
 
 }  // namespace

@@ -221,12 +221,6 @@ inline Layout layout(int curve, size_t d1) {
     return l;
 }
 
-template <class Fr>
-bool fr_reduced(const uint64_t* m, Fr& out) {
-    memcpy(out.v, m, 32);
-    return Fr::reduce_once(out) == out;
-}
-
 // the NAF of a canonical scalar (8 little-endian 32-bit words)
 inline Naf make_naf(const uint32_t* k8) {
     Naf nf;

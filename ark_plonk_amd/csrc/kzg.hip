@@ -13,12 +13,13 @@
 // -> per-chunk replay), 3 field multiplications per coefficient, output already in canonical
 // (into_repr) form for the opening MSM.
 #include "ctx.h"
-#include "fr_io.cuh"
+#include "zbound.cuh"
 
-// Arithmetic: the 29-bit-limb Montgomery type of fieldu.cuh (as in the NTT).  Data stay in the arkworks
+// Arithmetic: the 29-bit-limb Montgomery type of fieldu.cuh (as in the NTT), lazily reduced, with the bound carried in the type
+// (zbound.cuh: Z<FU, B> is below B / 10 r, and a formula that could overflow does not compile).  Data stay in the arkworks
 // Montgomery domain (R = 2^256): every constant multiplier (chi^k, z, z^CHUNK and the running powers of the
 // scan) is held in the R' = 2^261 form, so data * multiplier / R' keeps the factor R; chunk sums and chunk
-// carries are kept as lazily reduced limb vectors (48 B) between the phases.
+// carries are kept as lazily reduced limb vectors (48 B) between the phases, each buffer under one named type.
 
 namespace {
 
@@ -35,27 +36,37 @@ template <class FU>
 __global__ void kzg_rlc(RlcArgs a, uint64_t m, void* comb) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    FU acc = FU::zero();                     // <= 32 terms < 2r each
+    typedef ZRun<FU, 0, 20, MAX_POLYS> Sum;   // n_polys <= MAX_POLYS products: poly_lincomb and open_prepare refuse more
+    typename Sum::T acc(FU::zero());
     for (uint32_t k = 0; k < a.n_polys; ++k) {
-        if (i < a.len[k]) acc = FU::add(acc, FU::mul(ld_u<FU>(a.poly[k], i), unpack<FU>(a.chi_pow[k])));
+        if (i < a.len[k]) acc = Sum::step(acc, ld_c<FU>(a.poly[k], i) * unpack_c<FU>(a.chi_pow[k]));
     }
-    st_u<FU>(comb, i, FU::mul(acc, FU::one()));   // * 1 (R' form): back under 2r
+    st_c<FU>(comb, i, acc * z_one<FU>());
 }
 
 constexpr uint32_t CHUNK = 64;       // coefficients per lane in phases 1 and 3
 constexpr uint32_t SCAN_T = 1024;    // lanes of the single scan workgroup
+constexpr int SCAN_STEPS = 10;       // Hillis-Steele steps over them
+static_assert(1u << SCAN_STEPS == SCAN_T, "the scan's step count is log2 of its lanes");
 
-// phase 1: H[t] = sum_{j < CHUNK} c[t*CHUNK + j] z^j          (lazy, < 3r)
+// the 48-byte buffers between the phases: what the writer stores and the reader loads
+template <class FU> using ChunkSum = Z<FU, 30>;     // H: a Horner value c + acc * z
+template <class FU> using LaneSum = Z<FU, 50>;      // HQ, even entries: a Horner value over chunk sums, H + h * zk
+template <class FU> using LanePow = Z<FU, 20>;      // HQ, odd entries: a product of multipliers
+template <class FU> using ScanRun = ZRun<FU, 50, 20, SCAN_STEPS>;      // a lane sum after up to SCAN_STEPS steps of h + q * h'
+template <class FU> using Carry = typename ScanRun<FU>::T;           // the scan's carries and A, the value entering a chunk
+
+// phase 1: H[t] = sum_{j < CHUNK} c[t*CHUNK + j] z^j
 template <class FU>
 __global__ void kzg_chunk_horner(const void* comb, uint64_t m, Packed zp, void* H, uint64_t n_chunks) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_chunks) return;
-    const FU z = unpack<FU>(zp);
+    const Z<FU, 10> z = unpack_c<FU>(zp);
     const uint64_t lo = t * CHUNK;
     const uint64_t hi = lo + CHUNK < m ? lo + CHUNK : m;
-    FU acc = FU::zero();
-    for (uint64_t j = hi; j-- > lo;) acc = FU::add(ld_u<FU>(comb, j), FU::mul(acc, z));
-    st_l<FU>(H, t, acc);
+    ChunkSum<FU> acc(FU::zero());
+    for (uint64_t j = hi; j-- > lo;) acc = ld_c<FU>(comb, j) + acc * z;
+    st_z<ChunkSum<FU>>(H, t, acc);
 }
 
 // phase 2: A[t] = sum_{t' > t} H[t'] (z^CHUNK)^(t'-t-1), the value flowing into chunk t.  SCAN_T lanes own n_chunks / SCAN_T
@@ -73,53 +84,56 @@ ZK_D void scan_range(uint32_t u, uint64_t n_chunks, uint64_t& lo, uint64_t& hi) 
 template <class FU>
 __global__ void __launch_bounds__(64) kzg_scan_local(const void* H, uint64_t n_chunks, Packed zkp /* z^CHUNK, R' form */, void* HQ) {
     const uint32_t u = blockIdx.x * 64 + threadIdx.x;
-    const FU zk = unpack<FU>(zkp);
+    const Z<FU, 10> zk = unpack_c<FU>(zkp);
     uint64_t lo, hi;
     scan_range<FU>(u, n_chunks, lo, hi);
-    // local: h = sum_{t in [lo,hi)} H[t] zk^(t-lo) (data, < 5r),  q = zk^(hi-lo) (multiplier, R' form, < 2r)
-    FU h = FU::zero(), q = FU::one();
+    // local: h = sum_{t in [lo,hi)} H[t] zk^(t-lo) (data),  q = zk^(hi-lo) (multiplier, R' form)
+    LaneSum<FU> h(FU::zero());
+    LanePow<FU> q = z_one<FU>();
     for (uint64_t t = hi; t-- > lo;) {
-        h = FU::add(ld_l<FU>(H, t), FU::mul(h, zk));
-        q = FU::mul(q, zk);
+        h = ld_z<ChunkSum<FU>>(H, t) + h * zk;
+        q = q * zk;
     }
-    st_l<FU>(HQ, 2 * u, h);
-    st_l<FU>(HQ, 2 * u + 1, q);
+    st_z<LaneSum<FU>>(HQ, 2 * u, h);
+    st_z<LanePow<FU>>(HQ, 2 * u + 1, q);
 }
 template <class FU>
 __global__ void __launch_bounds__(SCAN_T) kzg_scan_cross(const void* HQ, void* carry_out) {
     extern __shared__ uint4 sh[];          // (h, q) per lane: 2 x 48 B
     const uint32_t u = threadIdx.x;
-    FU h = ld_l<FU>(HQ, 2 * u), q = ld_l<FU>(HQ, 2 * u + 1);
-    // exclusive suffix scan of (h, q) with (h1,q1) o (h2,q2) = (h1 + q1 h2, q1 q2): Hillis-Steele.
-    // h grows by < 2r per step (< 25r after 10 steps); q1 * h2 < 2r * 25r stays inside the product's range.
+    Carry<FU> h = ld_z<LaneSum<FU>>(HQ, 2 * u);
+    LanePow<FU> q = ld_z<LanePow<FU>>(HQ, 2 * u + 1);
+    // exclusive suffix scan of (h, q) with (h1,q1) o (h2,q2) = (h1 + q1 h2, q1 q2): Hillis-Steele.  Every step adds one product to
+    // h: h has the bound after the last of the SCAN_STEPS steps throughout, and q1 * h2 is checked against that.
     for (uint32_t d = 1; d < SCAN_T; d <<= 1) {
-        st_l<FU>(sh, 2 * u, h);
-        st_l<FU>(sh, 2 * u + 1, q);
+        st_z<Carry<FU>>(sh, 2 * u, h);
+        st_z<LanePow<FU>>(sh, 2 * u + 1, q);
         __syncthreads();
         if (u + d < SCAN_T) {
-            const FU oh = ld_l<FU>(sh, 2 * (u + d)), oq = ld_l<FU>(sh, 2 * (u + d) + 1);
-            h = FU::add(h, FU::mul(q, oh));
-            q = FU::mul(q, oq);
+            const Carry<FU> oh = ld_z<Carry<FU>>(sh, 2 * (u + d));
+            const LanePow<FU> oq = ld_z<LanePow<FU>>(sh, 2 * (u + d) + 1);
+            h = ScanRun<FU>::step(h, q * oh);
+            q = q * oq;
         }
         __syncthreads();
     }
     // h = inclusive suffix value starting at this lane's first chunk; the value entering the lane
     // from above is the inclusive value of lane u+1
-    st_l<FU>(sh, 2 * u, h);
+    st_z<Carry<FU>>(sh, 2 * u, h);
     __syncthreads();
-    st_l<FU>(carry_out, u, (u + 1 < SCAN_T) ? ld_l<FU>(sh, 2 * (u + 1)) : FU::zero());
+    st_z<Carry<FU>>(carry_out, u, (u + 1 < SCAN_T) ? ld_z<Carry<FU>>(sh, 2 * (u + 1)) : Carry<FU>(FU::zero()));
 }
 template <class FU>
 __global__ void __launch_bounds__(64) kzg_scan_replay(const void* H, uint64_t n_chunks, Packed zkp, const void* carry_in, void* A) {
     const uint32_t u = blockIdx.x * 64 + threadIdx.x;
-    const FU zk = unpack<FU>(zkp);
+    const Z<FU, 10> zk = unpack_c<FU>(zkp);
     uint64_t lo, hi;
     scan_range<FU>(u, n_chunks, lo, hi);
-    FU carry = ld_l<FU>(carry_in, u);
-    // replay the lane's chunks from the top to hand every chunk its incoming value
+    Carry<FU> carry = ld_z<Carry<FU>>(carry_in, u);
+    // replay the lane's chunks from the top to hand every chunk its incoming value (a LaneSum again after the first)
     for (uint64_t t = hi; t-- > lo;) {
-        st_l<FU>(A, t, carry);
-        carry = FU::add(ld_l<FU>(H, t), FU::mul(carry, zk));
+        st_z<Carry<FU>>(A, t, carry);
+        carry = ld_z<ChunkSum<FU>>(H, t) + carry * zk;
     }
 }
 
@@ -128,15 +142,15 @@ template <class FU>
 __global__ void kzg_witness(const void* comb, uint64_t m, Packed zp, const void* A, void* w_out, uint64_t n_chunks) {
     uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_chunks) return;
-    const FU z = unpack<FU>(zp);
-    FU unR = FU::zero();      // the plain integer R'/R = 2^5: (x R) * 2^5 / R' = x
-    unR.v[0] = 32u;
+    const Z<FU, 10> z = unpack_c<FU>(zp);
+    Z<FU, 10> unR(FU::zero());      // the plain integer R'/R = 2^5: (x R) * 2^5 / R' = x
+    unR.v.v[0] = 32u;
     const uint64_t lo = t * CHUNK;
     const uint64_t hi = lo + CHUNK < m ? lo + CHUNK : m;
-    FU run = ld_l<FU>(A, t);
+    Carry<FU> run = ld_z<Carry<FU>>(A, t);
     for (uint64_t j = hi; j-- > lo;) {
-        run = FU::add(ld_u<FU>(comb, j), FU::mul(run, z));   // = w[j-1] (Montgomery, lazy)
-        if (j >= 1) st_u<FU>(w_out, j - 1, FU::mul(run, unR));
+        run = ld_c<FU>(comb, j) + run * z;   // = w[j-1] (Montgomery, lazy: a ChunkSum)
+        if (j >= 1) st_c<FU>(w_out, j - 1, run * unR);
     }
 }
 
@@ -158,12 +172,12 @@ __global__ void poly_chunk_horner(EvalArgs a, void* H) {
     const uint32_t y = blockIdx.y;
     const uint64_t m = a.len[y];
     if (t * CHUNK >= m) return;
-    const FU z = unpack<FU>(a.z[y]);
+    const Z<FU, 10> z = unpack_c<FU>(a.z[y]);
     const uint64_t lo = t * CHUNK;
     const uint64_t hi = lo + CHUNK < m ? lo + CHUNK : m;
-    FU acc = FU::zero();
-    for (uint64_t j = hi; j-- > lo;) acc = FU::add(ld_u<FU>(a.poly[y], j), FU::mul(acc, z));
-    st_l<FU>(H, (uint64_t)y * a.max_chunks + t, acc);
+    ChunkSum<FU> acc(FU::zero());
+    for (uint64_t j = hi; j-- > lo;) acc = ld_c<FU>(a.poly[y], j) + acc * z;
+    st_z<ChunkSum<FU>>(H, (uint64_t)y * a.max_chunks + t, acc);
 }
 
 // phase 2 (one workgroup per polynomial): p(z) = sum_t H[t] (z^CHUNK)^t.  Lane u folds its `per` consecutive chunks by
@@ -176,32 +190,32 @@ __global__ void __launch_bounds__(FOLD_T) poly_chunk_fold(EvalArgs a, const void
     const uint64_t per = (n_chunks + FOLD_T - 1) / FOLD_T;
     const uint64_t lo = (uint64_t)u * per < n_chunks ? (uint64_t)u * per : n_chunks;
     const uint64_t hi = lo + per < n_chunks ? lo + per : n_chunks;
-    const FU zk = unpack<FU>(a.zk[y]);
-    FU h = FU::zero();
-    for (uint64_t t = hi; t-- > lo;) h = FU::add(ld_l<FU>(H, (uint64_t)y * a.max_chunks + t), FU::mul(h, zk));
-    // Q = zk^per (the same on every lane), then Q^u
-    FU Q = FU::one(), b = zk;
+    const Z<FU, 10> zk = unpack_c<FU>(a.zk[y]);
+    LaneSum<FU> h(FU::zero());
+    for (uint64_t t = hi; t-- > lo;) h = ld_z<ChunkSum<FU>>(H, (uint64_t)y * a.max_chunks + t) + h * zk;
+    // Q = zk^per (the same on every lane), then Q^u: products only
+    LanePow<FU> Q = z_one<FU>(), b = zk;
     for (uint64_t e = per; e; e >>= 1) {
-        if (e & 1) Q = FU::mul(Q, b);
-        b = FU::mul(b, b);
+        if (e & 1) Q = Q * b;
+        b = zmul_self(b);
     }
-    FU s = FU::one();
+    LanePow<FU> s = z_one<FU>();
     b = Q;
     for (uint32_t e = u; e; e >>= 1) {
-        if (e & 1) s = FU::mul(s, b);
-        b = FU::mul(b, b);
+        if (e & 1) s = s * b;
+        b = zmul_self(b);
     }
-    h = FU::mul(h, s);                      // < 2r
-    // tree sum; every level re-normalises (x * 1 in the R' form keeps the value, brings it under 2r)
-    st_l<FU>(sh, u, h);
+    // tree sum of the products h * s; every level re-normalises, so the shared array and the running sum stay below 2r
+    Z<FU, 20> sum = h * s;
+    st_z<Z<FU, 20>>(sh, u, sum);
     for (uint32_t d = FOLD_T / 2; d >= 1; d >>= 1) {
         __syncthreads();
         if (u < d) {
-            h = FU::mul(FU::add(h, ld_l<FU>(sh, u + d)), FU::one());
-            st_l<FU>(sh, u, h);
+            sum = (sum + ld_z<Z<FU, 20>>(sh, u + d)) * z_one<FU>();
+            st_z<Z<FU, 20>>(sh, u, sum);
         }
     }
-    if (u == 0) st_u<FU>(out, y, h);
+    if (u == 0) st_c<FU>(out, y, sum);
 }
 
 template <class C>
@@ -210,8 +224,6 @@ int poly_evaluate(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const
     typedef typename C::FrU FU;
     if (n_polys > (uint32_t)MAX_POLYS) return ZK_ERR_UNSUPPORTED;
     if (n_polys == 0) return ZK_OK;
-    Fr to_rp;
-    FU::one().pack_words(to_rp.v);
     EvalArgs a;
     memset(&a, 0, sizeof a);
     a.n_polys = n_polys;
@@ -219,11 +231,9 @@ int poly_evaluate(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const
     for (uint32_t k = 0; k < n_polys; ++k) {
         if (lens[k] && !d_polys[k]) return ZK_ERR_BAD_ARG;
         Fr z;
-        memcpy(z.v, points_mont + 4 * k, 32);
-        if (Fr::reduce_once(z) != z) return ZK_ERR_BAD_ARG;      // not a reduced field element
-        const Fr zr = Fr::mul(z, to_rp), zkr = Fr::mul(Fr::pow_u64(z, CHUNK), to_rp);
-        memcpy(a.z[k].w, zr.v, 32);
-        memcpy(a.zk[k].w, zkr.v, 32);
+        if (!fr_reduced(points_mont + 4 * k, z)) return ZK_ERR_BAD_ARG;
+        a.z[k] = pack_rp(z);
+        a.zk[k] = pack_rp(Fr::pow_u64(z, CHUNK));
         a.poly[k] = d_polys[k];
         a.len[k] = lens[k];
         m = lens[k] > m ? lens[k] : m;
@@ -254,18 +264,14 @@ int poly_lincomb(zk_ctx* c, uint32_t n_terms, const void* const* d_polys, const 
     typedef typename C::FrU FU;
     if (n_terms > (uint32_t)MAX_POLYS) return ZK_ERR_UNSUPPORTED;
     if (out_len == 0) return ZK_OK;
-    Fr to_rp;
-    FU::one().pack_words(to_rp.v);
     RlcArgs a;
     memset(&a, 0, sizeof a);
     a.n_polys = n_terms;
     for (uint32_t k = 0; k < n_terms; ++k) {
         if (lens[k] && !d_polys[k]) return ZK_ERR_BAD_ARG;
         Fr cf;
-        memcpy(cf.v, coeffs_mont + 4 * k, 32);
-        if (Fr::reduce_once(cf) != cf) return ZK_ERR_BAD_ARG;
-        const Fr r = Fr::mul(cf, to_rp);
-        memcpy(a.chi_pow[k].w, r.v, 32);
+        if (!fr_reduced(coeffs_mont + 4 * k, cf)) return ZK_ERR_BAD_ARG;
+        a.chi_pow[k] = pack_rp(cf);
         a.poly[k] = d_polys[k];
         a.len[k] = lens[k] < out_len ? lens[k] : out_len;
     }
@@ -287,18 +293,12 @@ int open_prepare(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const 
     *wlen = m > 0 ? m - 1 : 0;
     *d_w = nullptr;
     if (m <= 1) return ZK_OK;
+    // z and chi are not validated here (the other entry points refuse an unreduced scalar: fr_reduced); an unreduced word stands for
+    // its residue, as it always did: z * 1 is that residue, reduced, and chi enters through products only.
     Fr z, chi;
     memcpy(z.v, z_mont, 32);
     memcpy(chi.v, chal_mont, 32);
-    // R' mod r as a plain integer: x R -> x R' by one product in the arkworks domain (as ntt.hip's tables)
-    Fr to_rp;
-    FU::one().pack_words(to_rp.v);
-    auto pack = [&](const Fr& v_mont) {
-        Packed p;
-        const Fr rp = Fr::mul(v_mont, to_rp);
-        memcpy(p.w, rp.v, 32);
-        return p;
-    };
+    z = Fr::mul(z, Fr::one());
     RlcArgs a;
     memset(&a, 0, sizeof a);
     a.n_polys = n_polys;
@@ -306,7 +306,7 @@ int open_prepare(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const 
     for (uint32_t k = 0; k < n_polys; ++k) {
         a.poly[k] = d_polys[k];
         a.len[k] = lens[k];
-        a.chi_pow[k] = pack(pw);
+        a.chi_pow[k] = pack_rp(pw);
         pw = Fr::mul(pw, chi);
     }
     const uint64_t n_chunks = (m + CHUNK - 1) / CHUNK;
@@ -317,7 +317,7 @@ int open_prepare(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const 
     void* comb = c->io.a.p;
     void* H = c->io.b.p;
     void* A = (char*)c->io.b.p + n_chunks * 48;
-    const Packed zp = pack(z), zkp = pack(Fr::pow_u64(z, CHUNK));
+    const Packed zp = pack_rp(z), zkp = pack_rp(Fr::pow_u64(z, CHUNK));
     hipStream_t st = c->stream;
     ProfScope ps(c, "kzg_open_prep");
     const int T = 256;

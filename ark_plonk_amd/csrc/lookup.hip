@@ -15,7 +15,7 @@
 //    t's positions (odd-bucket parity; evens and odds offsets, packed in one 64-bit scan) and an output-parallel fill that finds its bucket by binary search in the offsets.  No sort, like the reference; results are the
 //    reference's exactly because the emission order is a function of (first index in t, count) only.
 #include "ctx.h"
-#include "fr_io.cuh"
+#include "zbound.cuh"
 
 namespace {
 
@@ -277,10 +277,11 @@ __global__ void lookup_query(QueryArgs a, uint64_t n, void* out) {
         o[1] = d.b;
         return;
     }
-    FU acc = ld_u<FU>(a.w[0], i);                 // < r
+    typedef ZRun<FU, 10, 20, 3> Sum;              // a stored element and three products
+    typename Sum::T acc = ld_c<FU>(a.w[0], i);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) acc = FU::add(acc, FU::mul(ld_u<FU>(a.w[k + 1], i), unpack<FU>(a.zeta[k])));   // + 3 terms < 2r
-    st_u<FU>(out, i, FU::mul(acc, FU::one()));
+    for (int k = 0; k < 3; ++k) acc = Sum::step(acc, ld_c<FU>(a.w[k + 1], i) * unpack_c<FU>(a.zeta[k]));
+    st_c<FU>(out, i, acc * z_one<FU>());
 }
 
 template <class C>
@@ -288,18 +289,14 @@ int query_run(zk_ctx* c, size_t n, const void* d_q, size_t q_len, const void* co
     typedef typename C::Fr Fr;
     typedef typename C::FrU FU;
     Fr z;
-    memcpy(z.v, zeta_mont, 32);
-    if (Fr::reduce_once(z) != z) return ZK_ERR_BAD_ARG;
-    Fr to_rp;
-    FU::one().pack_words(to_rp.v);
+    if (!fr_reduced(zeta_mont, z)) return ZK_ERR_BAD_ARG;
     QueryArgs a;
     memset(&a, 0, sizeof a);
     a.q_lookup = d_q;
     a.q_len = q_len < n ? q_len : n;
     Fr pw = z;
     for (int k = 0; k < 3; ++k) {
-        const Fr r = Fr::mul(pw, to_rp);
-        memcpy(a.zeta[k].w, r.v, 32);
+        a.zeta[k] = pack_rp(pw);
         pw = Fr::mul(pw, z);
     }
     for (int k = 0; k < 4; ++k) a.w[k] = d_w[k];

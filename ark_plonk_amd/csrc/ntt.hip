@@ -124,21 +124,13 @@ PowBits<Fr> make_powbits(Fr base) {
     return pb;
 }
 
-// R' mod r as a plain integer in the saturated type's limbs
-template <class C>
-typename C::Fr rprime_plain() {
-    typename C::Fr r;
-    C::FrU::one().pack_words(r.v);
-    return r;
-}
-
 template <class C>
 int launch_pow_table(zk_ctx* c, void* out, uint64_t n, typename C::Fr base, typename C::Fr mul, int mode, uint32_t log_m,
                      uint32_t log_mprev) {
     typedef typename C::Fr Fr;
     if (n == 0) return ZK_OK;
     PowBits<Fr> pb = make_powbits(base);
-    Fr to_rp = rprime_plain<C>();
+    const Fr to_rp = to_rprime(Fr::one());     // R' mod r as a plain integer: the kernel's x R -> x R' is one product with it
     const int T = 256;
     uint64_t blocks = (n + T - 1) / T;
     hipLaunchKernelGGL(gen_pow_table<Fr>, dim3((unsigned)blocks), dim3(T), 0, c->stream, out, n, pb, mul, mode, log_m, log_mprev, to_rp);
@@ -343,7 +335,6 @@ int ntt_run(zk_ctx* c, int kind, uint32_t log_n, uint32_t n_polys, const void* c
     }
     // the last pass multiplies every output by 1/N (inverse) or 1 (forward) -- the product that also
     // brings the lazily reduced value back under 2r -- and, for coset_ifft, by g^-j from the table
-    const Fr to_rp = rprime_plain<C>();
     uint32_t log_mprev = log_n;
     NttPassArgs a;
     ProfScope ps(c, "ntt_pass");       // one scope per call (all passes of the transform or batch): an event pair costs ~14 us of host time
@@ -384,7 +375,7 @@ int ntt_run(zk_ctx* c, int kind, uint32_t log_n, uint32_t n_polys, const void* c
             a.s1 = s1;
             a.s2 = pl->n_pass == 4 ? (uint32_t)pl->s[1] : 0u;
             a.post_mul = post;
-            Fr sc = Fr::mul(inverse ? n_inv : Fr::one(), to_rp);   // R'-form of 1/N or 1
+            const Fr sc = to_rprime(inverse ? n_inv : Fr::one());   // R'-form of 1/N or 1
             for (int i = 0; i < 8; ++i) a.scale[i] = sc.v[i];
             a.n_tiles = (uint32_t)(N >> ((uint32_t)s + logc));
         }

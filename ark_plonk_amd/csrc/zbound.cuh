@@ -1,6 +1,8 @@
-// Bounded lazy arithmetic over the 29-bit-limb Fr type of the NTT (fieldu.cuh), with the bound carried in the TYPE, and the load
-// conversion into its R' = 2^261 Montgomery form.  Shared by the quotient kernel (quotient.hip) and the gate terms of the circuit
-// check (check.hip), which tests the very summands the quotient enforces: a bound rule is corrected here, once, for both.
+// Bounded lazy arithmetic over the 29-bit-limb Fr type of the NTT (fieldu.cuh), with the bound carried in the TYPE: the operators,
+// the loads and stores of fr_io.cuh in typed form, and the load conversion into the R' = 2^261 Montgomery form.  Shared by every
+// kernel that computes lazily on that type outside the NTT passes -- the quotient (quotient.hip), the gate terms of the circuit check
+// (check.hip), which tests the very summands the quotient enforces, the KZG opening and evaluation kernels (kzg.hip) and the query
+// column (lookup.hip): a bound rule is corrected here, once, for all of them.
 #pragma once
 #include "fr_io.cuh"
 
@@ -13,6 +15,7 @@ namespace {
 // static_assert, so a formula that could overflow does not compile.
 template <class F, int B>
 struct Z {
+    typedef F Field;
     F v;
     ZK_D Z() {}
     ZK_D Z(const F& f) : v(f) {}
@@ -31,9 +34,16 @@ ZK_D Z<F, 20> zsqr(const Z<F, A>& a) {
     static_assert(A * A <= 6400, "square operand too large");
     return {F::sqr(a.v)};
 }
+// a * a by the general product, for the kernels that were written with it (kzg.hip's power loops) and keep their instructions; one
+// operand, so that the product is compiled knowing both are the same value, as it is where F::mul(a, a) stands in a kernel
+template <class F, int A>
+ZK_D Z<F, 20> zmul_self(const Z<F, A>& a) {
+    static_assert(A * A <= 6400, "square operand too large");
+    return {F::mul(a.v, a.v)};
+}
 template <class F, int A, int B>
 ZK_D Z<F, A + B> operator+(const Z<F, A>& a, const Z<F, B>& b) {
-    static_assert(A + B <= 600, "sum too large for the 261-bit container");
+    static_assert(A + B <= 640, "sum too large for the 261-bit container");
     return {F::add(a.v, b.v)};
 }
 template <int B>
@@ -43,11 +53,20 @@ struct SubK {
 };
 template <class F, int A, int B>
 ZK_D Z<F, A + SubK<B>::K> operator-(const Z<F, A>& a, const Z<F, B>& b) {
-    static_assert(A + SubK<B>::K <= 600, "difference too large for the 261-bit container");
+    static_assert(A + SubK<B>::K <= 640, "difference too large for the 261-bit container");
     if constexpr (SubK<B>::K == 20) return {F::sub2(a.v, b.v)};
     else if constexpr (SubK<B>::K == 80) return {F::sub8(a.v, b.v)};
     else return {F::sub16(a.v, b.v)};
 }
+// A value that starts below B0 / 10 r and takes up at most N terms below G / 10 r each, in a loop whose count is known at run time only
+// (N terms of a sum: B0 = 0; N steps of a scan).  The variable has the bound after the last step, T, from the start; the sum rule is
+// checked once, for that.  What keeps the count at N is the caller's: it names the constant that does.
+template <class F, int B0, int G, int N>
+struct ZRun {
+    static_assert(B0 + N * G <= 640, "sum too large for the 261-bit container");
+    typedef Z<F, B0 + N * G> T;
+    ZK_D static T step(const T& acc, const Z<F, G>& term) { return {F::add(acc.v, term.v)}; }
+};
 // value != 0 mod r, exactly.  Zero has several encodings (0, r, 2r, ...): a value below 2r is 0 or r when it is a multiple of r;
 // anything larger goes through a product with one
 template <class F, int B>
@@ -60,6 +79,22 @@ template <class F, int B>
 ZK_D Z<F, 20> delta4(const Z<F, B>& f, const Z<F, 10>& one, const Z<F, 10>& c2, const Z<F, 10>& c3) {   // f(f-1)(f-2)(f-3)
     return (f * (f - one)) * ((f - c2) * (f - c3));
 }
+
+// The accesses of fr_io.cuh, typed.  A stored 32-byte element and a kernel-argument multiplier are canonical (the host reduces the
+// latter: to_rprime); a 48-byte limb vector has the bound its buffer is declared with, T, on both sides: a value wider than T does not
+// convert ("bound would shrink"), so a writer cannot outgrow what the reader was compiled for.
+template <class F>
+ZK_D Z<F, 10> ld_c(const void* base, uint64_t idx) { return {ld_u<F>(base, idx)}; }
+template <class F>
+ZK_D Z<F, 10> unpack_c(const Packed& p) { return {unpack<F>(p)}; }
+template <class F>
+ZK_D Z<F, 10> z_one() { return {F::one()}; }          // 1 in the R' form: x * 1 keeps the value and brings it under 2r
+template <class F>
+ZK_D void st_c(void* base, uint64_t idx, const Z<F, 20>& x) { st_u<F>(base, idx, x.v); }     // canonical_lt2p: below 2r
+template <class T>
+ZK_D T ld_z(const void* base, uint64_t idx) { return {ld_l<typename T::Field>(base, idx)}; }
+template <class T>
+ZK_D void st_z(void* base, uint64_t idx, const T& x) { st_l<typename T::Field>(base, idx, x.v); }
 
 // arkworks Montgomery value x * 2^256 (canonical, 8 words) -> x * 2^261 mod r, < RP_B / 10 * r:
 // shift left by 5 bits (32 v < 32 r < 2^260), subtract q2 * r with q2 = floor(T * ratio_fx / 2^13), T = floor(32 v / 2^(BITS - 3)) < 256
@@ -103,11 +138,7 @@ ZK_D Z<F, RP_B> ld_rp(const void* base, uint64_t idx, const uint32_t (*rtab)[F::
 // ---- host side
 // arkworks-form Fr (R = 2^256) -> the canonical R' = 2^261 residue as 29-bit limbs
 template <class Cv>
-typename Cv::FrU to_rp_host(const typename Cv::Fr& v) {
-    typename Cv::Fr t = v;
-    for (int k = 0; k < 5; ++k) t = Cv::Fr::add(t, t);
-    return Cv::FrU::split_words(t.v);
-}
+typename Cv::FrU to_rp_host(const typename Cv::Fr& v) { return Cv::FrU::split_words(to_rprime(v).v); }
 // what to_rp reads: rtab[q] = q * r as 29-bit limbs for q < len, ratio_fx = floor(2^BITS / r * 2^10) - 1 and
 // top_shift = BITS - 29 * (NL - 1) (>= 3: to_rp keeps three bits below it).  len must cover the largest q2 (32 v / r < 32, and the
 // estimate never exceeds it).

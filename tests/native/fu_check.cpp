@@ -157,6 +157,25 @@ static void to_rp_many(const uint32_t* words_in, uint32_t* limbs_out, uint64_t n
         for (int i = 0; i < FU::NL; ++i) limbs_out[FU::NL * k + i] = z.v.v[i];
     }
 }
+// x R (stored words, canonical) -> x R' three ways: the packer behind every kernel-argument multiplier (pack_rp, fr_io.cuh: doublings),
+// to_rp_host (zbound.cuh) as limbs, and the route the units used to write out: one Montgomery product with R' mod r as a plain integer
+template <class Cv>
+static void pack_rp_many(const uint32_t* words_in, uint32_t* packed_out, uint32_t* limbs_out, uint32_t* product_out, uint64_t n) {
+    typedef typename Cv::Fr Fr;
+    typedef typename Cv::FrU FU;
+    Fr rp;
+    FU::one().pack_words(rp.v);
+    for (uint64_t k = 0; k < n; ++k) {
+        Fr v;
+        memcpy(v.v, words_in + 8 * k, 32);
+        const Packed p = pack_rp(v);
+        memcpy(packed_out + 8 * k, p.w, 32);
+        const FU l = to_rp_host<Cv>(v);
+        for (int i = 0; i < FU::NL; ++i) limbs_out[FU::NL * k + i] = l.v[i];
+        const Fr m = Fr::mul(v, rp);
+        memcpy(product_out + 8 * k, m.v, 32);
+    }
+}
 template <int W>
 static uint32_t key_hash_of(const uint32_t* words) {
     Key<W> k;
@@ -256,7 +275,11 @@ void fu_to_rp(int field, const uint32_t* words_in, uint32_t* limbs_out, uint64_t
     if (field == 1) to_rp_many<HostBls>(words_in, limbs_out, n);
     else to_rp_many<HostBn>(words_in, limbs_out, n);
 }
-int fu_rp_bound() { return RP_B; }        // a loaded value is < RP_B / 10 * r
+void fu_pack_rp(int field, const uint32_t* words_in, uint32_t* packed_out, uint32_t* limbs_out, uint32_t* product_out, uint64_t n) {
+    if (field == 1) pack_rp_many<HostBls>(words_in, packed_out, limbs_out, product_out, n);
+    else pack_rp_many<HostBn>(words_in, packed_out, limbs_out, product_out, n);
+}
+int fu_rp_bound() { return RP_B; }       // a loaded value is < RP_B / 10 * r
 int fu_rp_limbs() { return FrB::NL; }
 uint64_t fu_el_mix(uint64_t h, const uint32_t* words) { return el_mix(h, el_of(words)); }
 uint32_t fu_key_hash(int w, const uint32_t* words) { return w == 1 ? key_hash_of<1>(words) : key_hash_of<4>(words); }

@@ -239,3 +239,24 @@ def test_kzg_open_and_evaluate_past_one_chunk_per_lane(cid, ctx, oracle_cpu):
         exp_xy, exp_inf = oracle_cpu.kzg_commit(cid, b_host, w)
         got = ck.open([d_poly], zm, one)
         assert bool(got.infinity) == bool(exp_inf) and np.array_equal(got.xy(), exp_xy), name
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_kzg_sum_of_32_terms_at_its_extreme(cid, ctx, oracle_cpu):
+    """The one tight bound of the KZG kernels (kzg.hip: kzg_rlc adds up to MAX_POLYS = 32 lazily reduced products, below 64r, and the
+    product that follows has room for 70.7r on BLS12-381): 32 terms with every coefficient r - 1 and every multiplier r - 1.  The linear
+    combination at lengths 1 and 65 against poly_scale / poly_add, and the opening of 32 polynomials of 65 coefficients with the
+    challenge r - 1 at z = 1 and z = r - 1 against bo.kzg_open.  With 32 equal polynomials the powers of -1 cancel and the combination is
+    the zero polynomial, so the opening is also taken with polynomial k cut to 65 - k coefficients, where nothing cancels."""
+    cv = bo.CURVES[cid]
+    p, top = cv.r, cv.r - 1
+    for m in (1, 65):
+        polys = [[top] * m for _ in range(32)]
+        got = linearisation.lincomb([dev(cid, q) for q in polys], fr_to_mont(cid, [top] * 32), curve=cid, ctx=ctx)
+        assert back(cid, got) == bo.poly_add(*[bo.poly_scale(q, top, p) for q in polys], p=p), m
+    ck, _, powers = srs(cid, ctx, oracle_cpu)
+    for name, polys in (("equal", [[top] * 65 for _ in range(32)]), ("ragged", [[top] * (65 - k) for k in range(32)])):
+        d_polys = [dev(cid, q) for q in polys]
+        for z in (1, top):
+            got = ck.open(d_polys, m1(cid, z), m1(cid, top))
+            assert point_ints(cid, got) == bo.kzg_open(cv, powers, polys, z, top), (name, z)

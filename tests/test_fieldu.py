@@ -42,6 +42,8 @@ def fu():
     L.fu_raw_op.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
     L.fu_to_rp.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
     L.fu_to_rp.restype = None
+    L.fu_pack_rp.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_uint64]
+    L.fu_pack_rp.restype = None
     L.fu_el_mix.argtypes = [ctypes.c_uint64, ctypes.c_void_p]
     L.fu_el_mix.restype = ctypes.c_uint64
     L.fu_key_hash.argtypes = [ctypes.c_int, ctypes.c_void_p]
@@ -615,7 +617,7 @@ def test_lazy_limbs_at_the_edge_of_the_column_bound(field, fu):
 def test_z_rules_are_sound(field, fu):
     """The numbers of zbound.cuh (Z<F, B>: a value below B / 10 r) against the operators at the extreme each rule admits, on swept
     operands in the limb patterns of the test above.  Products with A B <= 6400: (8r, 8r), (64r, r), (32r, 2r) in both orders and the
-    square of 8r come out below 2r and congruent.  Sums up to 600: exact, normalised, the top limb inside 29 bits.  Differences through
+    square of 8r come out below 2r and congruent.  Sums up to 640 (kzg.hip: 32 products below 2r): exact, normalised, the top limb inside 29 bits.  Differences through
     sub2 / sub8 / sub16 (SubK: 2r / 8r / 16r): subtrahend just below the multiple, minuend 0 and at the most the sum rule leaves: exact,
     normalised, no negative top limb.  The two tests on values below 2r: exact on 0, r, r +- 1, 2r - 1 and random ones."""
     F = RawFu(fu, field)
@@ -624,7 +626,7 @@ def test_z_rules_are_sound(field, fu):
     prod_max = int(re.search(r"static_assert\(A \* B <= (\d+),", text).group(1))
     sum_max = int(re.search(r"static_assert\(A \+ B <= (\d+),", text).group(1))
     assert re.search(r"K = B <= 20 \? 20 : B <= 80 \? 80 : 160;", text) and "A * A <= %d" % prod_max in text
-    assert (prod_max, sum_max) == (6400, 600) and sum_max * r < 10 * Rp
+    assert (prod_max, sum_max) == (6400, 640) and sum_max * r < 10 * Rp
 
     def below(tenths, kind):
         return F.operand(1, tenths * r // 10, kind)
@@ -640,7 +642,7 @@ def test_z_rules_are_sound(field, fu):
         a = below(80, ka)
         got = F.call("sqr", a)
         assert got == F.call("mul", a, a) and F.swept(got) and F.val(got) < 2 * r and (F.val(got) * Rp - F.val(a) ** 2) % r == 0, ka
-    for A, B in ((300, 300), (590, 10), (10, 590), (400, 200)):
+    for A, B in ((320, 320), (630, 10), (10, 630), (440, 200)):
         assert A + B == sum_max
         for ka in FU_KINDS:
             for kb in FU_KINDS:
@@ -697,6 +699,28 @@ def test_to_rp_is_32v_below_its_bound(field, fu):
     print(f"to_rp field {field}: largest result {worst / r:.6f} r, largest multiple of r taken off {worst_q}")
     assert 10 * worst < bound * r, f"{worst / r:.4f} r against a bound of {bound / 10} r"
     assert worst_q < min(_table_rows())
+
+
+@pytest.mark.parametrize("field", [1, 3])
+def test_host_rprime_packer(field, fu):
+    """The one host conversion behind every kernel-argument multiplier and the NTT's tables (pack_rp / to_rprime, fr_io.cuh): the stored
+    word w = x R goes to 32 w mod r = x R', canonical -- against Python integers, against to_rp_host (zbound.cuh: the same value as
+    normalised limbs) and against the route the units used to write out, one Montgomery product with R' mod r.  0, 1, r - 1 and the
+    edge set, as values and as stored words."""
+    r = FIELDS[field][0]
+    cv = bo.BLS12_381 if field == 1 else bo.BN254
+    edges = [0, 1, r - 1] + list(ev.edge_elements(cv))
+    ws = sorted(set(edges + [ev.stored_word(cv, v) for v in edges]))
+    nl = fu.fu_rp_limbs()
+    win = np.frombuffer(b"".join(w.to_bytes(32, "little") for w in ws), dtype="<u4").copy()
+    packed, limbs, prod = np.zeros(8 * len(ws), dtype="<u4"), np.zeros(nl * len(ws), dtype="<u4"), np.zeros(8 * len(ws), dtype="<u4")
+    fu.fu_pack_rp(field, win.ctypes.data, packed.ctypes.data, limbs.ctypes.data, prod.ctypes.data, len(ws))
+    assert int(limbs.max()) < 1 << 29, "limbs not normalised"
+    for k, w in enumerate(ws):
+        want = 32 * w % r
+        assert unwords(packed[8 * k:8 * k + 8]) == want, hex(w)
+        assert unwords(prod[8 * k:8 * k + 8]) == want, hex(w)
+        assert sum(int(limbs[nl * k + i]) << (29 * i) for i in range(nl)) == want, hex(w)
 
 
 # ---- the hash of the device key maps (fr_io.cuh) and its restatement
