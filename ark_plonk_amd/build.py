@@ -26,6 +26,7 @@ HOST_HDRS = FIELD_HDRS + ["ecu.cuh", "ctx.h", "g1_host.h", "../../include/ark_pl
 API_HDRS = HOST_HDRS + ["api_internal.h"]
 # helpers with one definition each: Fr / 32-byte element access; bounded lazy arithmetic on the 29-bit Fr type; the MSM's point storage
 FR_IO, ZBOUND, POINT_IO = ["fr_io.cuh"], ["fr_io.cuh", "zbound.cuh"], ["point_io.cuh"]
+DOMAIN, DEV_SCAN = ["fr_io.cuh", "domain.cuh"], ["dev_scan.cuh"]       # domain and permutation constants; the integer exclusive scan
 GADGET = ["gadget_common.cuh"]            # what the two units of the device composer (layout, witness) share
 BLOCK_INV = ["block_inverse.cuh"]         # one field inversion per workgroup: the key fold, the gadget witnesses, the verifier's scalars
 # the C ABI, one unit per subsystem (api_internal.h is what they share)
@@ -35,29 +36,29 @@ MSM_UNITS = ("msm_accumulate", "msm_reduce", "msm_sort", "msm_plan")      # heav
 
 def jobs():
     """(object name, source, extra defines, header deps)"""
-    out = [(f"{u}.o", f"{u}.hip", [], API_HDRS) for u in API_UNITS] + [
+    out = [(f"{u}.o", f"{u}.hip", [], API_HDRS + (DOMAIN if u == "api_poly" else [])) for u in API_UNITS] + [
         ("hostio.o", "hostio.hip", [], HOST_HDRS),
         ("wire.o", "wire.hip", [], HOST_HDRS),
         ("kzg.o", "kzg.hip", [], HOST_HDRS + ZBOUND),
-        ("lookup.o", "lookup.hip", [], HOST_HDRS + ZBOUND),
-        ("grand_product.o", "grand_product.hip", [], HOST_HDRS + FR_IO),
-        ("quotient.o", "quotient.hip", [], HOST_HDRS + ZBOUND),
+        ("lookup.o", "lookup.hip", [], HOST_HDRS + ZBOUND + DEV_SCAN),
+        ("grand_product.o", "grand_product.hip", [], HOST_HDRS + DOMAIN),
+        ("quotient.o", "quotient.hip", [], HOST_HDRS + ZBOUND + DOMAIN),
         ("quadtest.o", "quadtest.hip", [], HOST_HDRS + ["ecq.cuh"]),
-        ("ntt.o", "ntt.hip", [], HOST_HDRS + FR_IO + ["ntt_pass.cuh"]),
+        ("ntt.o", "ntt.hip", [], HOST_HDRS + DOMAIN + ["ntt_pass.cuh"]),
         ("ntt_pass_table.o", "ntt_pass_table.hip", [], []),
         ("msm_dispatch.o", "msm_dispatch.hip", [], HOST_HDRS),
         # the inner-product-argument commitment; circuit compilation (the wire permutation from the variable map, the witness gather);
         # the circuit check (per-row masks of violated gate, copy and lookup constraints)
         ("ipa.o", "ipa.hip", [], API_HDRS + FR_IO + POINT_IO + BLOCK_INV),
-        ("compile.o", "compile.hip", [], API_HDRS + FR_IO),
-        ("check.o", "check.hip", [], API_HDRS + ZBOUND),
+        ("compile.o", "compile.hip", [], API_HDRS + DOMAIN + DEV_SCAN),
+        ("check.o", "check.hip", [], API_HDRS + ZBOUND + DOMAIN),
         # the device composer: gadget segments (rows, ids, selectors, insertions) and lookup tables, built once per circuit ...
         ("gadget_layout.o", "gadget_layout.hip", [], API_HDRS + FR_IO + GADGET),
         # ... and the values of the variables the segments create, replayed once per proof
         ("gadget_witness.o", "gadget_witness.hip", [], API_HDRS + FR_IO + GADGET + BLOCK_INV),
         # the verifier's device side: batch decoding of compressed G1 points, per-proof scalars, the column sum of a fold (its host
         # side, parse and replay, is in wire.hip)
-        ("verify.o", "verify.hip", [], API_HDRS + FR_IO + BLOCK_INV),
+        ("verify.o", "verify.hip", [], API_HDRS + DOMAIN + BLOCK_INV),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

@@ -1,6 +1,7 @@
 // Pass-throughs of the C ABI: argument checks and the ctx guard in front of the NTT, field, grand-product, lookup, quotient and
 // polynomial units.
 #include "api_internal.h"
+#include "domain.cuh"
 
 // ------------------------------------------------------------------------------------------- a1
 template <class C>
@@ -13,14 +14,12 @@ static int domain_new(uint64_t num_coeffs, zk_domain_info* out) {
         ++lg;
         if (lg > 63) return ZK_ERR_DOMAIN_TOO_LARGE;
     }
-    if (lg > (uint32_t)C::FrP::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
+    if (!domain_log_ok<C>(lg)) return ZK_ERR_DOMAIN_TOO_LARGE;
     memset(out, 0, sizeof *out);
     out->size = size;
     out->log_size_of_group = lg;
-    Fr root;
-    for (int i = 0; i < Fr::N; ++i) root.v[i] = C::FrP::ROOT(i);
-    for (uint32_t k = lg; k < (uint32_t)C::FrP::TWO_ADICITY; ++k) root = Fr::sqr(root);
-    Fr gen = Fr::from_u32(C::FrP::GENERATOR);
+    Fr root = domain_root<C>(lg);
+    Fr gen = coset_gen<C>();
     Fr size_inv = Fr::inverse(Fr::from_u64(size));
     Fr root_inv = Fr::inverse(root);
     Fr gen_inv = Fr::inverse(gen);

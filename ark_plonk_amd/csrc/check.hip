@@ -7,7 +7,7 @@
 // 51-63, range.rs:47-63, logic.rs:65-133, ecc/fixed_base_scalar_mul.rs:88-156, ecc/curve_addition.rs:62-97), taken one by one, with no
 // random challenge: a bit is set iff the selector of its widget and its term are both non-zero (DESIGN.md section 6d has the table).
 //   check_gates     bits 0-16: one lane per row, "next row" = (i + 1) mod n; plain store of the row's word
-//   check_id_keys   the 4n identity encodings K_w * omega^row of the permutation argument (K = 1, 7, 13, 17)
+//   check_id_keys   the 4n identity encodings K_w * omega^row of the permutation argument (domain.cuh)
 //   map_build       an open-addressing map (linear probing, capacity = the power of two >= 2 x keys) over keys of 1 or 4 field
 //                   elements; a slot holds the INDEX of its key and an occupant's key is always compared in full
 //   check_copy      bits 18-21: sigma_k[i] -> position through the identity map (no encoding: the flag word), the two cells compared
@@ -24,12 +24,12 @@
 // Working memory: one allocation per call, freed before return, no buffer of the ctx (the call runs inside an open deferred round):
 // 128 n (identity keys) + 32 n (their map) + 4 * capacity(table_rows) (<= 8 n) + 4 n when the caller takes no mask + 8 KiB.
 #include "api_internal.h"
+#include "domain.cuh"
 #include "zbound.cuh"
 
 namespace {
 
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
-constexpr uint32_t MAX_LOG_N = 28;                // 4n positions and the sentinel fit 32 bits; also BN254's two-adicity
 constexpr uint32_t FLAG_SIGMA = 1;                // a sigma entry that is no K_w * omega^row
 constexpr uint32_t CT = 256;                      // lanes per workgroup, every kernel
 constexpr size_t HEAD = 1024;                      // flag word at 0, summary at 256: cleared and read back as one block
@@ -85,17 +85,14 @@ __global__ void __launch_bounds__(CT) map_build(uint32_t* slots, uint32_t cap_ma
 }
 
 // ---------------------------------------------------------------------------------------------------------------- identity keys
-// consts: K_0..K_3 (Montgomery), then omega^(2^j), j < MAX_LOG_N.  keys[w * n + row] = K_w * omega^row, canonical like every sigma entry.
-constexpr uint32_t N_CONSTS = 4 + MAX_LOG_N;
+// consts: fill_id_consts (domain.cuh).  keys[w * n + row] = K_w * omega^row, canonical like every sigma entry.
 template <class Cv>
 __global__ void __launch_bounds__(CT) check_id_keys(uint32_t log_n, const void* consts, void* keys) {
     typedef typename Cv::Fr Fr;
     const uint64_t row = (uint64_t)blockIdx.x * CT + threadIdx.x;
     const uint64_t n = (uint64_t)1 << log_n;
     if (row >= n) return;
-    Fr pw = ld_fr<Fr>(consts, 0);                             // K_0 = 1
-    for (uint32_t j = 0; j < log_n; ++j)
-        if ((row >> j) & 1u) pw = Fr::mul(pw, ld_fr<Fr>(consts, 4 + j));
+    const Fr pw = id_omega_pow<Fr>(consts, (uint32_t)row, log_n);
     st_fr<Fr>(keys, row, pw);
 #pragma unroll 1
     for (uint32_t w = 1; w < 4; ++w) st_fr<Fr>(keys, w * n + row, Fr::mul(pw, ld_fr<Fr>(consts, w)));
@@ -277,20 +274,6 @@ __global__ void __launch_bounds__(CT) check_gates(const CArgsU<F>* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-template <class Cv>
-void fill_args(CArgsU<typename Cv::FrU>& A, const zk_circuit_check_args* q) {
-    typedef typename Cv::Fr Fr;
-    A.w_l = q->w_l; A.w_r = q->w_r; A.w_o = q->w_o; A.w_4 = q->w_4; A.pi = q->pi;
-    A.q_m = q->q_m; A.q_l = q->q_l; A.q_r = q->q_r; A.q_o = q->q_o; A.q_4 = q->q_4; A.q_c = q->q_c; A.q_arith = q->q_arith;
-    A.q_range = q->q_range; A.q_logic = q->q_logic; A.q_fixed = q->q_fixed_group_add; A.q_var = q->q_variable_group_add;
-    auto ldc = [](const uint64_t* src) { Fr v; memcpy(v.v, src, 32); return v; };
-    auto U = [](const Fr& v) { return to_rp_host<Cv>(v); };
-    A.coeff_a = U(ldc(q->coeff_a)); A.coeff_d = U(ldc(q->coeff_d)); A.one = U(Fr::one());
-    A.c2 = U(Fr::from_u32(2)); A.c3 = U(Fr::from_u32(3)); A.c4 = U(Fr::from_u32(4)); A.c9 = U(Fr::from_u32(9));
-    A.c18 = U(Fr::from_u32(18)); A.c81 = U(Fr::from_u32(81)); A.c83 = U(Fr::from_u32(83));
-    rp_table<Cv>(A.rtab, CTAB, A.ratio_fx, A.top_shift);
-}
-
 inline uint64_t capacity_for(uint64_t keys) {
     uint64_t cap = 2;
     while (cap < 2 * keys) cap <<= 1;
@@ -301,8 +284,8 @@ template <class Cv>
 int check_impl(zk_ctx* c, uint32_t log_n, const zk_circuit_check_args* q, uint32_t* d_mask, zk_circuit_check_summary* out) {
     typedef typename Cv::Fr Fr;
     typedef typename Cv::FrU FU;
-    if (log_n > (uint32_t)Cv::FrP::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
-    if (log_n > MAX_LOG_N) return ZK_ERR_UNSUPPORTED;
+    if (!domain_log_ok<Cv>(log_n)) return ZK_ERR_DOMAIN_TOO_LARGE;
+    if (log_n > ID_MAX_LOG_N) return ZK_ERR_UNSUPPORTED;
     const uint64_t n = (uint64_t)1 << log_n;
     const void* const cols[] = {q->w_l, q->w_r, q->w_o, q->w_4, q->q_m, q->q_l, q->q_r, q->q_o, q->q_4, q->q_c, q->q_arith, q->q_range, q->q_logic,
                                 q->q_fixed_group_add, q->q_variable_group_add, q->q_lookup, q->sigma[0], q->sigma[1], q->sigma[2], q->sigma[3]};
@@ -313,7 +296,7 @@ int check_impl(zk_ctx* c, uint32_t log_n, const zk_circuit_check_args* q, uint32
         if (q->table_rows && !q->table[k]) return ZK_ERR_BAD_ARG;
 
     const uint64_t cap_id = capacity_for(4 * n), cap_t = capacity_for(q->table_rows);
-    const size_t o_sum = 256, o_args = HEAD, o_consts = o_args + up256(sizeof(CArgsU<FU>)), o_keys = o_consts + up256(N_CONSTS * 32),
+    const size_t o_sum = 256, o_args = HEAD, o_consts = o_args + up256(sizeof(CArgsU<FU>)), o_keys = o_consts + up256(ID_N_CONSTS * 32),
                  o_slots_id = o_keys + up256(4 * n * 32), o_slots_t = o_slots_id + up256(cap_id * 4), o_mask = o_slots_t + up256(cap_t * 4),
                  total = o_mask + (d_mask ? 0 : up256(n * 4));
     static_assert(sizeof(zk_circuit_check_summary) <= HEAD - 256, "the summary shares the head of the buffer with the flag word");
@@ -338,19 +321,12 @@ int check_impl(zk_ctx* c, uint32_t log_n, const zk_circuit_check_args* q, uint32
         ZK_HIP_TRY(hipMemsetAsync(slots_t, 0xff, (size_t)cap_t * 4, st));
         {   // the argument block of the gate kernel and the constants of the identity encodings: host copies live until zk_h2d returns
             CArgsU<FU> A;
-            fill_args<Cv>(A, q);
+            fill_gate_columns(A, q);
+            fill_gate_consts<Cv>(A, q->coeff_a, q->coeff_d, CTAB);
             int r2 = zk_h2d(c, w + o_args, &A, sizeof A, st);
             if (r2) return r2;
-            Fr cs[N_CONSTS];
-            const uint32_t Kp[4] = {1, 7, 13, 17};                 // permutation/constants.rs:12-22
-            for (int k = 0; k < 4; ++k) cs[k] = Fr::from_u32(Kp[k]);
-            Fr pw;
-            for (int i = 0; i < Fr::N; ++i) pw.v[i] = Cv::FrP::ROOT(i);
-            for (uint32_t k = log_n; k < (uint32_t)Cv::FrP::TWO_ADICITY; ++k) pw = Fr::sqr(pw);
-            for (uint32_t j = 0; j < MAX_LOG_N; ++j) {
-                cs[4 + j] = pw;
-                pw = Fr::sqr(pw);
-            }
+            Fr cs[ID_N_CONSTS];
+            fill_id_consts<Cv>(log_n, cs);
             r2 = zk_h2d(c, w + o_consts, cs, sizeof cs, st);
             if (r2) return r2;
         }

@@ -7,7 +7,7 @@
 // least-significant-digit radix sort (8 bits a pass, only as many passes as num_vars has bits), so that every variable's positions are
 // one contiguous run in call order; sigma of a run's element is its right neighbour, of the last element the run's first.
 //   sigma_check      range of every (variable, position)                                   -> flag word
-//   sigma_sort_pass  <false>: digit counts per tile [digit][tile]; exclusive scan (scan_*); <true>: stable scatter
+//   sigma_sort_pass  <false>: digit counts per tile [digit][tile]; exclusive scan (dev_scan.cuh); <true>: stable scatter
 //   sigma_rotate     sigma_pos[pos_j] = pos of the right neighbour / of the run's head      (a second write of one cell -> flag word)
 //   sigma_encode     never-inserted cells -> themselves; evals[w][row] = K_w' * omega^row'
 // Skew is the normal case (every unused wire of every gate is the zero variable, composer.rs:308): no step gives a variable's run to
@@ -22,13 +22,13 @@
 // round).  With m <= 4n insertions: 16 m bytes (two key/value buffer pairs; 8 m when one pass is enough, none when num_vars = 1)
 // + m / 4 (digit counts) + 16 n when the caller takes no positions + 2 KiB.  At most 81 n bytes: 340 MB at n = 2^22.
 #include "api_internal.h"
-#include "fr_io.cuh"
+#include "dev_scan.cuh"
+#include "domain.cuh"
 
 namespace {
 
 constexpr uint32_t NO_POS = 0xffffffffu;          // a cell of sigma_pos nothing was written to (positions are < 2^30)
 constexpr uint32_t FLAG_RANGE = 1, FLAG_TWICE = 2;
-constexpr uint32_t MAX_LOG_N = 28;                // 4n positions and the sentinel fit 32 bits; also BN254's two-adicity
 
 constexpr uint32_t SORT_T = 256;                  // lanes per tile
 constexpr uint32_t SORT_WAVES = SORT_T / 64;
@@ -37,7 +37,7 @@ constexpr uint32_t WAVE_ITEMS = 64 * SORT_ITEMS;  // a wave owns this many CONSE
 constexpr uint32_t SORT_TILE = SORT_T * SORT_ITEMS;
 constexpr uint32_t RADIX = 256;
 
-constexpr uint32_t SCAN_T = 256, SCAN_ITEMS = 4, SCAN_CHUNK = SCAN_T * SCAN_ITEMS;
+constexpr uint32_t SCAN_T = 256, SCAN_ITEMS = 4, SCAN_CHUNK = SCAN_T * SCAN_ITEMS;      // the geometry of the digit counts' scan (dev_scan.cuh)
 
 // ---------------------------------------------------------------------------------------------------------------- range check
 // Every entry is looked at before any kernel uses one as an address; the kernels below guard their own writes as well, so a bad
@@ -120,60 +120,6 @@ __global__ void __launch_bounds__(SORT_T) sigma_sort_pass(const uint32_t* key_in
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- exclusive scan
-// of a u32 vector in place: chunk sums, the scan of the sums by one block, then every chunk on top of its sum
-ZK_D uint32_t block_inclusive_scan(uint32_t x, uint32_t* sh) {
-    const uint32_t t = threadIdx.x;
-    sh[t] = x;
-    __syncthreads();
-    for (uint32_t d = 1; d < SCAN_T; d <<= 1) {
-        const uint32_t v = t >= d ? sh[t - d] : 0u;
-        __syncthreads();
-        x += v;
-        sh[t] = x;
-        __syncthreads();
-    }
-    return x;
-}
-// exclusive scan of data[base, base + SCAN_CHUNK) (clipped to len) on top of `carry`; returns the chunk's sum
-ZK_D uint32_t chunk_scan(uint32_t* data, uint64_t base, uint64_t len, uint32_t carry, uint32_t* sh, bool write) {
-    const uint32_t t = threadIdx.x;
-    uint32_t v[SCAN_ITEMS], s = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < SCAN_ITEMS; ++i) {
-        const uint64_t idx = base + (uint64_t)t * SCAN_ITEMS + i;
-        v[i] = idx < len ? data[idx] : 0u;
-        s += v[i];
-    }
-    const uint32_t incl = block_inclusive_scan(s, sh);
-    const uint32_t total = sh[SCAN_T - 1];
-    __syncthreads();                                       // sh is reused by the caller's next chunk
-    if (write) {
-        uint32_t run = carry + incl - s;
-#pragma unroll
-        for (uint32_t i = 0; i < SCAN_ITEMS; ++i) {
-            const uint64_t idx = base + (uint64_t)t * SCAN_ITEMS + i;
-            if (idx < len) data[idx] = run;
-            run += v[i];
-        }
-    }
-    return total;
-}
-__global__ void __launch_bounds__(SCAN_T) scan_sums(uint32_t* data, uint64_t len, uint32_t* sums) {
-    __shared__ uint32_t sh[SCAN_T];
-    const uint32_t total = chunk_scan(data, (uint64_t)blockIdx.x * SCAN_CHUNK, len, 0, sh, false);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(SCAN_T) scan_top(uint32_t* sums, uint64_t n_chunks) {
-    __shared__ uint32_t sh[SCAN_T];
-    uint32_t carry = 0;
-    for (uint64_t base = 0; base < n_chunks; base += SCAN_CHUNK) carry += chunk_scan(sums, base, n_chunks, carry, sh, true);
-}
-__global__ void __launch_bounds__(SCAN_T) scan_apply(uint32_t* data, uint64_t len, const uint32_t* sums) {
-    __shared__ uint32_t sh[SCAN_T];
-    chunk_scan(data, (uint64_t)blockIdx.x * SCAN_CHUNK, len, sums[blockIdx.x], sh, true);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- rotate
 // var_s / pos_s: the call sequence sorted by variable (runs in call order).  Lane j writes sigma of ITS position.
 __global__ void __launch_bounds__(256) sigma_rotate(const uint32_t* var_s, const uint32_t* pos_s, uint64_t m, uint32_t n_pos,
@@ -212,9 +158,7 @@ __global__ void __launch_bounds__(256) sigma_rotate(const uint32_t* var_s, const
 }
 
 // ---------------------------------------------------------------------------------------------------------------- encode
-// consts: K_0..K_3 (Montgomery), then omega^(2^j), j < MAX_LOG_N.  omega^row is the product of omega^(2^j) over the set bits of row:
-// no n-entry table to build, keep and gather from.
-constexpr uint32_t N_CONSTS = 4 + MAX_LOG_N;
+// consts: fill_id_consts (domain.cuh)
 struct EvalPtrs {
     void* p[4];
 };
@@ -231,9 +175,7 @@ __global__ void __launch_bounds__(256) sigma_encode(uint32_t* sigma_pos, uint32_
     }
     if (!out.p[0]) return;
     const uint32_t row = s & (uint32_t)(n - 1);
-    Fr r = ld_fr<Fr>(consts, s >> log_n);
-    for (uint32_t j = 0; j < log_n; ++j)
-        if ((row >> j) & 1u) r = Fr::mul(r, ld_fr<Fr>(consts, 4 + j));
+    const Fr r = id_encode<Fr>(consts, s >> log_n, row, log_n);
     const uint32_t w = (uint32_t)(p >> log_n);
     void* dst = w == 0 ? out.p[0] : w == 1 ? out.p[1] : w == 2 ? out.p[2] : out.p[3];
     st_fr<Fr>(dst, p & (n - 1), r);
@@ -255,21 +197,12 @@ __global__ void __launch_bounds__(256) fr_gather(const void* values, uint64_t nu
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-int scan_in_place(zk_ctx* c, uint32_t* d_data, uint64_t len, uint32_t* d_sums) {
-    const uint64_t n_chunks = blocks_of(len, SCAN_CHUNK);
-    hipLaunchKernelGGL(scan_sums, dim3((unsigned)n_chunks), dim3(SCAN_T), 0, c->stream, d_data, len, d_sums);
-    hipLaunchKernelGGL(scan_top, dim3(1), dim3(SCAN_T), 0, c->stream, d_sums, n_chunks);
-    hipLaunchKernelGGL(scan_apply, dim3((unsigned)n_chunks), dim3(SCAN_T), 0, c->stream, d_data, len, (const uint32_t*)d_sums);
-    ZK_HIP_TRY(hipGetLastError());
-    return ZK_OK;
-}
-
 template <class Cv>
 int sigma_impl(zk_ctx* c, uint32_t log_n, const uint32_t* ins_var, const uint32_t* ins_pos, size_t m, uint32_t num_vars,
                uint32_t* d_sigma_pos, void* const* d_evals) {
     typedef typename Cv::Fr Fr;
-    if (log_n > (uint32_t)Cv::FrP::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
-    if (log_n > MAX_LOG_N) return ZK_ERR_UNSUPPORTED;
+    if (!domain_log_ok<Cv>(log_n)) return ZK_ERR_DOMAIN_TOO_LARGE;
+    if (log_n > ID_MAX_LOG_N) return ZK_ERR_UNSUPPORTED;
     const uint64_t n = (uint64_t)1 << log_n, n_pos = 4 * n;
     if (m > n_pos) return ZK_ERR_BAD_ARG;
     // radix passes: as many as num_vars - 1 has digits (none when there is one variable: the call sequence is its run)
@@ -279,7 +212,7 @@ int sigma_impl(zk_ctx* c, uint32_t log_n, const uint32_t* ins_var, const uint32_
     const uint64_t n_tiles = blocks_of(m, SORT_TILE);
     const uint64_t hist_len = passes ? RADIX * n_tiles : 0;
     // offsets behind the flag word (run_flagged)
-    const size_t o_consts = 0, o_hist = o_consts + up256(N_CONSTS * 32), o_sums = o_hist + up256(hist_len * 4),
+    const size_t o_consts = 0, o_hist = o_consts + up256(ID_N_CONSTS * 32), o_sums = o_hist + up256(hist_len * 4),
                  o_sort = o_sums + up256(blocks_of(hist_len, SCAN_CHUNK) * 4), sort_one = up256(m * 4),
                  o_pos = o_sort + (passes >= 2 ? 4 : passes ? 2 : 0) * sort_one, total = o_pos + (d_sigma_pos ? 0 : up256(n_pos * 4));
     hipStream_t st = c->stream;
@@ -301,8 +234,7 @@ int sigma_impl(zk_ctx* c, uint32_t log_n, const uint32_t* ins_var, const uint32_
                     uint32_t* val_out = (uint32_t*)(w + o_sort + (size_t)(2 * (i & 1u) + 1) * sort_one);
                     hipLaunchKernelGGL(sigma_sort_pass<false>, dim3((unsigned)n_tiles), dim3(SORT_T), 0, st, var_s, pos_s, (uint64_t)m, 8 * i,
                                        (uint32_t)n_tiles, d_hist, (uint32_t*)nullptr, (uint32_t*)nullptr);
-                    const int r2 = scan_in_place(c, d_hist, hist_len, d_sums);
-                    if (r2) return r2;
+                    scan_excl<uint32_t, SCAN_T, SCAN_ITEMS>(d_hist, d_hist, hist_len, d_sums, nullptr, st);
                     hipLaunchKernelGGL(sigma_sort_pass<true>, dim3((unsigned)n_tiles), dim3(SORT_T), 0, st, var_s, pos_s, (uint64_t)m, 8 * i,
                                        (uint32_t)n_tiles, d_hist, key_out, val_out);
                     var_s = key_out;
@@ -318,16 +250,8 @@ int sigma_impl(zk_ctx* c, uint32_t log_n, const uint32_t* ins_var, const uint32_
         EvalPtrs out = {{nullptr, nullptr, nullptr, nullptr}};
         if (d_evals) {
             for (int k = 0; k < 4; ++k) out.p[k] = d_evals[k];
-            Fr cs[N_CONSTS];
-            const uint32_t K[4] = {1, 7, 13, 17};                  // permutation/constants.rs:12-22
-            for (int k = 0; k < 4; ++k) cs[k] = Fr::from_u32(K[k]);
-            Fr pw;
-            for (int i = 0; i < Fr::N; ++i) pw.v[i] = Cv::FrP::ROOT(i);
-            for (uint32_t k = log_n; k < (uint32_t)Cv::FrP::TWO_ADICITY; ++k) pw = Fr::sqr(pw);
-            for (uint32_t j = 0; j < MAX_LOG_N; ++j) {
-                cs[4 + j] = pw;
-                pw = Fr::sqr(pw);
-            }
+            Fr cs[ID_N_CONSTS];
+            fill_id_consts<Cv>(log_n, cs);
             const int r2 = zk_h2d(c, w + o_consts, cs, sizeof cs, st);
             if (r2) return r2;
         }

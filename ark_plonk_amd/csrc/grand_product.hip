@@ -12,7 +12,7 @@
 // Field elements are canonical Montgomery residues, so the result is bit-identical with the serial loop.
 // A zero denominator makes the reference panic (`inverse().unwrap()`); here it is ZK_ERR_NOT_INVERTIBLE.
 #include "ctx.h"
-#include "fr_io.cuh"
+#include "domain.cuh"
 
 namespace {
 
@@ -24,7 +24,7 @@ struct PermArgs {
     const void* w[4];
     const void* s[4];
     Fr beta, gamma;
-    Fr bk[4];        // beta * K_k, K = (1, 7, 13, 17)  (permutation/constants.rs:12-22)
+    Fr bk[4];        // beta * K_k, K = PERM_K (domain.cuh)
     Fr omega;        // group generator of the size-n domain
     Fr omega_t;      // omega^TERM_T
 };
@@ -215,7 +215,7 @@ template <class C>
 int perm_product(zk_ctx* c, uint32_t log_n, const void* const* d_wires, const void* const* d_sigmas, const uint64_t* beta_mont,
                  const uint64_t* gamma_mont, void* d_out, uint64_t* last_mont) {
     typedef typename C::Fr Fr;
-    if (log_n > (uint32_t)C::FrP::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
+    if (!domain_log_ok<C>(log_n)) return ZK_ERR_DOMAIN_TOO_LARGE;
     const uint64_t n = 1ull << log_n;
     int rc;
     if ((rc = c->io.a.ensure(n * 32))) return rc;
@@ -223,15 +223,12 @@ int perm_product(zk_ctx* c, uint32_t log_n, const void* const* d_wires, const vo
     PermArgs<Fr> a;
     memcpy(a.beta.v, beta_mont, 32);
     memcpy(a.gamma.v, gamma_mont, 32);
-    const uint32_t K[4] = {1, 7, 13, 17};
     for (int k = 0; k < 4; ++k) {
         a.w[k] = d_wires[k];
         a.s[k] = d_sigmas[k];
-        a.bk[k] = Fr::mul(a.beta, Fr::from_u32(K[k]));
+        a.bk[k] = Fr::mul(a.beta, Fr::from_u32(PERM_K[k]));
     }
-    Fr root;
-    for (int i = 0; i < Fr::N; ++i) root.v[i] = C::FrP::ROOT(i);
-    for (uint32_t k = log_n; k < (uint32_t)C::FrP::TWO_ADICITY; ++k) root = Fr::sqr(root);
+    const Fr root = domain_root<C>(log_n);
     a.omega = root;
     a.omega_t = Fr::pow_u64(root, TERM_T);
     ProfScope ps(c, "grand_product");

@@ -295,10 +295,7 @@ int open_prepare(zk_ctx* c, uint32_t n_polys, const void* const* d_polys, const 
     if (m <= 1) return ZK_OK;
     // z and chi are not validated here (the other entry points refuse an unreduced scalar: fr_reduced); an unreduced word stands for
     // its residue, as it always did: z * 1 is that residue, reduced, and chi enters through products only.
-    Fr z, chi;
-    memcpy(z.v, z_mont, 32);
-    memcpy(chi.v, chal_mont, 32);
-    z = Fr::mul(z, Fr::one());
+    const Fr z = Fr::mul(fr_arg<Fr>(z_mont), Fr::one()), chi = fr_arg<Fr>(chal_mont);
     RlcArgs a;
     memset(&a, 0, sizeof a);
     a.n_polys = n_polys;

@@ -15,6 +15,7 @@
 //    t's positions (odd-bucket parity; evens and odds offsets, packed in one 64-bit scan) and an output-parallel fill that finds its bucket by binary search in the offsets.  No sort, like the reference; results are the
 //    reference's exactly because the emission order is a function of (first index in t, count) only.
 #include "ctx.h"
+#include "dev_scan.cuh"
 #include "zbound.cuh"
 
 namespace {
@@ -162,78 +163,8 @@ __global__ void ls_emit_counts(uint32_t n_t, const uint32_t* slots, const uint32
     eo[i] = v;
 }
 
-// ---- exclusive scan of n values (n <= SCAN_BLOCK^2), out has n + 1 entries (out[n] = total) --------------------------------
+// the geometry of the two scans over t's positions (dev_scan.cuh); out has n_t + 1 entries, out[n_t] = total
 constexpr uint32_t SCAN_T = 1024, SCAN_PER = 4, SCAN_BLOCK = SCAN_T * SCAN_PER;
-
-template <class T>
-ZK_D T block_excl_scan(T v, T* sh, T& total) {       // exclusive scan of one value per thread over the workgroup
-    const uint32_t u = threadIdx.x;
-    sh[u] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < SCAN_T; d <<= 1) {
-        T o = u >= d ? sh[u - d] : T(0);
-        __syncthreads();
-        sh[u] += o;
-        __syncthreads();
-    }
-    total = sh[SCAN_T - 1];
-    return sh[u] - v;
-}
-template <class T>
-__global__ void __launch_bounds__(SCAN_T) scan_blocks(const T* in, uint32_t n, T* out, T* block_tot) {
-    __shared__ T sh[SCAN_T];
-    const uint32_t base = blockIdx.x * SCAN_BLOCK + threadIdx.x * SCAN_PER;
-    T v[SCAN_PER], sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN_PER; ++k) {
-        v[k] = base + k < n ? in[base + k] : T(0);
-        sum += v[k];
-    }
-    T tot;
-    T run = block_excl_scan<T>(sum, sh, tot);
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN_PER; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-    }
-    if (threadIdx.x == 0) block_tot[blockIdx.x] = tot;
-}
-template <class T>
-__global__ void __launch_bounds__(SCAN_T) scan_totals(T* block_tot, uint32_t n_blocks, T* grand) {
-    __shared__ T sh[SCAN_T];
-    const uint32_t base = threadIdx.x * SCAN_PER;
-    T v[SCAN_PER], sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN_PER; ++k) {
-        v[k] = base + k < n_blocks ? block_tot[base + k] : T(0);
-        sum += v[k];
-    }
-    T tot;
-    T run = block_excl_scan<T>(sum, sh, tot);
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN_PER; ++k) {
-        if (base + k < n_blocks) block_tot[base + k] = run;
-        run += v[k];
-    }
-    if (threadIdx.x == 0) *grand = tot;
-}
-template <class T>
-__global__ void __launch_bounds__(SCAN_T) scan_add(T* out, uint32_t n, const T* block_tot) {
-    const uint32_t base = blockIdx.x * SCAN_BLOCK + threadIdx.x * SCAN_PER;
-    const T off = block_tot[blockIdx.x];
-#pragma unroll
-    for (uint32_t k = 0; k < SCAN_PER; ++k)
-        if (base + k < n) out[base + k] += off;
-}
-template <class T>
-int scan_excl(const T* in, uint32_t n, T* out /* n + 1 */, T* block_tot /* >= ceil(n / SCAN_BLOCK) */, hipStream_t st) {
-    const uint32_t nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    if (nb > SCAN_BLOCK) return ZK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(scan_blocks<T>, dim3(nb), dim3(SCAN_T), 0, st, in, n, out, block_tot);
-    hipLaunchKernelGGL(scan_totals<T>, dim3(1), dim3(SCAN_T), 0, st, block_tot, nb, out + n);
-    hipLaunchKernelGGL(scan_add<T>, dim3(nb), dim3(SCAN_T), 0, st, out, n, block_tot);
-    return ZK_OK;
-}
 
 // output position p of one half takes the value of the last position i of t whose offset is <= p (offsets are
 // non-decreasing; the positions after an owner that emit nothing repeat the NEXT offset, which is > p)
@@ -266,10 +197,7 @@ __global__ void lookup_query(QueryArgs a, uint64_t n, void* out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     bool sel = false;
-    if (i < a.q_len) {
-        const El q = ld_el(a.q_lookup, i);
-        sel = (q.a.x | q.a.y | q.a.z | q.a.w | q.b.x | q.b.y | q.b.z | q.b.w) != 0;
-    }
+    if (i < a.q_len) sel = !el_zero(ld_el(a.q_lookup, i));
     uint4* o = reinterpret_cast<uint4*>(out) + 2 * i;
     if (!sel) {                                   // prover.rs:262-264: the first row of the compressed table, then zeros
         const El d = ld_el(a.table, 0);
@@ -354,10 +282,10 @@ int lookup_combine_split_dev(zk_ctx* c, const void* d_t, size_t n_t, const void*
                                M - 1, cnt, err);
         hipLaunchKernelGGL(ls_owner_odd, dim3(gt), dim3(T), 0, st, (uint32_t)n_t, (const uint32_t*)slots, (const uint32_t*)slot_of,
                            (const uint32_t*)cnt, odd);
-        if ((rc = scan_excl<uint32_t>(odd, (uint32_t)n_t, par, (uint32_t*)btot, st))) return rc;
+        scan_excl<uint32_t, SCAN_T, SCAN_PER>(odd, par, n_t, (uint32_t*)btot, par + n_t, st);
         hipLaunchKernelGGL(ls_emit_counts, dim3(gt), dim3(T), 0, st, (uint32_t)n_t, (const uint32_t*)slots, (const uint32_t*)slot_of,
                            (const uint32_t*)cnt, (const uint32_t*)par, eo);
-        if ((rc = scan_excl<uint64_t>(eo, (uint32_t)n_t, off, btot, st))) return rc;
+        scan_excl<uint64_t, SCAN_T, SCAN_PER>(eo, off, n_t, btot, off + n_t, st);
         ZK_HIP_TRY(hipGetLastError());
     }
     // the totals decide the launch sizes of the fill (and ElementNotIndexed must surface before anything is written)

@@ -17,7 +17,7 @@
 // twiddles stored as w * 2^261 mod r so the data never leave the arkworks (R = 2^256) domain.
 // HBM-side the transform is 2 * N * 32 B algorithmic bytes; the kernel is integer-VALU bound.
 #include "ctx.h"
-#include "fr_io.cuh"
+#include "domain.cuh"
 
 #include "ntt_pass.cuh"
 
@@ -104,15 +104,6 @@ __global__ void fr_mul_kernel(const void* a, const void* b, void* out, uint64_t 
 }
 
 // ------------------------------------------------------------------------------------ host side
-template <class C>
-typename C::Fr root_of_unity_host(uint32_t log_n) {
-    typedef typename C::Fr Fr;
-    Fr r;
-    for (int i = 0; i < Fr::N; ++i) r.v[i] = C::FrP::ROOT(i);
-    for (uint32_t k = log_n; k < (uint32_t)C::FrP::TWO_ADICITY; ++k) r = Fr::sqr(r);
-    return r;
-}
-
 template <class Fr>
 PowBits<Fr> make_powbits(Fr base) {
     PowBits<Fr> pb;
@@ -174,7 +165,7 @@ int get_inner_tw(zk_ctx* c, int s, bool inverse, void** out) {
         (void)hipFree(packed);
         return ZK_ERR_OOM;
     }
-    Fr w = root_of_unity_host<C>((uint32_t)s);
+    Fr w = domain_root<C>((uint32_t)s);
     if (inverse) w = Fr::inverse(w);
     int rc = launch_pow_table<C>(c, packed, cnt, w, Fr::one(), 0, 0, 0);
     if (!rc) {
@@ -222,7 +213,7 @@ int get_plan(zk_ctx* c, uint32_t log_n, bool inverse, NttPlan** out) {
             uint64_t cnt = 1ull << log_mprev;
             hipError_t e = hipMalloc(&pl->tw_pass[p], cnt * sizeof(Fr));
             if (e != hipSuccess) { delete pl; return ZK_ERR_OOM; }
-            Fr w = root_of_unity_host<C>(log_mprev);
+            Fr w = domain_root<C>(log_mprev);
             if (inverse) w = Fr::inverse(w);
             int rc = launch_pow_table<C>(c, pl->tw_pass[p], cnt, w, Fr::one(), 1, log_m, log_mprev);
             if (rc) { delete pl; return rc; }
@@ -248,7 +239,7 @@ int ensure_coset(zk_ctx* c, bool inv, uint64_t len, void** out) {
         while (want < len) want <<= 1;
         int rc = buf.ensure(want * sizeof(Fr));
         if (rc) return rc;
-        Fr g = Fr::from_u32(C::FrP::GENERATOR);
+        Fr g = coset_gen<C>();
         if (inv) g = Fr::inverse(g);
         rc = launch_pow_table<C>(c, buf.p, want, g, Fr::one(), 0, 0, 0);
         if (rc) return rc;
@@ -277,7 +268,7 @@ int dispatch_pass(zk_ctx* c, int s, bool final_pass, const NttPassArgs& a) {
 template <class C>
 int ntt_run(zk_ctx* c, int kind, uint32_t log_n, uint32_t n_polys, const void* const* d_ins, const size_t* in_lens, void* const* d_outs) {
     typedef typename C::Fr Fr;
-    if (log_n > (uint32_t)C::FrP::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
+    if (!domain_log_ok<C>(log_n)) return ZK_ERR_DOMAIN_TOO_LARGE;
     if (n_polys == 0 || n_polys > 16) return ZK_ERR_BAD_ARG;
     const uint64_t N = 1ull << log_n;
     size_t in_len = 0;               // the longest input of the batch
@@ -293,9 +284,9 @@ int ntt_run(zk_ctx* c, int kind, uint32_t log_n, uint32_t n_polys, const void* c
     int rc;
     Fr n_inv = Fr::inverse(Fr::from_u64(N));
     if (log_n < 3) {
-        Fr w = root_of_unity_host<C>(log_n);
+        Fr w = domain_root<C>(log_n);
         if (inverse) w = Fr::inverse(w);
-        Fr g = Fr::from_u32(C::FrP::GENERATOR);
+        Fr g = coset_gen<C>();
         Fr pre_g = kind == ZK_NTT_COSET_FFT ? g : Fr::one();
         Fr post_g = kind == ZK_NTT_COSET_IFFT ? Fr::inverse(g) : Fr::one();
         ProfScope ps(c, "ntt_pass");
@@ -413,7 +404,7 @@ int ntt_prepare(zk_ctx* c, int curve, uint32_t log_n) {
     for (int inv = 0; inv < 2; ++inv) {
         const int rc = zk_on_curve(curve, ZK_ERR_BAD_ARG, [&](auto cv) {
             typedef decltype(cv) Cv;
-            if (log_n > (uint32_t)Cv::FrP::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
+            if (!domain_log_ok<Cv>(log_n)) return ZK_ERR_DOMAIN_TOO_LARGE;
             return get_plan<Cv>(c, log_n, inv != 0, &pl);
         });
         if (rc) return rc;

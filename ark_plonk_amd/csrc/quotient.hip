@@ -15,6 +15,7 @@
 //     unity: 4 inversions on the host instead of 4n;
 //   * l1_alpha_sq = coset_fft(alpha^2 L1) (quotient_poly.rs:292-294) is alpha^2 * l1 by linearity.
 #include "ctx.h"
+#include "domain.cuh"
 #include "zbound.cuh"
 
 namespace {
@@ -163,7 +164,7 @@ template <class C>
 int quotient_run(zk_ctx* c, uint32_t log_n, const zk_quotient_args* q, void* d_out) {
     typedef typename C::Fr Fr;
     typedef typename C::FrU FU;
-    if (log_n + 2 > (uint32_t)C::FrP::TWO_ADICITY) return ZK_ERR_DOMAIN_TOO_LARGE;
+    if (!domain_log_ok<C>(log_n + 2)) return ZK_ERR_DOMAIN_TOO_LARGE;
     const uint64_t n = 1ull << log_n, n4 = 4 * n;
     static QArgsU<FU> A;          // 4 KiB: filled under the ctx lock of the caller ... and a process-wide one here
     static std::mutex a_mu;
@@ -173,16 +174,14 @@ int quotient_run(zk_ctx* c, uint32_t log_n, const zk_quotient_args* q, void* d_o
                                   q->q_fixed_group_add, q->q_variable_group_add, q->q_lookup, q->sigma[0], q->sigma[1], q->sigma[2], q->sigma[3]};
     for (const void* p : cols)
         if (!p) return ZK_ERR_BAD_ARG;
-    A.w_l = q->w_l; A.w_r = q->w_r; A.w_o = q->w_o; A.w_4 = q->w_4; A.z = q->z; A.z2 = q->z2; A.f = q->f; A.table = q->table;
-    A.h1 = q->h1; A.h2 = q->h2; A.pi = q->pi; A.l1 = q->l1;
-    A.q_m = q->q_m; A.q_l = q->q_l; A.q_r = q->q_r; A.q_o = q->q_o; A.q_4 = q->q_4; A.q_c = q->q_c; A.q_arith = q->q_arith;
-    A.q_range = q->q_range; A.q_logic = q->q_logic; A.q_fixed = q->q_fixed_group_add; A.q_var = q->q_variable_group_add; A.q_lookup = q->q_lookup;
+    fill_gate_columns(A, q);
+    A.z = q->z; A.z2 = q->z2; A.f = q->f; A.table = q->table; A.h1 = q->h1; A.h2 = q->h2; A.l1 = q->l1; A.q_lookup = q->q_lookup;
     for (int k = 0; k < 4; ++k) A.sigma[k] = q->sigma[k];
-    auto ldc = [](const uint64_t* src) { Fr v; memcpy(v.v, src, 32); return v; };
+    fill_gate_consts<C>(A, q->coeff_a, q->coeff_d, QTAB);
+    auto ldc = fr_arg<Fr>;
     auto U = [](const Fr& v) { return to_rp_host<C>(v); };
     const Fr alpha = ldc(q->alpha), beta = ldc(q->beta), delta = ldc(q->delta), eps = ldc(q->epsilon);
     A.alpha = U(alpha); A.beta = U(beta); A.gamma = U(ldc(q->gamma)); A.delta = U(delta); A.eps = U(eps); A.zeta = U(ldc(q->zeta));
-    A.coeff_a = U(ldc(q->coeff_a)); A.coeff_d = U(ldc(q->coeff_d)); A.one = U(Fr::one());
     A.alpha_sq = U(Fr::sqr(alpha));
     const Fr opd = Fr::add(Fr::one(), delta);
     A.one_plus_delta = U(opd);
@@ -215,16 +214,11 @@ int quotient_run(zk_ctx* c, uint32_t log_n, const zk_quotient_args* q, void* d_o
         kappas(q->var_base_challenge, A.var, 3);
         // the lookup widget uses plain powers s, s^2, s^3 (widget/lookup.rs:97-151): already in place
     }
-    const uint32_t Kp[4] = {1, 7, 13, 17};   // permutation/constants.rs:12-22
-    for (int k = 0; k < 4; ++k) A.bk[k] = U(Fr::mul(beta, Fr::from_u32(Kp[k])));
-    A.c2 = U(Fr::from_u32(2)); A.c3 = U(Fr::from_u32(3)); A.c4 = U(Fr::from_u32(4)); A.c9 = U(Fr::from_u32(9));
-    A.c18 = U(Fr::from_u32(18)); A.c81 = U(Fr::from_u32(81)); A.c83 = U(Fr::from_u32(83));
-    Fr root;
-    for (int i = 0; i < Fr::N; ++i) root.v[i] = C::FrP::ROOT(i);
-    for (uint32_t k = log_n + 2; k < (uint32_t)C::FrP::TWO_ADICITY; ++k) root = Fr::sqr(root);
+    for (int k = 0; k < 4; ++k) A.bk[k] = U(Fr::mul(beta, Fr::from_u32(PERM_K[k])));
+    const Fr root = domain_root<C>(log_n + 2);
     A.omega = U(root);
     A.omega_t = U(Fr::pow_u64(root, QT));
-    const Fr g = Fr::from_u32(C::FrP::GENERATOR);
+    const Fr g = coset_gen<C>();
     A.g = U(g);
     // v_h over the coset takes 4 values: g^n * (omega^n)^k - 1; the stored inverse carries 2^-5 (R'/R)
     const Fr gn = Fr::pow_u64(g, n), wn = Fr::pow_u64(root, n);
@@ -236,7 +230,6 @@ int quotient_run(zk_ctx* c, uint32_t log_n, const zk_quotient_args* q, void* d_o
         A.inv_vh[k] = U(Fr::mul(Fr::inverse(vh), inv32));
         cur = Fr::mul(cur, wn);
     }
-    rp_table<C>(A.rtab, QTAB, A.ratio_fx, A.top_shift);
     ProfScope ps(c, "quotient");
     int rc = c->msm_tmp.ensure(sizeof A);
     if (rc) return rc;

@@ -8,7 +8,7 @@
 // constants of the curve, so every lane that reaches a loop takes the same branches in it.
 #include "api_internal.h"
 #include "block_inverse.cuh"
-#include "fr_io.cuh"
+#include "domain.cuh"
 
 namespace {
 
@@ -242,10 +242,7 @@ __global__ void __launch_bounds__(VT) verify_scalars(ScalarArgs A) {
     auto Ev = [&](int k) { return ld_fr<Fr>(A.evals, j * ZK_VERIFY_N_EVALS + k); };
     const Fr one = Fr::one();
     const Fr z = Ch(C_Z);
-    Fr w;                                                    // the root of unity of size n
-#pragma unroll
-    for (int i = 0; i < Fr::N; ++i) w.v[i] = FrP::ROOT(i);
-    for (uint32_t k = A.log_n; k < (uint32_t)FrP::TWO_ADICITY; ++k) w = Fr::sqr(w);
+    const Fr w = domain_root<FrP, Fr>(A.log_n);              // the root of unity of size n
     const Fr n_fr = Fr::from_u64((uint64_t)1 << A.log_n);
 
     // ---- the denominators: n (z - w^pos) per public input, then n (z - 1)
@@ -339,7 +336,7 @@ __global__ void __launch_bounds__(VT) verify_scalars(ScalarArgs A) {
     lp[P_H1] = Fr::neg(z2n * ls2 * (e1d + h2 + de * h1n));
     // permutation.rs:327-388
     const Fr bz = be * z;
-    lp[P_Z] = (a + bz + ga) * (b + Fr::from_u32(7) * bz + ga) * (c + Fr::from_u32(13) * bz + ga) * ((d + Fr::from_u32(17) * bz + ga) * al) + l1 * al2;
+    lp[P_Z] = (a + bz + ga) * (b + Fr::from_u32(PERM_K[1]) * bz + ga) * (c + Fr::from_u32(PERM_K[2]) * bz + ga) * ((d + Fr::from_u32(PERM_K[3]) * bz + ga) * al) + l1 * al2;
     lin[K_S3] = Fr::neg(sig * (be * perm * al));
     // proof.rs:590-606: -Z_H(z) z^(k n)
     Fr zp = one;

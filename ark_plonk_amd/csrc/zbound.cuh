@@ -159,5 +159,30 @@ void rp_table(uint32_t (*rtab)[Cv::FrU::NL], uint32_t len, uint32_t& ratio_fx, u
     static_assert(Cv::FrP::BITS - 29 * (FU::NL - 1) >= 3, "to_rp reads three bits below the 2^BITS place of the top limb");
     top_shift = (uint32_t)(Cv::FrP::BITS - 29 * (FU::NL - 1));
 }
+// The host side of the gate-argument blocks (QArgsU of quotient.hip, CArgsU of check.hip, from zk_quotient_args and
+// zk_circuit_check_args): what the two share, assigned by member name, so that neither layout matters.
+// the 4 x 64-bit words of an ABI argument as they are: no reduced-element test (fr_reduced, fr_io.cuh, where one is made)
+template <class Fr>
+Fr fr_arg(const uint64_t* m) {
+    Fr v;
+    memcpy(v.v, m, 32);
+    return v;
+}
+template <class A, class Q>
+void fill_gate_columns(A& a, const Q* q) {
+    a.w_l = q->w_l; a.w_r = q->w_r; a.w_o = q->w_o; a.w_4 = q->w_4; a.pi = q->pi;
+    a.q_m = q->q_m; a.q_l = q->q_l; a.q_r = q->q_r; a.q_o = q->q_o; a.q_4 = q->q_4; a.q_c = q->q_c; a.q_arith = q->q_arith;
+    a.q_range = q->q_range; a.q_logic = q->q_logic; a.q_fixed = q->q_fixed_group_add; a.q_var = q->q_variable_group_add;
+}
+// the curve coefficients, the small integers of the widgets and what to_rp reads (table_len rows of a.rtab)
+template <class Cv, class A>
+void fill_gate_consts(A& a, const uint64_t* coeff_a, const uint64_t* coeff_d, uint32_t table_len) {
+    typedef typename Cv::Fr Fr;
+    auto U = [](const Fr& v) { return to_rp_host<Cv>(v); };
+    a.coeff_a = U(fr_arg<Fr>(coeff_a)); a.coeff_d = U(fr_arg<Fr>(coeff_d)); a.one = U(Fr::one());
+    a.c2 = U(Fr::from_u32(2)); a.c3 = U(Fr::from_u32(3)); a.c4 = U(Fr::from_u32(4)); a.c9 = U(Fr::from_u32(9));
+    a.c18 = U(Fr::from_u32(18)); a.c81 = U(Fr::from_u32(81)); a.c83 = U(Fr::from_u32(83));
+    rp_table<Cv>(a.rtab, table_len, a.ratio_fx, a.top_shift);
+}
 
 }  // namespace

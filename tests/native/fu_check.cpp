@@ -17,6 +17,7 @@ struct uint4 {                            // the 16-byte vector type of the devi
 static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
 #endif
 #include "../../ark_plonk_amd/csrc/fr_io.cuh"
+#include "../../ark_plonk_amd/csrc/domain.cuh"
 #include "../../ark_plonk_amd/csrc/zbound.cuh"
 #include "fb_field.h"                     // the checked signed-limb field Fb: the contract of fields.cuh at every call
 #include "fb_laws.h"                      // ecu.cuh and ecq.cuh over Fb, one run per branch (brings in ecq.cuh with host wave primitives)
@@ -176,6 +177,34 @@ static void pack_rp_many(const uint32_t* words_in, uint32_t* packed_out, uint32_
         memcpy(product_out + 8 * k, m.v, 32);
     }
 }
+// the domain constants (domain.cuh) as stored words, and the shared constants of the two gate-argument blocks (fill_gate_consts,
+// zbound.cuh) filled into a block of the harness's own: the members the filler names, in an order neither kernel's block has
+template <class Cv>
+static void id_consts_of(uint32_t log_n, uint32_t* words_out) {
+    typename Cv::Fr cs[ID_N_CONSTS];
+    fill_id_consts<Cv>(log_n, cs);
+    for (uint32_t k = 0; k < ID_N_CONSTS; ++k) memcpy(words_out + 8 * k, cs[k].v, 32);
+}
+template <class FU>
+struct GateBlock {
+    uint32_t top_shift, ratio_fx;
+    uint32_t rtab[RP_ROWS][FU::NL];
+    FU c83, c81, c18, c9, c4, c3, c2, one, coeff_d, coeff_a;
+};
+template <class Cv>
+static void gate_consts_of(const uint64_t* coeff_a, const uint64_t* coeff_d, uint32_t table_len, uint32_t* limbs_out, uint32_t* rtab_out,
+                           uint32_t* scalars_out) {
+    typedef typename Cv::FrU FU;
+    static GateBlock<FU> A;
+    fill_gate_consts<Cv>(A, coeff_a, coeff_d, table_len);
+    const FU* c[10] = {&A.coeff_a, &A.coeff_d, &A.one, &A.c2, &A.c3, &A.c4, &A.c9, &A.c18, &A.c81, &A.c83};
+    for (int k = 0; k < 10; ++k)
+        for (int i = 0; i < FU::NL; ++i) limbs_out[FU::NL * k + i] = c[k]->v[i];
+    for (uint32_t q = 0; q < table_len; ++q)
+        for (int i = 0; i < FU::NL; ++i) rtab_out[FU::NL * q + i] = A.rtab[q][i];
+    scalars_out[0] = A.ratio_fx;
+    scalars_out[1] = A.top_shift;
+}
 template <int W>
 static uint32_t key_hash_of(const uint32_t* words) {
     Key<W> k;
@@ -279,7 +308,26 @@ void fu_pack_rp(int field, const uint32_t* words_in, uint32_t* packed_out, uint3
     if (field == 1) pack_rp_many<HostBls>(words_in, packed_out, limbs_out, product_out, n);
     else pack_rp_many<HostBn>(words_in, packed_out, limbs_out, product_out, n);
 }
-int fu_rp_bound() { return RP_B; }       // a loaded value is < RP_B / 10 * r
+// field: 1 Fr-BLS, 3 Fr-BN.  domain.cuh: the two-adicity guard; the root of unity of the size-2^log_n domain (8 stored words); the
+// ID_N_CONSTS constants of the identity encoding (8 words each)
+int fu_domain_log_ok(int field, uint32_t log_n) { return field == 1 ? domain_log_ok<HostBls>(log_n) : domain_log_ok<HostBn>(log_n); }
+void fu_domain_root(int field, uint32_t log_n, uint32_t* words_out) {
+    if (field == 1) memcpy(words_out, domain_root<HostBls>(log_n).v, 32);
+    else memcpy(words_out, domain_root<HostBn>(log_n).v, 32);
+}
+int fu_id_n_consts() { return (int)ID_N_CONSTS; }
+void fu_id_consts(int field, uint32_t log_n, uint32_t* words_out) {
+    if (field == 1) id_consts_of<HostBls>(log_n, words_out);
+    else id_consts_of<HostBn>(log_n, words_out);
+}
+// table_len <= 64 rows.  limbs_out: coeff_a, coeff_d, one, c2, c3, c4, c9, c18, c81, c83 (FrU::NL limbs each); rtab_out: table_len rows;
+// scalars_out: ratio_fx, top_shift
+void fu_gate_consts(int field, const uint64_t* coeff_a, const uint64_t* coeff_d, uint32_t table_len, uint32_t* limbs_out, uint32_t* rtab_out,
+                    uint32_t* scalars_out) {
+    if (field == 1) gate_consts_of<HostBls>(coeff_a, coeff_d, table_len, limbs_out, rtab_out, scalars_out);
+    else gate_consts_of<HostBn>(coeff_a, coeff_d, table_len, limbs_out, rtab_out, scalars_out);
+}
+int fu_rp_bound() { return RP_B; }      // a loaded value is < RP_B / 10 * r
 int fu_rp_limbs() { return FrB::NL; }
 uint64_t fu_el_mix(uint64_t h, const uint32_t* words) { return el_mix(h, el_of(words)); }
 uint32_t fu_key_hash(int w, const uint32_t* words) { return w == 1 ? key_hash_of<1>(words) : key_hash_of<4>(words); }

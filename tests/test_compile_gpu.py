@@ -156,6 +156,29 @@ def test_sigma_large(cid, log_n, ctx, oracle_cpu):
     assert cr.cycle_count(got) == np.unique(var).shape[0] + int(never.sum())
 
 
+def test_sigma_digit_count_scan_second_top_chunk(ctx):
+    """m = 2^24 + 8192 insertions at n = 2^23: the digit counts of a radix pass, 256 per tile of 4096 keys, are 256 * 4098 > 1024^2
+    values, so the scan's single top workgroup (csrc/dev_scan.cuh, 1024 sums a chunk) goes round its loop a second time -- the
+    smallest such shape.  Three radix passes; positions only (nothing here depends on the field).  Variable v is inserted at calls v
+    and v + m/2, at the positions pos[k] = (5k + 3) mod 2^25 (a bijection: no cell twice), so sigma swaps pos[v] and pos[v + m/2]
+    and fixes every other cell; whole vectors are compared, the expected one built on the device."""
+    import torch
+    log_n, m = 23, (1 << 24) + 8192
+    h, n_pos = m // 2, 4 << log_n
+    k = torch.arange(m, dtype=torch.int64, device="cuda")
+    pos = (5 * k + 3) % n_pos
+    ins_var, ins_pos = (k % h).to(torch.int32), pos.to(torch.int32)
+    got = torch.empty(n_pos, dtype=torch.int32, device="cuda")
+    ctx.use_torch_stream()
+    rc = _lib.lib().zk_perm_sigma_dev(ctx.handle, 0, log_n, ins_var.data_ptr(), ins_pos.data_ptr(), m, h, got.data_ptr(), None)
+    torch.cuda.synchronize()
+    assert rc == 0
+    want = torch.arange(n_pos, dtype=torch.int64, device="cuda")
+    want[pos[:h]] = pos[h:]
+    want[pos[h:]] = pos[:h]
+    assert torch.equal(got.to(torch.int64), want)
+
+
 # ---- 4. bad input is a code, and the ctx works afterwards
 @pytest.mark.parametrize("cid", [0, 1])
 def test_bad_input_is_refused(cid, ctx):

@@ -27,7 +27,7 @@ SO = os.path.join(ROOT, "tests", "native", "libfu_check.so")
 @pytest.fixture(scope="module")
 def fu():
     deps = [SRC] + [os.path.join(ROOT, "tests", "native", f) for f in ("fb_field.h", "fb_laws.h")]
-    deps += [os.path.join(ROOT, "ark_plonk_amd", "csrc", f) for f in ("field_common.cuh", "fieldu.cuh", "fields.cuh", "ecu.cuh", "ecq.cuh", "curve_params.h", "zk_common.h", "field.cuh", "fr_io.cuh", "zbound.cuh")]
+    deps += [os.path.join(ROOT, "ark_plonk_amd", "csrc", f) for f in ("field_common.cuh", "fieldu.cuh", "fields.cuh", "ecu.cuh", "ecq.cuh", "curve_params.h", "zk_common.h", "field.cuh", "fr_io.cuh", "domain.cuh", "zbound.cuh")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", SRC, "-o", SO])
     L = ctypes.CDLL(SO)
@@ -44,6 +44,13 @@ def fu():
     L.fu_to_rp.restype = None
     L.fu_pack_rp.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_uint64]
     L.fu_pack_rp.restype = None
+    L.fu_domain_log_ok.argtypes = [ctypes.c_int, ctypes.c_uint32]
+    L.fu_domain_root.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]
+    L.fu_domain_root.restype = None
+    L.fu_id_consts.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]
+    L.fu_id_consts.restype = None
+    L.fu_gate_consts.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 3
+    L.fu_gate_consts.restype = None
     L.fu_el_mix.argtypes = [ctypes.c_uint64, ctypes.c_void_p]
     L.fu_el_mix.restype = ctypes.c_uint64
     L.fu_key_hash.argtypes = [ctypes.c_int, ctypes.c_void_p]
@@ -721,6 +728,69 @@ def test_host_rprime_packer(field, fu):
         assert unwords(packed[8 * k:8 * k + 8]) == want, hex(w)
         assert unwords(prod[8 * k:8 * k + 8]) == want, hex(w)
         assert sum(int(limbs[nl * k + i]) << (29 * i) for i in range(nl)) == want, hex(w)
+
+
+# ---- the domain constants and the identity encoding (domain.cuh), the shared host fillers of the gate-argument blocks (zbound.cuh)
+@pytest.mark.parametrize("field", [1, 3])
+def test_domain_root_has_its_order(field, fu):
+    """domain_root(log_n), every log_n up to the two-adicity: its 2^log_n-th power is 1 and (log_n >= 1) its 2^(log_n - 1)-th is -1, so
+    its order is 2^log_n exactly; the guard admits the two-adicity and refuses the next size."""
+    cv = bo.BLS12_381 if field == 1 else bo.BN254
+    r, Rinv = cv.r, pow(1 << 256, -1, cv.r)
+    out = np.zeros(8, dtype="<u4")
+    for log_n in range(cv.two_adicity + 1):
+        assert fu.fu_domain_log_ok(field, log_n)
+        fu.fu_domain_root(field, log_n, out.ctypes.data)
+        assert unwords(out) < r
+        w = unwords(out) * Rinv % r
+        assert pow(w, 1 << log_n, r) == 1, log_n
+        if log_n >= 1:
+            assert pow(w, 1 << (log_n - 1), r) == r - 1, log_n
+        assert w == cv.root_of_unity(log_n), log_n
+    assert not fu.fu_domain_log_ok(field, cv.two_adicity + 1)
+
+
+@pytest.mark.parametrize("field,log_n", [(1, 13), (3, 9)])
+def test_identity_constants_against_integers(field, log_n, fu):
+    """fill_id_consts: K_0..K_3 = 1, 7, 13, 17 (the reference's permutation cosets), then omega^(2^j) for j < 28 -- the squares past
+    j = log_n are 1 -- as stored Montgomery words."""
+    cv = bo.BLS12_381 if field == 1 else bo.BN254
+    r, R = cv.r, 1 << 256
+    nc = fu.fu_id_n_consts()
+    assert nc == 4 + 28
+    out = np.zeros(8 * nc, dtype="<u4")
+    fu.fu_id_consts(field, log_n, out.ctypes.data)
+    w = cv.root_of_unity(log_n)
+    want = [1, 7, 13, 17] + [pow(w, 1 << j, r) for j in range(nc - 4)]
+    assert want[4 + log_n - 1] == r - 1 and want[4 + log_n] == 1
+    for k, v in enumerate(want):
+        assert unwords(out[8 * k:8 * k + 8]) == v * R % r, k
+
+
+@pytest.mark.parametrize("field", [1, 3])
+def test_gate_constants_against_integers(field, fu):
+    """fill_gate_consts, which fills the argument blocks of quotient.hip and check.hip: the ten shared constants are x R' mod r
+    (R' = 2^261) as normalised 29-bit limbs -- 32 w mod r for the two curve coefficients, which arrive as stored words w --; rtab[q] is
+    q r, ratio_fx = floor(2^(BITS + 10) / r) - 1, top_shift = BITS - 29 (NL - 1): what the two units' own fillers wrote."""
+    cv = bo.BLS12_381 if field == 1 else bo.BN254
+    r, nl = cv.r, fu.fu_rp_limbs()
+    rng = random.Random(0x6A + field)
+
+    def limbs(v):
+        return [(v >> (29 * i)) & ((1 << 29) - 1) for i in range(nl - 1)] + [v >> (29 * (nl - 1))]
+
+    for rows in sorted(set(_table_rows())) + [64]:
+        for wa, wd in ((0, r - 1), (rng.randrange(r), rng.randrange(r))):
+            ca, cd = np.frombuffer(wa.to_bytes(32, "little"), dtype="<u8").copy(), np.frombuffer(wd.to_bytes(32, "little"), dtype="<u8").copy()
+            lo, rt, sc = np.zeros(10 * nl, dtype="<u4"), np.zeros(rows * nl, dtype="<u4"), np.zeros(2, dtype="<u4")
+            fu.fu_gate_consts(field, ca.ctypes.data, cd.ctypes.data, rows, lo.ctypes.data, rt.ctypes.data, sc.ctypes.data)
+            want = [32 * wa % r, 32 * wd % r] + [x * (1 << 261) % r for x in (1, 2, 3, 4, 9, 18, 81, 83)]
+            for k, v in enumerate(want):
+                assert [int(x) for x in lo[nl * k:nl * (k + 1)]] == limbs(v), k
+            for q in range(rows):
+                assert [int(x) for x in rt[nl * q:nl * (q + 1)]] == limbs(q * r), q
+            bits = r.bit_length()
+            assert int(sc[0]) == (1 << (bits + 10)) // r - 1 and int(sc[1]) == bits - 29 * (nl - 1)
 
 
 # ---- the hash of the device key maps (fr_io.cuh) and its restatement

@@ -37,7 +37,8 @@ def test_combine_split_reference_vector(cid, ctx):
 
 
 @pytest.mark.parametrize("cid", [0, 1])
-@pytest.mark.parametrize("n_t,n_f,distinct", [(1, 0, 1), (1, 5, 1), (7, 7, 3), (1000, 1000, 37), (4099, 8191, 4099), (70001, 65536, 30000)])
+@pytest.mark.parametrize("n_t,n_f,distinct", [(1, 0, 1), (1, 5, 1), (7, 7, 3), (1000, 1000, 37), (4096, 4096, 4096), (4097, 1, 4097), (4099, 8191, 4099),
+                                                   (8192, 3, 5), (70001, 65536, 30000)])
 def test_combine_split_vs_oracle(cid, n_t, n_f, distinct, ctx):
     """Repeated table rows (a bucket's name is the FIRST index of its value), one value that most queries hit (the reference's
     dummy row), odd and even bucket sizes, an odd total (the halves differ by one), across workgroup and scan-block edges."""
