@@ -220,6 +220,9 @@ SYMBOLS = {
     "zk_g1_decompress_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "zk_proof_replay_batch": (c_int, [c_void_p, c_int, c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_size_t), c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ... and the same parse + replay on the device: every array a device pointer, `seeded` the host handle
+    "zk_proof_replay_batch_dev": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_verify_scalars_dev": (c_int, [c_void_p, c_int, c_u32, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_fr_column_sum_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_u32, c_void_p]),

@@ -29,6 +29,7 @@ FR_IO, ZBOUND, POINT_IO = ["fr_io.cuh"], ["fr_io.cuh", "zbound.cuh"], ["point_io
 DOMAIN, DEV_SCAN = ["fr_io.cuh", "domain.cuh"], ["dev_scan.cuh"]       # domain and permutation constants; the integer exclusive scan
 GADGET = ["gadget_common.cuh"]            # what the two units of the device composer (layout, witness) share
 BLOCK_INV = ["block_inverse.cuh"]         # one field inversion per workgroup: the key fold, the gadget witnesses, the verifier's scalars
+REPLAY = ["strobe.cuh", "replay_walk.cuh"]      # merlin's sponge and the verifier's parse + replay of one proof: host (wire) and device (replay)
 # the C ABI, one unit per subsystem (api_internal.h is what they share)
 API_UNITS = ("api_ctx", "residency", "srs", "commit", "round", "api_host", "api_poly")
 MSM_UNITS = ("msm_accumulate", "msm_reduce", "msm_sort", "msm_plan")      # heaviest first
@@ -38,7 +39,7 @@ def jobs():
     """(object name, source, extra defines, header deps)"""
     out = [(f"{u}.o", f"{u}.hip", [], API_HDRS + (DOMAIN if u == "api_poly" else [])) for u in API_UNITS] + [
         ("hostio.o", "hostio.hip", [], HOST_HDRS),
-        ("wire.o", "wire.hip", [], HOST_HDRS),
+        ("wire.o", "wire.hip", [], HOST_HDRS + REPLAY),
         ("kzg.o", "kzg.hip", [], HOST_HDRS + ZBOUND),
         ("lookup.o", "lookup.hip", [], HOST_HDRS + ZBOUND + DEV_SCAN),
         ("grand_product.o", "grand_product.hip", [], HOST_HDRS + DOMAIN),
@@ -59,6 +60,8 @@ def jobs():
         # the verifier's device side: batch decoding of compressed G1 points, per-proof scalars, the column sum of a fold (its host
         # side, parse and replay, is in wire.hip)
         ("verify.o", "verify.hip", [], API_HDRS + DOMAIN + BLOCK_INV),
+        # ... and the same parse and replay on the device, one proof per lane
+        ("replay.o", "replay.hip", [], API_HDRS + REPLAY),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

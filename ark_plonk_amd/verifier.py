@@ -11,10 +11,16 @@ and every proof of the batch is valid iff e(L, [tau]H) = e(R, H), except with pr
 is the caller's: this library has none.  Stages, each one entry point of the C ABI:
 
   1  zk_g1_decompress_batch_dev   the 15 points of every proof decoded and checked on the device (one lane per point)
-  2  zk_proof_replay_batch        host: bytes parsed, the transcript replayed -> 14 challenges and 23 evaluations per proof
+  2  zk_proof_replay_batch        host, serial: bytes parsed, the transcript replayed -> 14 challenges and 23 evaluations per proof
+     zk_proof_replay_batch_dev    the same parse and replay on the device, one proof per lane, the rows and the 15 point encodings
+                                  left where stages 1 and 3 read them (csrc/replay.hip; the walk is ONE piece of code for both)
   3  zk_verify_scalars_dev        per proof: 20 scalars over the verifier key's bases and G, 15 over its own points, 2 for L
   4  zk_fr_column_sum_dev + the existing MSM over the decoded points (zk_srs_register_dev, zk_msm_g1_srs_partial_dev,
      zk_g1_sum_partials), over any range [lo, hi) of the batch: the per-proof rows stay resident, another range costs only this stage
+
+`BatchVerifier(replay=...)` chooses stage 2: "host" decodes the points (1) while the host replays (2); "device" makes one upload and
+queues 2, 1, 3 behind it with no host synchronisation before the statuses come back; "auto" takes the device from
+REPLAY_ON_DEVICE_FROM proofs.  The two give bit-identical rows, statuses and (L, R).
 
 Field elements are 4 x uint64 Montgomery limbs and points `G1Affine`, as everywhere in this package.
 """
@@ -48,6 +54,10 @@ G1_OK, G1_BAD_FLAGS, G1_X_NOT_REDUCED, G1_NOT_ON_CURVE, G1_NOT_IN_SUBGROUP = ran
 (PROOF_OK, PROOF_TRUNCATED, PROOF_TRAILING, PROOF_BAD_OPTION, PROOF_FR_NOT_REDUCED, PROOF_MISSING_LABEL, PROOF_BAD_COUNT,
  PROOF_BAD_PUBLIC_INPUTS) = range(8)
 VERIFY_OK, VERIFY_BAD_POINT, VERIFY_Z_ON_DOMAIN = 0, 16, 32
+# BatchVerifier(replay="auto"): batches of at least this many proofs replay on the device.  The smallest B of the grid
+# {1, 8, 16, 32, 64, 128, 256, 1024, 4096} from which the device path's whole fold stays below the host path's
+# (profiles/verify/notes.md, the table of tools/verify_bench.py --replay host device); None: the device path never won
+REPLAY_ON_DEVICE_FROM = 1024
 
 
 def _torch():
@@ -118,6 +128,63 @@ def replay_batch(seeded, proofs, public_inputs=None, curve="bls12_381", with_poi
     return (ch, ev, st[:B], pts) if with_points else (ch, ev, st[:B])
 
 
+def _replay_dev(seeded, B, d_blob, n_bytes, d_poff, d_pioff, d_pos, d_vals, n_pi_total, cv, ctx):
+    """zk_proof_replay_batch_dev over arrays already on the device -> (challenges, evals, points, status), queued"""
+    torch = _torch()
+    dev = d_blob.device
+    g = lib().zk_g1_compressed_size(cv.curve_id)
+    ch = torch.empty((B, N_CHALLENGES, 4), dtype=torch.int64, device=dev)
+    ev = torch.empty((B, N_EVALS, 4), dtype=torch.int64, device=dev)
+    pts = torch.empty((B, N_PROOF_BASES, g), dtype=torch.uint8, device=dev)
+    st = torch.empty((B,), dtype=torch.uint8, device=dev)
+    ctx.use_torch_stream()
+    check(lib().zk_proof_replay_batch_dev(ctx.handle, seeded._h, cv.curve_id, B, ptr_of(d_blob), n_bytes, ptr_of(d_poff), ptr_of(d_pioff),
+                                          ptr_of(d_pos), ptr_of(d_vals), n_pi_total, ptr_of(ch), ptr_of(ev), ptr_of(pts), ptr_of(st)),
+          "zk_proof_replay_batch_dev")
+    return ch, ev, pts, st
+
+
+def _upload_batch(proofs, public_inputs, extra, dev):
+    """The inputs of a batch in ONE host buffer and one copy: the uint64 arrays first (proof offsets, public-input offsets, positions,
+    values, then `extra`), the proofs' bytes joined behind them.  Returns the device views and (bytes of proofs, public inputs)."""
+    torch = _torch()
+    B = len(proofs)
+    off, pos, vals = _flatten_public_inputs(public_inputs, B)
+    blob = b"".join(bytes(p) for p in proofs)
+    poff = np.zeros(B + 1, dtype=np.uint64)
+    np.cumsum([len(p) for p in proofs], out=poff[1:])
+    words = [poff, off, pos.reshape(-1), vals.reshape(-1)] + [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in extra]
+    starts, at = [], 0
+    for w in words:                                    # every array starts on 16 bytes: the kernels read field elements as 128-bit words
+        starts.append(at)
+        at += w.size + (w.size & 1)
+    host = np.zeros(8 * at + max(len(blob), 1), dtype=np.uint8)
+    head = host[:8 * at].view(np.uint64)
+    for w, o in zip(words, starts):
+        head[o:o + w.size] = w
+    host[8 * at:8 * at + len(blob)] = np.frombuffer(blob, dtype=np.uint8)
+    d = torch.from_numpy(host).to(dev)
+    d_words = d[:8 * at].view(torch.int64)
+    return [d_words[o:o + w.size] for w, o in zip(words, starts)], d[8 * at:], len(blob), int(off[B])
+
+
+def replay_batch_dev(seeded, proofs, public_inputs=None, curve="bls12_381", ctx: Context | None = None):
+    """Stage 2 on the device.  Arguments as `replay_batch`; the byte strings go up joined, with an offsets array, beside the flattened
+    public inputs.  Returns device tensors (challenges (B, 14, 4) int64, evaluations (B, 23, 4) int64, points (B, 15, g) uint8, status
+    (B,) uint8) with exactly the content `replay_batch(..., with_points=True)` returns; queued, not waited for."""
+    torch = _torch()
+    cv = get_curve(curve)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    B = len(proofs)
+    if B == 0:
+        g = lib().zk_g1_compressed_size(cv.curve_id)
+        return (torch.empty((0, N_CHALLENGES, 4), dtype=torch.int64, device=dev), torch.empty((0, N_EVALS, 4), dtype=torch.int64, device=dev),
+                torch.empty((0, N_PROOF_BASES, g), dtype=torch.uint8, device=dev), torch.empty((0,), dtype=torch.uint8, device=dev))
+    (d_poff, d_pioff, d_pos, d_vals), d_blob, n_bytes, n_pi = _upload_batch(proofs, public_inputs, [], dev)
+    return _replay_dev(seeded, B, d_blob, n_bytes, d_poff, d_pioff, d_pos, d_vals, n_pi, cv, ctx)
+
+
 def proof_point_bytes(proofs, curve="bls12_381") -> np.ndarray:
     """The 15 compressed points of every proof, (B, 15, g) uint8, by their fixed offsets (proof.rs:41-103: 13 commitments, then two
     openings followed by an Option byte each) -- no parsing, so stage 1 can start before stage 2.  A proof too short to hold them gets
@@ -162,6 +229,13 @@ def scalar_rows(log_n, challenges, evals, public_inputs, coeff_a, coeff_d, weigh
     w = ints_to_limbs([int(x) % cv.r for pair in weights for x in pair], 4) if B else np.zeros((1, 4), dtype=np.uint64)
     d_w = up(w)
     d_ps, d_pts = up(parse_status), up(point_status)
+    return _scalars_dev(log_n, B, d_ch, d_ev, d_off, d_pos, d_vals, coeff_a, coeff_d, d_w, d_ps, d_pts, cv, ctx)
+
+
+def _scalars_dev(log_n, B, d_ch, d_ev, d_off, d_pos, d_vals, coeff_a, coeff_d, d_w, d_ps, d_pts, cv, ctx):
+    """zk_verify_scalars_dev over arrays already on the device (coeff_a, coeff_d: host, 4 limbs) -> (key, proof, opening rows, status)"""
+    torch = _torch()
+    dev = d_ch.device
     key = torch.empty((B, N_KEY_BASES, 4), dtype=torch.int64, device=dev)
     prf = torch.empty((B, N_PROOF_BASES, 4), dtype=torch.int64, device=dev)
     opn = torch.empty((B, 2, 4), dtype=torch.int64, device=dev)
@@ -207,10 +281,15 @@ class BatchVerifier:
 
     vk: the dict `ProverKey.verifier_key` returns (name -> G1Affine); n: the circuit's domain size; seeded_transcript: the
     `transcript.Transcript` after `seed_transcript(vk, n)`; coeff_a, coeff_d: the embedded curve's coefficients (4 Montgomery limbs).
+    replay: where stage 2 runs -- "host", "device", or "auto" (the device from REPLAY_ON_DEVICE_FROM proofs); no result depends on it.
     The pairing check e(L, [tau]H) = e(R, H) is the caller's."""
 
-    def __init__(self, vk: dict, n: int, seeded_transcript, coeff_a, coeff_d, curve="bls12_381", ctx: Context | None = None):
+    def __init__(self, vk: dict, n: int, seeded_transcript, coeff_a, coeff_d, curve="bls12_381", ctx: Context | None = None,
+                 replay: str = "auto"):
         torch = _torch()
+        if replay not in ("host", "device", "auto"):
+            raise ValueError('replay is "host", "device" or "auto"')
+        self.replay = replay
         self.curve = get_curve(curve)
         self.ctx = ctx or default_context(0)
         if n <= 0 or n & (n - 1):
@@ -260,10 +339,13 @@ class BatchVerifier:
         if B == 0:
             self._res = _Resident(0, None, None, None, None, None, np.zeros(0, dtype=np.uint8))
             return self._res.status
-        # stage 1 first: the decode runs on the stream while the host replays the transcripts
-        pts, inf, pst = decompress_batch(proof_point_bytes(proofs, cv), cv, ctx)
-        ch, ev, parse_st = replay_batch(self.seeded, proofs, public_inputs, cv)
-        key, prf, opn, st = scalar_rows(self.log_n, ch, ev, public_inputs, self.coeff_a, self.coeff_d, weights, parse_st, pst, cv, ctx)
+        if self.replay_on_device(B):
+            pts, inf, key, prf, opn, st = self._stages_on_device(proofs, public_inputs, weights)
+        else:
+            # stage 1 first: the decode runs on the stream while the host replays the transcripts
+            pts, inf, pst = decompress_batch(proof_point_bytes(proofs, cv), cv, ctx)
+            ch, ev, parse_st = replay_batch(self.seeded, proofs, public_inputs, cv)
+            key, prf, opn, st = scalar_rows(self.log_n, ch, ev, public_inputs, self.coeff_a, self.coeff_d, weights, parse_st, pst, cv, ctx)
         L2 = 2 * cv.fq_limbs
         proof_ck = CommitterKey(pts, cv, ctx, infinity=inf)                       # proof-major: proof j owns bases [15 j, 15 j + 15)
         o_pts = pts.view(B, N_PROOF_BASES, L2)[:, 13:15].contiguous().view(2 * B, L2)
@@ -271,6 +353,28 @@ class BatchVerifier:
         open_ck = CommitterKey(o_pts, cv, ctx, infinity=o_inf)                    # the openings again, stride 2: the bases of L
         self._res = _Resident(B, key, prf, opn, proof_ck, open_ck, st.cpu().numpy())
         return self._res.status
+
+    def replay_on_device(self, n_proofs: int) -> bool:
+        """where stage 2 of a batch of n_proofs runs under this verifier's `replay` setting"""
+        if self.replay == "auto":
+            return REPLAY_ON_DEVICE_FROM is not None and n_proofs >= REPLAY_ON_DEVICE_FROM
+        return self.replay == "device"
+
+    def _stages_on_device(self, proofs, public_inputs, weights):
+        """Stages 2, 1, 3 behind ONE upload (proof bytes, offsets, public inputs, weights): the replay kernel's point encodings feed the
+        decode, its rows and statuses the scalars; nothing is waited for."""
+        torch = _torch()
+        cv, ctx = self.curve, self.ctx
+        B = len(proofs)
+        if len(weights) != B:
+            raise ValueError("one pair of weights per proof")
+        w = ints_to_limbs([int(x) % cv.r for pair in weights for x in pair], 4)
+        dev = torch.device("cuda", ctx.device)
+        (d_poff, d_pioff, d_pos, d_vals, d_w), d_blob, n_bytes, n_pi = _upload_batch(proofs, public_inputs, [w], dev)
+        ch, ev, enc, parse_st = _replay_dev(self.seeded, B, d_blob, n_bytes, d_poff, d_pioff, d_pos, d_vals, n_pi, cv, ctx)
+        pts, inf, pst = decompress_batch(enc, cv, ctx)
+        key, prf, opn, st = _scalars_dev(self.log_n, B, ch, ev, d_pioff, d_pos, d_vals, self.coeff_a, self.coeff_d, d_w, parse_st, pst, cv, ctx)
+        return pts, inf, key, prf, opn, st
 
     def rows(self):
         """The prepared batch's resident scalar rows: device tensors (key (B, 20, 4), proof (B, 15, 4), openings (B, 2, 4)), canonical."""

@@ -577,6 +577,19 @@ int zk_g1_decompress_batch_dev(zk_ctx* ctx, int curve_id, const void* d_in, size
 int zk_proof_replay_batch(const zk_transcript* seeded, int curve_id, size_t n_proofs, const uint8_t* const* proofs, const size_t* proof_lens,
                           const uint64_t* pi_offsets, const uint64_t* pi_positions, const uint64_t* pi_values_mont, uint64_t* out_challenges_mont,
                           uint64_t* out_evals_mont, uint8_t* out_points, uint8_t* out_status);
+/* Stage 2 on the device: the same parse and replay, one proof per lane (64 per workgroup), every array in device memory.  The proofs
+ * are one byte string d_proofs of proofs_bytes bytes, proof j being [d_proof_offsets[j], d_proof_offsets[j + 1]) of it (n_proofs + 1
+ * uint64); the public inputs are the three arrays of zk_proof_replay_batch with n_pi_total entries behind d_pi_offsets.  The four
+ * outputs have exactly the layout and content zk_proof_replay_batch writes (d_out_points may be NULL), so stages 1 and 3 take them where
+ * they are.  `seeded` is a host handle, read when the call is made and left untouched.  Queued on the ctx stream, no working memory.
+ * The offsets are data the host does not see, so where zk_proof_replay_batch returns ZK_ERR_BAD_ARG for them this call reports a
+ * status and reads nothing outside the buffers: a proof range that descends or ends beyond proofs_bytes is ZK_PROOF_TRUNCATED; a
+ * public-input range that descends or ends beyond n_pi_total is ZK_PROOF_BAD_PUBLIC_INPUTS (reported for a proof whose bytes parse: a
+ * malformed proof keeps the status of its bytes).  ZK_ERR_BAD_ARG: a null ctx or `seeded`, an unknown curve, a null array with
+ * n_proofs > 0 (the two public-input arrays only when n_pi_total > 0).  n_proofs == 0 is ZK_OK; n_proofs >= 2^31 ZK_ERR_UNSUPPORTED. */
+int zk_proof_replay_batch_dev(zk_ctx* ctx, const zk_transcript* seeded, int curve_id, size_t n_proofs, const void* d_proofs, size_t proofs_bytes,
+                              const void* d_proof_offsets, const void* d_pi_offsets, const void* d_pi_positions, const void* d_pi_values_mont,
+                              size_t n_pi_total, void* d_out_challenges_mont, void* d_out_evals_mont, void* d_out_points, void* d_out_status);
 
 /* Stage 3: the scalars of every proof's share of the two pairing inputs.  With u, u' the proof's two weights (d_weights: n_proofs x 2
  * canonical scalars), chi / chi' the aw / saw challenges and (C_k, v_k) the pairs of the two openings as Proof::verify forms them
