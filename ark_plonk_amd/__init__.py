@@ -20,12 +20,12 @@ from .circuit_check import BIT_NAMES, CheckReport, CircuitNotSatisfied, check_ci
 from . import composer  # noqa: F401  (gadget circuits and their witnesses, built on the device)
 from .composer import Composer  # noqa: F401
 from . import verifier  # noqa: F401  (batch verification up to the two pairing inputs)
-from .verifier import BatchVerifier  # noqa: F401
-from .msm import (CommitterKey, G1Affine, VariableBaseMSM, kzg_witness, srs_cache_config, srs_cache_stats, sum_partials,  # noqa: F401
-                  sum_partials_batch)
+from .verifier import BatchVerifier, IpaBatchVerifier  # noqa: F401
+from .msm import (CommitterKey, G1Affine, VariableBaseMSM, kzg_witness, srs_cache_config, segments_msm, srs_cache_stats,  # noqa: F401
+                  sum_partials, sum_partials_batch)
 
 __all__ = [
     "Context", "default_context", "BLS12_381", "BN254", "get_curve", "GeneralEvaluationDomain",
     "Radix2EvaluationDomain", "CommitterKey", "G1Affine", "VariableBaseMSM", "kzg_witness", "sum_partials", "sum_partials_batch", "srs_cache_stats", "srs_cache_config", "permutation", "quotient", "lookup", "linearisation", "prover", "transcript",
-    "verifier", "BatchVerifier", "composer", "Composer", "circuit_check", "check_circuit", "CheckReport", "CircuitNotSatisfied", "BIT_NAMES",
+    "verifier", "BatchVerifier", "IpaBatchVerifier", "segments_msm", "composer", "Composer", "circuit_check", "check_circuit", "CheckReport", "CircuitNotSatisfied", "BIT_NAMES",
 ]

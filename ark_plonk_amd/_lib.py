@@ -185,6 +185,9 @@ SYMBOLS = {
     "zk_ipa_check_coeffs_dev": (c_int, [c_void_p, c_int, c_u32, c_void_p, c_void_p]),
     "zk_ipa_check_combine_workspace_bytes": (c_size_t, [c_int, c_u32, c_size_t]),
     "zk_ipa_check_combine_dev": (c_int, [c_void_p, c_int, c_u32, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # segmented MSM: many small MSMs over one set of bases, each as a point
+    "zk_msm_g1_segments_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
     # circuit compilation: the wire permutation from the variable map, the witness gather
     "zk_perm_sigma_dev": (c_int, [c_void_p, c_int, c_u32, c_void_p, c_void_p, c_size_t, c_u32, c_void_p, ctypes.POINTER(c_void_p)]),
     "zk_fr_gather_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),

@@ -62,6 +62,8 @@ def jobs():
         ("verify.o", "verify.hip", [], API_HDRS + DOMAIN + BLOCK_INV),
         # ... and the same parse and replay on the device, one proof per lane
         ("replay.o", "replay.hip", [], API_HDRS + REPLAY),
+        # many small MSMs over one set of bases, each as a point: one wavefront per segment
+        ("g1_segments.o", "g1_segments.hip", [], API_HDRS + BLOCK_INV),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

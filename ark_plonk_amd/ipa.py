@@ -8,6 +8,8 @@
     assert ck.check(comms, z, values, proof, chi, digest="blake2b")
     assert ck.batch_check([IpaOpening(comms, z, values, proof, chi), ...])     # any number of openings, ONE MSM over the key
     bad = ck.locate_invalid(openings)                                          # which ones fail, by bisection
+    proof = prover.prove(pk, ck, ...)                                          # a PLONK proof over this commitment (prover.py)
+    ok = IpaBatchVerifier(vk, n, seeded, ca, cd, ck).verify(proofs, pis)       # ... and its verification (verifier.py)
 
 Every group operation and every O(n) vector pass runs in libark_plonk_amd.so: commit and the verifier's final-key MSM are the SRS
 MSM over the registered key, the opening's rounds are zk_ipa_round_dev / zk_ipa_fold_dev (include/ark_plonk_amd.h).  The device
@@ -29,7 +31,7 @@ import numpy as np
 from ._lib import check, lib
 from .context import Context, ptr_of
 from .curves import fq_from_mont, fq_to_mont, fr_from_mont, fr_to_mont, get_curve, ints_to_limbs
-from .msm import CommitterKey, sum_partials
+from .msm import CommitterKey, segments_msm, sum_partials
 
 DIGESTS = {"blake2b": hashlib.blake2b, "blake2s": hashlib.blake2s}
 
@@ -67,6 +69,69 @@ def transcript_hash(curve, digest: str, items) -> int:
         if x < cv.r:
             return x
         i += 1
+
+
+def g1_compress(curve, p) -> bytes:
+    """ark-serialize 0.3 `GroupAffine::serialize` of (x, y) | None: x little-endian in the base field's byte length, bit 7 of the last
+    byte set when y is the larger of (y, -y), bit 6 for infinity (x = 0) -- the rules zk_g1_decompress_batch_dev reads."""
+    cv = get_curve(curve)
+    g = 8 * cv.fq_limbs
+    if p is None:
+        return bytes(g - 1) + b"\x40"
+    b = bytearray(int(p[0]).to_bytes(g, "little"))
+    if int(p[1]) > cv.q - int(p[1]):
+        b[-1] |= 0x80
+    return bytes(b)
+
+
+# statuses of ipa_proof_parse
+IPA_PROOF_OK, IPA_PROOF_TRUNCATED, IPA_PROOF_BAD_COUNT, IPA_PROOF_BAD_OPTION, IPA_PROOF_C_NOT_REDUCED = range(5)
+
+
+def ipa_proof_bytes(proof: "IpaProof", curve) -> bytes:
+    """`ipa_pc::Proof` as ark-serialize 0.3 derives it, AS RECALLED (ark-poly-commit 0.3; parity with the crate is unpinned, like the
+    transcript's encodings above): l_vec and r_vec as a u64 count and compressed points each, final_comm_key compressed, c as 32 bytes
+    little-endian, then hiding_comm and rand as one `None` byte (0) each.  The ONE place that holds this layout, with its inverse
+    `ipa_proof_parse`; a `Proof<F, IPA>` is the KZG layout of proof.rs:41-103 with each kzg10::Proof replaced by these bytes."""
+    out = bytearray()
+    for vec in (proof.l_vec, proof.r_vec):
+        out += len(vec).to_bytes(8, "little")
+        for p in vec:
+            out += g1_compress(curve, p)
+    out += g1_compress(curve, proof.final_comm_key) + int(proof.c).to_bytes(32, "little") + b"\x00\x00"
+    return bytes(out)
+
+
+def ipa_proof_parse(data: bytes, curve, log_d: int, pos: int = 0):
+    """The inverse of `ipa_proof_bytes` on bytes that are DATA: reads one proof of a key of 2^log_d points at data[pos:] and returns
+    (status, fields, end).  fields: (l_vec encodings, r_vec encodings, final_comm_key encoding, c) -- the points stay compressed
+    (whether they decode is the device's check: zk_g1_decompress_batch_dev) -- and end the offset behind the proof; both None unless
+    status is IPA_PROOF_OK.  A count other than log_d, bytes that end inside a field, an option byte other than `None`, c >= r: a
+    status, never an exception."""
+    cv = get_curve(curve)
+    g = 8 * cv.fq_limbs
+    data = bytes(data)
+    vecs = []
+    for _ in range(2):
+        if pos + 8 > len(data):
+            return IPA_PROOF_TRUNCATED, None, None
+        if int.from_bytes(data[pos:pos + 8], "little") != log_d:
+            return IPA_PROOF_BAD_COUNT, None, None
+        pos += 8
+        if pos + log_d * g > len(data):
+            return IPA_PROOF_TRUNCATED, None, None
+        vecs.append([data[pos + k * g:pos + (k + 1) * g] for k in range(log_d)])
+        pos += log_d * g
+    if pos + g + 32 + 2 > len(data):
+        return IPA_PROOF_TRUNCATED, None, None
+    key = data[pos:pos + g]
+    c = int.from_bytes(data[pos + g:pos + g + 32], "little")
+    pos += g + 32
+    if data[pos] != 0 or data[pos + 1] != 0:
+        return IPA_PROOF_BAD_OPTION, None, None
+    if c >= cv.r:
+        return IPA_PROOF_C_NOT_REDUCED, None, None
+    return IPA_PROOF_OK, (vecs[0], vecs[1], key, c), pos + 2
 
 
 def check_poly_eval(curve, log_d: int, xis, z: int) -> int:
@@ -329,6 +394,29 @@ class IpaCommitterKey:
         pts = list(o.commitments) + list(pr.l_vec) + list(pr.r_vec) + [pr.final_comm_key]
         return all(p is None or (0 <= p[0] < cv.q and 0 <= p[1] < cv.q) for p in pts)
 
+    def _combined_commitments(self, openings) -> list:
+        """C_j = sum_k chi_j^k C_{j,k} of every opening, as points, in ONE launch: a segment per opening over the batch's commitments
+        (msm.segments_msm)."""
+        torch = self._torch()
+        cv = self.curve
+        if not openings:
+            return []
+        pts, sc, off = [], [], [0]
+        for o in openings:
+            pts += list(o.commitments)
+            sc += [pow(o.opening_challenge, i, cv.r) for i in range(len(o.commitments))]
+            off.append(len(pts))
+        dev = torch.device("cuda", self.ctx.device)
+        xy, inf = _pts_to_limbs(cv, pts)
+        out_xy, out_inf, st = segments_msm(torch.from_numpy(xy.view(np.int64)).to(dev), torch.from_numpy(inf).to(dev),
+                                           torch.tensor(off, dtype=torch.int64, device=dev),
+                                           torch.arange(len(pts), dtype=torch.int32, device=dev),
+                                           torch.from_numpy(ints_to_limbs(sc, 4).view(np.int64)).to(dev).view(-1, 4), cv, self.ctx)
+        if int(st.max()) != 0:
+            raise RuntimeError("segments_msm: a segment of the batch's own layout was refused")
+        out_xy, out_inf = out_xy.cpu().numpy().view(np.uint64), out_inf.cpu().numpy()
+        return [_pt_from_limbs(cv, out_xy[j], out_inf[j]) for j in range(len(openings))]
+
     def _prepare(self, openings, weights, digest: str) -> _PreparedBatch:
         """The per-opening host work of a batch, done once: C_j (a point: it is hashed), v_j, the challenges through transcript_hash,
         their inverses with one inversion for the batch, s_j(z_j); then the rows of the proof-point MSM
@@ -343,12 +431,14 @@ class IpaCommitterKey:
         if len(weights) != B:
             raise ValueError("one pair of weights per opening")
         malformed, heads, xis_all = [], [None] * B, [[0] * self.log_d for _ in range(B)]
+        formed = [j for j, o in enumerate(openings) if self._well_formed(o)]
+        combined = dict(zip(formed, self._combined_commitments([openings[j] for j in formed])))
         for j, o in enumerate(openings):
-            if not self._well_formed(o):
+            if j not in combined:
                 malformed.append(j)
                 continue
             chi, z = o.opening_challenge, o.point % r
-            C = self._msm_host(o.commitments, [pow(chi, i, r) for i in range(len(o.commitments))])
+            C = combined[j]
             v = sum(pow(chi, i, r) * x for i, x in enumerate(o.values)) % r
             xi0 = xi = transcript_hash(cv, digest, [("g1", C), ("fr", z), ("fr", v)])
             xis = []

@@ -426,6 +426,46 @@ class VariableBaseMSM:
         return _point(out, oinf, cv)
 
 
+SEG_OK, SEG_BAD_RANGE, SEG_BAD_INDEX = 0, 1, 2
+
+
+def segments_msm(bases_xy, bases_inf, seg_offsets, base_index, scalars, curve="bls12_381", ctx: Context | None = None):
+    """Many small MSMs over one set of bases, each as a point (zk_msm_g1_segments_dev): segment s is
+    sum over t in [seg_offsets[s], seg_offsets[s + 1]) of scalars[t] * bases[base_index[t]].
+
+    All device tensors: bases_xy (n_bases, 2L) Montgomery limbs (int64), bases_inf (n_bases,) uint8 or None, seg_offsets (n_seg + 1,)
+    int64, base_index (n_terms,) int32, scalars (n_terms, 4) plain 256-bit integers (int64 limbs).  Returns (xy (n_seg, 2L) int64,
+    inf (n_seg,) uint8, status (n_seg,) uint8 of SEG_*), queued on the current torch stream: offsets and indices are data, a bad one
+    is its segment's status (and infinity), not an exception."""
+    import torch
+    cv = get_curve(curve)
+    L = cv.fq_limbs
+    ctx = ctx or default_context(bases_xy.device.index)
+    n_bases = check_dev_tensor(bases_xy, 2 * L, ctx.device)
+    n_terms = check_dev_tensor(scalars, 4, ctx.device)
+    for name, t, dt in (("bases_inf", bases_inf, torch.uint8), ("seg_offsets", seg_offsets, torch.int64), ("base_index", base_index, torch.int32)):
+        if t is None and name == "bases_inf":
+            continue
+        if not t.is_cuda or t.device.index != ctx.device or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous {dt} tensor on device {ctx.device}")
+    if bases_inf is not None and bases_inf.numel() != n_bases:
+        raise ValueError("one infinity flag per base")
+    if base_index.numel() != n_terms:
+        raise ValueError("one base index per scalar")
+    if seg_offsets.numel() < 1:
+        raise ValueError("seg_offsets holds n_seg + 1 entries")
+    n_seg = seg_offsets.numel() - 1
+    dev = bases_xy.device
+    xy = torch.empty((n_seg, 2 * L), dtype=torch.int64, device=dev)
+    inf = torch.empty((n_seg,), dtype=torch.uint8, device=dev)
+    st = torch.empty((n_seg,), dtype=torch.uint8, device=dev)
+    ctx.use_torch_stream()
+    check(lib().zk_msm_g1_segments_dev(ctx.handle, cv.curve_id, n_bases, ptr_of(bases_xy), None if bases_inf is None else ptr_of(bases_inf),
+                                       n_seg, ptr_of(seg_offsets), n_terms, ptr_of(base_index), ptr_of(scalars), ptr_of(xy), ptr_of(inf),
+                                       ptr_of(st)), "zk_msm_g1_segments_dev")
+    return xy, inf, st
+
+
 def sum_partials(partials, curve="bls12_381") -> G1Affine:
     """Combine the all-gathered Jacobian partials of a sharded MSM (host, tiny)."""
     cv = get_curve(curve)

@@ -20,8 +20,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import linearisation, lookup, permutation, quotient
-from .curves import fr_from_mont, fr_to_mont, get_curve
+from .curves import fq_from_mont, fr_from_mont, fr_to_mont, get_curve
 from .domain import Radix2EvaluationDomain
+from .ipa import IpaCommitterKey, IpaProof, ipa_proof_bytes
 from .transcript import (CUSTOM_EVAL_LABELS, EVAL_LABELS, PROOF_EVAL_FIELDS, ProverTranscript, Transcript, proof_serialize)
 
 SELECTORS = quotient.COLUMNS[12:]       # q_m q_l q_r q_o q_4 q_c q_arith q_range q_logic q_fixed_group_add q_variable_group_add q_lookup
@@ -89,13 +90,22 @@ class Proof:
 
     def to_bytes(self) -> bytes:
         from .transcript import PROOF_COMMITMENTS
-        return proof_serialize([self.commitments[k] for k in PROOF_COMMITMENTS], [self.aw_opening, self.saw_opening],
-                               [self.evaluations[k] for k in PROOF_EVAL_FIELDS], [(k, self.evaluations[k]) for k in CUSTOM_EVAL_LABELS], self.curve)
+        cms = [self.commitments[k] for k in PROOF_COMMITMENTS]
+        evs, custom = [self.evaluations[k] for k in PROOF_EVAL_FIELDS], [(k, self.evaluations[k]) for k in CUSTOM_EVAL_LABELS]
+        if not isinstance(self.aw_opening, IpaProof):
+            return proof_serialize(cms, [self.aw_opening, self.saw_opening], evs, custom, self.curve)
+        # Proof<F, IPA>: the same layout with each kzg10::Proof replaced by an ipa_pc::Proof (ipa.ipa_proof_bytes)
+        kzg = proof_serialize(cms, [cms[0], cms[0]], evs, custom, self.curve)       # the two openings are cut out again
+        g = 8 * get_curve(self.curve).fq_limbs
+        return kzg[:13 * g] + ipa_proof_bytes(self.aw_opening, self.curve) + ipa_proof_bytes(self.saw_opening, self.curve) + kzg[15 * g + 2:]
 
 
 def prove(pk: ProverKey, ck, wires, public_inputs: dict, preprocessed: Transcript, coeff_a_mont, coeff_d_mont, lean: bool = False,
-          check: bool = False) -> Proof:
-    """`Prover::prove_with_preprocessed` (prover.rs:163-638) on the device: see `_prove`.  check=True first asks the device which rows
+          check: bool = False, digest: str = "blake2b") -> Proof:
+    """`Prover::prove_with_preprocessed` (prover.rs:163-638) on the device: see `_prove`.  ck: a `CommitterKey` (KZG10), or an
+    `IpaCommitterKey` of at least n points -- the reference's prover is generic over the commitment scheme (commitment.rs:8-91);
+    without hiding an IPA commitment is the MSM over comm_key a `CommitterKey` performs, so the rounds run unchanged over
+    `ck.key` and only the two openings differ (`_open_ipa`; digest: the hash of ipa_pc's own Fiat-Shamir transcript).  check=True first asks the device which rows
     the witness violates (`circuit_check.check_circuit`: before the transcript is touched, before any transform or commitment) and
     raises `CircuitNotSatisfied` with the report instead of computing a proof no verifier accepts; the proof of a satisfied circuit is
     the same bytes either way.  A failure between a round's first
@@ -107,8 +117,13 @@ def prove(pk: ProverKey, ck, wires, public_inputs: dict, preprocessed: Transcrip
         report = check_circuit(pk, wires, public_inputs, coeff_a_mont, coeff_d_mont, ctx=pk.domain._ctx_for(wires[0]))
         if not report.ok:
             raise CircuitNotSatisfied(report)
+    ipa_key = ck if isinstance(ck, IpaCommitterKey) else None
+    if ipa_key is not None:
+        if ipa_key.d1 < pk.domain.size():            # d1 is the power of two at or above n: every opened polynomial has n coefficients
+            raise ValueError("polynomial longer than the committer key")
+        ck = ipa_key.key
     try:
-        return _prove(pk, ck, wires, public_inputs, preprocessed, coeff_a_mont, coeff_d_mont, lean)
+        return _prove(pk, ck, wires, public_inputs, preprocessed, coeff_a_mont, coeff_d_mont, lean, ipa_key, digest)
     except BaseException:
         try:
             if ck.round_pending():
@@ -118,10 +133,13 @@ def prove(pk: ProverKey, ck, wires, public_inputs: dict, preprocessed: Transcrip
         raise
 
 
-def _prove(pk: ProverKey, ck, wires, public_inputs: dict, preprocessed: Transcript, coeff_a_mont, coeff_d_mont, lean: bool = False) -> Proof:
+def _prove(pk: ProverKey, ck, wires, public_inputs: dict, preprocessed: Transcript, coeff_a_mont, coeff_d_mont, lean: bool = False,
+           ipa_key=None, digest: str = "blake2b") -> Proof:
     """wires: the four wire columns padded to n (prover.rs:188-192), device tensors; public_inputs: position -> 4 Montgomery limbs
     (pi.rs:28-36); preprocessed: the transcript after the verifier key was seeded into it; coeff_a / coeff_d: the embedded
     curve's coefficients (`P::COEFF_A`, `P::COEFF_D`).
+    Everything up to the two opening challenges is shared by the commitment schemes; the openings are `_open_kzg` or, with ipa_key
+    (ck is then ipa_key.key), `_open_ipa`.
     lean=False issues the reference's 29 MSMs in the reference's 11 calls.  lean=True produces the SAME proof with 15 MSMs in 5
     calls: the 14 commitments of prover.rs:579,606 are never used (ark-poly-commit 0.3's SonicKZG10 `open` does not read its `commitments` argument (published source; the crate is not in this container), the
     `Proof` holds none of them except z's, which round 3 already has, and the verifier rebuilds them -- proof.rs:343-395), f / h_1 /
@@ -189,33 +207,61 @@ def _prove(pk: ProverKey, ck, wires, public_inputs: dict, preprocessed: Transcri
     aw_ch, saw_ch = tr.round5({lb: ev[_EVAL_FIELD[lb]] for lb in EVAL_LABELS}, [(lb, ev[lb]) for lb in CUSTOM_EVAL_LABELS])  # :516-563,593-594
     ch["aw_challenge"], ch["saw_challenge"] = aw_ch, saw_ch
     aw_polys = [lin_poly, pk.sigma_polys[0], pk.sigma_polys[1], pk.sigma_polys[2], f_poly, h2_poly, table_poly]     # :569-577
+    saw_polys = [z_poly, w_polys[0], w_polys[1], w_polys[3], h1_poly, z2_poly, table_poly]                # :596-604
+    zw = fr_to_mont(cv, [fr_from_mont(cv, ch["z_challenge"].reshape(1, 4))[0] * fr_from_mont(cv, np.asarray(d.group_gen()).reshape(1, 4))[0] % cv.r])[0]
+    if ipa_key is None:
+        aw_opening, saw_opening, witnesses = _open_kzg(ck, cv, ctx, lean, aw_polys, list(w_polys), saw_polys, ch, zw, z_commit)
+    else:
+        aw_opening, saw_opening, witnesses = _open_ipa(ipa_key, cv, aw_polys, list(w_polys), list(w_commits), saw_polys,
+                                                       [z_commit, w_commits[0], w_commits[1], w_commits[3], h1_commit, z2_commit], ch, zw, digest)
+    commitments = {"a_comm": w_commits[0], "b_comm": w_commits[1], "c_comm": w_commits[2], "d_comm": w_commits[3], "z_comm": z_commit,
+                   "f_comm": f_commit, "h_1_comm": h1_commit, "h_2_comm": h2_commit, "z_2_comm": z2_commit, "t_1_comm": t_commits[0],
+                   "t_2_comm": t_commits[1], "t_3_comm": t_commits[2], "t_4_comm": t_commits[3]}           # :620-637
+    polys = {"a_comm": w_polys[0], "b_comm": w_polys[1], "c_comm": w_polys[2], "d_comm": w_polys[3], "z_comm": z_poly, "f_comm": f_poly,
+             "h_1_comm": h1_poly, "h_2_comm": h2_poly, "z_2_comm": z2_poly, "t_1_comm": t_parts[0], "t_2_comm": t_parts[1],
+             "t_3_comm": t_parts[2], "t_4_comm": t_parts[3], "lin": lin_poly}
+    polys.update(witnesses)
+    return Proof(commitments, aw_opening, saw_opening, ev, ch, polys, cv.name)
+
+
+def _open_kzg(ck, cv, ctx, lean, aw_polys, w_polys, saw_polys, ch, zw, z_commit):
+    """The two KZG10 openings of prover.rs:579-618 -> (aw_opening, saw_opening, the witness polynomials)."""
+    from .msm import kzg_witness
+    aw_ch, saw_ch = ch["aw_challenge"], ch["saw_challenge"]
     # lean=False: the four PC calls of the round (both opening challenges are already drawn) as one deferred round of 16 jobs
     if not lean:
         ck.commit_begin(aw_polys)                                                                         # :579 (the verifier rebuilds these)
-    from .msm import kzg_witness
-    aw_witness = kzg_witness(aw_polys + list(w_polys), ch["z_challenge"], aw_ch, cv, ctx)                 # :582-591 PC::open =
+    aw_witness = kzg_witness(aw_polys + w_polys, ch["z_challenge"], aw_ch, cv, ctx)                       # :582-591 PC::open =
     if not lean:
         ck.commit_begin([aw_witness], canonical=[True])                                                   #   witness polynomial + its commitment
-    saw_polys = [z_poly, w_polys[0], w_polys[1], w_polys[3], h1_poly, z2_poly, table_poly]                # :596-604
     if not lean:
         ck.commit_begin(saw_polys)                                                                        # :606
-    zw = fr_to_mont(cv, [fr_from_mont(cv, ch["z_challenge"].reshape(1, 4))[0] * fr_from_mont(cv, np.asarray(d.group_gen()).reshape(1, 4))[0] % cv.r])[0]
     saw_witness = kzg_witness(saw_polys, zw, saw_ch, cv, ctx)                                             # :609-618
     if lean:
-        saw_commits = [z_commit]
         aw_opening, saw_opening = ck.commit_batch([aw_witness, saw_witness], canonical=[True, True])
     else:
         ck.commit_begin([saw_witness], canonical=[True])
         last = ck.round_end(16)
         aw_opening, saw_commits, saw_opening = last[7], last[8:15], last[15]
-    commitments = {"a_comm": w_commits[0], "b_comm": w_commits[1], "c_comm": w_commits[2], "d_comm": w_commits[3], "z_comm": saw_commits[0],
-                   "f_comm": f_commit, "h_1_comm": h1_commit, "h_2_comm": h2_commit, "z_2_comm": z2_commit, "t_1_comm": t_commits[0],
-                   "t_2_comm": t_commits[1], "t_3_comm": t_commits[2], "t_4_comm": t_commits[3]}           # :620-637
-    assert saw_commits[0] == z_commit
-    polys = {"a_comm": w_polys[0], "b_comm": w_polys[1], "c_comm": w_polys[2], "d_comm": w_polys[3], "z_comm": z_poly, "f_comm": f_poly,
-             "h_1_comm": h1_poly, "h_2_comm": h2_poly, "z_2_comm": z2_poly, "t_1_comm": t_parts[0], "t_2_comm": t_parts[1],
-             "t_3_comm": t_parts[2], "t_4_comm": t_parts[3], "lin": lin_poly, "aw_witness": aw_witness, "saw_witness": saw_witness}
-    return Proof(commitments, aw_opening, saw_opening, ev, ch, polys, cv.name)
+        assert saw_commits[0] == z_commit
+    return aw_opening, saw_opening, {"aw_witness": aw_witness, "saw_witness": saw_witness}
+
+
+def _open_ipa(ipa_key, cv, aw_polys, w_polys, w_commits, saw_polys, saw_commits_head, ch, zw, digest):
+    """The two openings as ipa_pc::open (no hiding, no degree bounds) -> (IpaProof, IpaProof, {}).  `open` hashes the combined
+    commitment, so the commitments of the opened polynomials the KZG path may drop are computed here: the seven of aw_polys (the
+    table's also closes saw's list)."""
+    def affine(g):
+        return None if g.infinity else tuple(fq_from_mont(cv, np.stack([g.x, g.y])))
+
+    def scalar(limbs):
+        return fr_from_mont(cv, np.asarray(limbs, dtype=np.uint64).reshape(1, 4))[0]
+
+    aw_commits = ipa_key.commit(aw_polys)
+    aw = ipa_key.open(aw_polys + w_polys, aw_commits + [affine(g) for g in w_commits], scalar(ch["z_challenge"]), scalar(ch["aw_challenge"]),
+                      digest)
+    saw = ipa_key.open(saw_polys, [affine(g) for g in saw_commits_head] + [aw_commits[6]], scalar(zw), scalar(ch["saw_challenge"]), digest)
+    return aw, saw, {}
 
 
 def check_identity(pk: ProverKey, proof: Proof, public_inputs: dict) -> bool:

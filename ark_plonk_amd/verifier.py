@@ -33,8 +33,9 @@ import numpy as np
 
 from ._lib import check, lib
 from .context import Context, default_context, ptr_of
-from .curves import fq_to_mont, get_curve, ints_to_limbs
-from .msm import CommitterKey, G1Affine, sum_partials
+from .curves import fq_from_mont, fq_to_mont, fr_from_mont, get_curve, ints_to_limbs, limbs_to_ints
+from .ipa import IPA_PROOF_OK, IPA_PROOF_TRUNCATED, IpaOpening, IpaProof, ipa_proof_parse
+from .msm import CommitterKey, G1Affine, segments_msm, sum_partials
 
 N_CHALLENGES, N_EVALS, N_KEY_BASES, N_PROOF_BASES = 14, 23, 20, 15
 CHALLENGES = ("zeta", "beta", "gamma", "delta", "epsilon", "alpha", "range", "logic", "fixed", "var", "lookup", "z", "aw", "saw")
@@ -435,3 +436,164 @@ class BatchVerifier:
         if B and not ok(0, B):
             search(0, B)
         return sorted(bad)
+
+
+class IpaBatchVerifier:
+    """B proofs of ONE circuit under the inner-product-argument commitment -> valid or not.  IPA needs no
+    pairing, so this is the one configuration in which the library verifies a PLONK proof to the end.
+
+    The stages in front of the openings are `BatchVerifier`'s, on a KZG-shaped byte string per proof (13 commitments, the two
+    final_comm_keys where the KZG witnesses stand, the evaluations): proof.rs never appends an opening to the transcript
+    (csrc/replay_walk.cuh), so the challenges are the proof's own, and the final keys get the opening points' curve and subgroup checks.
+    The IPA check hashes each opening's combined commitment C = sum_k chi^k C_k, so unlike the KZG fold every proof needs its own two
+    small MSMs as points: zk_verify_scalars_dev under the weights (1, 0) and (0, 1) gives their scalars (key columns 0..18, proof
+    columns 0..12; the G column is -v), and ONE `msm.segments_msm` call over [20 key points | 15 B proof points] gives all 2 B of them.
+    The 2 B openings ([C], [v], z or z w, the parsed ipa_pc::Proof) then go to `IpaCommitterKey.batch_check` / `locate_invalid`.
+
+    vk, n, seeded_transcript, coeff_a, coeff_d, replay: as `BatchVerifier`; ipa_key: the `IpaCommitterKey` the proofs were made
+    under; digest: the hash of ipa_pc's transcript."""
+
+    def __init__(self, vk: dict, n: int, seeded_transcript, coeff_a, coeff_d, ipa_key, curve="bls12_381", ctx: Context | None = None,
+                 digest: str = "blake2b", replay: str = "auto"):
+        torch = _torch()
+        from .domain import Radix2EvaluationDomain
+        if replay not in ("host", "device", "auto"):
+            raise ValueError('replay is "host", "device" or "auto"')
+        self.replay, self.digest, self.ipa_key = replay, digest, ipa_key
+        self.curve = cv = get_curve(curve)
+        self.ctx = ctx or ipa_key.ctx
+        if n <= 0 or n & (n - 1):
+            raise ValueError("the domain size is a power of two")
+        self.n, self.log_n = n, n.bit_length() - 1
+        self.seeded = seeded_transcript
+        self.coeff_a = np.ascontiguousarray(coeff_a, dtype=np.uint64).reshape(4).copy()
+        self.coeff_d = np.ascontiguousarray(coeff_d, dtype=np.uint64).reshape(4).copy()
+        self.omega = fr_from_mont(cv, np.asarray(Radix2EvaluationDomain.new(n, cv, self.ctx).group_gen()).reshape(1, 4))[0]
+        pts = [vk[k] for k in KEY_BASES]
+        g = fq_to_mont(cv, [cv.gx, cv.gy]).reshape(-1)
+        xy = np.stack([np.asarray(p.xy(), dtype=np.uint64) for p in pts] + [g])
+        inf = np.array([1 if p.infinity else 0 for p in pts] + [0], dtype=np.uint8)
+        dev = torch.device("cuda", self.ctx.device)
+        self._key_xy, self._key_inf = torch.from_numpy(xy.view(np.int64)).to(dev), torch.from_numpy(inf).to(dev)
+        self.last = None             # what the last batch left: per-proof C_aw, C_saw, v_aw, v_saw, statuses (tests, tools)
+
+    replay_on_device = BatchVerifier.replay_on_device
+
+    def split(self, proofs):
+        """Stage 1's host half: every proof -> (its KZG-shaped bytes, [aw fields, saw fields] of `ipa_proof_parse`), and the indices of
+        the proofs whose IPA parts do not parse (their KZG-shaped bytes are empty: stage 2 reports them too)."""
+        cv, log_d = self.curve, self.ipa_key.log_d
+        g = 8 * cv.fq_limbs
+        shaped, parts, bad = [], [], []
+        for j, p in enumerate(proofs):
+            p = bytes(p)
+            st1, f1, e1 = ipa_proof_parse(p, cv, log_d, 13 * g) if len(p) >= 13 * g else (IPA_PROOF_TRUNCATED, None, None)
+            st2, f2, e2 = ipa_proof_parse(p, cv, log_d, e1) if st1 == IPA_PROOF_OK else (st1, None, None)
+            if st2 != IPA_PROOF_OK:
+                bad.append(j)
+                shaped.append(b"")
+                parts.append(None)
+                continue
+            shaped.append(p[:13 * g] + f1[2] + b"\x00" + f2[2] + b"\x00" + p[e2:])
+            parts.append((f1, f2))
+        return shaped, parts, bad
+
+    def _stages(self, shaped, public_inputs):
+        """Stages 1 (head) to 2 and the scalars under (1, 0) and (0, 1) -> points, flags, (key, proof rows) x 2, challenges, status"""
+        torch = _torch()
+        cv, ctx = self.curve, self.ctx
+        B = len(shaped)
+        w_aw, w_saw = [(1, 0)] * B, [(0, 1)] * B
+        if self.replay_on_device(B):
+            dev = torch.device("cuda", ctx.device)
+            wa, ws = ints_to_limbs([x for pr in w_aw for x in pr], 4), ints_to_limbs([x for pr in w_saw for x in pr], 4)
+            (d_poff, d_pioff, d_pos, d_vals, d_wa, d_ws), d_blob, n_bytes, n_pi = _upload_batch(shaped, public_inputs, [wa, ws], dev)
+            ch, ev, enc, parse_st = _replay_dev(self.seeded, B, d_blob, n_bytes, d_poff, d_pioff, d_pos, d_vals, n_pi, cv, ctx)
+            pts, inf, pst = decompress_batch(enc, cv, ctx)
+            rows = [_scalars_dev(self.log_n, B, ch, ev, d_pioff, d_pos, d_vals, self.coeff_a, self.coeff_d, d_w, parse_st, pst, cv, ctx)
+                    for d_w in (d_wa, d_ws)]
+        else:
+            pts, inf, pst = decompress_batch(proof_point_bytes(shaped, cv), cv, ctx)
+            ch, ev, parse_st = replay_batch(self.seeded, shaped, public_inputs, cv)
+            rows = [scalar_rows(self.log_n, ch, ev, public_inputs, self.coeff_a, self.coeff_d, w, parse_st, pst, cv, ctx) for w in (w_aw, w_saw)]
+        return pts, inf, rows, ch
+
+    def combined_commitments(self, pts, inf, rows):
+        """Stage 3: C_aw and C_saw of every proof, 2 B segments of 32 terms over [20 key points | 15 B proof points] in one launch
+        (an opening uses fewer of the 32 columns: the others carry zero scalars and cost nothing).  Term arrays by torch indexing."""
+        torch = _torch()
+        B = rows[0][0].shape[0]
+        dev = pts.device
+        bases = torch.cat([self._key_xy, pts])
+        binf = torch.cat([self._key_inf, inf])
+        cols = torch.cat([torch.arange(19, device=dev), N_KEY_BASES + torch.arange(13, device=dev)])
+        shift = torch.cat([torch.zeros(19, dtype=torch.int64, device=dev), torch.full((13,), N_PROOF_BASES, dtype=torch.int64, device=dev)])
+        index = cols[None, None, :] + shift[None, None, :] * torch.arange(B, device=dev)[:, None, None]
+        index = index.expand(B, 2, 32).to(torch.int32).contiguous().view(-1)
+        sc = torch.stack([torch.cat([key[:, :19], prf[:, :13]], dim=1) for key, prf, _, _ in rows], dim=1).contiguous().view(-1, 4)
+        off = torch.arange(2 * B + 1, dtype=torch.int64, device=dev) * 32
+        return segments_msm(bases, binf, off, index, sc, self.curve, self.ctx)
+
+    def openings(self, proofs, public_inputs=None):
+        """Stages 1-4 up to the openings: (the 2 B' `IpaOpening`s of the B' proofs that got this far, their indices, the sorted indices
+        of the proofs already known invalid: malformed bytes, a point that does not decode, a status of the scalars stage)."""
+        torch = _torch()
+        cv, ctx, ik = self.curve, self.ctx, self.ipa_key
+        B, L, log_d = len(proofs), cv.fq_limbs, ik.log_d
+        if public_inputs is not None and len(public_inputs) != B:
+            raise ValueError("one public-input map per proof")
+        if B == 0:
+            self.last = {"C": [], "v": [], "status": np.zeros(0, dtype=np.uint8)}
+            return [], [], []
+        shaped, parts, bad = self.split(proofs)
+        bad = set(bad)
+        # the 4 log_d L / R encodings of every proof (infinity encodings for a proof that did not parse), decoded in one more call
+        g = 8 * L
+        inf_enc = bytes(g - 1) + b"\x40"
+        lr = b"".join(inf_enc * (4 * log_d) if pp is None else b"".join(pp[0][0] + pp[0][1] + pp[1][0] + pp[1][1]) for pp in parts)
+        pts, inf, rows, ch = self._stages(shaped, public_inputs)
+        c_xy, c_inf, c_st = self.combined_commitments(pts, inf, rows)
+        if log_d:
+            lr_xy, lr_inf, lr_st = decompress_batch(lr, cv, ctx)
+            lr_bad = lr_st.view(B, 4 * log_d).max(dim=1).values.cpu().numpy()
+        else:
+            lr_bad = np.zeros(B, dtype=np.uint8)
+        status = np.maximum(rows[0][3].cpu().numpy(), rows[1][3].cpu().numpy())
+        if int(c_st.max()) != 0:
+            raise RuntimeError("segments_msm: a segment of the batch's own layout was refused")
+        bad |= {int(j) for j in np.nonzero(status)[0]} | {int(j) for j in np.nonzero(lr_bad)[0]}
+
+        def points(xy, flags):
+            ints = fq_from_mont(cv, xy.cpu().numpy().view(np.uint64).reshape(-1, L))
+            return [None if f else (ints[2 * k], ints[2 * k + 1]) for k, f in enumerate(flags.cpu().numpy().tolist())]
+
+        C = points(c_xy, c_inf)                                                    # 2 B: C_aw, C_saw per proof
+        neg_v = [limbs_to_ints(rows[k][0][:, N_KEY_BASES - 1].contiguous().cpu().numpy().view(np.uint64)) for k in (0, 1)]
+        v = [[-x % cv.r for x in col] for col in neg_v]
+        z_rows = ch[:, CHALLENGES.index("z")]
+        z = fr_from_mont(cv, z_rows.contiguous().cpu().numpy().view(np.uint64) if torch.is_tensor(z_rows) else z_rows)
+        heads = points(pts.view(B, N_PROOF_BASES, 2 * L)[:, 13:15].contiguous(), inf.view(B, N_PROOF_BASES)[:, 13:15].contiguous().view(-1))
+        lrp = points(lr_xy, lr_inf) if log_d else []
+        self.last = {"C": C, "v": [(v[0][j], v[1][j]) for j in range(B)], "status": status}
+        good = [j for j in range(B) if j not in bad]
+        out = []
+        for j in good:
+            for k in (0, 1):
+                at = (4 * j + 2 * k) * log_d
+                pr = IpaProof(lrp[at:at + log_d], lrp[at + log_d:at + 2 * log_d], heads[2 * j + k], parts[j][k][3])
+                out.append(IpaOpening([C[2 * j + k]], z[j] * (self.omega if k else 1) % cv.r, [v[k][j]], pr, 1))
+        return out, good, sorted(bad)
+
+    def verify(self, proofs, public_inputs=None, weights=None) -> bool:
+        """True iff every proof of the batch is valid (up to the soundness error of `IpaCommitterKey.batch_check`).  weights: one pair
+        per OPENING (two openings per proof that reaches the openings stage) -- for tests; None draws them from the operating system."""
+        ops, good, bad = self.openings(list(proofs), public_inputs)
+        if bad:
+            return False
+        return self.ipa_key.batch_check(ops, weights, self.digest)
+
+    def locate_invalid(self, proofs, public_inputs=None) -> list:
+        """Indices of the proofs that do not verify, malformed ones included: opening j belongs to proof j // 2 of those that reached
+        the openings stage."""
+        ops, good, bad = self.openings(list(proofs), public_inputs)
+        return sorted(set(bad) | {good[j // 2] for j in self.ipa_key.locate_invalid(ops, self.digest)})

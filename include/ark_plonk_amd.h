@@ -621,6 +621,27 @@ int zk_verify_scalars_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, size_t n_pr
  * registered with zk_srs_register_dev (proof-major: base_offset = 15 lo, n = 15 (hi - lo)) and zk_g1_sum_partials. */
 int zk_fr_column_sum_dev(zk_ctx* ctx, int curve_id, const void* d_rows, size_t n_rows, uint32_t n_cols, void* d_out);
 
+/* ---- segmented MSM: many small MSMs, each as a point ------------------------------------------------------------- */
+/* n_seg independent small MSMs over one set of bases: out[s] = sum over t in [off[s], off[s+1]) of scalar[t] * base[index[t]] -- the
+ * batched form of HomomorphicCommitment::multi_scalar_mul (commitment.rs:8-91) and of the combined commitments an IPA check hashes.
+ * d_bases_xy / d_bases_inf: n_bases affine Montgomery points and flags in the layout zk_srs_register_dev takes and
+ * zk_g1_decompress_batch_dev writes (d_bases_inf may be NULL).  d_seg_offsets: n_seg + 1 uint64; d_base_index: n_terms uint32;
+ * d_scalars: n_terms x 4 limbs, plain 256-bit integers (canonical Fr is the normal case; no reduction test: s * P is the
+ * integer multiple).  d_out_xy / d_out_inf: n_seg affine Montgomery points, infinity written as (0, 1) with flag 1.
+ * d_status: one byte per segment.  A term with a zero scalar or an infinity-flagged base contributes nothing and its coordinates are
+ * not used (a base of all-zero words, what a rejected decoding leaves, contributes nothing either); other points are taken to be on the
+ * curve.  A segment with a non-zero status yields infinity; an empty one yields infinity with ZK_SEG_OK.  Offsets and indices are data on
+ * the device: a bad one is a status, never a fault, and nothing outside the buffers is read.  ZK_ERR_BAD_ARG: a null ctx, an unknown
+ * curve, a null array with n_seg > 0 (the two term arrays only when n_terms > 0, the bases only when n_bases > 0); n_seg == 0 is ZK_OK;
+ * n_seg > 2^31 ZK_ERR_UNSUPPORTED.  One 64-lane wavefront per segment, one double-and-add per term, the lane sums added in LDS with the
+ * group law's full addition, one field inversion per workgroup of four segments.  Queued on the ctx stream, no working memory. */
+#define ZK_SEG_OK 0
+#define ZK_SEG_BAD_RANGE 1   /* offsets descend or end beyond n_terms: nothing of the segment is read */
+#define ZK_SEG_BAD_INDEX 2   /* a term names a base >= n_bases: no base is read for it */
+int zk_msm_g1_segments_dev(zk_ctx* ctx, int curve_id, size_t n_bases, const void* d_bases_xy, const void* d_bases_inf, size_t n_seg,
+                           const void* d_seg_offsets, size_t n_terms, const void* d_base_index, const void* d_scalars,
+                           void* d_out_xy, void* d_out_inf, void* d_status);
+
 /* ---- inner-product-argument commitment (IPA) -------------------------------------------------------------------------------- */
 /* The reference's second HomomorphicCommitment (plonk-core/src/commitment.rs:50-91: ark-poly-commit 0.3 ipa_pc::InnerProductArgPC),
  * without hiding and degree bounds, as ark-plonk uses it (prover.rs:582-618).  The committer key is a zk_srs of d1 = d + 1 = 2^k
