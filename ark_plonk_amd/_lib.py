@@ -185,6 +185,10 @@ SYMBOLS = {
     "zk_ipa_check_coeffs_dev": (c_int, [c_void_p, c_int, c_u32, c_void_p, c_void_p]),
     "zk_ipa_check_combine_workspace_bytes": (c_size_t, [c_int, c_u32, c_size_t]),
     "zk_ipa_check_combine_dev": (c_int, [c_void_p, c_int, c_u32, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # IPA key derivation (ipa_pc::setup): hash-to-curve generators; from_random_bytes of caller-supplied strings
+    "zk_ipa_sample_generators_waves": (c_size_t, [c_size_t]),
+    "zk_ipa_sample_generators_dev": (c_int, [c_void_p, c_int, c_int, c_u64, c_size_t, c_u32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zk_g1_from_random_bytes_batch_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
     # segmented MSM: many small MSMs over one set of bases, each as a point
     "zk_msm_g1_segments_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),

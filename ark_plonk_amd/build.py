@@ -29,6 +29,7 @@ FR_IO, ZBOUND, POINT_IO = ["fr_io.cuh"], ["fr_io.cuh", "zbound.cuh"], ["point_io
 DOMAIN, DEV_SCAN = ["fr_io.cuh", "domain.cuh"], ["dev_scan.cuh"]       # domain and permutation constants; the integer exclusive scan
 GADGET = ["gadget_common.cuh"]            # what the two units of the device composer (layout, witness) share
 BLOCK_INV = ["block_inverse.cuh"]         # one field inversion per workgroup: the key fold, the gadget witnesses, the verifier's scalars
+G1_LIFT = ["g1_lift.cuh"]              # an x to a point of the curve (root, sign rule): the point decoder and the IPA key derivation
 REPLAY = ["strobe.cuh", "replay_walk.cuh"]      # merlin's sponge and the verifier's parse + replay of one proof: host (wire) and device (replay)
 # the C ABI, one unit per subsystem (api_internal.h is what they share)
 API_UNITS = ("api_ctx", "residency", "srs", "commit", "round", "api_host", "api_poly")
@@ -59,11 +60,13 @@ def jobs():
         ("gadget_witness.o", "gadget_witness.hip", [], API_HDRS + FR_IO + GADGET + BLOCK_INV),
         # the verifier's device side: batch decoding of compressed G1 points, per-proof scalars, the column sum of a fold (its host
         # side, parse and replay, is in wire.hip)
-        ("verify.o", "verify.hip", [], API_HDRS + DOMAIN + BLOCK_INV),
+        ("verify.o", "verify.hip", [], API_HDRS + DOMAIN + BLOCK_INV + G1_LIFT),
         # ... and the same parse and replay on the device, one proof per lane
         ("replay.o", "replay.hip", [], API_HDRS + REPLAY),
         # many small MSMs over one set of bases, each as a point: one wavefront per segment
         ("g1_segments.o", "g1_segments.hip", [], API_HDRS + BLOCK_INV),
+        # ipa_pc::setup: the committer key's generators hashed to the curve (wave-local candidate search, cofactor clearing)
+        ("ipa_setup.o", "ipa_setup.hip", [], API_HDRS + BLOCK_INV + G1_LIFT + ["h2c.cuh"]),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

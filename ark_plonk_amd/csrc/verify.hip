@@ -9,6 +9,7 @@
 #include "api_internal.h"
 #include "block_inverse.cuh"
 #include "domain.cuh"
+#include "g1_lift.cuh"
 
 namespace {
 
@@ -57,45 +58,11 @@ __global__ void __launch_bounds__(128) g1_decompress(const uint8_t* in, uint64_t
         status[i] = ZK_G1_OK;
         return;
     }
-    // x as a plain integer -> the device's Montgomery form: from_sat reads the words as x = v R and returns v R'; times R (in that form) is x R'
-    uint32_t r2[SAT], unit[SAT];
-#pragma unroll
-    for (int k = 0; k < SAT; ++k) {
-        r2[k] = FqP::R2(k);
-        unit[k] = k == 0 ? 1u : 0u;
-    }
-    const F one_plain = F::split_words(unit);                  // the integer 1: a product with it strips the Montgomery factor
-    const F x = F::mul(F::from_sat(w), F::from_sat(r2));
-    F b = F::one();
-    for (uint32_t k = 1; k < FqP::COEFF_B; ++k) b = F::add(b, F::one());
-    // every comparand below is a product: rhs = (x^3 + b) * 1
-    const F rhs = F::mul(F::add(F::mul(F::sqr(x), x), F::mul(b, F::one())), F::one());
-    // both base fields are 3 mod 4: sqrt(a) = a^((q + 1) / 4)
-    uint32_t e[SAT + 1];
-    uint64_t carry = 1;
-#pragma unroll
-    for (int k = 0; k < SAT; ++k) {
-        const uint64_t t = (uint64_t)FqP::MOD(k) + carry;
-        e[k] = (uint32_t)t;
-        carry = t >> 32;
-    }
-    e[SAT] = (uint32_t)carry;
-#pragma unroll
-    for (int k = 0; k < SAT; ++k) e[k] = (e[k] >> 2) | (e[k + 1] << 30);
-    F y = F::pow_words(rhs, e, SAT);
-    if (!F::sub(F::sqr(y), rhs).is_zero_mod()) return reject(ZK_G1_NOT_ON_CURVE);
-    // ark's Ord on Fp compares canonical integers: y > q - y  <=>  y > (q - 1) / 2
-    uint32_t yw[SAT];
-    F::canon_floor(F::mul(y, one_plain)).pack_words(yw);
-    bool greatest = false;
-    for (int k = SAT - 1; k >= 0; --k) {
-        const uint32_t half = (FqP::MOD(k) >> 1) | (k + 1 < SAT ? FqP::MOD(k + 1) << 31 : 0u);
-        if (yw[k] != half) {
-            greatest = yw[k] > half;
-            break;
-        }
-    }
-    if (greatest != ((flags & 2u) != 0)) y = F::neg(y);
+    // the lift of x (g1_lift.cuh): x into the device's Montgomery form, x^3 + b, its root, the sign the flag names
+    F x, rhs, y;
+    g1_curve_rhs<Cv>(w, x, rhs);
+    if (!g1_sqrt<Cv>(rhs, y)) return reject(ZK_G1_NOT_ON_CURVE);
+    y = g1_pick_root<Cv>(y, (flags & 2u) != 0);
     AffineU<F> p;
     p.x = F::canonical_lt2p(x);
     p.y = F::canonical_lt2p(y);

@@ -2,7 +2,9 @@
 `HomomorphicCommitment` (plonk-core/src/commitment.rs:50-91), without hiding and degree bounds -- what ark-plonk uses
 (prover.rs:582-618 passes no rng and no degree bounds).
 
-    ck = IpaCommitterKey(comm_key, h, "bls12_381")      # d + 1 = 2^k points (PC::trim rounds up: d + 1 = 2n for a circuit of n)
+    pp = IpaUniversalParams.setup(max_degree, "bls12_381", digest="blake2b")   # PC::setup: the generators hashed to the curve, on the device
+    ck = pp.trim(supported_degree)                      # PC::trim: a prefix of d + 1 = 2^k points (d + 1 = 2n for a circuit of n)
+    ck = IpaCommitterKey(comm_key, h, "bls12_381")      # ... or a key of the caller's own points
     comms = ck.commit(polys)
     proof = ck.open(polys, comms, z, chi, digest="blake2b")
     assert ck.check(comms, z, values, proof, chi, digest="blake2b")
@@ -13,8 +15,11 @@
 
 Every group operation and every O(n) vector pass runs in libark_plonk_amd.so: commit and the verifier's final-key MSM are the SRS
 MSM over the registered key, the opening's rounds are zk_ipa_round_dev / zk_ipa_fold_dev (include/ark_plonk_amd.h).  The device
-never hashes: every challenge is derived here, by `transcript_hash`, the ONE place that holds the byte encodings of the
-Fiat-Shamir transcript.  Parity with the Rust crate is unpinned (its source is not vendored): that function states what it assumes.
+never hashes a transcript: every challenge is derived here, by `transcript_hash`, the ONE place that holds the byte encodings of the
+Fiat-Shamir transcript.  The key's generators are hashed on the device (zk_ipa_sample_generators_dev, csrc/h2c.cuh); the host
+statement of that rule -- `generator_preimage`, `from_random_bytes`, `sample_generators_host` -- is the ONE place on this side that
+holds its encodings.  Parity with the Rust crate is unpinned for both (its source is not vendored): those functions state what they
+assume.
 
 Points cross this module as Python tuples (x, y) of canonical base-field integers, None for the point at infinity; field
 elements as canonical integers.
@@ -29,7 +34,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import check, lib
-from .context import Context, ptr_of
+from .context import Context, default_context, ptr_of
 from .curves import fq_from_mont, fq_to_mont, fr_from_mont, fr_to_mont, get_curve, ints_to_limbs
 from .msm import CommitterKey, segments_msm, sum_partials
 
@@ -82,6 +87,200 @@ def g1_compress(curve, p) -> bytes:
     if int(p[1]) > cv.q - int(p[1]):
         b[-1] |= 0x80
     return bytes(b)
+
+
+# ---- ipa_pc::setup: the generators of a committer key, hashed to the curve
+GENERATOR_TAG = b"PC-DL-2020"
+G1_COFACTOR = {"bls12_381": 0x396c8c005555e1568c00aaab0000aaab, "bn254": 1}
+DIGEST_IDS = {"blake2s": 0, "blake2b": 1}                 # ZK_H2C_BLAKE2S, ZK_H2C_BLAKE2B
+# per-point statuses (include/ark_plonk_amd.h)
+ZK_G1_OK, ZK_G1_BAD_FLAGS, ZK_G1_X_NOT_REDUCED, ZK_G1_NOT_ON_CURVE, ZK_G1_NOT_IN_SUBGROUP, ZK_G1_INF_FLAG_X_NONZERO, ZK_H2C_EXHAUSTED = range(7)
+H2C_DEFAULT_MAX_TRIES = 1024
+
+
+def generator_preimage(i: int, j: int | None = None) -> bytes:
+    """What `ipa_pc::sample_generators` hashes for generator i, AS RECALLED (ark-poly-commit 0.3; unpinned against the crate, like
+    `transcript_hash`): the protocol name and `to_bytes!(i as u64)` -- a u64 little-endian -- for the first attempt, and the same
+    followed by `to_bytes!(j as u64)` for the retries j = 0, 1, ... after a digest that is no point."""
+    out = GENERATOR_TAG + int(i).to_bytes(8, "little")
+    return out if j is None else out + int(j).to_bytes(8, "little")
+
+
+def from_random_bytes(curve, data: bytes):
+    """`GroupAffine::from_random_bytes` over `Fp::from_random_bytes_with_flags::<SWFlags>`, AS RECALLED (ark-ec / ark-ff 0.3):
+    (status, point) with point (x, y), or None for the point at infinity (status ZK_G1_OK) and for no point (any other status).
+      * min(len, G) bytes are copied into a zeroed buffer of G bytes, G the byte length of a compressed point;
+      * the flags are the top two bits of byte G - 1: bit 7 "y is the larger of (y, -y)", bit 6 "infinity";
+      * x is the buffer little-endian with every bit from MODULUS_BITS up cleared; x >= q is no point (ZK_G1_X_NOT_REDUCED), and is
+        found before the flags are looked at; both flags are no point (ZK_G1_BAD_FLAGS);
+      * the infinity flag gives infinity with x = 0 and no point otherwise (ZK_G1_INF_FLAG_X_NONZERO);
+      * else y = sqrt(x^3 + b), a non-residue being no point (ZK_G1_NOT_ON_CURVE), and of (y, -y) the one the flag names, by ark's
+        order on canonical integers.  There is no subgroup check."""
+    cv = get_curve(curve)
+    g = 8 * cv.fq_limbs
+    buf = bytearray(g)
+    data = bytes(data)[:g]
+    buf[:len(data)] = data
+    flags = buf[g - 1] >> 6
+    x = int.from_bytes(buf, "little") & ((1 << cv.q.bit_length()) - 1)
+    if x >= cv.q:
+        return ZK_G1_X_NOT_REDUCED, None
+    if flags == 3:
+        return ZK_G1_BAD_FLAGS, None
+    if flags & 1:
+        return (ZK_G1_OK, None) if x == 0 else (ZK_G1_INF_FLAG_X_NONZERO, None)
+    rhs = (x * x * x + cv.b) % cv.q
+    y = pow(rhs, (cv.q + 1) // 4, cv.q)                 # both base fields are 3 mod 4
+    if y * y % cv.q != rhs:
+        return ZK_G1_NOT_ON_CURVE, None
+    if (y > cv.q - y) != bool(flags & 2):
+        y = cv.q - y
+    return ZK_G1_OK, (x, y)
+
+
+def _g1_mul_any(cv, k: int, p):
+    """k * p for ANY point of the curve (not only of the subgroup) by affine double-and-add over Python integers"""
+    q = cv.q
+
+    def plus(p1, p2):
+        if p1 is None:
+            return p2
+        if p2 is None:
+            return p1
+        (x1, y1), (x2, y2) = p1, p2
+        if x1 == x2:
+            if (y1 + y2) % q == 0:
+                return None
+            lam = 3 * x1 * x1 * pow(2 * y1, -1, q) % q
+        else:
+            lam = (y2 - y1) * pow(x2 - x1, -1, q) % q
+        x3 = (lam * lam - x1 - x2) % q
+        return x3, (lam * (x1 - x3) - y1) % q
+
+    acc = None
+    for bit in bin(k)[2:]:
+        acc = plus(acc, acc)
+        if bit == "1":
+            acc = plus(acc, p)
+    return acc
+
+
+def sample_generators_host(curve, n: int, first_index: int = 0, digest: str = "blake2b", max_tries: int = 0) -> list:
+    """`ipa_pc::sample_generators` on Python integers, the host statement of what zk_ipa_sample_generators_dev computes: for every
+    index first_index <= i < first_index + n the triple (status, generator, attempts).  The generator is affine(cofactor * P) -- the
+    full cofactor of G1 -- for the first digest P = from_random_bytes(D(generator_preimage(i[, j]))) that is a point; max_tries (0:
+    1024) caps the attempts, and an index that runs out has status ZK_H2C_EXHAUSTED.  Milliseconds per point: for checks, never on a
+    compute path."""
+    cv = get_curve(curve)
+    h, cap = DIGESTS[digest], max_tries or H2C_DEFAULT_MAX_TRIES
+    out = []
+    for i in range(first_index, first_index + n):
+        res = (ZK_H2C_EXHAUSTED, None, cap)
+        for a in range(cap):
+            st, p = from_random_bytes(cv, h(generator_preimage(i, None if a == 0 else a - 1)).digest())
+            if st == ZK_G1_OK:
+                res = (ZK_G1_OK, None if p is None else _g1_mul_any(cv, G1_COFACTOR[cv.name], p), a + 1)
+                break
+        out.append(res)
+    return out
+
+
+def next_power_of_two(k: int) -> int:
+    return 1 if k <= 1 else 1 << (k - 1).bit_length()
+
+
+def _sample_generators_raw(curve, n: int, first_index: int, digest: str, ctx, max_tries: int):
+    """zk_ipa_sample_generators_dev with every output: (xy (n, 2L) int64, inf, tries int32, status, wave_rounds int32), device tensors"""
+    import torch
+    cv = get_curve(curve)
+    ctx = ctx or default_context(0)
+    dev = torch.device("cuda", ctx.device)
+    L = cv.fq_limbs
+    xy = torch.empty((n, 2 * L), dtype=torch.int64, device=dev)
+    inf = torch.empty(n, dtype=torch.uint8, device=dev)
+    st = torch.empty(n, dtype=torch.uint8, device=dev)
+    tries = torch.empty(n, dtype=torch.int32, device=dev)
+    rounds = torch.empty(lib().zk_ipa_sample_generators_waves(n), dtype=torch.int32, device=dev)
+    ctx.use_torch_stream()
+    check(lib().zk_ipa_sample_generators_dev(ctx.handle, cv.curve_id, DIGEST_IDS[digest], first_index, n, max_tries, ptr_of(xy), ptr_of(inf),
+                                             ptr_of(tries), ptr_of(st), ptr_of(rounds)), "zk_ipa_sample_generators_dev")
+    return xy, inf, tries, st, rounds
+
+
+def sample_generators(curve, n: int, first_index: int = 0, digest: str = "blake2b", ctx: Context | None = None, max_tries: int = 0):
+    """Generators first_index .. first_index + n of `ipa_pc::sample_generators` derived on the device: (xy, inf), device tensors in the
+    layout CommitterKey registers from ((n, 2L) affine Montgomery limbs, n infinity flags).  Ranks or chunks may each derive a range.
+    Raises when an index has a non-zero status (max_tries attempts, 0: 1024, and no point)."""
+    xy, inf, _, st, _ = _sample_generators_raw(curve, n, first_index, digest, ctx, max_tries)
+    if n and int(st.max()) != 0:
+        bad = int((st != 0).nonzero()[0])
+        raise RuntimeError(f"sample_generators: index {first_index + bad} has status {int(st[bad])}")
+    return xy, inf
+
+
+class IpaUniversalParams:
+    """`ipa_pc::UniversalParams` (PC::setup): comm_key of d + 1 generators for d = next_power_of_two(max_degree + 1) - 1, and h and s,
+    the two `pop()`s of sample_generators(d + 3): h is generator d + 2 and s generator d + 1.  s (the hiding generator) is derived and
+    carried; nothing here uses it.  The generators stay on the device; `trim` registers a prefix of them from there."""
+
+    def __init__(self, curve, max_degree: int, generators, ctx: Context | None = None, digest: str = "blake2b"):
+        """generators: the d + 3 points, as (xy, inf) device tensors (`setup`) or as a host list of (x, y) | None"""
+        self.curve = get_curve(curve)
+        self.ctx = ctx
+        self.digest = digest
+        self.max_degree = self.degree_bound(max_degree)
+        d = self.max_degree
+        self._gens = generators
+        if self._on_host():
+            if len(generators) != d + 3:
+                raise ValueError("setup takes d + 3 generators")
+            self.s, self.h = generators[d + 1], generators[d + 2]
+        else:
+            xy, inf = generators
+            if xy.shape[0] != d + 3 or inf.shape[0] != d + 3:
+                raise ValueError("setup takes d + 3 generators")
+            tail_xy, tail_inf = xy[d + 1:].cpu().numpy().view(np.uint64), inf[d + 1:].cpu().numpy()
+            self.s, self.h = (_pt_from_limbs(self.curve, tail_xy[k], tail_inf[k]) for k in range(2))
+
+    def _on_host(self) -> bool:
+        return isinstance(self._gens, list)
+
+    @staticmethod
+    def degree_bound(degree: int) -> int:
+        """the degree a key is rounded up to: next_power_of_two(degree + 1) - 1"""
+        return next_power_of_two(int(degree) + 1) - 1
+
+    @classmethod
+    def setup(cls, max_degree: int, curve="bls12_381", digest: str = "blake2b", ctx: Context | None = None) -> "IpaUniversalParams":
+        ctx = ctx or default_context(0)
+        d = cls.degree_bound(max_degree)
+        return cls(curve, d, sample_generators(curve, d + 3, 0, digest, ctx), ctx, digest)
+
+    @property
+    def comm_key(self):
+        """generators [0, d]: (xy, inf) views of the device tensors, or the host list"""
+        d1 = self.max_degree + 1
+        return self._gens[:d1] if self._on_host() else (self._gens[0][:d1], self._gens[1][:d1])
+
+    def trim_size(self, supported_degree: int) -> int:
+        """points of the key `trim` returns: next_power_of_two(supported_degree + 1); beyond max_degree + 1 is an error"""
+        t = self.degree_bound(supported_degree)
+        if t > self.max_degree:
+            raise ValueError(f"trim: supported degree {supported_degree} rounds to {t}, beyond the setup's {self.max_degree}")
+        return t + 1
+
+    def trim(self, supported_degree: int) -> "IpaCommitterKey":
+        """PC::trim: the key of comm_key[0 .. t + 1) with the same h (and s), registered from the device copy: no second derivation,
+        and the points do not pass through host memory"""
+        k = self.trim_size(supported_degree)
+        if self._on_host():
+            xy, inf = _pts_to_limbs(self.curve, self._gens[:k])
+            key = CommitterKey(xy, self.curve, self.ctx, infinity=inf)
+        else:
+            key = CommitterKey(self._gens[0][:k], self.curve, self.ctx, infinity=self._gens[1][:k])
+        ck = IpaCommitterKey(key, self.h, self.curve)
+        ck.s = self.s
+        return ck
 
 
 # statuses of ipa_proof_parse
@@ -215,7 +414,10 @@ def _pts_to_limbs(curve, pts):
 
 class IpaCommitterKey:
     """`ipa_pc::CommitterKey` without hiding: comm_key (d + 1 = 2^k affine G1 points, (n, 2L) Montgomery limbs as CommitterKey takes
-    them) and h, on the device as a registered SRS (CommitterKey).  Key generation (PC-DL-2020 hash-to-curve) is the caller's."""
+    them) and h, on the device as a registered SRS (CommitterKey).  `IpaUniversalParams.setup(...).trim(...)` derives one by ipa_pc's
+    PC-DL-2020 hash-to-curve, on the device; a caller may equally bring its own points.  A key whose points have KNOWN logarithms
+    (k_i * G: what the tests and tools build where they need the integer reference verifier) is good for checking this library and
+    for nothing else: whoever knows the k_i opens any commitment to any value."""
 
     def __init__(self, comm_key, h, curve="bls12_381", ctx: Context | None = None):
         self.curve = get_curve(curve)

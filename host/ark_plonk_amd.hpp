@@ -426,6 +426,19 @@ inline void lookup_table_block(Context& ctx, int curve, int op, uint32_t lower_b
     auto off = [&](DeviceVec& v) { return static_cast<void*>(static_cast<char*>(v.data()) + 32 * at); };
     check(zk_lookup_table_dev(ctx.handle(), curve, op, lower_bound, n_bits, off(a), off(b), off(c), off(d)), "zk_lookup_table_dev");
 }
+// ipa_pc::setup's generators first_index .. first_index + n (PC-DL-2020 hash-to-curve) into device buffers in the layout
+// zk_srs_register_dev takes: d_out_xy n x 2L limbs, d_out_inf n flags, d_status n bytes (an index out of attempts: ZK_H2C_EXHAUSTED)
+inline void ipa_sample_generators(Context& ctx, int curve, int digest, uint64_t first_index, size_t n, void* d_out_xy, void* d_out_inf,
+                                  void* d_status, uint32_t max_tries = 0, void* d_tries = nullptr, void* d_wave_rounds = nullptr) {
+    check(zk_ipa_sample_generators_dev(ctx.handle(), curve, digest, first_index, n, max_tries, d_out_xy, d_out_inf, d_tries, d_status, d_wave_rounds),
+          "zk_ipa_sample_generators_dev");
+}
+// GroupAffine::from_random_bytes of n strings of byte_len bytes each, one status byte per string
+inline void g1_from_random_bytes(Context& ctx, int curve, const void* d_bytes, size_t byte_len, size_t n, bool clear_cofactor, void* d_out_xy,
+                                 void* d_out_inf, void* d_status) {
+    check(zk_g1_from_random_bytes_batch_dev(ctx.handle(), curve, d_bytes, byte_len, n, clear_cofactor ? 1 : 0, d_out_xy, d_out_inf, d_status),
+          "zk_g1_from_random_bytes_batch_dev");
+}
 // compute_lookup_permutation_poly up to its ifft (permutation/mod.rs:754-797)
 inline DeviceVec lookup_permutation_evals(Context& ctx, int curve, const DeviceVec& f, const DeviceVec& t, const DeviceVec& h1,
                                           const DeviceVec& h2, const uint64_t* delta_mont, const uint64_t* epsilon_mont) {

@@ -688,6 +688,36 @@ size_t zk_ipa_check_combine_workspace_bytes(int curve_id, uint32_t log_d, size_t
 int zk_ipa_check_combine_dev(zk_ctx* ctx, int curve_id, uint32_t log_d, size_t n_open, const void* d_xis_mont, const void* d_weights_mont,
                              void* d_work, void* d_out);
 
+/* ---- IPA key derivation: ipa_pc::setup's generators ---------------------------------------------------------- */
+/* ark-poly-commit 0.3 `InnerProductArgPC::sample_generators`, AS RECALLED (the crate is not vendored; the encodings are stated once
+ * for the device in csrc/h2c.cuh and once for the host in ark_plonk_amd/ipa.py, unpinned against the crate like the IPA transcript):
+ * generator i is affine(cofactor * P) for the first P = from_random_bytes(D("PC-DL-2020" || u64_le(i) [|| u64_le(j)])) that is a
+ * point, attempt 1 without j, attempt a >= 2 with j = a - 2.  D is unkeyed Blake2s-256 or Blake2b-512.  setup(max_degree) takes
+ * d + 3 generators for d = next_power_of_two(max_degree + 1) - 1: comm_key = [0, d], s = d + 1, h = d + 2.
+ *
+ * zk_ipa_sample_generators_dev writes generators first_index .. first_index + n (ranks or chunks may each derive a range) in the
+ * layout zk_srs_register_dev takes: d_out_xy n x 2L limbs affine Montgomery, d_out_inf n flags, d_status n bytes.  max_tries caps
+ * the attempts per index (0: 1024; the worst per-attempt success probability is about 0.175, so 1024 fail with probability below
+ * 1e-80): an index that runs out has status ZK_H2C_EXHAUSTED and an all-zero row, and is never a hang.  d_tries (optional, n uint32):
+ * the attempts made.  d_wave_rounds (optional, zk_ipa_sample_generators_waves(n) uint32): the square-root rounds each wavefront ran,
+ * a wavefront owning ZK_H2C_CHUNK consecutive indices.  n = 0 is a no-op.  Queued on the ctx stream, no working memory. */
+#define ZK_H2C_BLAKE2S 0
+#define ZK_H2C_BLAKE2B 1
+#define ZK_H2C_CHUNK 512
+#define ZK_G1_INF_FLAG_X_NONZERO 5  /* from_random_bytes: the infinity flag on an x that is not 0 */
+#define ZK_H2C_EXHAUSTED 6          /* max_tries attempts and no point */
+size_t zk_ipa_sample_generators_waves(size_t n);
+int zk_ipa_sample_generators_dev(zk_ctx* ctx, int curve_id, int digest_id, uint64_t first_index, size_t n, uint32_t max_tries, void* d_out_xy,
+                                 void* d_out_inf, void* d_tries, void* d_status, void* d_wave_rounds);
+/* `GroupAffine::from_random_bytes` (over Fp::from_random_bytes_with_flags::<SWFlags>) of n strings of byte_len >= 0 bytes each, one
+ * lane per string: min(byte_len, G) bytes into a zeroed buffer of G = zk_g1_compressed_size bytes; flags in the top two bits of byte
+ * G - 1; x with every bit from MODULUS_BITS up cleared.  Status per string, in the order the rules apply: ZK_G1_X_NOT_REDUCED,
+ * ZK_G1_BAD_FLAGS, ZK_G1_INF_FLAG_X_NONZERO (the flag with x = 0 is infinity, ZK_G1_OK), ZK_G1_NOT_ON_CURVE.  No subgroup check.
+ * clear_cofactor != 0 multiplies every point by the cofactor of G1 (a point of the cofactor's torsion becomes infinity).  Rows as
+ * zk_g1_decompress_batch_dev writes them: infinity (0, 1) with flag 1, a rejected string all-zero words. */
+int zk_g1_from_random_bytes_batch_dev(zk_ctx* ctx, int curve_id, const void* d_bytes, size_t byte_len, size_t n, int clear_cofactor,
+                                      void* d_out_xy, void* d_out_inf, void* d_status);
+
 /* ---- circuit compilation (Circuit::compile, circuit.rs:226-259 -> preprocess.rs:126-423) ------------------------------------- */
 /* The wire permutation: `Permutation::compute_sigma_permutations` + `compute_permutation_lagrange` (permutation/mod.rs:101-169).
  * n = 2^log_n.  A position is wire * n + row, wire 0..3 = Left, Right, Output, Fourth.  d_ins_var[k], d_ins_pos[k] (u32, device,
@@ -864,7 +894,7 @@ int zk_lookup_table_dev(zk_ctx* ctx, int curve_id, int op, uint32_t lower_bound,
  * *mismatches = number of disagreeing pairs (0 expected); *case_mask (optional) = which cases failed. */
 int zk_selftest_quad_dev(zk_ctx* ctx, int curve_id, uint32_t n_quads, uint32_t* mismatches, uint32_t* case_mask);
 
-/* ---- utilities (synthetic SRS for tests/bench; stands in for PC::setup, out of scope) --------- */
+/* ---- utilities (a synthetic known-logarithm SRS for tests/bench; a real IPA key: zk_ipa_sample_generators_dev) --------- */
 /* out[i] = scalars[i] * G1 generator, affine Montgomery, device buffers. */
 int zk_g1_fixed_base_batch_dev(zk_ctx* ctx, int curve_id, const void* d_scalars, size_t n, void* d_out_xy);
 /* out[i] = a[i] * b[i] (Montgomery Fr, device) -- pointwise helper for property tests. */
