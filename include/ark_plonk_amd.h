@@ -656,14 +656,22 @@ int zk_msm_g1_segments_dev(zk_ctx* ctx, int curve_id, size_t n_bases, const void
  * round is open on the ctx (zk_kzg_round_pending) zk_ipa_round_dev -- which runs MSMs -- returns ZK_ERR_PENDING. */
 /* device bytes one opening over d1 = 2^k points needs (0 for an unknown curve or a d1 that is not a power of two) */
 size_t zk_ipa_workspace_bytes(int curve_id, size_t d1);
-/* d_out[i] = point^i, i < n (Montgomery Fr, device) */
+/* d_out[i] = point^i, i < n (Montgomery Fr, device); 0^0 = 1.  n = 0 writes nothing (d_out may be NULL); a point that is not below r
+ * is ZK_ERR_BAD_ARG and writes nothing. */
 int zk_ipa_powers_dev(zk_ctx* ctx, int curve_id, const uint64_t* point_mont, size_t n, void* d_out);
 /* One round on vectors of length 2m: L = MSM(key_l, a_r) + <a_r, b_l> h', R = MSM(key_r, a_l) + <a_l, b_r> h', affine Montgomery
  * (out_lr_xy: L then R, 2 x 2L limbs; out_lr_inf: 2 flags, may be NULL).  The key is key[0 .. 2m) in the first round (the SRS
- * table path) and the folded key in d_work afterwards (first_round = 0: 2m <= d1 / 2).  h_prime_xy: affine Montgomery (2L limbs). */
+ * table path) and the folded key in d_work afterwards (first_round = 0: 2m <= d1 / 2).  h_prime_xy: affine Montgomery (2L limbs);
+ * x = 0 with y = 0 (all-zero words) or y = 1 is the point at infinity, and the inner products then carry no weight.  An output at
+ * infinity is written as the words of (0, 1), with or without out_lr_inf.  A first round may cover fewer points than the key holds
+ * (2m < d1, a power of two): it and the folds after it read key[0 .. 2m) alone, in a workspace still sized for d1.  A key with a
+ * window-sharded table (zk_srs_precompute_rows) is ZK_ERR_UNSUPPORTED in the first round; a, b and the key are left as they were. */
 int zk_ipa_round_dev(zk_ctx* ctx, zk_srs* key, int first_round, size_t m, const void* d_a, const void* d_b, void* d_work,
                      const uint64_t* h_prime_xy, uint64_t* out_lr_xy, uint8_t* out_lr_inf);
 /* a <- a_l + xi^-1 a_r, b <- b_l + xi b_r (in place, to length m); key <- key_l + xi key_r into d_work.  xi: Montgomery, non-zero.
+ * A refused call (xi = 0, or words that are not below r: ZK_ERR_BAD_ARG) queues nothing: a, b, the folded key and the next round's
+ * L and R are what they were.  A key point sent to infinity by the challenge (key_l[i] = -xi key_r[i]) is a null point of the folded
+ * key, which the rounds and folds after it -- and zk_ipa_final_key_dev, as (0, 1) with flag 1 -- carry like any other.
  * Queued on the ctx stream. */
 int zk_ipa_fold_dev(zk_ctx* ctx, zk_srs* key, int first_round, size_t m, const uint64_t* xi_mont, void* d_a, void* d_b, void* d_work);
 /* after the last fold: final_comm_key = the one folded point in d_work (affine Montgomery); the caller reads c = a[0] itself */

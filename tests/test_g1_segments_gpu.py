@@ -151,6 +151,78 @@ def test_term_by_term_against_the_group_law(ctx, cid):
     assert st == [SEG_OK, SEG_OK] and got == [acc, pts[0]]
 
 
+def ladder_scalars(cv):
+    """256-bit scalars at and above r: the double-and-add walks the integer, so for a base of order r its accumulator passes through
+    -q (k = r: the last addition gives infinity), q (k = r + 2: the last addition doubles) and infinity in mid-ladder (k = 2r + 1)"""
+    r = cv.r
+    sc = [r, r + 1, r + 2, 2 * r, 2 * r + 1, 2 * r + 2, (1 << 256) - 1]
+    assert all(r <= k < 1 << 256 for k in sc)
+    return sc
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_scalars_at_and_above_the_group_order(ctx, cid):
+    """Each such scalar alone in a one-term segment, and in lanes 0, 1 and 63 of 65-term segments (the 65th term is lane 0's second)
+    whose other terms are random: (k mod r) P per term"""
+    cv = CURVES[cid]
+    logs = rand_logs(cv, 11, 31)
+    bases = points_of(ctx, cid, logs)
+    special = ladder_scalars(cv)
+    offsets, index, scalars = [0], [], []
+    for j, k in enumerate(special):
+        index.append(j % 11)
+        scalars.append(k)
+        offsets.append(len(index))
+    rng = np.random.default_rng(41)
+    for s in range(3):
+        ix = rng.integers(0, 11, size=65).tolist()
+        sc = rand_logs(cv, 65, 50 + s)
+        for slot, lane in enumerate((0, 1, 63)):
+            sc[lane] = special[(3 * s + slot) % len(special)]
+        index += ix
+        scalars += sc
+        offsets.append(len(index))
+    got, st = run(ctx, cid, bases, None, offsets, index, scalars)
+    assert st == [SEG_OK] * (len(offsets) - 1)
+    for s in range(len(offsets) - 1):
+        assert got[s] == expect(cv, logs, offsets, index, scalars, s), (cid, s)
+    G = (cv.gx, cv.gy)
+    assert got[0] is None and got[3] is None                                     # r P and 2r P
+    assert got[1] == bo.ec_mul(cv, logs[1], G) and got[2] == bo.ec_mul(cv, 2 * logs[2] % cv.r, G)
+
+
+def test_a_base_outside_the_subgroup_takes_the_integer_scalar(ctx):
+    """BLS12-381's (0, 2) has order 3 (the point test_from_random_bytes_on_crafted_strings feeds to the cofactor kernel): k P is the
+    integer multiple, k mod 3, never (k mod r) P -- the big-int double-and-add on the point itself, the scalar unreduced"""
+    import torch
+    import ark_plonk_amd as zk
+    cid, cv = 0, CURVES[0]
+    P3 = (0, 2)
+    assert bo.on_curve(cv, P3) and bo.ec_mul(cv, 3, P3) is bo.INF and bo.ec_mul(cv, 2, P3) == (0, cv.q - 2)
+    k_q = rand_logs(cv, 1, 33)[0]
+    Q = bo.ec_mul(cv, k_q, (cv.gx, cv.gy))
+    rows = np.concatenate([zk.curves.fq_to_mont(cid, list(P3)).reshape(1, -1), points_of(ctx, cid, [k_q]).cpu().numpy().view(np.uint64)])
+    bases = torch.from_numpy(rows.view(np.int64)).cuda()
+    ks = [1, 2, 3, 4, cv.r, (1 << 256) - 1]
+    assert sorted({k % 3 for k in ks}) == [0, 1, 2] and cv.r % 3 != 0
+    offsets, index, scalars = [0], [], []
+    for k in ks:                                             # alone
+        index.append(0)
+        scalars.append(k)
+        offsets.append(len(index))
+    for k in ks:                                             # next to a term of the subgroup
+        index += [0, 1]
+        scalars += [k, 5]
+        offsets.append(len(index))
+    got, st = run(ctx, cid, bases, None, offsets, index, scalars)
+    assert st == [SEG_OK] * (2 * len(ks))
+    for j, k in enumerate(ks):
+        want = bo.ec_mul(cv, k, P3)
+        assert want == [bo.INF, P3, (0, cv.q - 2)][k % 3]
+        assert got[j] == want, k
+        assert got[len(ks) + j] == bo.ec_add(cv, want, bo.ec_mul(cv, 5, Q)), k
+
+
 def test_no_segments_null_arguments_and_unknown_curve(ctx):
     import torch
     from ark_plonk_amd import _lib

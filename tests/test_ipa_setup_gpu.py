@@ -81,6 +81,20 @@ def test_ranges_equal_the_checker_index_by_index(ctx, curve, digest):
     assert rows_of(curve, xy, inf) == whole[0][59:124]
 
 
+@pytest.mark.parametrize("first", [2 ** 48 - 3, 2 ** 64 - 7])
+@pytest.mark.parametrize("curve, digest", ref.COMBOS)
+def test_indices_with_non_zero_upper_words(ctx, curve, digest, first):
+    """The preimage splits the 64-bit index over three words of the message and shares the last of them with the retry counter.
+    Six indices from 2^48 - 3 (the index crosses into the low half of that shared word) and from 2^64 - 7 (every bit of it set; the
+    last range whose first + n does not wrap): points, attempt counts and statuses against the checker, index by index."""
+    rows, tries, st, rounds = derive(ctx, curve, digest, first, 6)
+    want = expected(curve, digest, first, 6)
+    assert (rows, tries, st) == want, first
+    assert len(rows) == 6 and len(rounds) == 1
+    # not the points of the same range with the upper words dropped
+    assert rows != expected(curve, digest, first % 2 ** 32, 6)[0]
+
+
 @pytest.mark.parametrize("cap", [1, 3])
 @pytest.mark.parametrize("curve, digest", ref.COMBOS)
 def test_max_tries_exhausts_exactly_the_indices_that_need_more(ctx, curve, digest, cap):
