@@ -72,12 +72,14 @@ class GadgetArgs(ctypes.Structure):
     """zk_gadget_args"""
     _fields_ = [("kind", c_u32), ("num_bits", c_u32), ("flags", c_u32), ("reserved", c_u32), ("calls", c_u64), ("row0", c_u64), ("var0", c_u64),
                 ("inputs", c_void_p * 4), ("coeff", c_void_p * 6), ("coeff_const", c_u64 * 24), ("pi", c_void_p), ("coeff_a", c_u64 * 4),
-                ("coeff_d", c_u64 * 4), ("table", c_void_p), ("inputs_ext", c_void_p * 4)]
+                ("coeff_d", c_u64 * 4), ("table", c_void_p), ("inputs_ext", c_void_p * 4), ("lut", c_void_p * 4), ("lut_rows", c_u64),
+                ("lut_map", c_void_p), ("lut_slots", c_u64)]
 
 
 ZK_GADGET_POLY, ZK_GADGET_RANGE, ZK_GADGET_LOGIC, ZK_GADGET_CURVE_ADD, ZK_GADGET_FIXED_BASE = range(5)
 ZK_GADGET_CONST_WITNESS, ZK_GADGET_IS_ZERO, ZK_GADGET_IS_EQ, ZK_GADGET_SELECT = range(5, 9)         # 9 is no kind
 ZK_GADGET_POINT_SELECT, ZK_GADGET_POINT_NEG, ZK_GADGET_VAR_BASE, ZK_GADGET_LOOKUP = range(10, 14)
+ZK_GADGET_LOOKUP_OUT, ZK_GADGET_DUMMY = 15, 16                  # 14 is no kind either
 ZK_GADGET_COMPUTE_OUT, ZK_GADGET_XOR = 1, 2
 
 # every symbol include/ark_plonk_amd.h declares: name -> (restype, argtypes)
@@ -204,6 +206,12 @@ SYMBOLS = {
     "zk_gadget_witness_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
     # one insert_multi_* block of a lookup table
     "zk_lookup_table_dev": (c_int, [c_void_p, c_int, c_int, c_u32, c_u32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the output of a lookup: the (a, b, d) -> first-row map of a table, and its queries
+    "zk_lookup_map_slots": (c_size_t, [c_size_t]),
+    "zk_lookup_map_build_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "zk_lookup_map_query_dev": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), c_size_t, c_void_p, c_size_t, c_size_t, ctypes.POINTER(c_void_p),
+                                        ctypes.POINTER(c_void_p), c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_u64),
+                                        ctypes.POINTER(c_u64)]),
     "zk_fr_serialized_size": (c_size_t, [c_int]),
     "zk_g1_compressed_size": (c_size_t, [c_int]),
     "zk_fr_serialize": (c_int, [c_int, c_void_p, ctypes.c_char_p]),

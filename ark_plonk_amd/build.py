@@ -58,6 +58,8 @@ def jobs():
         ("gadget_layout.o", "gadget_layout.hip", [], API_HDRS + FR_IO + GADGET),
         # ... and the values of the variables the segments create, replayed once per proof
         ("gadget_witness.o", "gadget_witness.hip", [], API_HDRS + FR_IO + GADGET + BLOCK_INV),
+        # the output of a lookup: the (a, b, d) -> first-row map of a lookup table and its queries (compares 32-byte words: both curves)
+        ("lookup_map.o", "lookup_map.hip", [], API_HDRS + FR_IO),
         # the verifier's device side: batch decoding of compressed G1 points, per-proof scalars, the column sum of a fold (its host
         # side, parse and replay, is in wire.hip)
         ("verify.o", "verify.hip", [], API_HDRS + DOMAIN + BLOCK_INV + G1_LIFT),

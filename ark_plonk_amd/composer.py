@@ -31,7 +31,10 @@ conditional_select      4                    4                 16
 conditional_point_select  8                  8                 32
 conditional_point_neg   5                    5                 20
 variable_base_scalar_mul  8 M + 2            9 M + 257         32 M + 8
-lookup_gate             1                    0                 4                 against `Composer.lookup_table` (a `LookupTable`)
+lookup_gate             1                    0 or 1            4                 against `Composer.lookup_table` (a `LookupTable`); with
+                                                                                 c=None the output is a new variable: c of the FIRST table row
+                                                                                 whose (a, b, d) matches, from the table's map on the device
+add_dummy_constraints   2                    4                 8                 the rows of the reference's benchmark circuit (`bench_circuit`)
 
 conditional_select_zero / _one, add_affine, add_public_affine, add_affine_to_circuit_description, assert_equal_point,
 assert_equal_public_point and identity are compositions of the rows above with the reference's names."""
@@ -46,6 +49,7 @@ from ._lib import check, lib
 from .compile import CircuitDescription, padded_size
 from .context import check_dev_tensor, default_context
 from .curves import fr_to_mont, get_curve
+from .lookup import ElementNotIndexed
 from .prover import SELECTORS
 
 _REC_SHIFT = 30
@@ -65,15 +69,34 @@ class LookupTable:
     """`LookupTable` (lookup/lookup_table.rs): rows of four field elements in insertion order.  `insert_row` takes integers;
     the `insert_multi_*(lower_bound, n)` blocks -- every (a, b) with lower_bound <= a, b < 2^n, c = op(a, b) mod 2^n and the tag of the
     operation (add 0, mul 1, xor -1, and 2) -- are recorded and filled on the device when the columns are asked for
-    (zk_lookup_table_dev: one lane per row)."""
+    (zk_lookup_table_dev: one lane per row).  `lookup` computes c from (a, b, d) on the device (`LookupTable::lookup`,
+    lookup_table.rs:172-180: the first matching row) through a map from (a, b, d) to the smallest row index, built once per table
+    (zk_lookup_map_build_dev; 4 bytes per slot, slots = the power of two >= 2 x rows) and kept on the object with the columns until a
+    row or block is inserted."""
 
     def __init__(self):
         self._blocks = []                               # ("rows", [[a, b, c, d], ...]) / ("multi", op, lower_bound, n)
+        self._dev = None                                # (curve name, ctx, columns, map, slots): dropped by every insertion
 
     def insert_row(self, a, b, c, d):
+        self._dev = None
         if not self._blocks or self._blocks[-1][0] != "rows":
             self._blocks.append(("rows", []))
         self._blocks[-1][1].append([int(a), int(b), int(c), int(d)])
+
+    # one row of an operation (lookup_table.rs:51-84): c = op(a, b) % upper_bound -- the reference's code takes the remainder by
+    # upper_bound itself, whatever its comment says about 2^upper_bound -- and the tag of the operation
+    def insert_add_row(self, a, b, upper_bound):
+        self.insert_row(a, b, (int(a) + int(b)) % int(upper_bound), 0)
+
+    def insert_mul_row(self, a, b, upper_bound):
+        self.insert_row(a, b, (int(a) * int(b)) % int(upper_bound), 1)
+
+    def insert_xor_row(self, a, b, upper_bound):
+        self.insert_row(a, b, (int(a) ^ int(b)) % int(upper_bound), -1)
+
+    def insert_and_row(self, a, b, upper_bound):
+        self.insert_row(a, b, (int(a) & int(b)) % int(upper_bound), 2)
 
     def _multi(self, op, lower_bound, n):
         lower_bound, n = int(lower_bound), int(n)
@@ -82,6 +105,7 @@ class LookupTable:
         if not 0 <= lower_bound <= 1 << n:
             raise ValueError("lower_bound must lie in 0 .. 2^n")
         if lower_bound < 1 << n:                        # an empty range inserts nothing, as the reference's loops
+            self._dev = None
             self._blocks.append(("multi", op, lower_bound, n))
 
     def insert_multi_add(self, lower_bound, n):
@@ -137,6 +161,53 @@ class LookupTable:
                       "zk_lookup_table_dev")
             at += m
         return cols
+
+    def device_map(self, curve, ctx, device):
+        """(columns, map, slots) of the table on the device: the four columns, the u32 map from (a, b, d) to the first row that holds
+        it and its slot count -- built on first use, reused until a row or block is inserted"""
+        import torch
+        curve = get_curve(curve)
+        if self._dev is None or self._dev[0] != curve.name or self._dev[1] is not ctx:
+            cols = self.columns(curve, ctx, device)
+            rows = self.size()
+            slots = int(lib().zk_lookup_map_slots(rows))
+            if slots == 0:
+                raise ValueError("a lookup table of more than 2^30 rows has no map")
+            smap = torch.empty(slots, dtype=torch.int32, device=device)
+            ctx.use_torch_stream()
+            check(lib().zk_lookup_map_build_dev(ctx.handle, curve.curve_id, cols[0].data_ptr(), cols[1].data_ptr(), cols[3].data_ptr(), rows,
+                                                smap.data_ptr(), slots), "zk_lookup_map_build_dev")
+            self._dev = (curve.name, ctx, cols, smap, slots)
+        return self._dev[2], self._dev[3], self._dev[4]
+
+    def query(self, curve, ctx, n, operands, operand_ids, operand_rows, out, out_ids=None, out_rows=None, pos=None):
+        """zk_lookup_map_query_dev over the table's map: -> (return code, misses, first missing query).  operands: three data
+        pointers; operand_ids: None or three pointers (0: read directly)"""
+        curve = get_curve(curve)
+        cols, smap, slots = self.device_map(curve, ctx, out.device)
+        misses, first = _lib.c_u64(), _lib.c_u64()
+        ids = None if operand_ids is None else (_lib.c_void_p * 3)(*operand_ids)
+        ctx.use_torch_stream()
+        rc = lib().zk_lookup_map_query_dev(ctx.handle, curve.curve_id, (_lib.c_void_p * 4)(*[c.data_ptr() for c in cols]), self.size(),
+                                           smap.data_ptr(), slots, n, (_lib.c_void_p * 3)(*operands), ids, operand_rows, out.data_ptr(),
+                                           out_ids, n if out_rows is None else out_rows, None if pos is None else pos.data_ptr(),
+                                           ctypes.byref(misses), ctypes.byref(first))
+        return rc, misses.value, first.value
+
+    def lookup(self, a, b, d, curve="bls12_381", ctx=None):
+        """`LookupTable::lookup` (lookup_table.rs:172-180) for B queries: a, b, d (B, 4) Montgomery device tensors -> the (B, 4) column
+        of c, each from the FIRST row whose (a, b, d) matches; raises `lookup.ElementNotIndexed` naming the first query no row holds"""
+        import torch
+        ctx = ctx or default_context(a.device.index)
+        B = check_dev_tensor(a, 4, ctx.device)
+        if check_dev_tensor(b, 4, ctx.device) != B or check_dev_tensor(d, 4, ctx.device) != B:
+            raise ValueError("a, b and d hold one value per query")
+        out = torch.zeros((B, 4), dtype=torch.int64, device=a.device)
+        rc, misses, first = self.query(curve, ctx, B, [a.data_ptr(), b.data_ptr(), d.data_ptr()], None, B, out)
+        if rc == _lib.ZK_ERR_NOT_INDEXED:
+            raise ElementNotIndexed(f"query {first} matches no row of the table ({misses} of {B} queries do not)")
+        check(rc, "zk_lookup_map_query_dev")
+        return out
 
 
 class Composer:
@@ -240,6 +311,14 @@ class Composer:
         if seg["table"] is not None:
             a.table = seg["table"].data_ptr()
         return a
+
+    def _lut_args(self, a):
+        """the lookup table of a LOOKUP_OUT witness: columns, map and slot count of `self.lookup_table`, built or reused"""
+        cols, smap, slots = self.lookup_table.device_map(self.curve, self.ctx, self.device)
+        for w in range(4):
+            a.lut[w] = cols[w].data_ptr()
+        a.lut_rows, a.lut_map, a.lut_slots = self.lookup_table.size(), smap.data_ptr(), slots
+        return cols, smap
 
     def _segment(self, kind, B, inputs, num_bits=0, flags=0, coeff=(0,) * 6, pi=None, table=None) -> dict:
         import torch
@@ -408,10 +487,29 @@ class Composer:
         seg = self._gadget(_lib.ZK_GADGET_VAR_BASE, [scalar, point[0], point[1]])
         return self._new_vars(seg, seg["V"] - 2), self._new_vars(seg, seg["V"] - 1)
 
-    def lookup_gate(self, a, b, c, d=None, pi=None, B=None):
-        """`lookup_gate` (lookup.rs:18-65): the row (a, b, c, d) must be a row of `self.lookup_table`; d=None is the zero variable"""
+    def lookup_gate(self, a, b, c=None, d=None, pi=None, B=None):
+        """`lookup_gate` (lookup.rs:18-65): the row (a, b, c, d) must be a row of `self.lookup_table`; d=None is the zero variable.
+        With c=None the output is a new variable whose value `assign` takes from the table on the device -- c of the first row whose
+        (a, b, d) matches, `c = add_input(table.lookup(a, b, d)?)` in the reference's terms; a key in no row is refused at assign
+        time (`lookup.ElementNotIndexed`).  Returns c."""
+        if c is None:
+            return self._new_vars(self._gadget(_lib.ZK_GADGET_LOOKUP_OUT, [None] * 4 + [a, b, d], B, pi=pi), 0)
         seg = self._gadget(_lib.ZK_GADGET_LOOKUP, [a, b, c, d], B, pi=pi)
         return self._own(seg["inputs"][2])
+
+    def add_dummy_constraints(self, B=1):
+        """`add_dummy_constraints` (composer.rs:493-548), B calls: four new variables 6, 1, 7, -20 and two rows that satisfy the
+        arithmetic identity and are rows of the dummy table, each with q_arith = q_lookup = 1"""
+        self._gadget(_lib.ZK_GADGET_DUMMY, [], B)
+
+    def add_dummy_lookup_table(self):
+        """`add_dummy_lookup_table` (composer.rs:553-574): three rows, the first two the rows of `add_dummy_constraints`"""
+        for row in ((6, 7, -20, 1), (-20, 6, 7, 0), (3, 1, 4, 9)):
+            self.lookup_table.insert_row(*row)
+
+    def circuit_bound(self) -> int:
+        """`circuit_bound` (composer.rs:131-138)"""
+        return padded_size(self.n_gates, self.lookup_table.size())
 
     # ---- compositions of the rows above, with the reference's names
     def conditional_select_zero(self, bit, value):
@@ -470,6 +568,16 @@ class Composer:
         self.constrain_to_constant(h, 0, pi=self._pair_ints(public_point[0], public_point[1], B, -1))
 
     # ------------------------------------------------------------------------------------------------------------ results
+    def _first_miss(self, seg, values) -> str:
+        """the message of a LOOKUP_OUT segment whose witness found a key in no row: the same query again, for the first failing call"""
+        ins = seg["inputs"][4:7]
+        zero = self._handle(0, seg["B"])
+        ids = [(zero if h is None else h).data_ptr() for h in ins]
+        out = values[seg["var0"]:seg["var0"] + seg["B"]]
+        _, misses, first = self.lookup_table.query(self.curve, self.ctx, seg["B"], [values.data_ptr()] * 3, ids, seg["var0"], out)
+        return (f"lookup_gate segment at row {seg['row0']}: call {first} (row {seg['row0'] + first}) looks up a key (a, b, d) that is in no "
+                f"row of the lookup table ({misses} of {seg['B']} calls do)")
+
     def _pi_limbs(self, overrides=None) -> dict:
         pi = dict(self.public_inputs)
         for row, v in (overrides or {}).items():
@@ -480,7 +588,8 @@ class Composer:
 
     def description(self) -> CircuitDescription:
         import torch
-        has_lookup = any(what == "segment" and rest[0]["kind"] == _lib.ZK_GADGET_LOOKUP for what, *rest in self._program)
+        lookup_kinds = (_lib.ZK_GADGET_LOOKUP, _lib.ZK_GADGET_LOOKUP_OUT, _lib.ZK_GADGET_DUMMY)
+        has_lookup = any(what == "segment" and rest[0]["kind"] in lookup_kinds for what, *rest in self._program)
         if has_lookup and self.lookup_table.size() == 0:
             raise ValueError("the circuit has lookup gates but `lookup_table` is empty")
         table_cols = self.lookup_table.columns(self.curve, self.ctx, self.device) if self.lookup_table.size() else []
@@ -532,10 +641,28 @@ class Composer:
             if seg["pi"] is not None:
                 keep = self._column([pi[seg["row0"] + k] for k in range(seg["B"])])
                 a.pi = keep.data_ptr()
-            check(lib().zk_gadget_witness_dev(self.ctx.handle, self.curve.curve_id, ctypes.addressof(a), values.data_ptr(), self.num_vars),
-                  "zk_gadget_witness_dev")
+            lut = self._lut_args(a) if seg["kind"] == _lib.ZK_GADGET_LOOKUP_OUT else None       # kept alive over the call
+            rc = lib().zk_gadget_witness_dev(self.ctx.handle, self.curve.curve_id, ctypes.addressof(a), values.data_ptr(), self.num_vars)
+            if rc == _lib.ZK_ERR_NOT_INDEXED and lut is not None:
+                raise ElementNotIndexed(self._first_miss(seg, values))
+            check(rc, "zk_gadget_witness_dev")
         if not pi:
             return values
         rows = sorted(pi)
         limbs = fr_to_mont(self.curve, [pi[r_] for r_ in rows])
         return values, {r_: limbs[i] for i, r_ in enumerate(rows)}
+
+
+def bench_circuit(log_n: int, curve="bls12_381", ctx=None, coeffs=(0, 0)) -> Composer:
+    """`BenchCircuit::gadget` (benches/plonk.rs:45-68), the one circuit the reference benchmarks: `add_dummy_lookup_table`, then
+    `add_dummy_constraints` while `circuit_bound() < 2^log_n - 1` -- 2^(log_n - 1) + 2 gates for log_n >= 3 (the composer's first four
+    rows included; 4 gates below that), padded to 2^log_n.  The calls are ONE segment: the loop's trip count is known in advance,
+    because every call adds two rows and the table stays at three."""
+    c = Composer(curve, ctx, coeffs=coeffs)
+    c.add_dummy_lookup_table()
+    size, n, rows = 1 << int(log_n), c.n_gates, c.lookup_table.size()
+    calls = max(0, (size // 2 + 2 - n) // 2)            # the first gate count above size / 2 pads to size
+    assert padded_size(n + 2 * calls, rows) >= size - 1 and (calls == 0 or padded_size(n + 2 * (calls - 1), rows) < size - 1)
+    if calls:
+        c.add_dummy_constraints(calls)
+    return c

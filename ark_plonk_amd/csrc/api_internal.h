@@ -73,6 +73,10 @@ int run_flagged(zk_ctx* c, size_t work_bytes, Body&& body) {
 // a deferred round (zk_kzg_round_begin_dev ...) holds the ctx's MSM buffer sets until zk_kzg_round_end.  ctx lock held.
 inline bool round_open(const zk_ctx* c) { return c->round.n != 0; }
 
+// ---- lookup_map.hip: the witness of a ZK_GADGET_LOOKUP_OUT segment -- one query of the table's (a, b, d) -> first-row map with the
+// operands gathered from d_values by id and c written to d_values[var0 + k]; ZK_ERR_NOT_INDEXED on a miss.  ctx lock held.
+int lookup_out_witness(zk_ctx* c, const zk_gadget_args& a, void* d_values);
+
 // ---- srs.hip
 // upload + convert; use_cache: look the content digest up first / publish the new handle.  Takes the ctx lock itself.
 int srs_register_host(zk_ctx* c, int curve_id, const uint64_t* bases_xy, const uint8_t* inf_flags, size_t n, zk_srs** out, bool use_cache);

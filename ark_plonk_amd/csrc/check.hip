@@ -38,25 +38,8 @@ constexpr uint32_t CTAB = 48;                     // multiples of r held for the
 constexpr uint32_t BIT_ARITH = 0, BIT_RANGE = 1, BIT_LOGIC = 5, BIT_FIXED = 10, BIT_CURVE = 14, BIT_LOOKUP = 17, BIT_COPY = 18;
 
 // ---------------------------------------------------------------------------------------------------------------- key map
-// A key is W field elements (Key<W>, key_hash: fr_io.cuh): element k of key i is col[k][i] (W = 4: a table row; W = 1: an identity
-// encoding).
-struct KeyCols {
-    const void* col[4];
-};
-template <int W>
-ZK_D Key<W> ld_key(const KeyCols& c, uint64_t i) {
-    Key<W> k;
-#pragma unroll
-    for (int j = 0; j < W; ++j) k.e[j] = ld_el(c.col[j], i);
-    return k;
-}
-template <int W>
-ZK_D bool key_eq(const Key<W>& x, const Key<W>& y) {
-    bool eq = true;
-#pragma unroll
-    for (int j = 0; j < W; ++j) eq = eq && el_eq(x.e[j], y.e[j]);
-    return eq;
-}
+// A key is W field elements (Key<W>, KeyCols, ld_key, key_eq, key_hash: fr_io.cuh): element k of key i is col[k][i] (W = 4: a table
+// row; W = 1: an identity encoding).
 // Index of a key of the map equal to `q`, or EMPTY.  Every occupant on the way is compared in full.
 template <int W>
 ZK_D uint32_t map_find(const uint32_t* slots, uint32_t cap_mask, const KeyCols& cols, const Key<W>& q) {

@@ -37,6 +37,11 @@ ZK_D El ld_el(const void* base, uint64_t i) {
     e.b = q[1];
     return e;
 }
+ZK_D void st_el(void* base, uint64_t i, const El& e) {
+    uint4* q = reinterpret_cast<uint4*>(base) + 2 * i;
+    q[0] = e.a;
+    q[1] = e.b;
+}
 ZK_D bool el_eq(const El& x, const El& y) {
     return x.a.x == y.a.x && x.a.y == y.a.y && x.a.z == y.a.z && x.a.w == y.a.w && x.b.x == y.b.x && x.b.y == y.b.y && x.b.z == y.b.z &&
            x.b.w == y.b.w;
@@ -54,11 +59,29 @@ ZK_D uint64_t el_mix(uint64_t h, const El& e) {
     return h;
 }
 ZK_D uint32_t el_hash(const El& e) { return (uint32_t)el_mix(0, e); }
-// a key of W elements (check.hip's maps: W = 4 a table row, W = 1 an identity encoding) and its hash
+// a key of W elements (check.hip's maps: W = 4 a table row, W = 1 an identity encoding; lookup_map.hip's: W = 3, the (a, b, d) of a
+// table row) and its hash; element j of key i is col[j][i]
 template <int W>
 struct Key {
     El e[W];
 };
+struct KeyCols {
+    const void* col[4];
+};
+template <int W>
+ZK_D Key<W> ld_key(const KeyCols& c, uint64_t i) {
+    Key<W> k;
+#pragma unroll
+    for (int j = 0; j < W; ++j) k.e[j] = ld_el(c.col[j], i);
+    return k;
+}
+template <int W>
+ZK_D bool key_eq(const Key<W>& x, const Key<W>& y) {
+    bool eq = true;
+#pragma unroll
+    for (int j = 0; j < W; ++j) eq = eq && el_eq(x.e[j], y.e[j]);
+    return eq;
+}
 template <int W>
 ZK_D uint32_t key_hash(const Key<W>& k) {
     uint64_t h = 0;

@@ -19,7 +19,7 @@ constexpr uint64_t MAX_ROWS = (uint64_t)1 << 28, MAX_VARS = (uint64_t)1 << 31;
 // selector columns in the order of prover.SELECTORS
 constexpr int Q_M = 0, Q_L = 1, Q_R = 2, Q_O = 3, Q_4 = 4, Q_C = 5, Q_ARITH = 6, Q_RANGE = 7, Q_LOGIC = 8, Q_FIXED = 9, Q_VAR = 10, Q_LOOKUP = 11;
 constexpr int N_SEL = 12;
-constexpr uint32_t LAST_KIND = ZK_GADGET_LOOKUP;
+constexpr uint32_t LAST_KIND = ZK_GADGET_DUMMY;
 
 struct Shape {
     uint32_t rows, vars, ins;
@@ -41,6 +41,8 @@ ZK_HD Shape gadget_shape(uint32_t kind, uint32_t num_bits, uint32_t flags, uint3
     case ZK_GADGET_POINT_NEG: s = {5, 5, 20}; break;
     case ZK_GADGET_VAR_BASE: s = {8 * m_bits + 2, 9 * m_bits + 257, 32 * m_bits + 8}; break;
     case ZK_GADGET_LOOKUP: s = {1, 0, 4}; break;
+    case ZK_GADGET_LOOKUP_OUT: s = {1, 1, 4}; break;
+    case ZK_GADGET_DUMMY: s = {2, 4, 8}; break;
     default: break;
     }
     return s;
@@ -54,7 +56,7 @@ inline size_t gadget_work_bytes(uint32_t kind, uint32_t m_bits, uint64_t calls) 
 }
 
 // the handles of input w: inputs[0 .. 4), then inputs_ext; null where the segment has no such input
-constexpr int MAX_INPUTS = 5;
+constexpr int MAX_INPUTS = 7;
 ZK_HD const uint32_t* input_ptr(const zk_gadget_args& a, int w) { return (const uint32_t*)(w < 4 ? a.inputs[w] : a.inputs_ext[w - 4]); }
 // input w of call k; an input the segment does not have reads as the zero variable
 ZK_D uint32_t input_id(const zk_gadget_args& a, int w, uint64_t k) {
@@ -107,7 +109,7 @@ inline int inputs_needed(uint32_t kind) {
     case ZK_GADGET_POINT_NEG: return 2;
     case ZK_GADGET_VAR_BASE: return 3;
     case ZK_GADGET_LOOKUP: return 3;
-    default: return 0;
+    default: return 0;                                     // LOOKUP_OUT: a, b, d in inputs_ext, each may be the zero variable
     }
 }
 // num_bits of the kinds that take one: even, 2 .. 256

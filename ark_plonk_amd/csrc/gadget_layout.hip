@@ -5,7 +5,7 @@
 // (ecc/scalar_mul/fixed_base.rs:51-160), add_witness_to_circuit_description (composer.rs:192-196), is_zero_with_output /
 // is_eq_with_output (composer.rs:355-392), conditional_select (composer.rs:404-433), conditional_point_select /
 // conditional_point_neg (ecc/mod.rs:145-182), variable_base_scalar_mul (ecc/scalar_mul/variable_base.rs:27-95) and lookup_gate
-// (lookup.rs:18-65) -- and the blocks of a lookup table (lookup/lookup_table.rs:94-152).  Segments, shapes and errors: gadget_common.cuh.
+// (lookup.rs:18-65), with a given or a computed output, add_dummy_constraints (composer.rs:493-548) -- and the blocks of a lookup table (lookup/lookup_table.rs:94-152).  Segments, shapes and errors: gadget_common.cuh.
 //
 //   row_of             ONE description of row r of call k for every kind: the four variable ids and the selectors
 //   gadget_layout      one lane per (call, row): stores the ids and the twelve selector values of the row; input ids checked
@@ -21,8 +21,8 @@ struct SelPtrs {
     void* p[N_SEL];
 };
 
-// The selectors of a row.  Small integers: q_m, q_l, q_r, q_4, q_c in {-1, 0, 1}, q_o = -1 on every arithmetic row with an output,
-// logic = +-1: q_c = q_logic (logic.rs:237-260), pow2 >= 0: q_l = 2^pow2.  Field values are named here and read where they are stored.
+// The selectors of a row.  Small integers: q_m, q_l, q_r, q_4, q_c in {-1, 0, 1}, q_o = -1 on every arithmetic row with an output
+// (the dummy rows alone hold 2, 3, 4 and 127), logic = +-1: q_c = q_logic (logic.rs:237-260), pow2 >= 0: q_l = 2^pow2.  Field values are named here and read where they are stored.
 enum RowSrc {
     SRC_NONE,
     SRC_COEFFS,                                            // q_m, q_l, q_r, q_o, q_4, q_c: the six coefficients of the segment (coeff_of)
@@ -235,13 +235,32 @@ ZK_D void row_of(const zk_gadget_args& a, const Shape& s, uint32_t M, uint64_t k
         for (int w = 0; w < 4; ++w) id[w] = input_id(a, w, k);
         q.lookup = true;
         break;
+    case ZK_GADGET_LOOKUP_OUT:                             // a, b, d: inputs 4, 5, 6; the output is the new variable
+        id[0] = input_id(a, 4, k), id[1] = input_id(a, 5, k), id[2] = v0, id[3] = input_id(a, 6, k);
+        q.lookup = true;
+        break;
+    case ZK_GADGET_DUMMY:                                  // new variables v0 .. v0 + 3: six, one, seven, minus twenty
+        q.arith = q.lookup = true;
+        q.m = 1;
+        if (r == 0) {
+            id[0] = v0, id[1] = v0 + 2, id[2] = v0 + 3, id[3] = v0 + 1;
+            q.l = 2, q.r = 3, q.o = 4, q.c = 4, q.q4 = 1;
+        } else {
+            id[0] = v0 + 3, id[1] = v0, id[2] = v0 + 2;
+            q.l = 1, q.r = 1, q.o = 1, q.c = 127;
+        }
+        break;
     default: break;
     }
 }
 
 ZK_D uint32_t pick4(const uint32_t (&id)[4], uint32_t w) { return w == 0 ? id[0] : w == 1 ? id[1] : w == 2 ? id[2] : id[3]; }
 template <class Fr>
-ZK_D Fr small(int v) { return v == 0 ? Fr::zero() : v > 0 ? Fr::one() : Fr::neg(Fr::one()); }
+ZK_D Fr small(int v) {
+    if (v == 0) return Fr::zero();
+    const Fr m = v == 1 || v == -1 ? Fr::one() : Fr::from_u32((uint32_t)(v < 0 ? -v : v));
+    return v > 0 ? m : Fr::neg(m);
+}
 // 2^j (j < 256, below the modulus) in Montgomery form; the word is chosen by comparison, not by a run-time index
 template <class Fr>
 ZK_D Fr pow2_mont(uint32_t j) {

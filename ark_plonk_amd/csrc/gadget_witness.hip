@@ -10,8 +10,9 @@
 //                        projective accumulators stored to the call's workspace
 //   gadget_w_fixed_norm  one lane per (call, row): normalises with one shared inversion per block; writes acc_x, acc_y, xy_alpha and
 //                        the scalar accumulator (3e >> s) - (e >> s)
-//   gadget_w_select      one lane per call: the constant witness, the four values of a select, the eight of a point select, the
-//                        five of a point negation -- each the product with -q_o that arithmetic.rs:144-155 computes
+//   gadget_w_select      one lane per call: the constant witness, the four constants of add_dummy_constraints, the four values of a
+//                        select, the eight of a point select, the five of a point negation -- each the product with -q_o that
+//                        arithmetic.rs:144-155 computes
 //   gadget_w_is_zero     one lane per call: (a - b,) y = 1 / a or 1, b = 1 - a y; ONE field inversion per block, a zero input
 //                        enters the block's product as 1
 //   gadget_w_var_bits    one lane per (call, j < 256): bit j of the canonical scalar e, the accumulator e mod 2^(j+1) for j < M, the
@@ -20,6 +21,7 @@
 //                        selected point (bit x, 1 - bit + bit y)), the 2 M + 1 projective accumulators stored to the workspace
 //   gadget_w_var_norm    one lane per (call, iteration): the three accumulators of the iteration made affine with one inversion
 //                        per block (through the product of their Z), the eight values of the iteration
+// The output of a lookup gate (ZK_GADGET_LOOKUP_OUT) is no kernel of this unit: one query of the table's map (lookup_map.hip).
 // Values are canonical Montgomery Fr (field.cuh), what `assign` and the circuit check expect; the canonical integer of an input is one
 // Montgomery product, prefixes and bits are shifts and masks on its words with compile-time word indices (no array is indexed at run
 // time: both walks read the scalar's bits off the top of a word array that is shifted by constants).  The flag word: an input id that
@@ -344,6 +346,13 @@ __global__ void __launch_bounds__(GT) gadget_w_select(zk_gadget_args a, uint32_t
         st_value<Fr>(values, num_vars, v, Fr::neg(coeff_of<Fr>(a, Q_C, k)));
         return;
     }
+    if (a.kind == ZK_GADGET_DUMMY) {                       // composer.rs:494-497, in add_input order
+        st_value<Fr>(values, num_vars, v, Fr::from_u32(6));
+        st_value<Fr>(values, num_vars, v + 1, Fr::one());
+        st_value<Fr>(values, num_vars, v + 2, Fr::from_u32(7));
+        st_value<Fr>(values, num_vars, v + 3, Fr::neg(Fr::from_u32(20)));
+        return;
+    }
     const Fr bit = ld_input<Fr>(values, a, 0, k, flag), x = ld_input<Fr>(values, a, 1, k, flag);
     if (a.kind == ZK_GADGET_POINT_NEG) {
         const Fr nx = Fr::neg(x);
@@ -464,6 +473,7 @@ int witness_impl(zk_ctx* c, const zk_gadget_args& a, void* d_values, uint64_t nu
     if (rc) return rc;
     if (a.var0 + a.calls * s.vars > num_vars) return ZK_ERR_BAD_ARG;
     if (s.vars == 0) return ZK_OK;
+    if (a.kind == ZK_GADGET_LOOKUP_OUT) return lookup_out_witness(c, a, d_values);
     return run_flagged(c, gadget_work_bytes(a.kind, M, a.calls), [&](uint32_t* d_flag, void* work) -> int {
         // one kernel over `lanes` lanes under its own profile scope
         auto launch = [&](const char* name, auto kernel, uint64_t lanes, auto... args) {
@@ -486,7 +496,7 @@ int witness_impl(zk_ctx* c, const zk_gadget_args& a, void* d_values, uint64_t nu
             launch("gadget_w_var_walk", gadget_w_var_walk<Cv>, a.calls, d_values, work, d_flag);
             launch("gadget_w_var_norm", gadget_w_var_norm<Cv>, a.calls * M, d_values, num_vars, work, d_flag);
             break;
-        default:                                           // the constant witness, the selects, the point negation
+        default:                                           // the constant witness, the dummy constants, the selects, the point negation
             launch("gadget_w_select", gadget_w_select<Cv>, a.calls, s.vars, d_values, num_vars, d_flag);
             break;
         }

@@ -426,6 +426,24 @@ inline void lookup_table_block(Context& ctx, int curve, int op, uint32_t lower_b
     auto off = [&](DeviceVec& v) { return static_cast<void*>(static_cast<char*>(v.data()) + 32 * at); };
     check(zk_lookup_table_dev(ctx.handle(), curve, op, lower_bound, n_bits, off(a), off(b), off(c), off(d)), "zk_lookup_table_dev");
 }
+// `LookupTable::lookup` (lookup/lookup_table.rs:172-180) on the device: the map from (a, b, d) to the FIRST row of a table of `rows` rows
+// (d_slots: u32[lookup_map_slots(rows)], owned by the caller), and n queries against it.  The operands are device vectors of n
+// elements; d_out receives c of the first matching row.  Returns the number of queries that match no row (their smallest index in
+// *first_miss); the hits are written all the same.  The index-vector forms of the C call (zk_lookup_map_query_dev) are not mirrored.
+inline size_t lookup_map_slots(size_t rows) { return zk_lookup_map_slots(rows); }
+inline void lookup_map_build(Context& ctx, int curve, const void* d_a, const void* d_b, const void* d_d, size_t rows, void* d_slots) {
+    check(zk_lookup_map_build_dev(ctx.handle(), curve, d_a, d_b, d_d, rows, d_slots, zk_lookup_map_slots(rows)), "zk_lookup_map_build_dev");
+}
+inline uint64_t lookup_map_query(Context& ctx, int curve, const void* const d_table[4], size_t rows, const void* d_slots, size_t n,
+                                 const void* d_a, const void* d_b, const void* d_d, void* d_out, void* d_pos = nullptr,
+                                 uint64_t* first_miss = nullptr) {
+    const void* operands[3] = {d_a, d_b, d_d};
+    uint64_t misses = 0;
+    const int rc = zk_lookup_map_query_dev(ctx.handle(), curve, d_table, rows, d_slots, zk_lookup_map_slots(rows), n, operands, nullptr, n, d_out,
+                                           nullptr, n, d_pos, &misses, first_miss);
+    if (rc != ZK_ERR_NOT_INDEXED) check(rc, "zk_lookup_map_query_dev");
+    return misses;
+}
 // ipa_pc::setup's generators first_index .. first_index + n (PC-DL-2020 hash-to-curve) into device buffers in the layout
 // zk_srs_register_dev takes: d_out_xy n x 2L limbs, d_out_inf n flags, d_status n bytes (an index out of attempts: ZK_H2C_EXHAUSTED)
 inline void ipa_sample_generators(Context& ctx, int curve, int digest, uint64_t first_index, size_t n, void* d_out_xy, void* d_out_inf,

@@ -812,6 +812,9 @@ int zk_circuit_check_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* 
  *   ZK_GADGET_POINT_NEG   conditional_point_neg(bit, p)                     5                  5            20
  *   ZK_GADGET_VAR_BASE    variable_base_scalar_mul(scalar, point)           8 M + 2            9 M + 257    32 M + 8
  *   ZK_GADGET_LOOKUP      lookup_gate(a, b, c, d)                           1                  0            4
+ *   ZK_GADGET_LOOKUP_OUT  lookup_gate(a, b, c, d) with
+ *                         c = add_input(table.lookup(a, b, d)?)             1                  1            4
+ *   ZK_GADGET_DUMMY       add_dummy_constraints()                           2                  4            8
  * The kinds from CONST_WITNESS on map every cell of every row, row by row (Left, Right, Output, Fourth).
  * Values (zk_gadget_witness_dev; canonical Montgomery Fr, what zk_fr_gather_dev and the circuit check take):
  *   POLY with ZK_GADGET_COMPUTE_OUT: (q_m a b + q_l a + q_r b + q_c + q_4 d + pi) (-q_o), as arithmetic.rs:144-155 writes it -- a
@@ -835,6 +838,12 @@ int zk_circuit_check_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* 
  *       the affine law above.  Rows: M x (boolean row, accumulator row with q_l = 2^j, q_r = 1), the assert_equal with the scalar, the
  *       row of the one, M x (2 rows of the doubling, select_zero, select_one, 2 rows of the addition).
  *   LOOKUP: no new variable; the row (a, b, c, d) has q_lookup = 1 alone.
+ *   LOOKUP_OUT: the row (a, b, new, d) has q_lookup = 1 alone; the new variable holds c of the FIRST row of the lookup table whose
+ *       (a, b, d) equals the values of the three inputs (`LookupTable::lookup`, lookup_table.rs:172-180: `.position` returns the first
+ *       match, and rows with one key and different c are legal) -- one zk_lookup_map_query_dev over lut / lut_map.  The witness
+ *       returns ZK_ERR_NOT_INDEXED when a call's key is in no row (Error::ElementNotIndexed); the calls that hit are still written;
+ *   DUMMY (composer.rs:493-548): new variables 6, 1, 7, -20 in that order; row 0 is (six, seven, -20, one) with q_m q_l q_r q_o q_c q_4 =
+ *       1, 2, 3, 4, 4, 1 and row 1 is (-20, six, seven, the zero variable) with 1, 1, 1, 1, 127, 0; both rows have q_arith = q_lookup = 1.
  * ZK_ERR_BAD_ARG, by one flag word read back once per call: an input id that is not smaller than var0 (an undefined variable); a
  * scalar whose NAF has more than M digits (3e >= 2^(M+1); the reference asserts); a zero denominator of the group law.  The outputs
  * of a refused call are unspecified; nothing is read or written outside the buffers. */
@@ -851,6 +860,8 @@ int zk_circuit_check_dev(zk_ctx* ctx, int curve_id, uint32_t log_n, const void* 
 #define ZK_GADGET_POINT_NEG 11
 #define ZK_GADGET_VAR_BASE 12
 #define ZK_GADGET_LOOKUP 13
+#define ZK_GADGET_LOOKUP_OUT 15                      /* 14 is no kind either: callers probe ZK_GADGET_LOOKUP + 1 for the end of the first table */
+#define ZK_GADGET_DUMMY 16
 #define ZK_GADGET_COMPUTE_OUT 1                      /* flags, POLY: the output wire is a new variable whose value is computed */
 #define ZK_GADGET_XOR 2                              /* flags, LOGIC: q_c = q_logic = -1 (XOR); without it +1 (AND) */
 typedef struct zk_gadget_args {
@@ -869,7 +880,12 @@ typedef struct zk_gadget_args {
     const void* inputs_ext[4];                       /* inputs 4 .. 7, as `inputs`: the kinds from CONST_WITNESS on take, in order --
                                                       * IS_ZERO: a; IS_EQ: a, b; SELECT: bit, a, b; POINT_SELECT: bit, p1.x, p0.x, p1.y,
                                                       * p0.y (the fifth is inputs_ext[0]); POINT_NEG: bit, x; VAR_BASE: scalar, x, y of
-                                                      * the point; LOOKUP: a, b, c, d (NULL: the zero variable) */
+                                                      * the point; LOOKUP: a, b, c, d (NULL: the zero variable); LOOKUP_OUT: a, b, d
+                                                      * (each may be NULL: the zero variable) */
+    const void* lut[4];                              /* LOOKUP_OUT, read by the witness only: the four columns of the lookup table ... */
+    uint64_t lut_rows;                               /* ... of this many rows (Montgomery Fr, device), */
+    const void* lut_map;                             /* its map (zk_lookup_map_build_dev over columns 0, 1, 3) */
+    uint64_t lut_slots;                              /* and the map's slot count, zk_lookup_map_slots(lut_rows).  Other kinds ignore them */
 } zk_gadget_args;
 /* Host only: the shape of one call and the device bytes a witness of `calls` calls allocates (layout: 256). */
 int zk_gadget_shape(int kind, int curve_id, uint32_t num_bits, uint32_t flags, size_t calls, uint32_t* rows, uint32_t* vars, uint32_t* insertions,
@@ -887,7 +903,8 @@ int zk_gadget_layout_dev(zk_ctx* ctx, int curve_id, const void* args, void* d_wi
  * values are read from the same vector, so segments are replayed in build order.  Working memory: one device allocation, freed on
  * every path -- 256 bytes, + 96 (M + 1) calls for FIXED_BASE and + 96 (2 M + 1) calls for VAR_BASE (the projective accumulators
  * between the two phases of a scalar multiplication: a walk of one lane per call, then a normalisation with one inversion per 256
- * lanes).  No buffer of the ctx is used: the call runs inside an open deferred round.  Blocks once. */
+ * lanes).  No buffer of the ctx is used: the call runs inside an open deferred round.  Blocks once.  LOOKUP_OUT: ZK_ERR_BAD_ARG for
+ * a null table column or map (with lut_rows > 0) or a slot count that is not the table's; ZK_ERR_NOT_INDEXED for a key in no row. */
 int zk_gadget_witness_dev(zk_ctx* ctx, int curve_id, const void* args, void* d_values, size_t num_vars);
 /* One block of a lookup table (lookup/lookup_table.rs:94-152 insert_multi_add / _mul / _xor / _and(lower_bound, n_bits)) on the device:
  * with w = 2^n_bits - lower_bound, row r < w^2 holds a = lower_bound + r / w, b = lower_bound + r % w, c = op(a, b) mod 2^n_bits and the
@@ -895,6 +912,34 @@ int zk_gadget_witness_dev(zk_ctx* ctx, int curve_id, const void* args, void* d_v
  * d_a, d_b, d_c, d_d (w^2 elements each; a caller concatenates blocks by offsetting the pointers).  ZK_ERR_BAD_ARG: a null ctx or
  * column, an unknown op, n_bits > 12, lower_bound >= 2^n_bits.  Queued on the ctx stream; uses no buffer of the ctx. */
 int zk_lookup_table_dev(zk_ctx* ctx, int curve_id, int op, uint32_t lower_bound, uint32_t n_bits, void* d_a, void* d_b, void* d_c, void* d_d);
+
+/* ---- the output of a lookup: (a, b, d) -> c of the first matching row (lookup/lookup_table.rs:172-180 `LookupTable::lookup`) ------ */
+/* An open-addressing map (linear probing) from the key (a, b, d) of a table row to the SMALLEST index of a row that holds it: the
+ * reference's `.position(..)` returns the first match, and rows with one key and different c are legal.  Keys are compared as 32-byte
+ * strings: pass reduced (canonical Montgomery) elements, as everywhere.  Memory: 4 * slots bytes per table, owned by the caller.
+ * Host only: the slot count of a table of `rows` rows -- the power of two >= 2 * rows, at least 64; 0 for more than 2^30 rows. */
+size_t zk_lookup_map_slots(size_t rows);
+/* d_a, d_b, d_d: the three key columns, `rows` elements each (may be NULL when rows = 0); d_slots: u32[slots], slots =
+ * zk_lookup_map_slots(rows), overwritten.  Afterwards every distinct key names its smallest row index, whatever order the lanes
+ * arrive in (first claim of a slot by compare-and-swap, then a minimum).  rows = 0 gives an empty map.  ZK_ERR_BAD_ARG: a null ctx,
+ * column or buffer, a slot count that is not the table's; ZK_ERR_UNSUPPORTED: more than 2^30 rows.  Queued on the ctx stream; uses no
+ * buffer of the ctx. */
+int zk_lookup_map_build_dev(zk_ctx* ctx, int curve_id, const void* d_a, const void* d_b, const void* d_d, size_t rows, void* d_slots,
+                            size_t slots);
+/* n queries (n < 2^32) against the table d_table (its four columns a, b, c, d of `rows` rows) and its map.  Operand w of query i
+ * (w = 0, 1, 2: a, b, d; d_operands holds three pointers) is d_operands[w][i], or d_operands[w][d_operand_ids[w][i]] where d_operand_ids is not NULL and its entry w
+ * is a u32[n] vector on the device; every operand vector holds operand_rows elements.  c of the first matching row goes to d_out[i], or
+ * to d_out[d_out_ids[i]] when d_out_ids (u32[n]) is not NULL; d_out holds out_rows elements.  d_pos (u32[n], or NULL) receives the
+ * matching row index, 0xFFFFFFFF for a miss.  ZK_ERR_NOT_INDEXED when a query matches no row (Error::ElementNotIndexed): *misses
+ * (or NULL) receives how many do, *first_miss (or NULL) the smallest such i (n when there is none); the hits are written all the
+ * same and a miss writes nothing but its d_pos.  ZK_ERR_BAD_ARG: a null ctx, table column (with rows > 0), map, operand vector or
+ * d_out, a slot count that is not the table's, operand_rows < n or out_rows < n for a vector read or written directly, an index
+ * that is not below operand_rows / out_rows (by one flag word; such a query reads and writes nothing); ZK_ERR_UNSUPPORTED: n >= 2^32.
+ * Working memory: one device allocation of 256 bytes, freed before return; no buffer of the ctx is used: the call runs inside an
+ * open deferred round.  Blocks once (one 12-byte read-back of the flag, the miss count and the first miss). */
+int zk_lookup_map_query_dev(zk_ctx* ctx, int curve_id, const void* const d_table[4], size_t rows, const void* d_slots, size_t slots, size_t n,
+                            const void* const* d_operands, const void* const* d_operand_ids, size_t operand_rows, void* d_out,
+                            const void* d_out_ids, size_t out_rows, void* d_pos, uint64_t* misses, uint64_t* first_miss);
 
 /* ---- device self-test ------------------------------------------------------------------------------ */
 /* Runs the quad-cooperative point arithmetic of the bucket-reduction kernels (csrc/ecq.cuh) against the
