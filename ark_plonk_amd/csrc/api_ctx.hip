@@ -293,7 +293,10 @@ int zk_dev_alloc(zk_ctx* c, size_t bytes, void** d_ptr) {
     if (!c || !d_ptr) return ZK_ERR_BAD_ARG;
     Guard g(c);
     *d_ptr = nullptr;
-    if (hipMalloc(d_ptr, bytes ? bytes : 1) != hipSuccess) return ZK_ERR_OOM;
+    if (hipMalloc(d_ptr, bytes ? bytes : 1) != hipSuccess) {
+        *d_ptr = nullptr;
+        return zk_alloc_refused();
+    }
     return ZK_OK;
 }
 int zk_dev_free(zk_ctx* c, void* d_ptr) {

@@ -53,7 +53,7 @@ int run_flagged(zk_ctx* c, size_t work_bytes, Body&& body) {
     DeviceAlloc wk;
     if (hipMalloc(&wk.base, 256 + work_bytes) != hipSuccess) {
         wk.base = nullptr;
-        return ZK_ERR_OOM;
+        return zk_alloc_refused();
     }
     uint32_t* d_flag = (uint32_t*)wk.base;
     hipStream_t st = c->stream;

@@ -286,7 +286,7 @@ int check_impl(zk_ctx* c, uint32_t log_n, const zk_circuit_check_args* q, uint32
     DeviceAlloc wk;
     if (hipMalloc(&wk.base, total) != hipSuccess) {
         wk.base = nullptr;
-        return ZK_ERR_OOM;
+        return zk_alloc_refused();
     }
     char* w = (char*)wk.base;
     uint32_t* d_flag = (uint32_t*)w;

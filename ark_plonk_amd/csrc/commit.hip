@@ -5,7 +5,7 @@
 
 static int ensure_pinned_small(zk_ctx* c) {
     if (c->pinned_small) return ZK_OK;
-    if (hipHostMalloc(&c->pinned_small, 4096, hipHostMallocDefault) != hipSuccess) return ZK_ERR_OOM;
+    if (hipHostMalloc(&c->pinned_small, 4096, hipHostMallocDefault) != hipSuccess) return zk_alloc_refused();
     return ZK_OK;
 }
 

@@ -81,6 +81,16 @@ constexpr int ZK_MAX_FQ64 = 6, ZK_MAX_AFFINE64 = 2 * ZK_MAX_FQ64, ZK_MAX_JACOBIA
 
 void zk_note_hip_error(hipError_t e, const char* what, const char* file, int line);
 
+// The runtime refused an allocation (hipMalloc / hipHostMalloc returned an error).  The runtime keeps the last error of the calling
+// thread until hipGetLastError() reads it, and a later successful call does not reset it: left in place, the check behind the next
+// kernel launch (ZK_HIP_TRY(hipGetLastError())) would report this allocation's error for work that was queued without fault --
+// in the middle of the very recovery (release buffers, flush the round, retry) that the refusal starts.  Every site that tests an
+// allocation's return value leaves through here: the error is read away and the refusal becomes ZK_ERR_OOM, whatever its code.
+inline int zk_alloc_refused() {
+    (void)hipGetLastError();
+    return ZK_ERR_OOM;
+}
+
 // device buffer that grows on demand and is reused across calls (no hipMalloc in steady state)
 // Persistent helper threads for the host-side tails of a batch (window combine + affine normalisation:
 // ~70 us of serial field arithmetic per job while the GPU waits).  Creating a std::thread costs ~35 us on
@@ -182,7 +192,7 @@ struct DevBuf {
         hipError_t e = hipMalloc(&p, want);
         if (e != hipSuccess) {
             p = nullptr;
-            return ZK_ERR_OOM;
+            return zk_alloc_refused();
         }
         cap = want;
         return ZK_OK;

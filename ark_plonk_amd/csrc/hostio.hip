@@ -30,7 +30,7 @@ bool is_pinned(const void* p) {
 int stage_setup(zk_ctx* c) {
     for (int i = 0; i < zk_ctx::HostIo::STAGE_SLOTS; ++i) {
         if (!c->io.stage_pin[i]) {
-            if (hipHostMalloc(&c->io.stage_pin[i], zk_ctx::HostIo::STAGE_BYTES, hipHostMallocDefault) != hipSuccess) return ZK_ERR_OOM;
+            if (hipHostMalloc(&c->io.stage_pin[i], zk_ctx::HostIo::STAGE_BYTES, hipHostMallocDefault) != hipSuccess) return zk_alloc_refused();
             ZK_HIP_TRY(hipEventCreateWithFlags(&c->io.stage_ev[i], hipEventDisableTiming));
             c->io.stage_busy[i] = false;
         }

@@ -547,7 +547,7 @@ int zk_ipa_fold_key_dev(zk_ctx* c, int curve_id, size_t m, const void* d_key_xy,
     if (m == 0) return ZK_OK;
     const size_t pb = msm_ops(curve_id)->point_bytes();
     void* tmp = nullptr;
-    if (hipMalloc(&tmp, 3 * m * pb) != hipSuccess) return ZK_ERR_OOM;
+    if (hipMalloc(&tmp, 3 * m * pb) != hipSuccess) return zk_alloc_refused();
     void* folded = (char*)tmp + 2 * m * pb;
     int rc = msm_ops(curve_id)->convert_bases(c, d_key_xy, d_key_inf, 2 * m, tmp);
     if (!rc) rc = zk_on_curve(curve_id, ZK_ERR_BAD_ARG, [&](auto cv) { return launch_fold_key<decltype(cv)>(c, tmp, folded, m, xi_mont); });

@@ -155,7 +155,7 @@ int query_locked(zk_ctx* c, const QueryCall& qc, uint64_t* misses, uint64_t* fir
     DeviceAlloc wk;
     if (hipMalloc(&wk.base, 256) != hipSuccess) {
         wk.base = nullptr;
-        return ZK_ERR_OOM;
+        return zk_alloc_refused();
     }
     hipStream_t st = c->stream;
     QueryArgs q;

@@ -259,17 +259,13 @@ int msm_precompute_run(zk_ctx* c, zk_srs* s, uint32_t window_bits, uint32_t w0, 
     const size_t pb = s->point_bytes;
     void* tab = nullptr;
     void* scratch = nullptr;
-    if (hipMalloc(&tab, (size_t)rows * s->n * pb) != hipSuccess) {
-        (void)hipGetLastError();
-        return ZK_ERR_OOM;
-    }
+    if (hipMalloc(&tab, (size_t)rows * s->n * pb) != hipSuccess) return zk_alloc_refused();
     // row 0 is a copy of the SRS when the first owned window is window 0; the chain computes the others
     const uint32_t out0 = w0 == 0 ? 1u : 0u, chain_rows = rows - out0;
     const uint32_t rb = chain_rows < CHAIN_RB ? chain_rows : CHAIN_RB;
     if (hipMalloc(&scratch, (size_t)(rb ? rb : 1) * s->n * 3 * (pb / 2)) != hipSuccess) {
-        (void)hipGetLastError();
         (void)hipFree(tab);
-        return ZK_ERR_OOM;
+        return zk_alloc_refused();
     }
     hipError_t e = hipSuccess;
     if (w0 == 0) e = hipMemcpyAsync(tab, s->d_xy, s->n * pb, hipMemcpyDeviceToDevice, c->stream);

@@ -334,7 +334,7 @@ int ensure_pinned(zk_ctx* c, size_t bytes) {
     if (c->pinned) (void)hipHostFree(c->pinned);
     c->pinned = nullptr;
     c->pinned_cap = 0;
-    if (hipHostMalloc(&c->pinned, bytes, hipHostMallocDefault) != hipSuccess) return ZK_ERR_OOM;
+    if (hipHostMalloc(&c->pinned, bytes, hipHostMallocDefault) != hipSuccess) return zk_alloc_refused();
     c->pinned_cap = bytes;
     return ZK_OK;
 }

@@ -160,10 +160,10 @@ int get_inner_tw(zk_ctx* c, int s, bool inverse, void** out) {
     uint64_t cnt = s >= 1 ? (1ull << (s - 1)) : 1;
     void* packed = nullptr;
     void* p = nullptr;
-    ZK_HIP_TRY(hipMalloc(&packed, cnt * sizeof(Fr)));
+    if (hipMalloc(&packed, cnt * sizeof(Fr)) != hipSuccess) return zk_alloc_refused();
     if (hipMalloc(&p, cnt * TW_INNER_U4 * 16) != hipSuccess) {
         (void)hipFree(packed);
-        return ZK_ERR_OOM;
+        return zk_alloc_refused();
     }
     Fr w = domain_root<C>((uint32_t)s);
     if (inverse) w = Fr::inverse(w);
@@ -212,7 +212,7 @@ int get_plan(zk_ctx* c, uint32_t log_n, bool inverse, NttPlan** out) {
             uint32_t log_m = log_mprev - (uint32_t)pl->s[p];
             uint64_t cnt = 1ull << log_mprev;
             hipError_t e = hipMalloc(&pl->tw_pass[p], cnt * sizeof(Fr));
-            if (e != hipSuccess) { delete pl; return ZK_ERR_OOM; }
+            if (e != hipSuccess) { delete pl; return zk_alloc_refused(); }
             Fr w = domain_root<C>(log_mprev);
             if (inverse) w = Fr::inverse(w);
             int rc = launch_pow_table<C>(c, pl->tw_pass[p], cnt, w, Fr::one(), 1, log_m, log_mprev);

@@ -14,9 +14,11 @@ static void res_recycle(zk_ctx* c, DevBuf& buf) {
     buf = DevBuf();
 }
 
-static ResEntry* res_find(zk_ctx* c, size_t bytes, const uint64_t dig[4]) {
+// *held: the running call had touched the entry before this look-up -- an earlier input of the call may use its buffer
+static ResEntry* res_find(zk_ctx* c, size_t bytes, const uint64_t dig[4], bool* held) {
     for (auto it = c->res.entries.begin(); it != c->res.entries.end(); ++it)
         if (it->valid && it->bytes == bytes && memcmp(it->dig, dig, 32) == 0) {
+            *held = it->epoch == c->res.epoch;
             it->epoch = c->res.epoch;
             if (it != c->res.entries.begin()) c->res.entries.splice(c->res.entries.begin(), c->res.entries, it);
             ++c->res.hits;
@@ -29,8 +31,14 @@ static ResEntry* res_find(zk_ctx* c, size_t bytes, const uint64_t dig[4]) {
 static void res_drop(zk_ctx* c, ResEntry* e);
 
 // option "cache_verify": a hit is believed only after the resident bytes were compared with the caller's (both streams drained, one
-// blocking download); a mismatch -- two vectors under one keyed digest, or a bug -- is counted, the entry dropped, the call uploads
-static bool res_verify_hit(zk_ctx* c, ResEntry* e, const void* host_bytes) {
+// blocking download); a mismatch -- two vectors under one keyed digest, or a bug -- is counted, the entry dropped, the call uploads.
+// An entry the running call already held (`held`: res_find) is NOT dropped: an earlier input of this res_resolve was given its buffer
+// (two different vectors of one length under one digest in one batch: the first matched the resident bytes, the second does not).
+// Dropped, the buffer would go to the free list, the res_new that follows for this very input would take it from there, and the
+// upload would overwrite what the earlier input reads.  Such an entry is invalidated in place instead: it keeps its buffer and its
+// epoch, so nothing evicts it while the call runs; no look-up finds it again, and eviction reclaims it like any other entry.  (No
+// test builds two vectors under one keyed 256-bit digest; the argument stands in for one.)
+static bool res_verify_hit(zk_ctx* c, ResEntry* e, const void* host_bytes, bool held) {
     if (!c->cache_verify) return true;
     if (e->born == c->res.epoch) return true;       // created by this very call (the same vector twice in one batch): its upload has not been queued yet
     (void)hipStreamSynchronize(c->stream);
@@ -43,7 +51,8 @@ static bool res_verify_hit(zk_ctx* c, ResEntry* e, const void* host_bytes) {
         ++c->verify_mismatch;
         --c->res.hits;
         ++c->res.misses;
-        res_drop(c, e);
+        if (held) e->valid = false;
+        else res_drop(c, e);
     }
     return same;
 }
@@ -92,8 +101,9 @@ void res_digest(zk_ctx* c, const void* host, size_t bytes, uint64_t dig[4]) {
 }
 ResEntry* res_lookup(zk_ctx* c, const void* host, size_t bytes, uint64_t dig[4]) {
     res_digest(c, host, bytes, dig);
-    ResEntry* e = res_find(c, bytes, dig);
-    return e && res_verify_hit(c, e, host) ? e : nullptr;
+    bool held = false;
+    ResEntry* e = res_find(c, bytes, dig, &held);
+    return e && res_verify_hit(c, e, host, held) ? e : nullptr;
 }
 
 static void res_drop(zk_ctx* c, ResEntry* e) {        // an entry whose production failed
@@ -143,8 +153,9 @@ void res_resolve(zk_ctx* c, uint32_t n, const void* const* h_ptrs, const size_t*
     host_digest256_multi(c->pool.get(), hp, hb, m, RES_SEED, dig);
     for (uint32_t j = 0; j < m; ++j) {
         const uint32_t k = idx[j];
-        ResEntry* e = res_find(c, hb[j], dig[j]);
-        if (e && !res_verify_hit(c, e, hp[j])) e = nullptr;
+        bool held = false;
+        ResEntry* e = res_find(c, hb[j], dig[j], &held);
+        if (e && !res_verify_hit(c, e, hp[j], held)) e = nullptr;
         if (e) {
             out[k].d_ptr = e->buf.p;
             out[k].upload = false;

@@ -5,7 +5,7 @@
 constexpr size_t PINNED_JOB_SLOT = 512;
 static int ensure_pinned_jobs(zk_ctx* c) {
     if (c->round.pinned_jobs) return ZK_OK;
-    if (hipHostMalloc(&c->round.pinned_jobs, ZK_MAX_JOBS * PINNED_JOB_SLOT, hipHostMallocDefault) != hipSuccess) return ZK_ERR_OOM;
+    if (hipHostMalloc(&c->round.pinned_jobs, ZK_MAX_JOBS * PINNED_JOB_SLOT, hipHostMallocDefault) != hipSuccess) return zk_alloc_refused();
     return ZK_OK;
 }
 

@@ -50,7 +50,7 @@ static int srs_build(zk_ctx* c, int curve_id, const void* d_sat, const uint8_t* 
     if (n) {
         if (hipMalloc(&s->d_xy, n * s->point_bytes) != hipSuccess) {
             delete s;
-            return ZK_ERR_OOM;
+            return zk_alloc_refused();
         }
         int rc = msm_ops(curve_id)->convert_bases(c, d_sat, d_inf, n, s->d_xy);
         hipError_t e = hipStreamSynchronize(c->stream);

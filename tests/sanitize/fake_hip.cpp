@@ -6,6 +6,16 @@
 //   * a kernel launch does nothing.  Device results are therefore all-zero bytes -- the point at infinity, the zero digest -- which
 //     is enough for what the sanitizers are here to watch: locks, reference counts, list and buffer management, thread hand-offs.
 // Arithmetic on real points is covered by the host-only entry points the harness calls directly (zk_g1_sum_partials*, wire.hip).
+//
+// The last error.  Since ROCm 7.0 hipGetLastError() returns the last error that ANY runtime call produced on the calling thread and
+// only then resets it to hipSuccess; a call that succeeds in between does not reset it.  The fake models exactly that: every entry
+// point that returns something other than hipSuccess records it in a thread-local (note()), hipGetLastError() returns and clears it.
+// The library checks ZK_HIP_TRY(hipGetLastError()) behind its kernel launches, so an error it tested and handled but did not read
+// away (a refused hipMalloc before a retry) surfaces there -- as it would on a card.  This behaviour of the real runtime is measured
+// on the GPU by tests/test_alloc_refusal_gpu.py::test_runtime_last_error_is_kept_until_read; the fake follows that measurement.
+//
+// Hooks for the harness: fake_hip_set_memory (a device of a given size), fake_hip_fail_alloc_after (one chosen allocation fails),
+// fake_hip_flip_byte (corrupt the "device" copy of a buffer of a given size).
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
@@ -34,22 +44,51 @@ extern "C" size_t fake_hip_live_bytes() {
     std::lock_guard<std::mutex> lk(g_mem_mu);
     return g_live_bytes;
 }
+// The k-th hipMalloc / hipHostMalloc from now (k = 0: the next one) fails once with hipErrorOutOfMemory; a negative k switches the
+// hook off.  Returns the count that was still to go: negative when the hook was off or the failure has fired.
+static std::atomic<long> g_fail_after{-1};
+extern "C" long fake_hip_fail_alloc_after(long k) { return g_fail_after.exchange(k < 0 ? -1 : k); }
+static bool fail_this_alloc() { return g_fail_after.load() >= 0 && g_fail_after.fetch_sub(1) == 0; }
+// Inverts the first byte of every live allocation of exactly `alloc_bytes` (device memory is host memory here): a resident copy that
+// no longer holds what its digest names.  Returns how many allocations it touched.
+extern "C" long fake_hip_flip_byte(size_t alloc_bytes) {
+    std::lock_guard<std::mutex> lk(g_mem_mu);
+    long hit = 0;
+    for (auto& kv : g_mem)
+        if (kv.second == alloc_bytes && alloc_bytes) {
+            unsigned char* b = (unsigned char*)kv.first;
+            b[0] = (unsigned char)~b[0];
+            ++hit;
+        }
+    return hit;
+}
+// the calling thread's last error: see the header
+static thread_local hipError_t t_last_error = hipSuccess;
+static hipError_t note(hipError_t e) {
+    if (e != hipSuccess) t_last_error = e;
+    return e;
+}
 
 extern "C" {
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 hipError_t hipDeviceSynchronize() { return hipSuccess; }
-hipError_t hipGetLastError() { return hipSuccess; }
+hipError_t hipGetLastError() {
+    hipError_t e = t_last_error;
+    t_last_error = hipSuccess;
+    return e;
+}
 const char* hipGetErrorString(hipError_t) { return "fake hip"; }
 hipError_t hipMalloc(void** p, size_t n) {
     *p = nullptr;
+    if (fail_this_alloc()) return note(hipErrorOutOfMemory);
     {
         std::lock_guard<std::mutex> lk(g_mem_mu);
-        if (g_budget && g_live_bytes + n > g_budget) return hipErrorOutOfMemory;
+        if (g_budget && g_live_bytes + n > g_budget) return note(hipErrorOutOfMemory);
     }
     *p = calloc(n ? n : 1, 1);
-    if (!*p) return hipErrorOutOfMemory;
+    if (!*p) return note(hipErrorOutOfMemory);
     ++g_allocs;
     std::lock_guard<std::mutex> lk(g_mem_mu);
     g_mem[*p] = n;
@@ -86,7 +125,7 @@ hipError_t hipHostRegister(void*, size_t, unsigned) { return hipSuccess; }
 hipError_t hipHostUnregister(void*) { return hipSuccess; }
 hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void*) {
     memset(a, 0, sizeof *a);
-    return hipErrorInvalidValue;      // "not a registered pointer": the library then treats the buffer as pageable
+    return note(hipErrorInvalidValue);      // "not a registered pointer": the library then treats the buffer as pageable
 }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) {
     if (n) memmove(d, s, n);

@@ -8,9 +8,13 @@
 //     deferred rounds (begin / open_begin / reduce / end / abort, the ZK_ERR_PENDING refusals), the commitment cache (LRU list);
 //   * the persistent host pool (HostPool::run from several ctxs at once) and the host tails of a round;
 //   * with REAL points: zk_g1_sum_partials(_batch) -- Jacobian -> XYZZ, host additions incl. doubling and cancellation, Fermat
-//     inversion, affine normalisation -- on the group generator decoded by wire.hip's own deserialiser.
+//     inversion, affine normalisation -- on the group generator decoded by wire.hip's own deserialiser;
+//   * every allocation of one pass over the library refused in turn (section 2d: the codes returned, the ctx afterwards, what is left
+//     allocated), under a fake runtime that keeps its last error until it is read, as the real one does;
+//   * a residency-cache hit whose device copy is wrong, under option "cache_verify" (section 2e).
 // Exit code 0 and "host_stress ok" = every call returned what it must; the sanitizer's own report fails the test otherwise.
 #include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -23,6 +27,8 @@ extern "C" long fake_hip_launches();
 extern "C" long fake_hip_live_allocations();
 extern "C" void fake_hip_set_memory(size_t budget, size_t report_extra);
 extern "C" size_t fake_hip_live_bytes();
+extern "C" long fake_hip_fail_alloc_after(long k);          // the k-th allocation from now fails once (negative: off); returns what was left
+extern "C" long fake_hip_flip_byte(size_t alloc_bytes);     // inverts the first byte of every live allocation of that size; returns how many
 void zk_process_key_reset_for_tests(const char* path);      // csrc/hostio.hip: test hook, not part of the C ABI
 
 #define REQUIRE(cond)                                                              \
@@ -107,6 +113,86 @@ static std::atomic<int> g_fail{0};
             return;                                                                           \
         }                                                                                     \
     } while (0)
+
+// ---- the scenario of the allocation-failure sweep (section 2d): one pass over the calls that allocate -- a ctx, an SRS and its 16-bit
+// table, a blocking batch, a deferred round with an opening, the host-pointer calls behind both caches, an NTT with its plan, a circuit
+// check, a lookup map and one IPA key fold -- at the sizes the sections above use.  Any one hipMalloc / hipHostMalloc of it may be the
+// one fake_hip_fail_alloc_after() refuses.  What must hold whichever it is: every call returns ZK_OK or ZK_ERR_OOM and nothing else
+// (a stale runtime error would come back as ZK_ERR_HIP or as a second ZK_ERR_OOM from a call that allocated nothing); at most ONE call
+// of a pass fails, since the hook fires once and a ctx that has refused a call works again at the next; an open round can be aborted.
+// A call that needs what a failed call did not deliver (the ctx, the SRS, a device buffer) is skipped.
+struct Scenario {
+    const std::vector<uint64_t>* srs_bytes;
+    const std::vector<std::vector<uint64_t>>* polys;
+    size_t n;
+    int ooms = 0;           // calls of this pass that returned ZK_ERR_OOM
+    int bad_line = 0;       // the first call that returned anything else, or a round that could not be aborted
+    bool note(int rc, int line) {
+        if (rc == ZK_ERR_OOM) ++ooms;
+        else if (rc != ZK_OK && !bad_line) bad_line = line;
+        return rc == ZK_OK;
+    }
+    // *pc: the ctx to use, created here when null (and left to the caller, who destroys it)
+    void run(zk_ctx** pc) {
+#define STEP(call) note((call), __LINE__)
+        ooms = 0, bad_line = 0;
+        if (!*pc && !STEP(zk_ctx_create(0, pc))) return;
+        zk_ctx* c = *pc;
+        zk_srs* s = nullptr;
+        void* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // four polynomials, an output vector, a lookup map
+        const size_t slots = zk_lookup_map_slots(64);
+        [&] {
+            if (!STEP(zk_srs_register(c, CURVE, srs_bytes->data(), nullptr, n, &s))) return;
+            STEP(zk_srs_precompute(c, s));             // refused: no table, the calls below take the per-window path
+            for (int k = 0; k < 6; ++k)
+                if (!STEP(zk_dev_alloc(c, k == 5 ? slots * 4 : n * 32, &d[k]))) return;
+            for (int k = 0; k < 4; ++k)
+                if (!STEP(zk_dev_upload(c, d[k], (*polys)[k].data(), n * 32))) return;
+            const void* in[4] = {d[0], d[1], d[2], d[3]};
+            const uint64_t* hp[4] = {(*polys)[0].data(), (*polys)[1].data(), (*polys)[2].data(), (*polys)[3].data()};
+            size_t lens[4] = {n, n, n - 1, 64};
+            uint64_t xy[16 * 12], z[4] = {5, 0, 0, 0}, ch[4] = {7, 0, 0, 0};
+            uint8_t inf[16];
+            STEP(zk_kzg_commit_batch_dev(c, s, 4, in, lens, xy, inf));
+            // a deferred round: whatever refuses, the round can be dropped and leaves nothing pending
+            const bool queued = STEP(zk_kzg_round_begin_dev(c, s, 2, in, lens, nullptr)) && STEP(zk_kzg_open_begin_dev(c, s, 3, in, lens, z, ch));
+            if (!queued || !STEP(zk_kzg_round_end(c, 3, xy, inf))) {
+                uint32_t pend = 9;
+                if ((zk_kzg_round_abort(c) != ZK_OK || zk_kzg_round_pending(c, &pend) != ZK_OK || pend != 0) && !bad_line) bad_line = __LINE__;
+            }
+            // the host-pointer calls with the residency and the commitment cache on
+            if (STEP(zk_ctx_set_residency_cache(c, 1, 0, 0)) && STEP(zk_ctx_set_commit_cache(c, 1, 8))) {
+                STEP(zk_kzg_commit_batch(c, s, 4, hp, lens, xy, inf));
+                STEP(zk_kzg_open(c, s, 3, hp, lens, z, ch, xy, inf));
+            }
+            STEP(zk_ctx_set_residency_cache(c, 0, 0, 0));
+            STEP(zk_ctx_set_commit_cache(c, 0, 0));
+            STEP(zk_ntt_prepare(c, CURVE, 13));
+            STEP(zk_ntt_dev(c, CURVE, ZK_NTT_IFFT, 13, d[0], n, d[4]));
+            {   // a circuit check over 2^13 rows: every column is one of the vectors above (the fake device computes nothing)
+                zk_circuit_check_args a;
+                memset(&a, 0, sizeof a);
+                a.w_l = d[0], a.w_r = d[1], a.w_o = d[2], a.w_4 = d[3];
+                a.q_m = a.q_l = a.q_r = a.q_o = a.q_4 = a.q_c = a.q_arith = a.q_range = a.q_logic = a.q_fixed_group_add = a.q_variable_group_add = a.q_lookup = d[0];
+                for (int k = 0; k < 4; ++k) a.sigma[k] = d[k], a.table[k] = d[k];
+                a.table_rows = 64;
+                zk_circuit_check_summary sum;
+                STEP(zk_circuit_check_dev(c, CURVE, 13, &a, nullptr, &sum));
+            }
+            {   // a lookup map over the first 64 rows and 64 queries of it
+                const void* ops[3] = {d[0], d[1], d[3]};
+                uint64_t misses = 0, first = 0;
+                if (STEP(zk_lookup_map_build_dev(c, CURVE, d[0], d[1], d[3], 64, d[5], slots)))
+                    STEP(zk_lookup_map_query_dev(c, CURVE, in, 64, d[5], slots, 64, ops, nullptr, 64, d[4], nullptr, 64, nullptr, &misses, &first));
+            }
+            STEP(zk_ipa_fold_key_dev(c, CURVE, 64, d[0], nullptr, z, d[4], nullptr));      // 128 key points in, 64 out
+        }();
+        for (int k = 0; k < 6; ++k)
+            if (d[k]) STEP(zk_dev_free(c, d[k]));
+        if (s) zk_srs_free(s);
+#undef STEP
+    }
+};
 
 int main() {
     REQUIRE(real_point_arithmetic() == 0);
@@ -365,6 +451,84 @@ int main() {
         zk_srs_free(s2);
         zk_ctx_destroy(c);
         zk_process_key_reset_for_tests(nullptr);
+    }
+
+    // ---- 2d. the allocation-failure sweep: the scenario above with its k-th allocation refused, for every k it has
+    {
+        std::vector<uint64_t> srs_c(n * 2 * L);
+        for (size_t i = 0; i < srs_c.size(); ++i) srs_c[i] = 0x5000 + 7 * i;      // bytes no other section registers
+        REQUIRE(zk_srs_cache_config(0) == ZK_OK && zk_srs_cache_config((size_t)32 << 30) == ZK_OK);      // idle entries of the sections above
+        const auto t0 = std::chrono::steady_clock::now();
+        const long live0 = fake_hip_live_allocations(), far = 1l << 40;
+        Scenario sc{&srs_c, &polys, n};
+        // one pass of the scenario on *pc (created when null), then the ctx destroyed and the SRS evicted: nothing of the pass is left
+        auto pass = [&](zk_ctx** pc, bool keep_ctx) {
+            sc.run(pc);
+            if (!keep_ctx && *pc) {
+                zk_ctx_destroy(*pc);
+                *pc = nullptr;
+            }
+            return zk_srs_cache_config(0) == ZK_OK && zk_srs_cache_config((size_t)32 << 30) == ZK_OK && sc.bad_line == 0;
+        };
+        zk_ctx* c = nullptr;
+        fake_hip_fail_alloc_after(far);                              // counts, never fires
+        REQUIRE(pass(&c, false) && sc.ooms == 0);
+        const long counted = far - fake_hip_fail_alloc_after(-1);
+        REQUIRE(counted > 20 && fake_hip_live_allocations() == live0);
+        long swept = 0;
+        for (long k = 0;; ++k) {
+            fake_hip_fail_alloc_after(k);
+            const bool ok = pass(&c, true);
+            const bool fired = fake_hip_fail_alloc_after(-1) < 0;
+            if (!ok || sc.ooms > 1 || (!fired && sc.ooms)) {
+                fprintf(stderr, "host_stress: allocation %ld refused: host_stress.cpp:%d returned neither ZK_OK nor ZK_ERR_OOM, or %d calls failed\n", k,
+                        sc.bad_line, sc.ooms);
+                return 1;
+            }
+            if (fired) {
+                ++swept;
+                if (c) REQUIRE(pass(&c, false) && sc.ooms == 0);      // the ctx that met the refusal: everything works
+            } else if (c) {
+                zk_ctx_destroy(c);
+                c = nullptr;
+            }
+            REQUIRE(fake_hip_live_allocations() == live0);
+            if (!fired) break;                                        // the scenario has no k-th allocation: every one was refused once
+            REQUIRE(pass(&c, false) && sc.ooms == 0);                 // ... and so does a fresh one
+            REQUIRE(fake_hip_live_allocations() == live0);
+        }
+        REQUIRE(swept >= counted);                                    // a scenario that shrank under injection would pass with fewer
+        printf("host_stress: allocation sweep: %ld allocation sites refused one by one (%ld counted without injection), %.1f s\n", swept, counted,
+               std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    }
+
+    // ---- 2e. cache_verify meets a wrong hit: the resident copy of a vector no longer holds what its digest names
+    {
+        zk_ctx* c = nullptr;
+        REQUIRE(zk_ctx_create(0, &c) == ZK_OK);
+        REQUIRE(zk_ctx_set_residency_cache(c, 1, 0, 0) == ZK_OK && zk_ctx_set_option(c, "cache_verify", 1) == ZK_OK);
+        const size_t m = n - 5, bytes = m * 32;                       // a length no other vector of the program has
+        const size_t alloc = bytes + bytes / 8 + 256;                 // what a device buffer of `bytes` allocates (DevBuf::want_for, csrc/ctx.h)
+        const uint64_t* hp[3] = {polys[3].data(), polys[3].data(), polys[0].data()};
+        size_t hl[3] = {m, m, n};
+        uint64_t xy[3 * 12];
+        uint8_t inf[3];
+        REQUIRE(zk_kzg_commit_batch(c, srs, 3, hp, hl, xy, inf) == ZK_OK);              // both vectors resident
+        uint64_t h0 = 0, m0 = 0, e0 = 0, b0 = 0, h1 = 0, m1 = 0, e1 = 0, b1 = 0, chk0 = 0, bad0 = 9, chk1 = 0, bad1 = 9;
+        REQUIRE(zk_residency_cache_stats(c, &h0, &m0, &e0, &b0) == ZK_OK && e0 == 2 && b0 == bytes + n * 32);
+        REQUIRE(zk_cache_verify_stats(c, &chk0, &bad0) == ZK_OK && bad0 == 0);
+        const long live = fake_hip_live_allocations();
+        REQUIRE(fake_hip_flip_byte(alloc) >= 1);                      // the device copy (and the ctx's scratch buffers of that length, which
+                                                                      // nothing reads on the fake device): the one mismatch below is the proof
+        // the vector twice in one batch, and the other one: the first finds the entry wrong and replaces it, the second uses the replacement
+        REQUIRE(zk_kzg_commit_batch(c, srs, 3, hp, hl, xy, inf) == ZK_OK && inf[0] && inf[2]);
+        REQUIRE(zk_cache_verify_stats(c, &chk1, &bad1) == ZK_OK && bad1 == bad0 + 1 && chk1 == chk0 + 2);
+        REQUIRE(zk_residency_cache_stats(c, &h1, &m1, &e1, &b1) == ZK_OK && e1 == e0 && b1 == b0 && h1 == h0 + 2 && m1 == m0 + 1);
+        REQUIRE(fake_hip_live_allocations() == live);                 // the dropped entry's buffer took the upload
+        REQUIRE(zk_kzg_commit_batch(c, srs, 3, hp, hl, xy, inf) == ZK_OK);              // again: three hits, all checked, nothing wrong
+        REQUIRE(zk_cache_verify_stats(c, &chk0, &bad0) == ZK_OK && bad0 == bad1 && chk0 == chk1 + 3);
+        REQUIRE(zk_residency_cache_stats(c, &h0, &m0, &e0, &b0) == ZK_OK && e0 == e1 && b0 == b1 && h0 == h1 + 3 && m0 == m1);
+        zk_ctx_destroy(c);
     }
 
     // ---- 3. eviction: drop every unreferenced entry, then the last references
