@@ -21,6 +21,8 @@ from . import composer  # noqa: F401  (gadget circuits and their witnesses, buil
 from .composer import Composer  # noqa: F401
 from . import verifier  # noqa: F401  (batch verification up to the two pairing inputs)
 from .verifier import BatchVerifier, IpaBatchVerifier  # noqa: F401
+from . import pairing  # noqa: F401  (the KZG pairing check: a prepared G2 key, one check on the host, B checks on the device)
+from .pairing import G2Affine, PairingKey  # noqa: F401
 from .msm import (CommitterKey, G1Affine, VariableBaseMSM, kzg_witness, srs_cache_config, segments_msm, srs_cache_stats,  # noqa: F401
                   sum_partials, sum_partials_batch)
 
@@ -28,4 +30,5 @@ __all__ = [
     "Context", "default_context", "BLS12_381", "BN254", "get_curve", "GeneralEvaluationDomain",
     "Radix2EvaluationDomain", "CommitterKey", "G1Affine", "VariableBaseMSM", "kzg_witness", "sum_partials", "sum_partials_batch", "srs_cache_stats", "srs_cache_config", "permutation", "quotient", "lookup", "linearisation", "prover", "transcript",
     "verifier", "BatchVerifier", "IpaBatchVerifier", "segments_msm", "composer", "Composer", "circuit_check", "check_circuit", "CheckReport", "CircuitNotSatisfied", "BIT_NAMES",
+    "pairing", "PairingKey", "G2Affine",
 ]

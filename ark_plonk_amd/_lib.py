@@ -243,6 +243,13 @@ SYMBOLS = {
     "zk_verify_scalars_dev": (c_int, [c_void_p, c_int, c_u32, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zk_fr_column_sum_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_u32, c_void_p]),
+    # the KZG pairing check: a prepared key (host), one check on the host, n checks / GT values on the device
+    "zk_pairing_key_new": (c_int, [c_int, c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
+    "zk_pairing_key_free": (None, [c_void_p]),
+    "zk_kzg_pairing_check": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "zk_kzg_pairing_check_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "zk_pairing_gt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "zk_pairing_gt_batch_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

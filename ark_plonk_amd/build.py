@@ -30,6 +30,7 @@ DOMAIN, DEV_SCAN = ["fr_io.cuh", "domain.cuh"], ["dev_scan.cuh"]       # domain 
 GADGET = ["gadget_common.cuh"]            # what the two units of the device composer (layout, witness) share
 BLOCK_INV = ["block_inverse.cuh"]         # one field inversion per workgroup: the key fold, the gadget witnesses, the verifier's scalars
 G1_LIFT = ["g1_lift.cuh"]              # an x to a point of the curve (root, sign rule): the point decoder and the IPA key derivation
+PAIRING = ["pairing.cuh", "pairing_params.h"]      # the Fq12 tower, the Miller loop over a line table, the final exponentiation: host and device
 REPLAY = ["strobe.cuh", "replay_walk.cuh"]      # merlin's sponge and the verifier's parse + replay of one proof: host (wire) and device (replay)
 # the C ABI, one unit per subsystem (api_internal.h is what they share)
 API_UNITS = ("api_ctx", "residency", "srs", "commit", "round", "api_host", "api_poly")
@@ -69,6 +70,8 @@ def jobs():
         ("g1_segments.o", "g1_segments.hip", [], API_HDRS + BLOCK_INV),
         # ipa_pc::setup: the committer key's generators hashed to the curve (wave-local candidate search, cofactor clearing)
         ("ipa_setup.o", "ipa_setup.hip", [], API_HDRS + BLOCK_INV + G1_LIFT + ["h2c.cuh"]),
+        # the KZG pairing check: prepared G2 keys (host), one check on the host, one check per lane on the device
+        ("pairing.o", "pairing.hip", [], API_HDRS + PAIRING),
     ]
     for c in (0, 1):
         # ARK_PLONK_AMD_MSM_FLAGS: extra compiler flags for the MSM objects only (scheduler experiments: tools/ab_bench.sh)

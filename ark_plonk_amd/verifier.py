@@ -1,4 +1,4 @@
-"""Batch verification of proofs of one circuit, up to the two pairing inputs.
+"""Batch verification of proofs of one circuit: the two pairing inputs and the pairing check (section 6i).
 
 `Proof::verify` (proof_system/proof.rs:110-425) ends in two KZG checks, e(C - v G, H) = e(W, tau H - z H) each.  Everything in front of
 them is G1 and Fr arithmetic, and with unpredictable weights it folds across proofs: B proofs of one verifier key go in, TWO points
@@ -7,8 +7,10 @@ come out,
     L = sum_j (u_j W_aw,j + u'_j W_saw,j)
     R = sum_j (u_j (sum_k chi^k (C_k - v_k G) + z W_aw) + u'_j (sum_k chi'^k (C'_k - v'_k G) + z w W_saw))_j
 
-and every proof of the batch is valid iff e(L, [tau]H) = e(R, H), except with probability about 2^-128 over the weights.  The pairing
-is the caller's: this library has none.  Stages, each one entry point of the C ABI:
+and every proof of the batch is valid iff e(L, [tau]H) = e(R, H), except with probability about 2^-128 over the weights.  That check
+is `pairing.PairingKey` (the G2 side of the verifier key, prepared once): given one, `BatchVerifier.verify` answers yes or no with
+one check on the host, `locate_invalid` bisects with it, and `verdicts` gives every proof its own answer with no bisection -- every
+(L_j, R_j) from one segmented MSM, then one launch of B checks, one per lane.  Stages, each one entry point of the C ABI:
 
   1  zk_g1_decompress_batch_dev   the 15 points of every proof decoded and checked on the device (one lane per point)
   2  zk_proof_replay_batch        host, serial: bytes parsed, the transcript replayed -> 14 challenges and 23 evaluations per proof
@@ -17,6 +19,8 @@ is the caller's: this library has none.  Stages, each one entry
   3  zk_verify_scalars_dev        per proof: 20 scalars over the verifier key's bases and G, 15 over its own points, 2 for L
   4  zk_fr_column_sum_dev + the existing MSM over the decoded points (zk_srs_register_dev, zk_msm_g1_srs_partial_dev,
      zk_g1_sum_partials), over any range [lo, hi) of the batch: the per-proof rows stay resident, another range costs only this stage
+  5  zk_kzg_pairing_check         host: e(L, [tau]H) e(-R, H) = 1 for one fold
+     zk_msm_g1_segments_dev + zk_kzg_pairing_check_batch_dev   per-proof (L_j, R_j) and their B checks, one per lane
 
 `BatchVerifier(replay=...)` chooses stage 2: "host" decodes the points (1) while the host replays (2); "device" makes one upload and
 queues 2, 1, 3 behind it with no host synchronisation before the statuses come back; "auto" takes the device from
@@ -266,9 +270,10 @@ def column_sum(rows, curve="bls12_381", ctx: Context | None = None):
 class _Resident:
     """what one batch leaves on the device: the decoded points as MSM bases and the scalar rows"""
 
-    def __init__(self, n, key_rows, proof_rows, open_rows, proof_ck, open_ck, status):
+    def __init__(self, n, key_rows, proof_rows, open_rows, proof_ck, open_ck, status, pts=None, inf=None):
         self.n, self.key_rows, self.proof_rows, self.open_rows = n, key_rows, proof_rows, open_rows
         self.proof_ck, self.open_ck, self.status = proof_ck, open_ck, status
+        self.pts, self.inf = pts, inf             # the decoded points and their flags as plain tensors: the bases of `verdicts`
 
     def close(self):
         for ck in (self.proof_ck, self.open_ck):
@@ -278,20 +283,24 @@ class _Resident:
 
 
 class BatchVerifier:
-    """B proofs of ONE circuit -> the two pairing inputs (L, R) and a status per proof.
+    """B proofs of ONE circuit -> the two pairing inputs (L, R) and a status per proof; with a pairing key, valid or not.
 
     vk: the dict `ProverKey.verifier_key` returns (name -> G1Affine); n: the circuit's domain size; seeded_transcript: the
     `transcript.Transcript` after `seed_transcript(vk, n)`; coeff_a, coeff_d: the embedded curve's coefficients (4 Montgomery limbs).
     replay: where stage 2 runs -- "host", "device", or "auto" (the device from REPLAY_ON_DEVICE_FROM proofs); no result depends on it.
-    The pairing check e(L, [tau]H) = e(R, H) is the caller's."""
+    pairing_key: the `pairing.PairingKey` of the verifier key's G2 points -- the check e(L, [tau]H) = e(R, H) behind `verify`,
+    `verdicts` and `locate_invalid`; without one the verifier stops at (L, R) and `locate_invalid` takes the caller's check."""
 
     def __init__(self, vk: dict, n: int, seeded_transcript, coeff_a, coeff_d, curve="bls12_381", ctx: Context | None = None,
-                 replay: str = "auto"):
+                 replay: str = "auto", pairing_key=None):
         torch = _torch()
         if replay not in ("host", "device", "auto"):
             raise ValueError('replay is "host", "device" or "auto"')
         self.replay = replay
         self.curve = get_curve(curve)
+        if pairing_key is not None and pairing_key.curve != self.curve:
+            raise ValueError("the pairing key is of another curve")
+        self.pairing_key = pairing_key
         self.ctx = ctx or default_context(0)
         if n <= 0 or n & (n - 1):
             raise ValueError("the domain size is a power of two")
@@ -305,7 +314,8 @@ class BatchVerifier:
         xy = np.stack([np.asarray(p.xy(), dtype=np.uint64) for p in pts] + [g])
         inf = np.array([1 if p.infinity else 0 for p in pts] + [0], dtype=np.uint8)
         dev = torch.device("cuda", self.ctx.device)
-        self._key_ck = CommitterKey(torch.from_numpy(xy.view(np.int64)).to(dev), cv, self.ctx, infinity=torch.from_numpy(inf).to(dev))
+        self._key_xy, self._key_inf = torch.from_numpy(xy.view(np.int64)).to(dev), torch.from_numpy(inf).to(dev)
+        self._key_ck = CommitterKey(self._key_xy, cv, self.ctx, infinity=self._key_inf)
         self._res = None
 
     def close(self):
@@ -352,7 +362,7 @@ class BatchVerifier:
         o_pts = pts.view(B, N_PROOF_BASES, L2)[:, 13:15].contiguous().view(2 * B, L2)
         o_inf = inf.view(B, N_PROOF_BASES)[:, 13:15].contiguous().view(2 * B)
         open_ck = CommitterKey(o_pts, cv, ctx, infinity=o_inf)                    # the openings again, stride 2: the bases of L
-        self._res = _Resident(B, key, prf, opn, proof_ck, open_ck, st.cpu().numpy())
+        self._res = _Resident(B, key, prf, opn, proof_ck, open_ck, st.cpu().numpy(), pts, inf)
         return self._res.status
 
     def replay_on_device(self, n_proofs: int) -> bool:
@@ -410,10 +420,69 @@ class BatchVerifier:
         L, R = self.fold_range(lo, hi)
         return L, R, st
 
-    def locate_invalid(self, proofs, public_inputs, accepts, weights=None) -> list:
-        """Indices of the proofs that do not verify: those with a non-zero status, and those a bisection over ranges finds with the
-        caller's `accepts(L, R) -> bool` (its pairing check).  The rows stay resident, so a range costs one fold; `accepts` is called at
-        most 1 + 2 k ceil(log2 B) times for k failing proofs."""
+    def _need_key(self):
+        if self.pairing_key is None:
+            raise ValueError("this verifier has no pairing key: pass pairing_key=PairingKey(h, tau_h, curve)")
+        return self.pairing_key
+
+    def verify(self, proofs, public_inputs=None, weights=None) -> bool:
+        """True iff every proof of the batch is valid, except with probability about 2^-128 over the weights: no status is non-zero
+        and the fold of the whole batch passes ONE pairing check, on the host.  weights: as `fold`."""
+        key = self._need_key()
+        st = self.prepare(proofs, public_inputs, weights)
+        if np.any(st):
+            return False
+        return key.check(*self.fold_range())
+
+    def pairing_inputs(self):
+        """(L_j, R_j) of every proof of the prepared batch, each under its own weights: device tensors (xy_L (B, 2L), inf_L (B,),
+        xy_R, inf_R), queued.  ONE `msm.segments_msm` call over [20 key points | 15 B proof points] with the resident rows as scalars,
+        two segments per proof: 2 terms (the openings) for L_j, 35 for R_j.  Rows of a proof with a non-zero status are zero: both of
+        its points are infinity."""
+        torch = _torch()
+        res = self._res
+        if res is None:
+            raise RuntimeError("prepare a batch first")
+        B, dev = res.n, self._key_xy.device
+        L2 = 2 * self.curve.fq_limbs
+        if B == 0:
+            e = torch.empty((0, L2), dtype=torch.int64, device=dev), torch.empty((0,), dtype=torch.uint8, device=dev)
+            return e[0], e[1], e[0].clone(), e[1].clone()
+        bases = torch.cat([self._key_xy, res.pts.view(-1, L2)])
+        binf = torch.cat([self._key_inf, res.inf.view(-1)])
+        own = N_KEY_BASES + N_PROOF_BASES * torch.arange(B, device=dev)[:, None]                  # proof j's first base
+        idx_l = own + torch.arange(13, 15, device=dev)[None, :]
+        idx_r = torch.cat([torch.arange(N_KEY_BASES, device=dev)[None, :].expand(B, N_KEY_BASES),
+                           own + torch.arange(N_PROOF_BASES, device=dev)[None, :]], dim=1)
+        index = torch.cat([idx_l, idx_r], dim=1).to(torch.int32).contiguous().view(-1)
+        sc = torch.cat([res.open_rows, res.key_rows, res.proof_rows], dim=1).contiguous().view(-1, 4)
+        per = 2 + N_KEY_BASES + N_PROOF_BASES
+        off = (torch.arange(B, dtype=torch.int64, device=dev)[:, None] * per + torch.tensor([0, 2], dtype=torch.int64, device=dev)[None, :])
+        off = torch.cat([off.view(-1), torch.tensor([B * per], dtype=torch.int64, device=dev)])
+        xy, inf, st = segments_msm(bases, binf, off, index, sc, self.curve, self.ctx)
+        self._seg_status = st
+        xy, inf = xy.view(B, 2, L2), inf.view(B, 2)
+        return xy[:, 0].contiguous(), inf[:, 0].contiguous(), xy[:, 1].contiguous(), inf[:, 1].contiguous()
+
+    def verdicts(self, proofs, public_inputs=None, weights=None) -> np.ndarray:
+        """Valid or not for every proof of the batch, with no bisection: (B,) bool.  After `prepare`, one segmented MSM gives every
+        (L_j, R_j) and one launch runs the B pairing checks, one per lane.  A proof with a non-zero status is False without a pairing."""
+        key = self._need_key()
+        st = self.prepare(proofs, public_inputs, weights)
+        if len(proofs) == 0:
+            return np.zeros(0, dtype=bool)
+        xy_l, inf_l, xy_r, inf_r = self.pairing_inputs()
+        ok = key.check_batch(xy_l, inf_l, xy_r, inf_r, self.ctx).cpu().numpy()
+        if int(self._seg_status.max()) != 0:
+            raise RuntimeError("segments_msm: a segment of the batch's own layout was refused")
+        return (ok != 0) & (st == 0)
+
+    def locate_invalid(self, proofs, public_inputs, accepts=None, weights=None) -> list:
+        """Indices of the proofs that do not verify: those with a non-zero status, and those a bisection over ranges finds with
+        `accepts(L, R) -> bool` -- the verifier's own pairing key when `accepts` is None, else the caller's check.  The rows stay
+        resident, so a range costs one fold; `accepts` is called at most 1 + 2 k ceil(log2 B) times for k failing proofs."""
+        if accepts is None:
+            accepts = self._need_key().check
         st = self.prepare(proofs, public_inputs, weights)
         bad = {int(j) for j in np.nonzero(st)[0]}
         B = len(proofs)
@@ -440,7 +509,7 @@ class BatchVerifier:
 
 class IpaBatchVerifier:
     """B proofs of ONE circuit under the inner-product-argument commitment -> valid or not.  IPA needs no
-    pairing, so this is the one configuration in which the library verifies a PLONK proof to the end.
+    pairing: where `BatchVerifier` ends in `pairing.PairingKey`, this verifier ends in `IpaCommitterKey.batch_check`.
 
     The stages in front of the openings are `BatchVerifier`'s, on a KZG-shaped byte string per proof (13 commitments, the two
     final_comm_keys where the KZG witnesses stand, the evaluations): proof.rs never appends an opening to the transcript

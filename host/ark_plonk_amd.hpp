@@ -531,4 +531,41 @@ inline DeviceVec lincomb(Context& ctx, int curve, const std::vector<const Device
     return out;
 }
 
+// The G2 side of a KZG verifier key, prepared (ark_ec::PairingEngine::product_of_pairings as kzg10::KZG10::check calls it):
+// h, tau_h as x.c0 x.c1 y.c0 y.c1, fq_limbs(curve) Montgomery limbs each.  Validation failures throw Error(ZK_ERR_BAD_ARG).
+class PairingKey {
+public:
+    PairingKey(int curve, const std::vector<uint64_t>& h, const std::vector<uint64_t>& tau_h) : curve_(curve) {
+        const size_t want = 4 * (size_t)fq_limbs(curve);
+        if (h.size() != want || tau_h.size() != want) throw Error(ZK_ERR_BAD_ARG, "G2 point: x.c0 x.c1 y.c0 y.c1");
+        check(zk_pairing_key_new(curve, h.data(), tau_h.data(), &key_), "zk_pairing_key_new");
+    }
+    ~PairingKey() { zk_pairing_key_free(key_); }
+    PairingKey(const PairingKey&) = delete;
+    PairingKey& operator=(const PairingKey&) = delete;
+    // e(L, [tau]H) e(-R, H) == 1, on the host: one check per fold
+    bool check_pair(const G1Affine& L, const G1Affine& R) const {
+        int ok = 0;
+        check(zk_kzg_pairing_check(key_, L.xy.data(), L.infinity ? 1 : 0, R.xy.data(), R.infinity ? 1 : 0, &ok), "zk_kzg_pairing_check");
+        return ok != 0;
+    }
+    // n checks, one per lane: device points (n x 2 fq_limbs limbs), optional flag bytes, n verdict bytes; queued on the ctx stream
+    void check_batch(Context& ctx, const void* d_L, const uint8_t* d_L_inf, const void* d_R, const uint8_t* d_R_inf, size_t n, uint8_t* d_ok) {
+        check(zk_kzg_pairing_check_batch_dev(ctx.handle(), key_, d_L, d_L_inf, d_R, d_R_inf, n, d_ok), "zk_kzg_pairing_check_batch_dev");
+    }
+    // e(P, which ? tau_h : h)^c, 12 fq_limbs(curve) limbs in tower order (c: ZK_PAIRING_GT_POWER_* of csrc/pairing.cuh)
+    std::vector<uint64_t> gt(const G1Affine& P, int which) const {
+        std::vector<uint64_t> out(12 * (size_t)fq_limbs(curve_));
+        check(zk_pairing_gt(key_, which, P.xy.data(), P.infinity ? 1 : 0, out.data()), "zk_pairing_gt");
+        return out;
+    }
+    void gt_batch(Context& ctx, int which, const void* d_P, const uint8_t* d_inf, size_t n, void* d_out) {
+        check(zk_pairing_gt_batch_dev(ctx.handle(), key_, which, d_P, d_inf, n, d_out), "zk_pairing_gt_batch_dev");
+    }
+
+private:
+    int curve_;
+    void* key_ = nullptr;
+};
+
 }  // namespace zk

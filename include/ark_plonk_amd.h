@@ -941,6 +941,38 @@ int zk_lookup_map_query_dev(zk_ctx* ctx, int curve_id, const void* const d_table
                             const void* const* d_operands, const void* const* d_operand_ids, size_t operand_rows, void* d_out,
                             const void* d_out_ids, size_t out_rows, void* d_pos, uint64_t* misses, uint64_t* first_miss);
 
+/* ---- the KZG pairing check (csrc/pairing.hip, csrc/pairing.cuh) --------------------------------------- */
+/* Replaces ark_ec::PairingEngine::product_of_pairings as kzg10::KZG10::check calls it: ok = [ e(L, [tau]H) e(-R, H) == 1 ] for the two
+ * G1 inputs (L, R) a batch of KZG proofs folds into (zk_verify_scalars_dev and the MSMs behind it), with both G2 points fixed by the
+ * verifier key.  A key is prepared once: its two Miller loops are walked on the host into line tables, and a check is then line
+ * evaluations at G1 points, sparse Fq12 products and the final exponentiation -- no G2 arithmetic where a check runs.
+ *
+ * The key is an opaque handle that crosses as an untyped pointer (`key` below; zk_pairing_key_new writes it to *out).
+ * G2 points: affine, x.c0 x.c1 y.c0 y.c1, L limbs each (L = 6 / 4), Montgomery form, Fq2 = Fq[u]/(u^2 + 1).
+ * G1 points: what the library writes -- x y, L limbs each, Montgomery; infinity by flag or as (0, 1) / (0, 0).  They are the
+ * library's own outputs and are not validated again.
+ * GT values: 12 Fq elements, Montgomery, in arkworks' tower order c0.c0.c0, c0.c0.c1, c0.c1.c0, ... (Fq6 = Fq2[v]/(v^3 - xi),
+ * Fq12 = Fq6[w]/(w^2 - v)).  The value is e(P, Q)^c for the reduced pairing e with the exponent (q^12 - 1) / r exactly and the small
+ * constant c of the curve, coprime to r: c = 3 on BLS12-381 (the x-chain of the hard part), c = 1 on BN254
+ * (ZK_PAIRING_GT_POWER_* in csrc/pairing.cuh). */
+/* Validates h and tau_h (each coordinate reduced; on the twist y^2 = x^3 + 4(1 + u) / y^2 = x^3 + 3/(9 + u); not infinity; [r]Q =
+ * infinity) and prepares both tables, on the host: no ctx, no GPU.  ZK_ERR_BAD_ARG: a null pointer, an unknown curve, a point
+ * that fails a test. */
+int zk_pairing_key_new(int curve_id, const uint64_t* h, const uint64_t* tau_h, void** out);
+/* Frees the key and its device copies (one per device a batch call ran on; waits for that device).  NULL is a no-op. */
+void zk_pairing_key_free(void* key);
+/* *ok = [ e(L, tau_h) e(-R, h) == 1 ].  Host only: milliseconds, the form for one check per fold. */
+int zk_kzg_pairing_check(const void* key, const uint64_t* L_xy, int L_inf, const uint64_t* R_xy, int R_inf, int* ok);
+/* n independent checks, one per lane of one launch: d_ok[j] (n bytes) = the verdict of (d_L[j], d_R[j]).  d_L_inf / d_R_inf: n flag
+ * bytes, or NULL (infinity by encoding only).  Queued on the ctx stream; nothing is read back.  The first call on a device uploads
+ * the key's tables there (blocking, once).  n == 0 is a no-op. */
+int zk_kzg_pairing_check_batch_dev(zk_ctx* ctx, void* key, const void* d_L, const uint8_t* d_L_inf, const void* d_R, const uint8_t* d_R_inf,
+                                   size_t n, uint8_t* d_ok);
+/* out = e(P, which ? tau_h : h)^c as 12 L limbs (the identity for P = infinity): what the tests pin to an independent pairing. */
+int zk_pairing_gt(const void* key, int which, const uint64_t* P_xy, int P_inf, uint64_t* out);
+/* ... for n points on the device, one per lane: d_out holds n GT values. */
+int zk_pairing_gt_batch_dev(zk_ctx* ctx, void* key, int which, const void* d_P, const uint8_t* d_inf, size_t n, void* d_out);
+
 /* ---- device self-test ------------------------------------------------------------------------------ */
 /* Runs the quad-cooperative point arithmetic of the bucket-reduction kernels (csrc/ecq.cuh) against the
  * single-lane group law on n_quads point pairs incl. doubling, cancellation and infinity cases.
