@@ -214,6 +214,14 @@ ZK_HD G1In<PR> g1_read(const uint32_t* xy, bool flag) {
     return p;
 }
 
+// the host entry points' G1 contract: both coordinates of a point that is not flagged as infinity are below the modulus.  An unreduced
+// y would change the verdict (Fp::neg of it is not the negation), and (q, 1) or (q, q) would read as the encodings of infinity.
+template <class Cv>
+bool g1_reduced(const uint64_t* xy, bool flag) {
+    const uint32_t* w = (const uint32_t*)xy;
+    return flag || (words_below_modulus<Cv>(w) && words_below_modulus<Cv>(w + PairOf<Cv>::T::N));
+}
+
 // [ e(L, tau_h) e(-R, h) == 1 ]
 template <class PR>
 ZK_HD bool check_one(const uint8_t* steps, int n_steps, const uint32_t* lines_tau, const uint32_t* lines_h, const uint32_t* l_xy, bool l_inf,
@@ -315,6 +323,7 @@ int zk_kzg_pairing_check(const void* handle, const uint64_t* L_xy, int L_inf, co
     if (!key || !L_xy || !R_xy || !ok) return ZK_ERR_BAD_ARG;
     return zk_on_curve(key->curve, ZK_ERR_BAD_ARG, [&](auto cv) {
         typedef typename PairOf<decltype(cv)>::T PR;
+        if (!g1_reduced<decltype(cv)>(L_xy, L_inf != 0) || !g1_reduced<decltype(cv)>(R_xy, R_inf != 0)) return (int)ZK_ERR_BAD_ARG;
         *ok = check_one<PR>(key->steps.data(), (int)key->steps.size(), key->lines[1].data(), key->lines[0].data(), (const uint32_t*)L_xy,
                             L_inf != 0, (const uint32_t*)R_xy, R_inf != 0)
                   ? 1
@@ -328,6 +337,7 @@ int zk_pairing_gt(const void* handle, int which, const uint64_t* P_xy, int P_inf
     if (!key || !P_xy || !out || (which != 0 && which != 1)) return ZK_ERR_BAD_ARG;
     return zk_on_curve(key->curve, ZK_ERR_BAD_ARG, [&](auto cv) {
         typedef typename PairOf<decltype(cv)>::T PR;
+        if (!g1_reduced<decltype(cv)>(P_xy, P_inf != 0)) return (int)ZK_ERR_BAD_ARG;
         gt_one<PR>(key->steps.data(), (int)key->steps.size(), key->lines[which].data(), (const uint32_t*)P_xy, P_inf != 0, (uint32_t*)out);
         return (int)ZK_OK;
     });

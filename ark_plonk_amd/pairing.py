@@ -96,7 +96,8 @@ class PairingKey:
         return self._h
 
     def check(self, L: G1Affine, R: G1Affine) -> bool:
-        """e(L, [tau]H) e(-R, H) == 1, on the host"""
+        """e(L, [tau]H) e(-R, H) == 1, on the host.  Raises `ZkError` (ZK_ERR_BAD_ARG) for a point that is not flagged as infinity
+        and has a coordinate that is not below q: the verdict would depend on the representation of R.y."""
         cv = self.curve
         (l, li), (r, ri) = _g1_args(L, cv), _g1_args(R, cv)
         ok = ctypes.c_int(0)
@@ -104,7 +105,8 @@ class PairingKey:
         return bool(ok.value)
 
     def gt(self, P: G1Affine, which: int) -> np.ndarray:
-        """e(P, which ? [tau]H : H)^GT_POWER as (12, L) uint64 Montgomery limbs in tower order (c0.c0.c0, c0.c0.c1, c0.c1.c0, ...)"""
+        """e(P, which ? [tau]H : H)^GT_POWER as (12, L) uint64 Montgomery limbs in tower order (c0.c0.c0, c0.c0.c1, c0.c1.c0, ...).
+        An unreduced coordinate is a `ZkError`, as in `check`."""
         cv = self.curve
         p, pi = _g1_args(P, cv)
         out = np.zeros((12, cv.fq_limbs), dtype=np.uint64)
@@ -125,7 +127,8 @@ class PairingKey:
 
     def check_batch(self, d_L, d_L_inf, d_R, d_R_inf, ctx: Context | None = None):
         """n checks in one launch: d_L, d_R (n, 2L) int64 device tensors (Montgomery affine), d_L_inf, d_R_inf (n,) uint8 or None.
-        Returns the (n,) uint8 device tensor of verdicts; queued on the current torch stream, nothing is waited for."""
+        Returns the (n,) uint8 device tensor of verdicts; queued on the current torch stream, nothing is waited for.  The coordinates
+        are the library's own device outputs, reduced; the kernels do not look (unreduced input is outside the contract here)."""
         import torch
         ctx = ctx or default_context(d_L.device.index)
         n = self._dev_points(d_L, d_L_inf, ctx, "d_L")

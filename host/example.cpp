@@ -1,7 +1,9 @@
 // Smallest C++ caller of the host layer (host/ark_plonk_amd.hpp): a round trip through the transforms and
 // the commitments of one "prover round" on device-resident data.  tests/test_host_cpp_gpu.py builds it with
 // g++ against libark_plonk_amd.so, runs it on the GPU and compares its output with the Python mirror.
-//   usage: example <log_n>        prints  "<label> <hex limbs>"  lines
+//   usage: example <log_n> [<60 hex limbs>]       prints  "<label> <hex limbs>"  lines
+// The optional limbs are a pairing key and an opening of it on BLS12-381: H and [tau]H (24 limbs each: x.c0 x.c1 y.c0 y.c1) and
+// tau * 3 G (12 limbs), Montgomery form; 3 G is the first point of the example's own SRS.  With them a "pairing" line is printed.
 #include <cstdio>
 #include <cstdlib>
 
@@ -108,11 +110,44 @@ int main(int argc, char** argv) {
         auto zeta = t.challenge_scalar("zeta");
         t.append("zeta", zeta.data());
         print("zeta", zeta, 4);
+        bool pairing_ok = true;
+        if (argc >= 2 + 60) {
+            auto limbs = [&](int at, size_t count) {
+                std::vector<uint64_t> v(count);
+                for (size_t i = 0; i < count; ++i) v[i] = std::strtoull(argv[at + i], nullptr, 16);
+                return v;
+            };
+            zk::PairingKey key(ZK_CURVE_BLS12_381, limbs(2, 24), limbs(26, 24));
+            zk::G1Affine L, R;
+            L.xy.assign(srs.begin(), srs.begin() + 12);                  // 3 G
+            R.xy = limbs(50, 12);                                         // tau * 3 G
+            pairing_ok = key.check_pair(L, R) && !key.check_pair(L, L) && !key.check_pair(R, L);
+            // four lanes on the device: (L, R) (L, L) (R, R) (L, R), read back as verdict bytes
+            std::vector<uint64_t> ls, rs;
+            for (const zk::G1Affine* p : {&L, &L, &R, &L}) ls.insert(ls.end(), p->xy.begin(), p->xy.end());
+            for (const zk::G1Affine* p : {&R, &L, &R, &R}) rs.insert(rs.end(), p->xy.begin(), p->xy.end());
+            zk::DeviceVec d_ls(ctx, ls), d_rs(ctx, rs), d_ok(ctx, 1);
+            key.check_batch(ctx, d_ls.data(), nullptr, d_rs.data(), nullptr, 4, (uint8_t*)d_ok.data());
+            const uint64_t verdicts = d_ok.to_host()[0] & 0xFFFFFFFFull;
+            pairing_ok = pairing_ok && verdicts == 0x01000001ull;
+            // an unreduced coordinate is refused, not decided
+            zk::G1Affine bad = R;
+            for (size_t i = 6; i < 12; ++i) bad.xy[i] = ~0ull;
+            bool thrown = false;
+            try {
+                key.check_pair(L, bad);
+            } catch (const zk::Error& e) {
+                thrown = e.code == ZK_ERR_BAD_ARG;
+            }
+            pairing_ok = pairing_ok && thrown;
+            std::printf("pairing %s\n", pairing_ok ? "ok" : "MISMATCH");
+            print("pairing_gt", key.gt(L, 1), 72);
+        }
         auto enc = zk::serialize(single);
         std::printf("commit_ser");
         for (uint8_t b : enc) std::printf(" %02x", b);
         std::printf("\n");
-        return (back == ev && round[0].xy == single.xy && host_round[0].xy == single.xy) ? 0 : 1;
+        return (back == ev && round[0].xy == single.xy && host_round[0].xy == single.xy && pairing_ok) ? 0 : 1;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 2;

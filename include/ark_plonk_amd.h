@@ -950,7 +950,11 @@ int zk_lookup_map_query_dev(zk_ctx* ctx, int curve_id, const void* const d_table
  * The key is an opaque handle that crosses as an untyped pointer (`key` below; zk_pairing_key_new writes it to *out).
  * G2 points: affine, x.c0 x.c1 y.c0 y.c1, L limbs each (L = 6 / 4), Montgomery form, Fq2 = Fq[u]/(u^2 + 1).
  * G1 points: what the library writes -- x y, L limbs each, Montgomery; infinity by flag or as (0, 1) / (0, 0).  They are the
- * library's own outputs and are not validated again.
+ * library's own outputs and are not tested for the curve or the subgroup.  Both coordinates must be reduced (below q): an unreduced
+ * y changes a verdict, since its negation is not the negation of the residue.  The host entry points (zk_kzg_pairing_check,
+ * zk_pairing_gt) return ZK_ERR_BAD_ARG, and write nothing, for a point without its infinity flag that has a coordinate >= q -- the
+ * unreduced spellings (q, 1), (q, q) of infinity included; a point passed with its flag set is not inspected.  The device entry
+ * points read arrays the library wrote on the device and do not look: unreduced coordinates are outside the contract there.
  * GT values: 12 Fq elements, Montgomery, in arkworks' tower order c0.c0.c0, c0.c0.c1, c0.c1.c0, ... (Fq6 = Fq2[v]/(v^3 - xi),
  * Fq12 = Fq6[w]/(w^2 - v)).  The value is e(P, Q)^c for the reduced pairing e with the exponent (q^12 - 1) / r exactly and the small
  * constant c of the curve, coprime to r: c = 3 on BLS12-381 (the x-chain of the hard part), c = 1 on BN254

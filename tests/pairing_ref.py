@@ -218,9 +218,11 @@ def g1_add(c, p1, p2):
     return x3, (lam * (x1 - x3) - y1) % q
 
 
-def g1_mul(c, k, pt=None):
+def g1_mul(c, k, pt=None, reduce=True):
+    """k * pt on the curve (pt = the generator by default); reduce=False keeps k as it is (points of the curve outside G1)"""
     pt = c.g1 if pt is None else pt
-    k %= c.r
+    if reduce:
+        k %= c.r
     acc = None
     while k:
         if k & 1:

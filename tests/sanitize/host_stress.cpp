@@ -12,6 +12,11 @@
 //   * every allocation of one pass over the library refused in turn (section 2d: the codes returned, the ctx afterwards, what is left
 //     allocated), under a fake runtime that keeps its last error until it is read, as the real one does;
 //   * a residency-cache hit whose device copy is wrong, under option "cache_verify" (section 2e).
+//   * the pairing (section 2f): key validation, zk_kzg_pairing_check and zk_pairing_gt against constants on both curves -- the Fq12
+//     tower, the Miller loop and both final exponentiations on the host -- then one key shared by four host threads while two ctxs
+//     race its first device upload, and the key freed with its device copy; the first upload is also a site of the sweep (2d).
+//     Measured on the build machine: section 2f takes 0.4 s under ASan + UBSan and 0.4 s under TSan (the program prints it); the
+//     sweep, now 67 sites with a BN254 key made in every pass, 9.5 s and 23.6 s of the program's 10.3 s and 25.2 s.
 // Exit code 0 and "host_stress ok" = every call returned what it must; the sanitizer's own report fails the test otherwise.
 #include <atomic>
 #include <chrono>
@@ -114,9 +119,200 @@ static std::atomic<int> g_fail{0};
         }                                                                                     \
     } while (0)
 
+// ---- the pairing (csrc/pairing.hip): constants for sections 2d and 2f.  Montgomery limbs, made once with the package's own Python:
+// H = (curves.g2x, curves.g2y) and [TAU]H = curves.g2_mul(cv, TAU) with TAU = 0x7A5C0DE of tests/conftest.py, G and TAU G = curves.g1_mul,
+// each through curves.fq_to_mont; the GT values are the (1, 1) and (1, TAU) cases of tests/golden/pairing_gt.json raised to the
+// library's GT_POWER (3 / 1), taken from the polynomial basis back to tower order (the inverse of pairing_ref.tower_to_poly) and
+// through fq_to_mont: what zk_pairing_gt must write word for word.
+static const uint64_t BLS_H[24] = {
+    0xf5f28fa202940a10ull, 0xb3f5fb2687b4961aull, 0xa1a893b53e2ae580ull, 0x9894999d1a3caee9ull, 0x6f67b7631863366bull, 0x058191924350bcd7ull,
+    0xa5a9c0759e23f606ull, 0xaaa0c59dbccd60c3ull, 0x3bb17e18e2867806ull, 0x1b1ab6cc8541b367ull, 0xc2b6ed0ef2158547ull, 0x11922a097360edf3ull,
+    0x4c730af860494c4aull, 0x597cfa1f5e369c5aull, 0xe7e6856caa0a635aull, 0xbbefb5e96e0d495full, 0x07d3a975f0ef25a2ull, 0x0083fd8e7e80dae5ull,
+    0xadc0fc92df64b05dull, 0x18aa270a2b1461dcull, 0x86adac6a3be4eba0ull, 0x79495c4ec93da33aull, 0xe7175850a43ccaedull, 0x0b2bc2a163de1bf2ull,
+};
+static const uint64_t BLS_TAU_H[24] = {
+    0x05c4f1e50e9717aeull, 0x607304248c6a8dc0ull, 0x465890a3fdf96d60ull, 0x66aa5df2809ec30full, 0x25c282a0d0dce546ull, 0x1906ad808634f2caull,
+    0x0954e3038342f9f9ull, 0xbd78334bbd518f86ull, 0x7c63d6247f8955e4ull, 0x80104760ee2bd4c5ull, 0x6009d59e286c1e32ull, 0x08280fb9ed8f78cdull,
+    0x4c4389123130b04eull, 0x0b07b88733524c8cull, 0x6b02b81f410f2cceull, 0x271c0b8ba00719d0ull, 0x053bf5a3b56579d6ull, 0x1317a1d5d793d6e1ull,
+    0x8ac124a68201968eull, 0xb4de75dc19c246b4ull, 0x41c5705277967080ull, 0x7892c32593f850e8ull, 0xee1ac39ebb12551bull, 0x11d357ec0f0ce730ull,
+};
+static const uint64_t BLS_G[12] = {
+    0x5cb38790fd530c16ull, 0x7817fc679976fff5ull, 0x154f95c7143ba1c1ull, 0xf0ae6acdf3d0e747ull, 0xedce6ecc21dbf440ull, 0x120177419e0bfb75ull,
+    0xbaac93d50ce72271ull, 0x8c22631a7918fd8eull, 0xdd595f13570725ceull, 0x51ac582950405194ull, 0x0e1c8c3fad0059c0ull, 0x0bbc3efc5008a26aull,
+};
+static const uint64_t BLS_TAU_G[12] = {
+    0x1de380e05ef9e2d6ull, 0x30d4170a5d3c527cull, 0x88ecee5b18420fe6ull, 0x380111e9d2a65ef2ull, 0xc415adf69338294dull, 0x109853e2d0b38f88ull,
+    0x534606a667efb488ull, 0x886d34da19d33237ull, 0x18a88105febd6527ull, 0xe3b24c58b3fc24cbull, 0xbf8ef4f639e7805bull, 0x1a010558cbf9d3b3ull,
+};
+static const uint64_t BLS_NEG_TAU_G[12] = {
+    0x1de380e05ef9e2d6ull, 0x30d4170a5d3c527cull, 0x88ecee5b18420fe6ull, 0x380111e9d2a65ef2ull, 0xc415adf69338294dull, 0x109853e2d0b38f88ull,
+    0x66b8f959980ff623ull, 0x963ecb249780cdc8ull, 0x4e88519af7f390fcull, 0x80c4ff2c3f88edf4ull, 0x8b8cb2c009642c7bull, 0x00000c916d8612e6ull,
+};
+static const uint64_t BLS_GT_G_H[72] = {
+    0x1972e433a01f85c5ull, 0x97d32b76fd772538ull, 0xc8ce546fc96bcdf9ull, 0xcef63e7366d40614ull, 0xa611342781843780ull, 0x13f3448a3fc6d825ull,
+    0xd26331b02e9d6995ull, 0x9d68a482f7797e7dull, 0x9c9b29248d39ea92ull, 0xf4801ca2e13107aaull, 0xa16c0732bdbcb066ull, 0x083ca4afba360478ull,
+    0x59e261db0916b641ull, 0x2716b6f4b23e960dull, 0xc8e55b10a0bd9c45ull, 0x0bdb0bd99c4deda8ull, 0x8cf89ebf57fdaac5ull, 0x12d6b7929e777a5eull,
+    0x5fc85188b0e15f35ull, 0x34a06e3a8f096365ull, 0xdb3126a6e02ad62cull, 0xfc6f5aa97d9a990bull, 0xa12f55f5eb89c210ull, 0x1723703a926f8889ull,
+    0x93588f2971828778ull, 0x43f65b8611ab7585ull, 0x3183aaf5ec279fdfull, 0xfa73d7e18ac99df6ull, 0x64e176a6a64c99b0ull, 0x179fa78c58388f1full,
+    0x672a0a11ca2aef12ull, 0x0d11b9b52aa3f16bull, 0xa44412d0699d056eull, 0xc01d0177221a5ba5ull, 0x66e0cede6c735529ull, 0x05f5a71e9fddc339ull,
+    0xd30a88a1b062c679ull, 0x5ac56a5d35fc8304ull, 0xd0c834a6a81f290dull, 0xcd5430c2da3707c7ull, 0xf0c27ff780500af0ull, 0x09245da6e2d72eaeull,
+    0x9f2e0676791b5156ull, 0xe2d1c8234918fe13ull, 0x4c9e459f3c561bf4ull, 0xa3e85e53b9d3e3c1ull, 0x820a121e21a70020ull, 0x15af618341c59accull,
+    0x7c95658c24993ab1ull, 0x73eb38721ca886b9ull, 0x5256d749477434bcull, 0x8ba41902ea504a8bull, 0x04a3d3f80c86ce6dull, 0x18a64a87fb686eaaull,
+    0xbb83e71bb920cf26ull, 0x2a5277ac92a73945ull, 0xfc0ee59f94f046a0ull, 0x7158cdf3786058f7ull, 0x7cc1061b82f945f6ull, 0x03f847aa9fdbe567ull,
+    0x8078dba56134e657ull, 0x1cd7ec9a43998a6eull, 0xb1aa599a1a993766ull, 0xc9a0f62f0842ee44ull, 0x8e159be3b605dffaull, 0x0c86ba0d4af13fc2ull,
+    0xe80ff2a06a52ffb1ull, 0x7694ca48721a906cull, 0x7583183e03b08514ull, 0xf567afdd40cee4e2ull, 0x9a6d96d2e526a5fcull, 0x197e9f49861f2242ull,
+};
+static const uint64_t BLS_GT_G_TAU_H[72] = {
+    0xf891e6792be5d77bull, 0x5f75840872016b4dull, 0xb5beb3ef5dfde979ull, 0xac8e0c5aef0fcf2cull, 0xd91424d8750d3b24ull, 0x070308987882f269ull,
+    0xd2734f20962de844ull, 0xcf74c5f49a3c1752ull, 0xb5400a62186c3ec3ull, 0xec0cd0a6454eb702ull, 0xba2f44791cbb7d1aull, 0x0d070ea7c06aed93ull,
+    0xe6dfe61ea6321aacull, 0xc8ecf31261da9ab6ull, 0xb40d40b993c153d9ull, 0x4123c5f712d225ebull, 0x700d64f5a0663c07ull, 0x083aea0bdfdb21b2ull,
+    0xbf99a0e987d78d53ull, 0x1046fe75a1ac0054ull, 0xd0a01cace6dd7a62ull, 0x51c260861cd2600dull, 0x05509baf6ede78a6ull, 0x006b43670629fad9ull,
+    0xa422dbc538e3ff80ull, 0x911f4cc50363ac86ull, 0xf563d868f48802d0ull, 0x0e9db17ef61dfeb0ull, 0x17cb3ff164081658ull, 0x10e8dd6e22991cd2ull,
+    0xd807b86ee3e820e1ull, 0xb29c6194b8dfe831ull, 0x9216553b13e6319aull, 0x299ca43a50125be9ull, 0x603f790d28b0ad27ull, 0x145e20155b1e89dcull,
+    0x1b39fd1c71fcf8bdull, 0x2af93c354df1206dull, 0x650e05e27bc9f60bull, 0x66e1697aae59ed14ull, 0x85f52c113bf3aa99ull, 0x05e91b7254f6dc14ull,
+    0x30db38a90c8a2f6aull, 0xdc89cb96fa12df5dull, 0xb9ad149ca57d1744ull, 0xfe7ac9db536a5380ull, 0x40793157618168e9ull, 0x0e96c22bc944d90aull,
+    0x39343e3a54fb0626ull, 0x52591fdfe046db5cull, 0xfdb43d95e41ed925ull, 0x4991482c706574caull, 0x8ca92f2d1cc5d236ull, 0x0e9c4d4626d68344ull,
+    0x93d19c2249ee3e00ull, 0xc92d99f9a041b749ull, 0x51df92f9b8c38c80ull, 0x6fdb1df98e8e1c4aull, 0x28e547a9175ce8efull, 0x1565f82d4467d5abull,
+    0xe71b4cfe6d57d309ull, 0x88e4c97e5084219eull, 0xbc3df21f80101d6aull, 0xbcc33d500cd16669ull, 0xc19d7fedfdaa0761ull, 0x04a38448b58690f8ull,
+    0x075c1d44d4072fefull, 0x96976f605dce4f83ull, 0xdd8949cc21d5cfafull, 0x8209ce42ad156857ull, 0x7a504bd0ae3cade7ull, 0x0f4a18028978404eull,
+};
+static const uint64_t BN_H[16] = {
+    0x8e83b5d102bc2026ull, 0xdceb1935497b0172ull, 0xfbb8264797811adfull, 0x19573841af96503bull,
+    0xafb4737da84c6140ull, 0x6043dd5a5802d8c4ull, 0x09e950fc52a02f86ull, 0x14fef0833aea7b6bull,
+    0x619dfa9d886be9f6ull, 0xfe7fd297f59e9b78ull, 0xff9e1a62231b7dfeull, 0x28fd7eebae9e4206ull,
+    0x64095b56c71856eeull, 0xdc57f922327d3cbbull, 0x55f935be33351076ull, 0x0da4a0e693fd6482ull,
+};
+static const uint64_t BN_TAU_H[16] = {
+    0x7ef48249112bc295ull, 0xd5d8cd22462a0cefull, 0x40ce95b211add7b2ull, 0x08b88fa4fb652be7ull,
+    0xbbd8ec6698df1001ull, 0x15a39b4b99a50df4ull, 0xdd724f51aac24f16ull, 0x2b3c958b169d6dd5ull,
+    0x3787060df63b6a69ull, 0xe5faddef602a6d3cull, 0x48bd642ad0c99a15ull, 0x25848ee0f8fe38f3ull,
+    0xa4c5f5affb9bb702ull, 0x660faf6708fa9908ull, 0x1ea00892e9c8435eull, 0x1ec6a58a8da8802eull,
+};
+static const uint64_t BN_G[8] = {
+    0xd35d438dc58f0d9dull, 0x0a78eb28f5c70b3dull, 0x666ea36f7879462cull, 0x0e0a77c19a07df2full,
+    0xa6ba871b8b1e1b3aull, 0x14f1d651eb8e167bull, 0xccdd46def0f28c58ull, 0x1c14ef83340fbe5eull,
+};
+static const uint64_t BN_TAU_G[8] = {
+    0x8490f525a1113284ull, 0xab521dfebcb8486bull, 0x57c46a2bf913bcbbull, 0x0211e2a79da72c80ull,
+    0x0390ead4c3bfd111ull, 0xab4d584de84f04d3ull, 0xeac5066271b4973dull, 0x2fe6afee0a82f178ull,
+};
+static const uint64_t BN_NEG_TAU_G[8] = {
+    0x8490f525a1113284ull, 0xab521dfebcb8486bull, 0x57c46a2bf913bcbbull, 0x0211e2a79da72c80ull,
+    0x388fa14214bd2c36ull, 0xec3412438022c5baull, 0xcd8b3f540fccc11full, 0x007d9e84d6aeaeb0ull,
+};
+static const uint64_t BN_GT_G_H[48] = {
+    0xc556f62b2a98671dull, 0x23a59ac167bcf363ull, 0x5ef208445f5f6f37ull, 0x12adf27ccb29382aull,
+    0x2e02a64acbd60549ull, 0xd618018ea58e4addull, 0x14d585f1a45ba647ull, 0x1832226987c434fcull,
+    0x2306e4312363b991ull, 0x465f6072d4023bf4ull, 0xa2ff062a4a77e736ull, 0x076ea6f18435864aull,
+    0x172d1f257a4d598eull, 0xddf5bc7b7ffb5ac0ull, 0xae0b22c0bbb0f602ull, 0x1b158f3c2fae9b18ull,
+    0x5cf9cc917da86724ull, 0xc799dc487a0b2753ull, 0x0df2027bf1de17a7ull, 0x197cda6cc3e20636ull,
+    0xf16c96d081754cdbull, 0xce0394312bceeb55ull, 0x644e4dcf1f01ff0aull, 0x0cbea85ee0b236ccull,
+    0x1bb0ce0def1b82a1ull, 0x4c4c9fe1cadefa95ull, 0x746d9990cb12b27eull, 0x13495c08e5d415c5ull,
+    0x9458abcb56d24998ull, 0xb17540bd2a9e5adbull, 0x9a9983c82e401a9full, 0x1614817a84c16291ull,
+    0x8975b68a2bab1f9cull, 0x2fdd826b796e0f35ull, 0x6a90a35fa03dfaa5ull, 0x1ffef4581607fc37ull,
+    0x7002907c28ebfe11ull, 0x7b0591d3d080da67ull, 0xde7e5aa2181f138eull, 0x210e437dfc43d951ull,
+    0x988ae2485b36cf53ull, 0x5091cc0581334e54ull, 0xda7903229312ca0full, 0x2a2341538eaee95cull,
+    0xd34bab373157aa84ull, 0x3511ed44fd0d8598ull, 0x67e42a0bc2ced972ull, 0x2b8f1d5dfd20c55bull,
+};
+
+// key validation, one check each way and the GT value itself on both curves: the whole tower, the Miller loop and both final
+// exponentiations on the host
+static int pairing_values() {
+    struct Cv {
+        int id;
+        size_t l;
+        const uint64_t *h, *tau_h, *g, *tau_g, *neg_tau_g, *gt_h, *gt_tau_h;
+    };
+    const Cv cvs[2] = {{ZK_CURVE_BLS12_381, 6, BLS_H, BLS_TAU_H, BLS_G, BLS_TAU_G, BLS_NEG_TAU_G, BLS_GT_G_H, BLS_GT_G_TAU_H},
+                       {ZK_CURVE_BN254, 4, BN_H, BN_TAU_H, BN_G, BN_TAU_G, BN_NEG_TAU_G, BN_GT_G_H, nullptr}};
+    for (const Cv& cv : cvs) {
+        const size_t l = cv.l;
+        void* key = nullptr;
+        uint64_t pt[24];
+        // off the twist: y.c0 changed in its lowest bit; unreduced: x.c0 with every bit set; either place
+        memcpy(pt, cv.h, 4 * l * 8);
+        pt[2 * l] ^= 1;
+        REQUIRE(zk_pairing_key_new(cv.id, pt, cv.tau_h, &key) == ZK_ERR_BAD_ARG && !key);
+        REQUIRE(zk_pairing_key_new(cv.id, cv.h, pt, &key) == ZK_ERR_BAD_ARG && !key);
+        memcpy(pt, cv.h, 4 * l * 8);
+        for (size_t i = 0; i < l; ++i) pt[i] = ~0ull;
+        REQUIRE(zk_pairing_key_new(cv.id, pt, cv.tau_h, &key) == ZK_ERR_BAD_ARG && !key);
+        REQUIRE(zk_pairing_key_new(cv.id, cv.h, pt, &key) == ZK_ERR_BAD_ARG && !key);
+        REQUIRE(zk_pairing_key_new(cv.id, cv.h, cv.tau_h, &key) == ZK_OK && key);
+        int ok = 7;
+        REQUIRE(zk_kzg_pairing_check(key, cv.g, 0, cv.tau_g, 0, &ok) == ZK_OK && ok == 1);              // (G, TAU G)
+        REQUIRE(zk_kzg_pairing_check(key, cv.g, 0, cv.neg_tau_g, 0, &ok) == ZK_OK && ok == 0);          // R.y negated
+        REQUIRE(zk_kzg_pairing_check(key, cv.g, 1, cv.tau_g, 1, &ok) == ZK_OK && ok == 1);              // both infinity by flag
+        REQUIRE(zk_kzg_pairing_check(key, cv.g, 1, cv.tau_g, 0, &ok) == ZK_OK && ok == 0);
+        // an unreduced G1 coordinate is a code and leaves *ok alone
+        uint64_t un[12];
+        memcpy(un, cv.tau_g, 2 * l * 8);
+        for (size_t i = 0; i < l; ++i) un[l + i] = ~0ull;
+        ok = 7;
+        REQUIRE(zk_kzg_pairing_check(key, cv.g, 0, un, 0, &ok) == ZK_ERR_BAD_ARG && ok == 7);
+        uint64_t gt[72];
+        REQUIRE(zk_pairing_gt(key, 0, un, 0, gt) == ZK_ERR_BAD_ARG);
+        REQUIRE(zk_pairing_gt(key, 0, cv.g, 0, gt) == ZK_OK && memcmp(gt, cv.gt_h, 12 * l * 8) == 0);
+        if (cv.gt_tau_h) REQUIRE(zk_pairing_gt(key, 1, cv.g, 0, gt) == ZK_OK && memcmp(gt, cv.gt_tau_h, 12 * l * 8) == 0);
+        REQUIRE(zk_pairing_gt(key, 1, cv.g, 1, gt) == ZK_OK && memcmp(gt, cv.gt_h, 12 * l * 8) != 0);   // infinity: one
+        zk_pairing_key_free(key);
+    }
+    zk_pairing_key_free(nullptr);
+    return 0;
+}
+
+// several threads share ONE key on the host while two ctxs make its first device calls on the same device: the first upload is raced
+// under the key's mutex (launches do nothing here; the point is the key object), then the key goes with its device copy
+static int pairing_threads() {
+    const long live0 = fake_hip_live_allocations();
+    void* key = nullptr;
+    REQUIRE(zk_pairing_key_new(ZK_CURVE_BN254, BN_H, BN_TAU_H, &key) == ZK_OK && key);
+    zk_ctx* cs[2] = {nullptr, nullptr};
+    void* d[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    const size_t lanes = 70;
+    for (int k = 0; k < 2; ++k) {
+        REQUIRE(zk_ctx_create(0, &cs[k]) == ZK_OK);
+        for (int j = 0; j < 3; ++j) REQUIRE(zk_dev_alloc(cs[k], lanes * 12 * 4 * 8, &d[k][j]) == ZK_OK);
+    }
+    const long live1 = fake_hip_live_allocations();
+    std::atomic<int> go{0};
+    std::vector<std::thread> th;
+    for (int t = 0; t < 4; ++t)
+        th.emplace_back([&, t] {
+            while (!go.load()) std::this_thread::yield();
+            for (int it = 0; it < 3; ++it) {
+                int ok = 7;
+                const bool valid = (t + it) & 1;
+                TCHECK(zk_kzg_pairing_check(key, BN_G, 0, valid ? BN_TAU_G : BN_NEG_TAU_G, 0, &ok) == ZK_OK && ok == (valid ? 1 : 0));
+            }
+        });
+    for (int k = 0; k < 2; ++k)
+        th.emplace_back([&, k] {
+            while (!go.load()) std::this_thread::yield();
+            for (int it = 0; it < 4; ++it) {
+                if ((it + k) & 1)
+                    TCHECK(zk_kzg_pairing_check_batch_dev(cs[k], key, d[k][0], nullptr, d[k][1], nullptr, lanes, (uint8_t*)d[k][2]) == ZK_OK);
+                else
+                    TCHECK(zk_pairing_gt_batch_dev(cs[k], key, it & 1, d[k][0], nullptr, lanes, d[k][2]) == ZK_OK);
+            }
+        });
+    go.store(1);
+    for (auto& t : th) t.join();
+    REQUIRE(g_fail.load() == 0);
+    REQUIRE(fake_hip_live_allocations() == live1 + 1);            // ONE device copy, whichever ctx came first
+    zk_pairing_key_free(key);
+    REQUIRE(fake_hip_live_allocations() == live1);
+    for (int k = 0; k < 2; ++k) {
+        for (int j = 0; j < 3; ++j) REQUIRE(zk_dev_free(cs[k], d[k][j]) == ZK_OK);
+        zk_ctx_destroy(cs[k]);
+    }
+    REQUIRE(fake_hip_live_allocations() == live0);
+    return 0;
+}
+
 // ---- the scenario of the allocation-failure sweep (section 2d): one pass over the calls that allocate -- a ctx, an SRS and its 16-bit
 // table, a blocking batch, a deferred round with an opening, the host-pointer calls behind both caches, an NTT with its plan, a circuit
-// check, a lookup map and one IPA key fold -- at the sizes the sections above use.  Any one hipMalloc / hipHostMalloc of it may be the
+// check, a lookup map, one IPA key fold and a pairing key's first device call -- at the sizes the sections above use.  Any one hipMalloc / hipHostMalloc of it may be the
 // one fake_hip_fail_alloc_after() refuses.  What must hold whichever it is: every call returns ZK_OK or ZK_ERR_OOM and nothing else
 // (a stale runtime error would come back as ZK_ERR_HIP or as a second ZK_ERR_OOM from a call that allocated nothing); at most ONE call
 // of a pass fails, since the hook fires once and a ctx that has refused a call works again at the next; an open round can be aborted.
@@ -186,6 +382,23 @@ struct Scenario {
                     STEP(zk_lookup_map_query_dev(c, CURVE, in, 64, d[5], slots, 64, ops, nullptr, 64, d[4], nullptr, 64, nullptr, &misses, &first));
             }
             STEP(zk_ipa_fold_key_dev(c, CURVE, 64, d[0], nullptr, z, d[4], nullptr));      // 128 key points in, 64 out
+            {   // a pairing key's first device call uploads its tables: refused, it leaves no device copy behind and the next call uploads
+                void* key = nullptr;
+                if (zk_pairing_key_new(ZK_CURVE_BN254, BN_H, BN_TAU_H, &key) != ZK_OK) {
+                    if (!bad_line) bad_line = __LINE__;
+                } else {
+                    const long live = fake_hip_live_allocations();
+                    if (!STEP(zk_kzg_pairing_check_batch_dev(c, key, d[0], nullptr, d[1], nullptr, 4, (uint8_t*)d[4]))) {
+                        if (fake_hip_live_allocations() != live && !bad_line) bad_line = __LINE__;
+                        if (zk_kzg_pairing_check_batch_dev(c, key, d[0], nullptr, d[1], nullptr, 4, (uint8_t*)d[4]) != ZK_OK && !bad_line) bad_line = __LINE__;
+                    }
+                    if (fake_hip_live_allocations() != live + 1 && !bad_line) bad_line = __LINE__;
+                    STEP(zk_pairing_gt_batch_dev(c, key, 1, d[0], nullptr, 4, d[4]));      // the copy is there: nothing to allocate
+                    if (fake_hip_live_allocations() != live + 1 && !bad_line) bad_line = __LINE__;
+                    zk_pairing_key_free(key);
+                    if (fake_hip_live_allocations() != live && !bad_line) bad_line = __LINE__;
+                }
+            }
         }();
         for (int k = 0; k < 6; ++k)
             if (d[k]) STEP(zk_dev_free(c, d[k]));
@@ -500,6 +713,16 @@ int main() {
         REQUIRE(swept >= counted);                                    // a scenario that shrank under injection would pass with fewer
         printf("host_stress: allocation sweep: %ld allocation sites refused one by one (%ld counted without injection), %.1f s\n", swept, counted,
                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    }
+
+    // ---- 2f. the pairing: values on both curves; one key shared by host threads while two ctxs race its first upload
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        REQUIRE(pairing_values() == 0);
+        const auto t1 = std::chrono::steady_clock::now();
+        REQUIRE(pairing_threads() == 0);
+        printf("host_stress: pairing: values %.1f s, threads %.1f s\n", std::chrono::duration<double>(t1 - t0).count(),
+               std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count());
     }
 
     // ---- 2e. cache_verify meets a wrong hit: the resident copy of a vector no longer holds what its digest names

@@ -37,12 +37,28 @@ def test_cpp_example_matches_python_mirror(tmp_path, ctx):
                         "-L", libdir, "-l:libark_plonk_amd.so", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     log_n = 13
-    run = subprocess.run([exe, str(log_n)], capture_output=True, text=True, timeout=300)
+    # a pairing key over (H, [TAU]H) and the opening R = TAU * 3 G of the example's first SRS point L = 3 G, as Montgomery limbs
+    from ark_plonk_amd.curves import fq_to_mont, g1_mul, g2_mul, get_curve
+    from ark_plonk_amd.pairing import PairingKey
+    from tests.conftest import TAU
+    cv = get_curve(0)
+    tau_h = g2_mul(cv, TAU)
+    pairing_limbs = fq_to_mont(cv, [*cv.g2x, *cv.g2y, *tau_h[0], *tau_h[1], *g1_mul(cv, 3 * TAU)]).reshape(-1)
+    assert pairing_limbs.size == 60
+    run = subprocess.run([exe, str(log_n)] + [f"{int(v):016x}" for v in pairing_limbs], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, run.stdout + run.stderr
     lines = dict(ln.split(" ", 1) for ln in run.stdout.strip().splitlines())
     assert lines["roundtrip"] == "ok" and lines["commit_round"] == "ok" and lines["host_batch"] == "ok" and lines["deferred_round"] == "ok"
     assert lines["device_winsums"] == "ok"
     assert lines["residency_cache"] == "ok"
+    # zk::PairingKey: a valid and two invalid check_pair, four lanes of check_batch, an unreduced coordinate thrown as ZK_ERR_BAD_ARG;
+    # the GT words it printed are PairingKey.gt's in Python
+    assert lines["pairing"] == "ok"
+    three_g = fq_to_mont(cv, list(g1_mul(cv, 3)))
+    key = PairingKey.from_trapdoor(TAU, 0)
+    want_gt = key.gt(zk.G1Affine(three_g[0], three_g[1], False, cv.name), 1)
+    key.close()
+    assert lines["pairing_gt"].split() == [f"{int(v):016x}" for v in want_gt.reshape(-1)]
     n = 1 << log_n
     ev = _inputs(n)
     dom = zk.Radix2EvaluationDomain.new(n, 0, ctx)

@@ -147,6 +147,138 @@ def test_check_against_the_trapdoor(name):
     assert key.check(inf, inf) is True and key.check(inf, G) is False
 
 
+# ---- edge coordinates: tests/golden/pairing_edges.json (tests/golden/gen_pairing_edges.py), values of the independent reference at G1
+# inputs whose coordinates are ends of Fq, its middle and 32/64-bit word boundaries, as values and as stored Montgomery words, and at
+# off-curve extremes no curve point reaches -- the library's value is an algebraic function of (x, y), and so is the reference's
+EDGE_FIXTURE = os.path.join(ROOT, "tests", "golden", "pairing_edges.json")
+_EDGES = {}
+
+
+def edge_fixture(name):
+    """(points [(x, y, {0: gt with H, 1: gt with [tau]H}, on_curve)], checks [(L, R, valid, row)]) of one curve"""
+    if not _EDGES:
+        fx = json.load(open(EDGE_FIXTURE))
+        assert fx["tau"] == TAU
+        for c in CURVES:
+            pts = [(int(p["x"], 16), int(p["y"], 16), {0: [int(v, 16) for v in p["gt_h"]], 1: [int(v, 16) for v in p["gt_tau_h"]]}, p["on_curve"])
+                   for p in fx[c]["points"]]
+            chk = [(tuple(int(v, 16) for v in r["L"]), tuple(int(v, 16) for v in r["R"]), r["valid"], r) for r in fx[c]["checks"]]
+            _EDGES[c] = (pts, chk)
+    return _EDGES[name]
+
+
+def _edge_generator():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_pairing_edges", os.path.join(ROOT, "tests", "golden", "gen_pairing_edges.py"))
+    mod = importlib.util.module_from_spec(spec)
+    path = list(sys.path)
+    try:
+        spec.loader.exec_module(mod)                     # a script: it puts tests/ in front of sys.path for its two imports
+    finally:
+        sys.path[:] = path
+    return mod
+
+
+@pytest.mark.parametrize("name", CURVES)
+def test_edge_fixture_is_current(name):
+    """the committed point list is the generator's, and three values and one verdict per curve are what the reference says today"""
+    gen = _edge_generator()
+    assert gen.TAU == TAU
+    rc = pr.CURVES[name]
+    pts, chk = edge_fixture(name)
+    raw = json.load(open(EDGE_FIXTURE))[name]
+    want = gen.point_list(gen.pr.CURVES[name])
+    assert [(x, y, oc) for x, y, _, oc in pts] == [(x, y, oc) for x, y, _, oc in want]
+    assert [p["what"] for p in raw["points"]] == [w for _, _, w, _ in want]
+    assert len(pts) >= 30 and sum(oc for _, _, _, oc in pts) == len(pts) - 6 and len(chk) == 4 * (len(pts) - 6)
+    if name == "bls12_381":
+        assert (0, 2) in [(x, y) for x, y, _, _ in pts]
+    tau_h = pr.g2_mul(rc, TAU)
+    for i, which in ((0, 0), (len(pts) // 2, 1), (len(pts) - 1, 0)):        # the first, a middle one, the last (off the curve)
+        x, y, gt, _ = pts[i]
+        assert gt[which] == pr.ref_pairing(rc, (x, y), tau_h if which else rc.g2), (i, which)
+    L, R, valid, row = chk[len(chk) // 8 * 4 + 2]                           # of a middle point, the "edge in R" case
+    assert row["edge_in"] == "R" and not row["r_negated"]
+    e = pr.f_mul(rc, pr.ref_pairing(rc, L, tau_h), pr.ref_pairing(rc, (R[0], -R[1] % rc.q), rc.g2))
+    assert valid == (e == pr.f_one())
+    if name == "bn254":
+        assert all(v == (not r["r_negated"]) for _, _, v, r in chk)
+
+
+@pytest.mark.parametrize("which", (0, 1))
+@pytest.mark.parametrize("name", CURVES)
+def test_gt_at_edge_coordinates_equals_the_fixture(name, which):
+    """PairingKey.gt at every fixture point, on or off the curve, == fixture ** c in the polynomial basis, bit for bit"""
+    cv, rc, key, c = get_curve(name), pr.CURVES[name], key_of(name), GT_POWER[name]
+    for i, (x, y, gt, _) in enumerate(edge_fixture(name)[0]):
+        assert gt_poly(cv, rc, key.gt(g1_point(cv, (x, y)), which)) == pr.f_pow(rc, gt[which], c), (i, hex(x), hex(y))
+
+
+@pytest.mark.parametrize("name", CURVES)
+def test_check_at_edge_coordinates_equals_the_fixture(name):
+    """PairingKey.check of every fixture case == the reference's verdict: edge coordinates in L, in R (whose y the check negates),
+    and both with R.y replaced by q - R.y"""
+    cv, key = get_curve(name), key_of(name)
+    pts, chk = edge_fixture(name)
+    assert any(v for _, _, v, _ in chk) and any(not v for _, _, v, _ in chk)
+    for j, (L, R, valid, row) in enumerate(chk):
+        assert key.check(g1_point(cv, L), g1_point(cv, R)) is valid, (j, row["point"], row["edge_in"], row["r_negated"])
+
+
+# ---- unreduced G1 coordinates are a code on the host (include/ark_plonk_amd.h, the G1 paragraph of the pairing section)
+def _unreduced(cv, limbs):
+    """the same residue plus q where the sum fits the limbs, else q itself (the smallest unreduced value)"""
+    L = cv.fq_limbs
+    v = int.from_bytes(np.ascontiguousarray(limbs).tobytes(), "little") + cv.q
+    if v >= 1 << (64 * L):
+        v = cv.q
+    return np.frombuffer(v.to_bytes(8 * L, "little"), dtype="<u8").copy()
+
+
+@pytest.mark.parametrize("name", CURVES)
+def test_unreduced_g1_coordinates_are_a_code(name):
+    cv, key = get_curve(name), key_of(name)
+    lib, bad, Ln = _lib.lib(), _lib.ZK_ERR_BAD_ARG, cv.fq_limbs
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)           # noqa: E731
+    l = np.ascontiguousarray(g1(cv, 12345).xy(), dtype=np.uint64).reshape(-1).copy()
+    r = np.ascontiguousarray(g1(cv, 12345 * TAU).xy(), dtype=np.uint64).reshape(-1).copy()
+    ok = ctypes.c_int(7)
+    assert lib.zk_kzg_pairing_check(key._h, p(l), 0, p(r), 0, ctypes.byref(ok)) == _lib.ZK_OK and ok.value == 1
+    q_limbs = np.frombuffer(cv.q.to_bytes(8 * Ln, "little"), dtype="<u8").copy()
+    one = fq_to_mont(cv, [1]).reshape(-1)
+    for k in range(4):                                         # L.x, L.y, R.x, R.y
+        pts = [l.copy(), r.copy()]
+        pts[k // 2][(k % 2) * Ln:(k % 2 + 1) * Ln] = _unreduced(cv, pts[k // 2][(k % 2) * Ln:(k % 2 + 1) * Ln])
+        ok = ctypes.c_int(7)
+        assert lib.zk_kzg_pairing_check(key._h, p(pts[0]), 0, p(pts[1]), 0, ctypes.byref(ok)) == bad, k
+        assert ok.value == 7, k                                # untouched
+        with pytest.raises(_lib.ZkError) as e:
+            key.check(G1Affine(pts[0][:Ln], pts[0][Ln:], False, cv.name), G1Affine(pts[1][:Ln], pts[1][Ln:], False, cv.name))
+        assert e.value.code == bad
+        if k < 2:
+            for which in (0, 1):
+                out = np.full((12, Ln), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+                assert lib.zk_pairing_gt(key._h, which, p(pts[0]), 0, p(out)) == bad, (k, which)
+                assert (out == 0x5A5A5A5A5A5A5A5A).all()
+            # ... and a point passed with its infinity flag is not inspected
+            ok = ctypes.c_int(7)
+            assert lib.zk_kzg_pairing_check(key._h, p(pts[0]), 1, p(r), 1, ctypes.byref(ok)) == _lib.ZK_OK and ok.value == 1
+    # the unreduced spellings of the encodings of infinity: (q, one) and (q, q) without a flag
+    for y in (one, q_limbs):
+        spelled = np.concatenate([q_limbs, y])
+        for args in ((spelled, r), (l, spelled), (spelled, spelled)):
+            ok = ctypes.c_int(7)
+            assert lib.zk_kzg_pairing_check(key._h, p(args[0]), 0, p(args[1]), 0, ctypes.byref(ok)) == bad and ok.value == 7
+        out = np.zeros((12, Ln), dtype=np.uint64)
+        assert lib.zk_pairing_gt(key._h, 0, p(spelled), 0, p(out)) == bad and not out.any()
+        ok = ctypes.c_int(7)
+        assert lib.zk_kzg_pairing_check(key._h, p(spelled), 1, p(spelled), 1, ctypes.byref(ok)) == _lib.ZK_OK and ok.value == 1
+    # the largest reduced values pass the test (and are decided, whatever the verdict)
+    top = np.frombuffer((cv.q - 1).to_bytes(8 * Ln, "little"), dtype="<u8").copy()
+    ok = ctypes.c_int(7)
+    assert lib.zk_kzg_pairing_check(key._h, p(np.concatenate([top, top])), 0, p(r), 0, ctypes.byref(ok)) == _lib.ZK_OK and ok.value == 0
+
+
 def _key_new(cid, h, tau_h):
     out = ctypes.c_void_p()
     rc = _lib.lib().zk_pairing_key_new(cid, None if h is None else h.ctypes.data_as(ctypes.c_void_p),

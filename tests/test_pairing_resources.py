@@ -11,6 +11,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KERNELS = ("pairing_check_batch", "pairing_gt_batch")
+# Wavefronts of these kernels that one SIMD holds at once: 512 registers per lane // .vgpr_count of the line printed below, which is
+# 404 (BN254) and 511 (BLS12-381) for both kernels: 1.  tests/test_pairing_gpu.py sizes its more-waves-than-the-card-holds batch by it
+# (4 SIMDs per CU, one wavefront per workgroup); the assertion below keeps it an upper bound of what the compiler allows.
+WAVES_PER_SIMD = 1
 
 
 def kernel_metadata(asm):
@@ -40,3 +44,4 @@ def test_pairing_kernels_fit_the_register_file_and_the_lds():
         assert v.get("agpr_count", 0) <= regs <= 512, (k, v)
         assert v["group_segment_fixed_size"] <= 160 * 1024, (k, v)
         assert v["max_flat_workgroup_size"] == 64 and v["wavefront_size"] == 64, (k, v)
+        assert 1 <= 512 // regs <= WAVES_PER_SIMD, (k, regs)
